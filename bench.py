@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- NCA cell-updates/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR writes what the last timed step computed (rank 0's final state, float32) as DIR/state_out.npy;
+the inputs depend on the arguments only, so two builds run with the same arguments can be compared output for output.
+--full adds every other measurement below (rooflines, informational legs, train leg, CPU baseline); --no-extras,
+--no-cpu-baseline and --train-iters trim a --full run.
 
 One bench "step" = one pass of the hot path over one batch: ConditionedNCA.grow's loop
 (EncoderConditioning/nca.py:207-208) of T=64 fused NCA steps + finalize on BASELINE configs[1]
@@ -12,7 +18,7 @@ fire mask drawn in-kernel (Philox).  value = N*B*H*W*T*K / t, t = max over ranks
 bracketed wall time of the K steps.  Each rank owns an independent shard of the sample pool
 (weak scaling, no data-path collective -- SURVEY.md 8e).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline          fused step kernel (dominant): exact-f32 MFMA bound, algorithmic flops/launch over
                     the HIP-event launch time (events on the launch stream).
   roofline_stencil  standalone DyNCA perception stencil: HBM bound, 20*C bytes/cell.
@@ -112,11 +118,12 @@ def cpu_baseline(prm, x0, goal):
     from oracle import nca_oracle as O
     gpad = O.cond_pad_goal(goal, C)
     ncpu = os.cpu_count() or 1
+    allowed = min(ncpu, int(os.environ.get("OMP_NUM_THREADS") or ncpu))     # OMP_NUM_THREADS, where set, bounds the threads tried
     with torch.no_grad():
         # pick the thread count that serves the reference's op sequence best on this host
         # (all cores oversubscribes these small convs badly); then time the bounded sample with it
         best = (None, 1e30)
-        for th in sorted({t for t in (8, 16, 32, 64, ncpu) if t <= ncpu}):
+        for th in sorted({t for t in (8, 16, 32, 64, allowed) if t <= allowed}):
             torch.set_num_threads(th)
             O.cond_grow_rng(x0, gpad, 1, prm, ALIVE_CH)
             t0 = time.perf_counter()
@@ -231,10 +238,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + rooflines only (profiling passes)")
-    ap.add_argument("--train-iters", type=int, default=5, help="iterations of the training-shaped legs (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (rank 0's final state, float32) as DIR/state_out.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the rooflines, the informational legs, the train leg and the CPU baseline (plain run: headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full with headline + rooflines only (profiling passes)")
+    ap.add_argument("--train-iters", type=int, default=5, help="--full: iterations of the training-shaped legs (0: skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -317,11 +330,28 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    alive_frac = float(ops.cond_alive(out, ALIVE_CH).float().mean())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step: the final state (B x C x H x W fp32, 33.5 MB)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "state_out.npy"), out.cpu().numpy())
 
     result = None
     if rank == 0:
         value = world * B * H * W * T * args.steps / dt
+        result = {
+            "metric": "NCA cell-updates/sec (B*H*W*steps/s) at 256^2 C=16", "value": value, "unit": "cell-updates/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "ms_per_step_median": med_ms, "value_from_median": B * H * W * T / (med_ms * 1e-3),   # rank 0's per-step HIP events (SURVEY 8d: median of >= 10)
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: ConditionedNCA grow loop, B=8 C=16 256x256, 64 NCA steps per bench step, fp32 forward",
+                       "B_per_gpu": B, "C": C, "H": H, "W": W, "nca_steps_per_bench_step": T, "hidden": HIDDEN,
+                       "mask_rng": "in-kernel philox4x32-10",
+                       "parallelism": f"pool-shard x{world} (no data-path collective)" +
+                                      (f" [REHEARSAL: backend={backend}, share_gpu={int(share_gpu)}]" if (share_gpu or backend != "nccl") else "")},
+        }
+    if rank == 0 and args.full:
+        alive_frac = float(ops.cond_alive(out, ALIVE_CH).float().mean())
         # ---- roofline of the dominant kernel: step launches only, events on the launch stream
         # one event-timed region = one grow call (T step launches issued by the C driver + one finalize launch, which is
         # <0.3 % of it and counted against the step: conservative)
@@ -337,17 +367,8 @@ def main():
         gbs = cells * STENCIL_BYTES_PER_CELL / (ms_st * 1e-3) / 1e9
         tr_step = pmc_traffic("cond_step_fwd_pc_kernel", "StF32, false")
         tr_st = pmc_traffic("dynca_perceive_rows_kernel")
-        result = {
-            "metric": "NCA cell-updates/sec (B*H*W*steps/s) at 256^2 C=16", "value": value, "unit": "cell-updates/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_median": med_ms, "value_from_median": B * H * W * T / (med_ms * 1e-3),   # rank 0's per-step HIP events (SURVEY 8d: median of >= 10)
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: ConditionedNCA grow loop, B=8 C=16 256x256, 64 NCA steps per bench step, fp32 forward",
-                       "B_per_gpu": B, "C": C, "H": H, "W": W, "nca_steps_per_bench_step": T, "hidden": HIDDEN,
-                       "mask_rng": "in-kernel philox4x32-10", "alive_fraction_at_end": round(alive_frac, 4),
-                       "alive_fraction_roofline_run": round(alive_frac_roof, 4),
-                       "parallelism": f"pool-shard x{world} (no data-path collective)" +
-                                      (f" [REHEARSAL: backend={backend}, share_gpu={int(share_gpu)}]" if (share_gpu or backend != "nccl") else "")},
+        result["config"].update({"alive_fraction_at_end": round(alive_frac, 4), "alive_fraction_roofline_run": round(alive_frac_roof, 4)})
+        result.update({
             "roofline": {"kernel": "cond_step_fwd_pc_kernel<16,*>", "bound": "mfma", "achieved": tflops,
                          "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": tflops / PEAK_F32_MFMA_TFLOPS,
                          "traffic": tr_step[0], "traffic_provenance": tr_step[1], "launch_ms": ms_launch, "flops_per_cell": FLOPS_PER_CELL,
@@ -356,7 +377,7 @@ def main():
                                  "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS, "traffic": tr_st[0], "traffic_provenance": tr_st[1], "launch_ms": ms_st,
                                  "bytes_per_cell": STENCIL_BYTES_PER_CELL, "cells_per_launch": cells,
                                  "cells_per_s": cells / (ms_st * 1e-3)},
-        }
+        })
         if not args.no_extras:
             # ---- the same grow loop with bf16 state storage (ncahip_cond_grow_fwd_bf16; BASELINE configs[2]'s storage type):
             # reported beside the fp32 headline, never as `value`
@@ -432,11 +453,11 @@ def main():
                 del st_h, pre_h
             del x20, gl20, cot20
     # ---- training-shaped leg on EVERY rank (the path that contains the gradient all-reduce when N > 1): informational
-    train = train_leg(dev, world, args.train_iters) if (args.train_iters > 0 and not args.no_extras) else None
+    train = train_leg(dev, world, args.train_iters) if (args.full and args.train_iters > 0 and not args.no_extras) else None
     if rank == 0:
         if train is not None:
             result["train"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(prm, x0, goal)
             result["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]
         print(json.dumps(result), flush=True)

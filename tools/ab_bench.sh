@@ -5,7 +5,7 @@ other=$1; n=${2:-3}
 cur=video-stylization-with-nca_amd/libncahip.so
 for i in $(seq $n); do
   for lib in $cur $other; do
-    NCAHIP_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-extras --train-iters 0 2>/dev/null | python -c "
+    NCAHIP_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-extras --train-iters 0 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['value']/1e9,4), round(d['roofline']['launch_ms']*1e3,2), round(d['roofline_stencil']['frac'],3))"
   done
 done

@@ -6,7 +6,7 @@ set -o pipefail
 n=${1:-2}
 out=gpurun_out; mkdir -p $out
 NCAHIP_BENCH_SHARE_GPU=1 NCAHIP_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n --steps 3 --warmup 1 --train-iters 1 > $out/rehearse_dist.json 2> $out/rehearse_dist.err \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n --steps 3 --warmup 1 --full --train-iters 1 > $out/rehearse_dist.json 2> $out/rehearse_dist.err \
   || { tail -30 $out/rehearse_dist.err; exit 1; }
 python - <<'PY'
 import json
