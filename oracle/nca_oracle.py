@@ -19,6 +19,12 @@ The restatement is written with the same aten ops, in the same order, as the
 reference so that results are bit-identical on CPU.  A second, independent
 restatement with explicit numpy loops (``*_np``) exists for small cases to
 guard against a shared misunderstanding of an aten op's semantics.
+
+Device and dtype follow the inputs: every constant (fixed filters, positional
+encoding, gate-helper accumulators) is built on the input's device in its dtype,
+so the same functions run as a float64 reference on the GPU.  In float64 the
+1x1 convolutions are evaluated as matrix products (``_conv1x1``); fp32 keeps the
+reference's own aten ops and stays bit-identical.
 """
 from __future__ import annotations
 
@@ -64,13 +70,25 @@ def cond_perceive(z: torch.Tensor, wp: torch.Tensor) -> torch.Tensor:
     return F.conv2d(z, wp, None, 1, 1, 1, z.shape[1])
 
 
+def _conv1x1(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, w, b) for a 1x1 kernel w [O,K,1,1].  float64: the same sum as one matrix product per item (no library
+    convolution in double precision is relied on); every other dtype: F.conv2d itself, bit-identical to the reference."""
+    if x.dtype != torch.float64:
+        return F.conv2d(x, w, b)
+    B, K, H, W = x.shape
+    wm = w.reshape(1, w.shape[0], K).expand(B, -1, -1)
+    if b is None:
+        return torch.bmm(wm, x.reshape(B, K, H * W)).reshape(B, w.shape[0], H, W)
+    return torch.baddbmm(b.reshape(1, -1, 1), wm, x.reshape(B, K, H * W)).reshape(B, w.shape[0], H, W)
+
+
 def cond_update_net(p: torch.Tensor, prm: Dict[str, torch.Tensor]) -> torch.Tensor:
     """nca.py:40-46,57-58 -- 1x1 conv -> ReLU -> 1x1 conv -> ReLU -> 1x1 conv (no bias)."""
-    h = F.conv2d(p, prm["update_net.out.0.weight"], prm["update_net.out.0.bias"])
+    h = _conv1x1(p, prm["update_net.out.0.weight"], prm["update_net.out.0.bias"])
     h = F.relu(h)
-    h = F.conv2d(h, prm["update_net.out.2.weight"], prm["update_net.out.2.bias"])
+    h = _conv1x1(h, prm["update_net.out.2.weight"], prm["update_net.out.2.bias"])
     h = F.relu(h)
-    return F.conv2d(h, prm["update_net.out.4.weight"], None)
+    return _conv1x1(h, prm["update_net.out.4.weight"], None)
 
 
 def cond_step(x: torch.Tensor, goal_enc: torch.Tensor, u: torch.Tensor,
@@ -162,7 +180,7 @@ def image_encoder(img: torch.Tensor, prm: Dict[str, torch.Tensor], prefix: str =
 def _depthwise_fixed(z: torch.Tensor, filt, pad_mode: str) -> torch.Tensor:
     """dynca.py:83-86 -- F.pad(z,[1,1,1,1],mode) then grouped conv with one repeated 3x3."""
     c = z.shape[1]
-    w = torch.tensor(filt, dtype=torch.float32).reshape(1, 1, 3, 3).repeat(c, 1, 1, 1)
+    w = torch.tensor(filt, dtype=z.dtype, device=z.device).reshape(1, 1, 3, 3).repeat(c, 1, 1, 1)
     z = F.pad(z, [1, 1, 1, 1], pad_mode)
     return F.conv2d(z, w, groups=c)
 
@@ -194,20 +212,21 @@ def dynca_perceive_multiscale(x: torch.Tensor, pad_mode: str, scales: Sequence[i
 
 def edge_extractor(img: torch.Tensor, transform: Optional[str] = "tanh") -> torch.Tensor:
     """dynca.py:182-213 -- sobel_x, sobel_y, laplacian of a 1-channel image, ZERO pad, optional tanh."""
-    sx = F.conv2d(img, torch.tensor([[SOBEL_X]]), padding=1)
-    sy = F.conv2d(img, torch.tensor([[SOBEL_Y]]), padding=1)
-    lp = F.conv2d(img, torch.tensor([[LAPLACIAN]]), padding=1)
+    k = dict(dtype=img.dtype, device=img.device)
+    sx = F.conv2d(img, torch.tensor([[SOBEL_X]], **k), padding=1)
+    sy = F.conv2d(img, torch.tensor([[SOBEL_Y]], **k), padding=1)
+    lp = F.conv2d(img, torch.tensor([[LAPLACIAN]], **k), padding=1)
     out = torch.cat((sx, sy, lp), dim=1)
     return torch.tanh(out) if transform == "tanh" else out
 
 
-def cpe2d(b: int, h: int, w: int) -> torch.Tensor:
-    """dynca.py:226-253 -- Cartesian positional encoding, [b,2,h,w]."""
-    xs = torch.arange(h) / h
-    ys = torch.arange(w) / w
+def cpe2d(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """dynca.py:226-253 -- Cartesian positional encoding, [b,2,h,w] (on ``device`` in ``dtype``)."""
+    xs = torch.arange(h, device=device, dtype=dtype) / h
+    ys = torch.arange(w, device=device, dtype=dtype) / w
     xs = 2.0 * (xs - 0.5 + 0.5 / h)
     ys = 2.0 * (ys - 0.5 + 0.5 / w)
-    emb = torch.zeros((2, h, w))
+    emb = torch.zeros((2, h, w), device=device, dtype=dtype)
     emb[:1] = xs[None, :, None]
     emb[1:2] = ys[None, None, :]
     return emb.unsqueeze(0).repeat(b, 1, 1, 1)
@@ -219,8 +238,8 @@ def dynca_step(x: torch.Tensor, cond: Optional[torch.Tensor], u: torch.Tensor,
     """One DyNCA.forward, dynca.py:117-138; ``cond`` is the already-extracted
     conditioning [B,c_cond,H,W] (edges or CPE) or None; ``u`` the torch.rand draw (:131)."""
     y = dynca_perceive_multiscale(x, pad_mode, scales, cond)            # :125
-    h = F.relu(F.conv2d(y, prm["w1.weight"], prm["w1.bias"]))          # :128
-    dx = F.conv2d(h, prm["w2.weight"], prm["w2.bias"])                 # :128
+    h = F.relu(_conv1x1(y, prm["w1.weight"], prm["w1.bias"]))          # :128
+    dx = _conv1x1(h, prm["w2.weight"], prm["w2.bias"])                 # :128
     m = (u + update_rate).floor()                                       # :131
     xn = x + dx * m                                                     # :133
     if return_all:
@@ -294,16 +313,16 @@ def cond_gate_margin(x0, goal_enc_padded, us, prm, alive_ch, thr=0.1, fire_rate=
     w1, b1 = prm["update_net.out.0.weight"], prm["update_net.out.0.bias"]
     w2, b2 = prm["update_net.out.2.weight"], prm["update_net.out.2.bias"]
     x = x0
-    best = torch.full((x0.shape[0],), float("inf"))
+    best = torch.full((x0.shape[0],), float("inf"), dtype=x0.dtype, device=x0.device)
     with torch.no_grad():
         for u in us:
             d = cond_step(x, goal_enc_padded, u, prm, alive_ch, thr, fire_rate, use_living_channel, return_all=True)
             carries = (d["rmask"] * d["life"][:, :1]) > 0     # [B,1,H,W] (life has C channels when use_living_channel is off)
-            pre1 = F.conv2d(d["p"], w1, b1)
-            bnd1 = F.conv2d(d["p"].abs(), w1.abs(), b1.abs())
+            pre1 = _conv1x1(d["p"], w1, b1)
+            bnd1 = _conv1x1(d["p"].abs(), w1.abs(), b1.abs())
             h1 = F.relu(pre1)
-            pre2 = F.conv2d(h1, w2, b2)
-            bnd2 = F.conv2d(h1, w2.abs(), b2.abs())
+            pre2 = _conv1x1(h1, w2, b2)
+            bnd2 = _conv1x1(h1, w2.abs(), b2.abs())
             for pre, bnd in ((pre1, bnd1), (pre2, bnd2)):
                 m = (pre.abs() / bnd.clamp_min(1e-30)).masked_fill(~carries.expand_as(pre), float("inf"))
                 best = torch.minimum(best, m.flatten(1).min(dim=1).values)
@@ -319,17 +338,17 @@ def cond_gate_influence(x0, goal_enc_padded, us, prm, alive_ch, k, thr=0.1, fire
     w1, b1 = prm["update_net.out.0.weight"], prm["update_net.out.0.bias"]
     w2, b2 = prm["update_net.out.2.weight"], prm["update_net.out.2.bias"]
     x = x0
-    region = torch.zeros(x0.shape[0], 1, x0.shape[2], x0.shape[3], dtype=torch.bool)
-    count = torch.zeros(x0.shape[0], dtype=torch.long)
+    region = torch.zeros(x0.shape[0], 1, x0.shape[2], x0.shape[3], dtype=torch.bool, device=x0.device)
+    count = torch.zeros(x0.shape[0], dtype=torch.long, device=x0.device)
     with torch.no_grad():
         for t, u in enumerate(us):
             d = cond_step(x, goal_enc_padded, u, prm, alive_ch, thr, fire_rate, use_living_channel, return_all=True)
             carries = (d["rmask"] * d["life"][:, :1]) > 0
-            pre1 = F.conv2d(d["p"], w1, b1)
-            bnd1 = F.conv2d(d["p"].abs(), w1.abs(), b1.abs())
+            pre1 = _conv1x1(d["p"], w1, b1)
+            bnd1 = _conv1x1(d["p"].abs(), w1.abs(), b1.abs())
             h1 = F.relu(pre1)
-            pre2 = F.conv2d(h1, w2, b2)
-            bnd2 = F.conv2d(h1, w2.abs(), b2.abs())
+            pre2 = _conv1x1(h1, w2, b2)
+            bnd2 = _conv1x1(h1, w2.abs(), b2.abs())
             amb = ((pre1.abs() < k * bnd1).any(1, keepdim=True) | (pre2.abs() < k * bnd2).any(1, keepdim=True)) & carries
             count += ((pre1.abs() < k * bnd1) & carries).flatten(1).sum(1) + ((pre2.abs() < k * bnd2) & carries).flatten(1).sum(1)
             r = t + 1
@@ -342,12 +361,12 @@ def dynca_gate_margin(x0, cond, us, prm, pad_mode, update_rate=0.5, scales=(0,))
     """As cond_gate_margin for the DyNCA step (one hidden layer, dynca.py:126-133): per batch item, min over steps, updated
     cells (m = 1) and hidden units of |w1 y + b1| / (|w1| |y| + |b1|)."""
     x = x0
-    best = torch.full((x0.shape[0],), float("inf"))
+    best = torch.full((x0.shape[0],), float("inf"), dtype=x0.dtype, device=x0.device)
     with torch.no_grad():
         for u in us:
             r = dynca_step(x, cond, u, prm, pad_mode, update_rate, scales, return_all=True)
-            pre = F.conv2d(r["y"], prm["w1.weight"], prm["w1.bias"])
-            bnd = F.conv2d(r["y"].abs(), prm["w1.weight"].abs(), prm["w1.bias"].abs())
+            pre = _conv1x1(r["y"], prm["w1.weight"], prm["w1.bias"])
+            bnd = _conv1x1(r["y"].abs(), prm["w1.weight"].abs(), prm["w1.bias"].abs())
             m = (pre.abs() / bnd.clamp_min(1e-30)).masked_fill(~(r["m"] > 0).expand_as(pre), float("inf"))
             best = torch.minimum(best, m.flatten(1).min(dim=1).values)
             x = r["x"]
@@ -359,14 +378,14 @@ def dynca_gate_influence(x0, cond, us, prm, pad_mode, k, update_rate=0.5, scales
     relative margin k of zero can move -- Chebyshev distance t + 1 of the cell for a gate at step t, one more ring per coarser
     perception scale; circular padding wraps --, number of such gates per item)."""
     x = x0
-    region = torch.zeros(x0.shape[0], 1, x0.shape[2], x0.shape[3], dtype=torch.bool)
-    count = torch.zeros(x0.shape[0], dtype=torch.long)
+    region = torch.zeros(x0.shape[0], 1, x0.shape[2], x0.shape[3], dtype=torch.bool, device=x0.device)
+    count = torch.zeros(x0.shape[0], dtype=torch.long, device=x0.device)
     reach = 1 if tuple(scales) == (0,) else 2 ** max(scales) * 2
     with torch.no_grad():
         for t, u in enumerate(us):
             r = dynca_step(x, cond, u, prm, pad_mode, update_rate, scales, return_all=True)
-            pre = F.conv2d(r["y"], prm["w1.weight"], prm["w1.bias"])
-            bnd = F.conv2d(r["y"].abs(), prm["w1.weight"].abs(), prm["w1.bias"].abs())
+            pre = _conv1x1(r["y"], prm["w1.weight"], prm["w1.bias"])
+            bnd = _conv1x1(r["y"].abs(), prm["w1.weight"].abs(), prm["w1.bias"].abs())
             near = (pre.abs() < k * bnd) & (r["m"] > 0)
             count += near.flatten(1).sum(1)
             amb = near.any(1, keepdim=True).float()
@@ -519,12 +538,13 @@ def cond_step_np(x, goal_enc, u, prm, alive_ch, thr=0.1, fire_rate=0.5):
 # bf16 state/goal, f32 perception, bf16 matrix operands with f32 accumulation, bf16 store).  "parity unpinned" by
 # reference fixtures by construction; it is pinned to the fp32 oracle through the bound tested in tests/.
 def _bf(t):
-    return t.to(torch.bfloat16).to(torch.float32)
+    """round to bf16, keep the dtype (float32, or float64 for a float64 reference around the same roundings)"""
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def cond_step_bf16(x, goal_pad, u, prm, alive_ch=3, thr=0.1, fire_rate=0.5, lo=-10.0, hi=10.0):
-    """x, goal_pad: float32 tensors holding bf16-representable values ([B,C,H,W]; goal_pad already padded to C channels).
-    Returns (x_next, pre, x_pending): x_next = resolved next state (bf16-representable float32)."""
+    """x, goal_pad: float32 (or float64) tensors holding bf16-representable values ([B,C,H,W]; goal_pad already padded to C
+    channels).  Returns (x_next, pre, x_pending): x_next = resolved next state (bf16-representable, x's dtype)."""
     pre = cond_alive(x, alive_ch, thr) if alive_ch >= 0 else torch.ones_like(x[:, :1], dtype=torch.bool)
     z = x + goal_pad * pre.float()
     p = cond_perceive(z, prm["perception_net.weight"])
@@ -533,8 +553,8 @@ def cond_step_bf16(x, goal_pad, u, prm, alive_ch=3, thr=0.1, fire_rate=0.5, lo=-
     B, K, H, W = p.shape
     pm = _bf(p).permute(0, 2, 3, 1).reshape(-1, K).double()
     h1 = torch.relu(pm @ w1.double().t() + prm["update_net.out.0.bias"].double())
-    h2 = torch.relu(_bf(h1.float()).double() @ w2.double().t() + prm["update_net.out.2.bias"].double())
-    out = (_bf(h2.float()).double() @ w3.double().t()).float().reshape(B, H, W, -1).permute(0, 3, 1, 2)
+    h2 = torch.relu(_bf(h1.to(x.dtype)).double() @ w2.double().t() + prm["update_net.out.2.bias"].double())
+    out = (_bf(h2.to(x.dtype)).double() @ w3.double().t()).to(x.dtype).reshape(B, H, W, -1).permute(0, 3, 1, 2)
     mask = (u.clamp(0.0, 1.0) < fire_rate).float().reshape(B, 1, H, W)
     x_pend = _bf(x + mask * out)
     post = cond_alive(x_pend, alive_ch, thr) if alive_ch >= 0 else torch.ones_like(pre)
@@ -561,9 +581,9 @@ def cond_grow_bf16_loss_grads(x0, goal_pad, us, prm, alive_ch, thr, fire_rate, c
         pre = cond_alive(cur, alive_ch, thr) if alive_ch >= 0 else torch.ones_like(cur[:, :1], dtype=torch.bool)
         z = cur + g * pre.float()
         pc = cond_perceive(z, p["perception_net.weight"])
-        h1 = F.relu(F.conv2d(_bf_ste(pc), w1, p["update_net.out.0.bias"]))
-        h2 = F.relu(F.conv2d(_bf_ste(h1), w2, p["update_net.out.2.bias"]))
-        out = F.conv2d(_bf_ste(h2), w3, None)
+        h1 = F.relu(_conv1x1(_bf_ste(pc), w1, p["update_net.out.0.bias"]))
+        h2 = F.relu(_conv1x1(_bf_ste(h1), w2, p["update_net.out.2.bias"]))
+        out = _conv1x1(_bf_ste(h2), w3, None)
         x1 = _bf_ste(cur + cond_fire_mask(u, fire_rate) * out)
         post = cond_alive(x1, alive_ch, thr) if alive_ch >= 0 else torch.ones_like(pre)
         cur = torch.clamp(x1 * (pre & post).float(), lo, hi)
