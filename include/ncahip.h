@@ -408,8 +408,33 @@ int ncahip_dynca_nsteps_fwd_persist_ms_f32(const float *x_in, float *x_out, int 
                                            int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                            float update_rate, uint64_t seed, uint64_t step0,
                                            void *workspace, size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream);
-/* Test hook: the next persistent launches leave out their last n tiles -- what a workgroup that never becomes resident looks
- * like to its neighbours (their bounded polls expire; the launch drains; NCAHIP_EDEVICE).  0 restores normal launches. */
+/* ---- a whole ConditionedNCA grow in ONE launch (small grids: the reference's training shape, 8 x 20 x 64^2) ---------------
+ * Same contract and results as ncahip_cond_grow_fwd_f32 (nca.py:152-209), bit for bit, but every 16 x 16 tile is owned by one
+ * workgroup for all T steps and the final finalize: weight image and goal tile staged once, the tile's pending state in LDS, and
+ * per step one exchange of each tile's border band (x' ring, alpha' 3 deep, pre mask 2 deep) as (value, tag) pairs in
+ * `workspace`, tag = epoch * 4096 + step.  ring == T + 1: states slots 1..T and pre slots 1..T are written exactly as the per-step
+ * driver writes them (ncahip_cond_grow_bwd_f32 consumes them unchanged); slot 0 of `states` holds the input.  ring == 2: `states`
+ * slot 0 is the input and only x_final is defined (pre may be NULL).
+ * Workspace contract: ncahip_cond_grow_persist_workspace bytes (pure host arithmetic; 0 for shapes that are never covered),
+ * 256-byte aligned, ZEROED ONCE by the caller; every call passes a strictly larger epoch (1 .. 2^20 - 1).  Because the epoch is a
+ * kernel argument the call can NOT be captured into a graph and replayed.
+ * Covered: C <= 20, hidden == 64, goal_ch >= 0, alive_ch >= 0 or < 0, H % 16 == 0, W % 16 == 0, T < 4096, bit-packed fire masks
+ * (NCAHIP_SEED_U_IS_BITS) or in-kernel Philox (u == NULL), 16-byte aligned states / x_final / goal, precision mode 0 and no
+ * ncahip_debug_force_generic bit, and B * H/16 * W/16 tiles <= the device's CUs (one workgroup per CU, every tile resident);
+ * NCAHIP_ERANGE otherwise (explicit float uniforms included) -- the caller then runs ncahip_cond_grow_fwd_f32.  Arguments are
+ * checked on the host first (NCAHIP_EINVAL / NCAHIP_ERANGE, nothing enqueued); then a set sticky error word refuses the call
+ * exactly as ncahip_cond_grow_fwd_f32 does (NCAHIP_EDEVICE); residency is tested last.  Every neighbour poll is bounded (2 s of
+ * device wall clock); on expiry bit 1 of the sticky error word is set, the launch drains and x_final holds NaN. */
+size_t ncahip_cond_grow_persist_workspace(int B, int C, int H, int W, int hidden, int goal_ch);
+int ncahip_cond_grow_fwd_persist_f32(float *states, uint8_t *pre, int ring, int T, float *x_final,
+                                     const float *goal, int goal_ch, const float *u, const float *wp, const float *w1,
+                                     const float *b1, const float *w2, const float *b2, const float *w3, int B, int C,
+                                     int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate,
+                                     float clamp_lo, float clamp_hi, uint64_t seed, uint64_t step0, void *workspace,
+                                     size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream);
+/* Test hook: the next persistent DyNCA launches leave out their last n tiles -- what a workgroup that never becomes resident
+ * looks like to its neighbours (their bounded polls expire; the launch drains; NCAHIP_EDEVICE).  0 restores normal launches.
+ * (The persistent ConditionedNCA grow does not take it.) */
 int ncahip_debug_persist_drop_tiles(int n);
 
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------

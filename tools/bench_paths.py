@@ -5,6 +5,8 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
   cond_train      ConditionedNCA grow with history + backward, B=8 T=16 (fp32 and bf16 history)
   cond_c20        the reference's DEFAULT ConditionedNCA (C = 20, 16 hidden channels): forward, forward with history + fused backward
   cond_small      the reference's default training shape (train.py: C = 20, 64 x 64, batch 8) and C = 16 at that size: launch-bound regime
+  cond_small_persist  the persistent ConditionedNCA grow (one launch for the whole grow) against the per-step kernels in the same
+                  run: 8 x 20 x 64^2 T = 64 with and without history, 1 x 20 x 256^2 without
   cfg3            BASELINE configs[2] shape: B=32 C=16 256^2 T=96, forward with history + backward, fp32 and bf16
   dynca_fwd       DyNCA forward steps: C=16/fc=128, C=12/fc=96, C=32/fc=128 and C=32/fc=256 at 2x512^2 (configs[4])
   dynca_train     DyNCA forward with history + backward (the C driver): C=16/fc=128, C=12/fc=96, C=32/fc=256 at 2x512^2
@@ -89,6 +91,22 @@ def cond_train(B, T, dtype, name, iters=10, C=16, HW=256):
     emit(path=name, C=C, HW=HW, storage=str(dtype).split(".")[-1], B=B, T=T, fwd_frac_f32_mfma=cells * flop / tf / 1e9 / 157.3, fwd_ms=tf, bwd_ms=tb, fwd_us_per_step=tf / T * 1e3,
          bwd_us_per_step=tb / T * 1e3, fwd_bwd_Gcells_s=cells / (tf + tb) / 1e6, bwd_over_fwd=tb / tf,
          history_GB=(T + 1) * x.numel() * x.element_size() / 1e9, min_fwd_ms=mf, min_bwd_ms=mb)
+
+
+def cond_persist(B, HW, T, hist, C=20):
+    """us per step of ops.cond_grow with the persistent grow (ops.persistent_cond) and with the per-step kernels, same inputs"""
+    x, goal, _, w = cond_case(B, H=HW, W=HW, C=C)
+    default, runs = ops.persistent_cond, {}
+    for name, on in (("persistent", True), ("per_step", False)):
+        def f(on=on):
+            ops.persistent_cond = on
+            ops.cond_grow(x, T, goal, None, w, 3, seed=1, step0=0, keep_history=hist)
+        runs[name] = timed([f])
+    ops.persistent_cond = default
+    (tp,), (mp,) = runs["persistent"]
+    (ts,), (ms,) = runs["per_step"]
+    emit(path="cond_small_persist", C=C, HW=HW, B=B, T=T, history=hist, persistent_us_per_step=tp / T * 1e3,
+         per_step_us_per_step=ts / T * 1e3, speedup=ts / tp, min_persistent_us_per_step=mp / T * 1e3, min_per_step_us_per_step=ms / T * 1e3)
 
 
 def dyn_weights(C, fc, cc, gen):
@@ -297,6 +315,10 @@ def main(names):
         cond_train(8, 64, torch.float32, "cond_small_default", C=20, HW=64)
         cond_train(8, 64, torch.float32, "cond_small", C=16, HW=64)
         cond_train(8, 64, torch.bfloat16, "cond_small", C=16, HW=64)
+    if allp or "cond_small_persist" in names:
+        cond_persist(8, 64, 64, True)      # the training forward (history for the backward)
+        cond_persist(8, 64, 64, False)
+        cond_persist(1, 256, 64, False)
     if allp or "cfg3" in names:
         cond_train(32, 96, torch.float32, "cfg3", iters=10)
         cond_train(32, 96, torch.bfloat16, "cfg3", iters=10)

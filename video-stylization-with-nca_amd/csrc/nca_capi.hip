@@ -120,7 +120,7 @@ static int device_error_rc(const char* where) {
     const unsigned v = nca_error_word_read(false);
     if (!v) return 0;
     return fail(NCAHIP_EDEVICE, "%s: a device-side failure was recorded earlier on this device (error word 0x%x: bit 0 = "
-                "producer/consumer hand-off poll expired, bit 1 = neighbour poll of the persistent DyNCA kernel expired); results since "
+                "producer/consumer hand-off poll expired, bit 1 = neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired); results since "
                 "the last ncahip_check_errors are not valid", where, v);
 }
 
@@ -132,7 +132,7 @@ int ncahip_check_errors(ncahip_stream_t stream, int clear) {
     const unsigned v = nca_error_word_read(clear != 0);
     if (!v) return 0;
     return fail(NCAHIP_EDEVICE, "device error word 0x%x (bit 0: a producer/consumer hand-off poll expired -- the affected launch "
-                "produced stale tiles; bit 1: a neighbour poll of the persistent DyNCA kernel expired -- that launch stopped early)", v);
+                "produced stale tiles; bit 1: a neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired -- that launch stopped early)", v);
 }
 
 int ncahip_debug_inject_error(unsigned bits) {   // test hook: what a kernel does when a poll expires
@@ -156,7 +156,9 @@ int ncahip_cond_precision(int mode) {
     return 0;
 }
 
+static int g_force_bits = 0;   // the last ncahip_debug_force_generic argument: the persistent grow runs only with none set
 int ncahip_debug_force_generic(int on) {
+    g_force_bits = on;
     nca_set_force_generic((on & 1) != 0);    // bit 0: generic any-shape kernels
     nca_set_cond_variant((on >> 1) & 1);     // bit 1: symmetric wave-private ConditionedNCA kernel instead of producer/consumer
     nca_set_bwd_bf16_exact((on & 4) != 0);   // bit 2: bf16-history backward with exact-f32 products instead of bf16 MFMA
@@ -279,6 +281,51 @@ int ncahip_dynca_nsteps_fwd_persist_ms_f32(const float* x_in, float* x_out, int 
                                            size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream) {
     return dynca_persist_impl(true, x_in, x_out, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0,
                               workspace, workspace_bytes, epoch, stream);
+}
+
+// ---- a whole ConditionedNCA grow in ONE launch for small grids, nca_cond_persist.hip -------------------------------------------
+size_t ncahip_cond_grow_persist_workspace(int B, int C, int H, int W, int hidden, int goal_ch) {
+    if (!dims_ok(B, C, H, W) || !nca_cond_persist_shape_ok(B, C, H, W, hidden, goal_ch)) return 0;
+    // abort word + the exchange: 2 parities x tiles x (C state channels + the pre mask) x 156 band cells (value, tag) pairs
+    return 256 + align256((size_t)2 * nca_cond_persist_xch_pairs(B, C, H, W) * sizeof(unsigned long long));
+}
+
+int ncahip_cond_grow_fwd_persist_f32(float* states, uint8_t* pre, int ring, int T, float* x_final, const float* goal, int goal_ch,
+                                     const float* u, const float* wp, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, const float* w3, int B, int C, int H, int W, int hidden, int alive_ch,
+                                     float alive_thr, float fire_rate, float clamp_lo, float clamp_hi, uint64_t seed, uint64_t step0,
+                                     void* workspace, size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream) {
+    // host-side checks first: nothing below touches the device before the sticky-word refusal
+    if (T < 1 || (ring != 2 && ring != T + 1)) return fail(NCAHIP_EINVAL, "cond grow persist: T >= 1 and ring 2 or T + 1 required");
+    if (!states || !x_final || !workspace || (ring == T + 1 && !pre)) return fail(NCAHIP_EINVAL, "cond grow persist: null pointer");
+    if (int rc = check_cond(states, x_final, ring == T + 1 ? (const void*)pre : (const void*)x_final, goal, wp, w1, b1, w2, b2, w3, B, C, H,
+                            W, hidden, goal_ch, alive_ch, kMaxCCondFwd))
+        return rc;
+    if (epoch < 1 || epoch >= (1u << 20)) return fail(NCAHIP_EINVAL, "cond grow persist: epoch must be in [1, 2^20) (zero the workspace and restart at 1 when it runs out)");
+    const size_t need = ncahip_cond_grow_persist_workspace(B, C, H, W, hidden, goal_ch);
+    if (need == 0 || T >= 4096)
+        return fail(NCAHIP_ERANGE, "cond grow persist: shape not covered (C <= 20, hidden 64, H %% 16 == 0, W %% 16 == 0, T < 4096); use ncahip_cond_grow_fwd_f32");
+    if (workspace_bytes < need) return fail(NCAHIP_EINVAL, "cond grow persist: workspace too small");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NCAHIP_ERANGE, "cond grow persist: 256-byte aligned workspace required");
+    // the per-step driver runs the producer/consumer family only on 16-byte aligned tensors: anything else is not this path's twin
+    if ((((uintptr_t)states | (uintptr_t)x_final | (uintptr_t)goal) & 15) != 0)
+        return fail(NCAHIP_ERANGE, "cond grow persist: 16-byte aligned states / x_final / goal required");
+    const bool ubits = u_is_bits(u, seed);
+    if (u && !ubits) return fail(NCAHIP_ERANGE, "cond grow persist: explicit float uniforms not covered (bit-packed masks or Philox); use ncahip_cond_grow_fwd_f32");
+    if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
+    if (nca_get_cond_precision() != 0 || g_force_bits != 0 || !nca_cond_default_family())
+        return fail(NCAHIP_ERANGE, "cond grow persist: only the default exact-f32 producer/consumer family has a persistent twin; use ncahip_cond_grow_fwd_f32");
+    if (int rc = device_error_rc("cond grow")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    NcaCondPersistArgs a{states, states, pre, ring == T + 1 ? 1 : 0, x_final, goal, ubits ? u : nullptr, wp, w1, b1, w2, b2, w3,
+                         B, C, H, W, goal_ch, alive_ch, T, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0, (int*)workspace, epoch,
+                         (unsigned long long*)((char*)workspace + 256), nca_cond_persist_xch_pairs(B, C, H, W), nullptr, ubits ? 1 : 0, 0,
+                         nullptr};
+    bool fits = false;
+    if (int rc = hip_result(nca_launch_cond_persist(a, st, true, &fits), "cond grow persist (residency)")) return rc;
+    if (!fits) return fail(NCAHIP_ERANGE, "cond grow persist: %d tiles need a CU each on this device; use ncahip_cond_grow_fwd_f32",
+                           nca_cond_persist_tiles(B, H, W));
+    return hip_result(nca_launch_cond_persist(a, st, false, &fits), "cond_grow_fwd_persist");     // ONE launch: no copy, no memset
 }
 
 // ---- conditioning front ends (fixed-filter part of the encoders) ---------------------------------------------------------

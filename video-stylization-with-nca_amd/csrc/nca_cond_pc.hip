@@ -348,6 +348,7 @@ unsigned long long* nca_debug_stamp_ptr() { return g_stamp_pc; }
 #endif
 static int g_cond_precision = 0;
 void nca_set_cond_precision(int mode) { g_cond_precision = mode; }
+int nca_get_cond_precision() { return g_cond_precision; }
 hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) {
     NcaCondArgs a = a_in;
     a.dbg = g_stamp_pc;

@@ -558,7 +558,8 @@ __device__ __forceinline__ void perceive_tile(const float* __restrict__ WS, cons
 // perceive_tile with the LDS operands of channel group c4+1 in flight while group c4 is computed (46 more registers:
 // used where the wave has them, i.e. the bf16-operand consumer).  All 16 reads of a group are inline asm, so the one
 // counter the hardware keeps is managed here: s_waitcnt lgkmcnt(16) = "everything but the group just issued has landed".
-template <int CP, int NT>
+// ZCS: channel stride of Z (the wave tiles' [CP][6][RS] carve by default; the persistent grow reads a whole [CP][18][RS] tile)
+template <int CP, int NT, int ZCS = CS>
 __device__ __forceinline__ void perceive_tile_pipe(const float* __restrict__ WS, const float* __restrict__ Z, int lane_in,
                                                    int n0, float (&P)[NT][3 * CP / 4]) {
     using K = WCfg<CP>;
@@ -570,9 +571,9 @@ __device__ __forceinline__ void perceive_tile_pipe(const float* __restrict__ WS,
     f32x4 wt[2][7];
     f32x2 nb[2][9];
     const unsigned wa0 = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)(WS + K::OFF_WP + g * K::WPS);
-    const unsigned za0 = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)(Z + g * CS + n0 * RS + ci + 3);
+    const unsigned za0 = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)(Z + g * ZCS + n0 * RS + ci + 3);
     auto issue = [&](int c4, int b) {
-        const unsigned wa = wa0 + (unsigned)(4 * c4 * K::WPS * 4), za = za0 + (unsigned)(4 * c4 * CS * 4);
+        const unsigned wa = wa0 + (unsigned)(4 * c4 * K::WPS * 4), za = za0 + (unsigned)(4 * c4 * ZCS * 4);
 #define NCA_RDW(j) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wt[b][j]) : "v"(wa), "n"(16 * (j)))
         NCA_RDW(0); NCA_RDW(1); NCA_RDW(2); NCA_RDW(3); NCA_RDW(4); NCA_RDW(5); NCA_RDW(6);
 #undef NCA_RDW
@@ -740,8 +741,9 @@ __device__ __forceinline__ void mlp_load_regs(const float* __restrict__ WS, int 
 // VALU instruction that lands between two MFMAs drains the matrix pipe first (measured: ~25 cycles per isolated v_max,
 // tools/micro/mlp_pass.hip).  The ReLUs are therefore issued as fenced groups of 8 / 32, and the layer-1 chain of hidden
 // tile m+1 is issued BEFORE the ReLU group of tile m so that group never waits for the chain it reads.
-// XR must provide 16*M3T channel rows (CP <= 16) / exactly CP rows (CP > 16: the last output tile's rows are guarded).
-template <int CP, int NT>
+// XR must provide 16*M3T channel rows (CP <= 16) / exactly CP rows (CP > 16: the last output tile's rows are guarded), XCS
+// floats apart (XRS: the wave tiles' carve; the persistent grow keeps a whole 16 x 16 tile per channel row).
+template <int CP, int NT, int XCS = XRS>
 __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
                                               const float* __restrict__ MK, int lane_in, int n0,
                                               const float (&P)[NT][3 * CP / 4]) {
@@ -760,7 +762,7 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
     }
     // LDS offsets of the residual read-modify-write, computed (and pinned) here: left to the compiler their integer
     // multiplies land inside the MFMA stream next to the reads
-    int xoff = 4 * g * XRS + n0 * WTW + ci, moff = n0 * WTW + ci;
+    int xoff = 4 * g * XCS + n0 * WTW + ci, moff = n0 * WTW + ci;
     asm volatile("" : "+v"(xoff), "+v"(moff));
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc2[4][NT], acc1[NT], acc1n[NT];
@@ -808,7 +810,7 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 // CP <= 16: XR holds 16*M3T channel rows (rows >= CP are scratch): no per-lane guard, no exec masking
-                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3) xr[n][m3][r] = XR[xoff + (16 * m3 + r) * XRS + n * WTW];
+                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3) xr[n][m3][r] = XR[xoff + (16 * m3 + r) * XCS + n * WTW];
                 else xr[n][m3][r] = 0.0f;
             }
     }
@@ -853,7 +855,7 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3)
-                    XR[xoff + (16 * m3 + r) * XRS + n * WTW] = fmaf(mk[n], acc3[m3][n][r], xr[n][m3][r]);
+                    XR[xoff + (16 * m3 + r) * XCS + n * WTW] = fmaf(mk[n], acc3[m3][n][r], xr[n][m3][r]);
             }
 }
 

@@ -98,6 +98,36 @@ hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st
 // two-scale perception (perception_scales = [0, 1]): exchanges 108 pairs per channel and tile (60 fine ring cells + 48 coarse means)
 hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
 
+// A whole ConditionedNCA grow in one launch (nca_cond_persist.hip): one workgroup per 16 x 16 tile for all T steps + finalize
+struct NcaCondPersistArgs {
+    const float* x0;          // [B,C,H,W] input state (states slot 0)
+    float* states;            // hist: [T+1][B,C,H,W]; slots 1..T (the pending states) are written
+    uint8_t* pre;             // hist: [T+1][B,H,W]; slots 1..T are written
+    int hist;                 // 1: ring == T + 1 (history for the backward); 0: only x_final
+    float* x_final;           // [B,C,H,W] finalized state after T steps
+    const float* goal;        // [B,goal_ch,H,W] or null
+    const float* u;           // bit-packed fire masks [T][ceil(B*H*W/32)] (u_bits) or null: Philox (seed, step0 + t)
+    const float *wp, *w1, *b1, *w2, *b2, *w3;
+    int B, C, H, W, goal_ch, alive_ch, T;
+    float thr, fire_rate, lo, hi;
+    uint64_t seed, step0;
+    int* abort_w;             // device word: holds the epoch of a launch that gave up
+    unsigned epoch;           // strictly increasing per workspace (1 .. 2^20 - 1): pair tags are epoch * 4096 + step
+    unsigned long long* xch;  // [2 parities][tile][C + 1 slots][156 band cells] (value, tag) pairs; zeroed once by the caller
+    size_t xch_words;         // pairs per parity
+    unsigned* err;            // sticky error word (bit 1: a neighbour poll expired)
+    int u_bits;
+    uint64_t poll_ticks;      // bound of one neighbour poll in device wall-clock ticks (0: the launcher's default)
+    unsigned long long* dbg;  // diagnostic builds (-DNCA_STAMPS) only: per-workgroup wall-clock sums of the step phases
+};
+bool nca_cond_persist_shape_ok(int B, int C, int H, int W, int hidden, int goal_ch);
+int nca_cond_persist_tiles(int B, int H, int W);
+size_t nca_cond_persist_xch_pairs(int B, int C, int H, int W);
+// query_only: only decide whether every tile gets a CU of its own on the current device (*fits)
+hipError_t nca_launch_cond_persist(const NcaCondPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
+int nca_get_cond_precision();
+bool nca_cond_default_family();   // no test hook / environment override routes the ConditionedNCA step away from its default kernels
+
 struct NcaCondArgs {
     const float* x_in;
     const uint8_t* pre_in;  // null: x_in is a true state; else x_in is pending with this pre mask

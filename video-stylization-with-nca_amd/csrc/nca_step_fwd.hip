@@ -1347,6 +1347,7 @@ static bool g_force_generic = getenv("NCAHIP_FORCE_GENERIC") != nullptr;
 static int g_cond_variant = getenv("NCAHIP_COND_VARIANT") ? atoi(getenv("NCAHIP_COND_VARIANT")) : 0;
 void nca_set_force_generic(bool on) { g_force_generic = on; }
 void nca_set_cond_variant(int v) { g_cond_variant = v; }
+bool nca_cond_default_family() { return !g_force_generic && g_cond_variant == 0; }
 
 // ---- dispatch: smallest instantiation that covers (C, fc); padding lanes carry zero weights ---
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st) {

@@ -52,6 +52,9 @@ SIGNATURES = {
     "ncahip_dynca_nsteps_bwd_workspace": [_I, _I, _I, _I, _I, _I],
     "ncahip_dynca_nsteps_persist_workspace": [_I, _I, _I, _I, _I, _I],
     "ncahip_debug_persist_drop_tiles": [_I],
+    "ncahip_cond_grow_persist_workspace": [_I, _I, _I, _I, _I, _I],
+    "ncahip_cond_grow_fwd_persist_f32": [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F,
+                                         _F, _F, _F, _U64, _U64, _P, ctypes.c_size_t, ctypes.c_uint, _P],
     "ncahip_dynca_nsteps_fwd_persist_ms_f32": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, ctypes.c_size_t,
                                                ctypes.c_uint, _P],
     "ncahip_dynca_nsteps_fwd_persist_f32": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, ctypes.c_size_t,
@@ -75,7 +78,8 @@ SIGNATURES = {
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_bwd_ms_workspace": ctypes.c_size_t,
-             "ncahip_dynca_nsteps_bwd_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_persist_workspace": ctypes.c_size_t}
+             "ncahip_dynca_nsteps_bwd_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_persist_workspace": ctypes.c_size_t,
+             "ncahip_cond_grow_persist_workspace": ctypes.c_size_t}
 
 _lib = None
 

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: marshal torch CUDA tensors to raw pointers, enqueue on the
 current torch stream.  Every function here fails loudly for non-CUDA tensors -- the product path
 has no CPU fallback (the CPU restatement lives in oracle/ and is test infrastructure only)."""
+import re
 from typing import Optional, Sequence
 
 import torch
@@ -93,7 +94,15 @@ def set_cond_precision(mode) -> None:
 def check_errors(clear: bool = True) -> None:
     """Synchronise the current stream and raise NcaHipError if a kernel recorded a device-side failure (a producer/consumer
     hand-off poll that expired) since the last check -- see ncahip_check_errors in include/ncahip.h."""
-    check(lib().ncahip_check_errors(_stream(), int(clear)), "ncahip_check_errors")
+    rc = lib().ncahip_check_errors(_stream(), int(clear))
+    if rc == _capi.EDEVICE:
+        msg = (lib().ncahip_last_error() or b"").decode()
+        word = re.search(r"error word 0x([0-9a-f]+)", msg)
+        if word and int(word.group(1), 16) & 2:      # bit 1: a neighbour poll of a persistent launch expired
+            raise _capi.NcaHipError(f"ncahip_check_errors failed (rc={rc}): {msg} -- the persistent grow (ConditionedNCA, "
+                                    "ops.persistent_cond = False) and the persistent DyNCA steps (ops.persistent_steps = False) "
+                                    "need every tile resident at once; switch them off to run the per-step kernels")
+    check(rc, "ncahip_check_errors")
 
 
 def selftest(device=None) -> None:
@@ -235,6 +244,9 @@ def dynca_step(x: torch.Tensor, cond: Optional[torch.Tensor], u: Optional[torch.
 
 
 persistent_steps = True     # dynca_nsteps: use the one-launch persistent kernel where it applies (tests / A-B timing switch it off)
+# cond_grow (fp32 state): the whole grow in ONE launch where it applies (ncahip_cond_grow_fwd_persist_f32: the same bits as the
+# per-step kernels).  Off by default: at the reference's training shape it only matches the per-step path so far
+persistent_cond = False
 
 
 def two_scale_fused_ok(C: int, H: int, W: int, fc: int) -> bool:
@@ -368,6 +380,28 @@ def cond_grow(x: torch.Tensor, T: int, goal: Optional[torch.Tensor], us: Optiona
     goal, gch = _goal_args(goal, B, C, H, W, dt)
     us, seed = _u_args(us, T, B, H, W, seed)
     assert w.c == C
+    if sfx == "f32" and persistent_cond and not torch.cuda.is_current_stream_capturing():
+        # small grids (the reference's training shape): the whole grow in ONE launch, one workgroup per tile
+        # (ncahip_cond_grow_fwd_persist_f32; its epoch is a kernel argument, so never inside a captured graph).
+        # NCAHIP_ERANGE = shape / mode not covered or not every tile gets a CU -> the per-step kernels below
+        nbytes = lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch)
+        if nbytes:
+            ws, epoch = _persist_workspace(nbytes, x.device)
+            out = torch.empty_like(x)
+            if keep_history:
+                states = torch.empty(T + 1, B, C, H, W, device=x.device, dtype=dt)
+                pre = torch.empty(T + 1, B, H, W, device=x.device, dtype=torch.uint8)
+                states[0].copy_(x)
+            else:
+                states, pre = x, None          # ring 2: only slot 0 (the input) is read
+            rc = lib().ncahip_cond_grow_fwd_persist_f32(
+                _p(states), _p(pre), T + 1 if keep_history else 2, T, _p(out), _p(goal), gch, _p(us), _p(w.wp), _p(w.w1), _p(w.b1),
+                _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate, lo, hi, seed, step0, _p(ws), nbytes,
+                epoch, _stream())
+            if rc == 0:
+                return (out, states, pre) if keep_history else (out, None, None)
+            if rc != _capi.ERANGE:
+                check(rc, "cond_grow_fwd_persist")
     ring = T + 1 if keep_history else 2
     states = torch.empty(ring, B, C, H, W, device=x.device, dtype=dt)
     pre = torch.empty(ring, B, H, W, device=x.device, dtype=torch.uint8)
