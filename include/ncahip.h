@@ -77,7 +77,10 @@ int ncahip_cond_precision(int mode);
  * bit 3 = the ConditionedNCA backward runs its main kernel in the other of its two forms (one launch <-> front kernel +
  * matrix kernel; same results, each mode defaults to the faster one: an independent implementation to cross-check with);
  * bit 4 = the matrix kernel walks whole super-tiles on small grids as well (by default a grid with fewer super-tiles than half
- * the CUs gives each workgroup half a super-tile; with this bit its summation order equals the one-launch form's bit for bit). */
+ * the CUs gives each workgroup half a super-tile; with this bit its summation order equals the one-launch form's bit for bit);
+ * bit 5 = the fp32 producer/consumer ConditionedNCA step runs perception and UpdateNet on every cell, as before firing-cell lists
+ * (by default it runs them on the cells that fire only; same values, see ncahip_cond_step_fwd_f32).
+ * Any bit set also keeps ncahip_cond_grow_fwd_persist_f32 from running (it returns NCAHIP_ERANGE). */
 int ncahip_debug_force_generic(int on);
 
 /* Device-side check that the MFMA operand/accumulator lane maps the kernels assume hold on
@@ -263,6 +266,11 @@ int ncahip_gram_rows_f32(const float *a, int ma, const float *b1, int nb1, const
  *   u     [B,1,H,W] rand_like draw (:172) or NULL (in-kernel Philox); mask = u < fire_rate.
  *   wp [3C,9]; w1 [hidden,3C], b1 [hidden]; w2 [hidden,hidden], b2 [hidden]; w3 [C,hidden].
  *   alive_ch < 0  <=>  use_living_channel=False (:153-154): every cell alive.
+ * The aligned fast path (W % 4 == 0) evaluates UpdateNet for the cells whose mask is 1 only (firing-cell lists); a cell
+ * whose mask is 0 keeps its resolved state.  Against x + 0*out this differs only (a) in the sign of a zero: x = -0 stays
+ * -0 where the reference gives +0 (equal as values), and (b) where out is +-inf or NaN, which only weights that overflow
+ * produce: the reference's cell becomes NaN, this one keeps x.  The kernels of ncahip_debug_force_generic bits 0, 1 and 5 compute
+ * x + 0*out for every cell.
  * ---------------------------------------------------------------------------------------- */
 int ncahip_cond_step_fwd_f32(const float *x_in, const uint8_t *pre_in, float *x_out, uint8_t *pre_out,
                              const float *goal, int goal_ch, const float *u,

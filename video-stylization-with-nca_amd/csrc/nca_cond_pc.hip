@@ -67,9 +67,13 @@ struct PCfg {
     }
 };
 
-template <int CP, bool EXACT, typename ST, bool SPLIT = false>
+// FC: the producer compacts the tile's firing cells into a list (stage_tile FCL) and the consumer runs perception and UpdateNet
+// on those cells only, in groups of 16 MFMA columns (two groups per pass, one for an odd last group).  x' = x + fire * out
+// (nca.py:189): a cell that does not fire keeps its resolved state, which XR already holds -- store_tile is unchanged.
+template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false>
 __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const NcaCondArgs a) {
     static_assert(!SPLIT || ST::BYTES == 4, "bf16x3 emulation is an option of the fp32-storage kernel");
+    static_assert(!FC || (ST::BYTES == 4 && !SPLIT), "firing-cell lists: the exact-f32 fp32-storage consumer");
     constexpr bool BF = ST::BYTES == 2;   // bf16 storage: UpdateNet on bf16 MFMA (operands rounded from the same LDS image)
     using K = WCfg<CP>;
     using PK = PCfg<CP>;
@@ -127,7 +131,8 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     auto lds_of = [&](int which) -> TileLds {
         const typename PK::Offs o = PK::offs(pair, which);
         float* const S = smem + o.scr;
-        return TileLds{smem + o.z, smem + o.xr, S + PK::SCR_A3, S + PK::SCR_A3, S + PK::SCR_LIFE, S + PK::SCR_A2, smem + o.mk};
+        return TileLds{smem + o.z, smem + o.xr, S + PK::SCR_A3, S + PK::SCR_A3, S + PK::SCR_LIFE, S + PK::SCR_A2, smem + o.mk,
+                       reinterpret_cast<int*>(S + PK::SCR_FLAG) + 2 + which};
     };
 
     // every pair walks the same super-tile sequence
@@ -184,10 +189,10 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         const TileLds L = lds_of(which);
         if (t.inner) {
             issue_loads<CP, true, true, 0, EXACT, ST>(a, t, lane, R);
-            stage_tile<CP, false, EXACT, ST>(a, t, L, lane, R, tile_no);
+            stage_tile<CP, false, EXACT, ST, true, FC>(a, t, L, lane, R, tile_no);
         } else {
             issue_loads<CP, true, true, 1, EXACT, ST>(a, t, lane, R);
-            stage_tile<CP, true, EXACT, ST>(a, t, L, lane, R, tile_no);
+            stage_tile<CP, true, EXACT, ST, true, FC>(a, t, L, lane, R, tile_no);
         }
     };
     MlpRegs<CP> Wr;        // exact-f32 operands (f32 storage)
@@ -196,36 +201,62 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     auto consume = [&](const WTile& t, int which) {
         if (!t.valid) return;
         const TileLds L = lds_of(which);
-        constexpr int NT = 2;
+        if constexpr (FC) {
+            // groups of 16 listed cells; padding entries (kFirePad) compute on a real cell and write XR's padding column
+            const int* const FL = reinterpret_cast<const int*>(L.MK);
+            const int ng = (__builtin_amdgcn_readfirstlane(*L.NF) + 15) >> 4;
+            auto cells = [&](auto nt, int gi) {
+                constexpr int NTC = decltype(nt)::value;
+                int zc[NTC], xc[NTC];
+#pragma unroll
+                for (int n = 0; n < NTC; ++n) {
+                    const int e = FL[16 * (gi + n) + (lane & 15)];
+                    zc[n] = e & 0xFFFF;
+                    xc[n] = e >> 16;
+                }
+                float P[NTC][K::K1S];
+                if (gi == 0) NCA_STAMP(4);
+                perceive_cells_pipe<CP, NTC>(smem, L.Z, lane, zc, P);
+                if (gi == 0) NCA_STAMP(5);
+                mlp_cells_regs<CP, NTC>(Wr, smem, L.XR, lane, xc, P);
+                if (gi == 0) NCA_STAMP(6);
+            };
+            int gi = 0;
 #pragma unroll 1
-        for (int pass = 0; pass < WTH / NT; ++pass) {
-            float P[NT][K::K1S];
-            if (pass == 0) NCA_STAMP(4);
+            for (; gi + 2 <= ng; gi += 2) cells(std::integral_constant<int, 2>{}, gi);
+            if (gi < ng) cells(std::integral_constant<int, 1>{}, gi);
+        } else {
+            constexpr int NT = 2;
+#pragma unroll 1
+            for (int pass = 0; pass < WTH / NT; ++pass) {
+                float P[NT][K::K1S];
+                if (pass == 0) NCA_STAMP(4);
 #ifdef NCA_STAMPS
-            // diagnostic knobs (stamps build only): 0xD1A8 = no perception, 0xD1A9 = no MLP
-            if (a.seed == 0xD1A8ull || a.seed == 0xD1AAull || a.seed == 0xD1ADull) {
+                // diagnostic knobs (stamps build only): 0xD1A8 = no perception, 0xD1A9 = no MLP
+                if (a.seed == 0xD1A8ull || a.seed == 0xD1AAull || a.seed == 0xD1ADull) {
 #pragma unroll
-                for (int n = 0; n < NT; ++n)
+                    for (int n = 0; n < NT; ++n)
 #pragma unroll
-                    for (int s_ = 0; s_ < K::K1S; ++s_) P[n][s_] = L.Z[lane + n];
-            } else
+                        for (int s_ = 0; s_ < K::K1S; ++s_) P[n][s_] = L.Z[lane + n];
+                } else
 #endif
-            perceive_tile_pipe<CP, NT>(smem, L.Z, lane, pass * NT, P);   // next channel group's LDS reads in flight
-            if (pass == 0) NCA_STAMP(5);
+                perceive_tile_pipe<CP, NT>(smem, L.Z, lane, pass * NT, P);   // next channel group's LDS reads in flight
+                if (pass == 0) NCA_STAMP(5);
 #ifdef NCA_STAMPS
-            if (a.seed == 0xD1A9ull || a.seed == 0xD1ABull || a.seed == 0xD1ADull) {
-                float acc_ = 0.0f;
+                if (a.seed == 0xD1A9ull || a.seed == 0xD1ABull || a.seed == 0xD1ADull) {
+                    float acc_ = 0.0f;
 #pragma unroll
-                for (int n = 0; n < NT; ++n)
+                    for (int n = 0; n < NT; ++n)
 #pragma unroll
-                    for (int s_ = 0; s_ < K::K1S; ++s_) acc_ += P[n][s_];
-                L.XR[lane] = acc_;
-            } else
+                        for (int s_ = 0; s_ < K::K1S; ++s_) acc_ += P[n][s_];
+                    L.XR[lane] = acc_;
+                } else
 #endif
-            if constexpr (SPLIT) mlp_tile_split<CP, NT>(Ws, smem + K::OFF_B1, smem + K::OFF_B2, L.XR, L.MK, lane, pass * NT, P);
-            else if constexpr (BF) mlp_tile_bf16<CP, NT>(Wb, smem + K::OFF_B1, smem + K::OFF_B2, L.XR, L.MK, lane, pass * NT, P);
-            else mlp_tile_regs<CP, NT>(Wr, smem, L.XR, L.MK, lane, pass * NT, P);
-            if (pass == 0) NCA_STAMP(6);
+                if constexpr (SPLIT) mlp_tile_split<CP, NT>(Ws, smem + K::OFF_B1, smem + K::OFF_B2, L.XR, L.MK, lane, pass * NT, P);
+                else if constexpr (BF) mlp_tile_bf16<CP, NT>(Wb, smem + K::OFF_B1, smem + K::OFF_B2, L.XR, L.MK, lane, pass * NT, P);
+                else mlp_tile_regs<CP, NT>(Wr, smem, L.XR, L.MK, lane, pass * NT, P);
+                if (pass == 0) NCA_STAMP(6);
+            }
         }
         NCA_STAMP(7);
 #ifdef NCA_STAMPS
@@ -324,10 +355,10 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     }
 }
 
-template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false>
+template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false>
 hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     using PK = PCfg<CP>;
-    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT>;
+    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC>;
     const size_t lds = (size_t)PK::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
@@ -337,7 +368,16 @@ hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+bool g_pc_dense = false;   // test hook (ncahip_debug_force_generic bit 5): the exact-f32 consumer runs every cell
+// the exact-f32, fp32-storage step: firing-cell lists unless the test hook asks for the dense consumer
+template <int CP, bool EXACT>
+hipError_t launch_cond_pc_f32(const NcaCondArgs& a, hipStream_t st) {
+    return g_pc_dense ? launch_cond_pc<CP, EXACT, StF32, false, false>(a, st) : launch_cond_pc<CP, EXACT, StF32, false, true>(a, st);
+}
+
 }  // namespace
+
+void nca_set_cond_pc_dense(bool on) { g_pc_dense = on; }
 
 // W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_step_fwd.hip dispatch) guarantees it.
 extern "C" void nca_debug_set_stamp_buffer_pc(void* p);
@@ -358,13 +398,13 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) 
         if (a.C == 12) return launch_cond_pc<12, true, StF32, true>(a, st);
         if (a.C == 16) return launch_cond_pc<16, true, StF32, true>(a, st);
     }
-    if (a.C == 12 && h64) return launch_cond_pc<12, true>(a, st);
-    if (a.C == 16 && h64) return launch_cond_pc<16, true>(a, st);
-    if (a.C <= 12) return launch_cond_pc<12, false>(a, st);
-    if (a.C <= 16) return launch_cond_pc<16, false>(a, st);
+    if (a.C == 12 && h64) return launch_cond_pc_f32<12, true>(a, st);
+    if (a.C == 16 && h64) return launch_cond_pc_f32<16, true>(a, st);
+    if (a.C <= 12) return launch_cond_pc_f32<12, false>(a, st);
+    if (a.C <= 16) return launch_cond_pc_f32<16, false>(a, st);
     // the reference's default model, C = 3 + 1 + 16 = 20 (nca.py:62-94)
-    if (a.C == 20 && h64) return launch_cond_pc<20, true>(a, st);
-    if (a.C <= 20) return launch_cond_pc<20, false>(a, st);
+    if (a.C == 20 && h64) return launch_cond_pc_f32<20, true>(a, st);
+    if (a.C <= 20) return launch_cond_pc_f32<20, false>(a, st);
     return hipErrorInvalidValue;
 }
 

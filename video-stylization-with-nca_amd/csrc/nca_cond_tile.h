@@ -153,8 +153,13 @@ struct TileLds {
     float* PN;    // pre-life mask of this step, halo 1 (6 rows); may alias A3
     float* LIFE;  // life mask of the previous step, halo 2 (8 rows)
     float* A2;    // resolved alpha, halo 2 (8 rows)
-    float* MK;    // fire mask, [4][16]
+    float* MK;    // fire mask, [4][16]; with the firing-cell list (stage_tile FCL): the list, as ints
+    int* NF;      // firing-cell list only: number of firing cells of the tile
 };
+// Firing-cell list (stage_tile FCL): entry = Z offset (row*RS + col) | XR offset (row*WTW + col) << 16 of a firing cell, in
+// cell order; entries count..63 are kFirePad -- cell 0's Z offset for the perception and XR column 64, the unused padding
+// column of every XR channel row (XRS = 68), as the residual's target: a padding lane never writes a cell.
+constexpr int kFirePad = WTH * WTW << 16;
 template <int CP>
 __device__ __forceinline__ TileLds wave_private_lds(float* PWR) {
     using K = WCfg<CP>;
@@ -372,7 +377,8 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
 // Resolve the pending life mask, build z = x + goal*pre in LDS (halo 1), keep the resolved state for
 // the residual.  CHECK=false: no bounds logic.  KEEPX=false: the resolved-state copy XR is not written (callers that only
 // want z, the masks and the fire mask: the backward's front kernel).
-template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true>
+// FCL: instead of the fire mask MK, write the firing-cell list (see kFirePad) into MK and its length into *NF.
+template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true, bool FCL = false>
 __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t, const TileLds& L, int lane_in,
                                            const TileRegs<CP, ST>& R, int tile_no) {
     float* const Z = L.Z;
@@ -457,7 +463,19 @@ __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t,
             const unsigned cellg = (unsigned)((size_t)t.b * plane) + (cin ? (unsigned)(__mul24(cgy, W) + cgx) : 0u);
             uf = ((__float_as_uint(R.uu) >> (cellg & 31u)) & 1u) ? 0.0f : 2.0f;
         }
-        MK[lane] = (cin && wclamp(uf, 0.0f, 1.0f) < a.fire_rate) ? 1.0f : 0.0f;  // nca.py:171-174
+        const bool fires = cin && wclamp(uf, 0.0f, 1.0f) < a.fire_rate;  // nca.py:171-174
+        if constexpr (FCL) {
+            // compaction: firing cell j of the tile (in cell order) -> entry j; invalid cells never fire
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(fires);
+            const int pre = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+            const int cnt = __popcll(bal);
+            int* const FL = reinterpret_cast<int*>(MK);
+            if (fires) FL[pre] = (q4 * RS + ci) | (lane << 16);
+            if (lane >= cnt) FL[lane] = kFirePad;
+            if (lane == 0) *L.NF = cnt;
+        } else {
+            MK[lane] = fires ? 1.0f : 0.0f;
+        }
         wave_sync();
         if (cin && a.pre_out)
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)PN[(q4 + 1) * RS + ci + 4], nca_rsrc(a.pre_out + (size_t)t.b * plane),
@@ -615,6 +633,80 @@ __device__ __forceinline__ void perceive_tile_pipe(const float* __restrict__ WS,
     }
 }
 
+// perceive_tile_pipe over gathered cells (firing-cell list): lane (g, ci) computes the features of the cell at Z offset zc[n]
+// (row*RS + col) instead of (row n0+n, col ci).  Same fma chain per cell => the same bits wherever the cell lands.  The cells
+// of a lane are no longer vertically adjacent: every tap is one ds_read_b32 per cell, and the two cells of a lane still meet
+// in one v_pk_fma_f32 (NT = 2).  A group is 7 + 9*NT reads, more than lgkmcnt counts; LDS returns in order, so lgkmcnt(15)
+// after the next group's issue still means "this group has landed".
+template <int CP, int NT>
+__device__ __forceinline__ void perceive_cells_pipe(const float* __restrict__ WS, const float* __restrict__ Z, int lane_in,
+                                                    const int (&zc)[NT], float (&P)[NT][3 * CP / 4]) {
+    using K = WCfg<CP>;
+    static_assert(NT == 1 || NT == 2, "one or two cells per lane");
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
+    const int g = (lane >> 4) & 3;
+    constexpr int NG = CP / 4;
+    f32x4 wt[2][7];
+    float nb[2][NT][9];
+    const unsigned wa0 = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)(WS + K::OFF_WP + g * K::WPS);
+    const unsigned zb = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)(Z + g * CS + 3);
+    unsigned za0[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) za0[n] = zb + 4u * (unsigned)zc[n];
+    auto issue = [&](int c4, int b) {
+        const unsigned wa = wa0 + (unsigned)(4 * c4 * K::WPS * 4);
+#define NCA_RDW(j) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wt[b][j]) : "v"(wa), "n"(16 * (j)))
+        NCA_RDW(0); NCA_RDW(1); NCA_RDW(2); NCA_RDW(3); NCA_RDW(4); NCA_RDW(5); NCA_RDW(6);
+#undef NCA_RDW
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const unsigned za = za0[n] + (unsigned)(4 * c4 * CS * 4);
+#define NCA_RD1(i, o) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(nb[b][n][i]) : "v"(za), "n"(4 * (o)))
+            NCA_RD1(0, 0); NCA_RD1(1, 1); NCA_RD1(2, 2);
+            NCA_RD1(3, RS); NCA_RD1(4, RS + 1); NCA_RD1(5, RS + 2);
+            NCA_RD1(6, 2 * RS); NCA_RD1(7, 2 * RS + 1); NCA_RD1(8, 2 * RS + 2);
+#undef NCA_RD1
+        }
+    };
+    issue(0, 0);
+#pragma unroll
+    for (int c4 = 0; c4 < NG; ++c4) {
+        const int b = c4 & 1;
+        if (c4 + 1 < NG) {
+            issue(c4 + 1, b ^ 1);
+            asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+        // the loaded registers are tied to the wait (the compiler does not count inline-asm loads)
+#pragma unroll
+        for (int j = 0; j < 7; ++j) asm volatile("" : "+v"(wt[b][j]));
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) asm volatile("" : "+v"(nb[b][n][t]));
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {
+            if constexpr (NT == 2) {
+                f32x2 acc = {0.0f, 0.0f};
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const float w = wt[b][(9 * f + t) >> 2][(9 * f + t) & 3];
+                    acc = __builtin_elementwise_fma(f32x2{w, w}, f32x2{nb[b][0][t], nb[b][1][t]}, acc);
+                }
+                P[0][3 * c4 + f] = acc[0];
+                P[1][3 * c4 + f] = acc[1];
+            } else {
+                float acc = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) acc = fmaf(wt[b][(9 * f + t) >> 2][(9 * f + t) & 3], nb[b][0][t], acc);
+                P[0][3 * c4 + f] = acc;
+            }
+        }
+    }
+}
+
 // relu as ONE integer max on the bit pattern (sign bit set <=> negative int): no NaN-canonicalising pre-pass.
 __device__ __forceinline__ float relu(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
 
@@ -743,10 +835,12 @@ __device__ __forceinline__ void mlp_load_regs(const float* __restrict__ WS, int 
 // tile m+1 is issued BEFORE the ReLU group of tile m so that group never waits for the chain it reads.
 // XR must provide 16*M3T channel rows (CP <= 16) / exactly CP rows (CP > 16: the last output tile's rows are guarded), XCS
 // floats apart (XRS: the wave tiles' carve; the persistent grow keeps a whole 16 x 16 tile per channel row).
-template <int CP, int NT, int XCS = XRS>
-__device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
-                                              const float* __restrict__ MK, int lane_in, int n0,
-                                              const float (&P)[NT][3 * CP / 4]) {
+// FCL (mlp_cells_regs): the columns are gathered firing cells, column n of lane ci at XR offset xc[n]: x' = x + out there
+// (== fmaf(1, out, x)), MK and n0 unused.
+template <int CP, int NT, int XCS, bool FCL>
+__device__ __forceinline__ void mlp_tile_regs_impl(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
+                                                   const float* __restrict__ MK, int lane_in, int n0, const int (&xc)[NT],
+                                                   const float (&P)[NT][3 * CP / 4]) {
     using K = WCfg<CP>;
     constexpr bool WIDE = MlpRegs<CP>::W3_LDS;
     int lane_o = lane_in;
@@ -763,7 +857,16 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
     // LDS offsets of the residual read-modify-write, computed (and pinned) here: left to the compiler their integer
     // multiplies land inside the MFMA stream next to the reads
     int xoff = 4 * g * XCS + n0 * WTW + ci, moff = n0 * WTW + ci;
-    asm volatile("" : "+v"(xoff), "+v"(moff));
+    int xo[NT];   // FCL: per-column residual offsets
+    if constexpr (FCL) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            xo[n] = 4 * g * XCS + xc[n];
+            asm volatile("" : "+v"(xo[n]));
+        }
+    } else {
+        asm volatile("" : "+v"(xoff), "+v"(moff));
+    }
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc2[4][NT], acc1[NT], acc1n[NT];
 #pragma unroll
@@ -804,13 +907,14 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
     float xr[NT][K::M3T][4], mk[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
-        mk[n] = MK[moff + n * WTW];
+        if constexpr (!FCL) mk[n] = MK[moff + n * WTW];
+        const int xon = FCL ? xo[n] : xoff + n * WTW;
 #pragma unroll
         for (int m3 = 0; m3 < K::M3T; ++m3)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 // CP <= 16: XR holds 16*M3T channel rows (rows >= CP are scratch): no per-lane guard, no exec masking
-                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3) xr[n][m3][r] = XR[xoff + (16 * m3 + r) * XCS + n * WTW];
+                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3) xr[n][m3][r] = XR[xon + (16 * m3 + r) * XCS];
                 else xr[n][m3][r] = 0.0f;
             }
     }
@@ -849,14 +953,31 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
                 }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int n = 0; n < NT; ++n)
+    for (int n = 0; n < NT; ++n) {
+        const int xon = FCL ? xo[n] : xoff + n * WTW;
 #pragma unroll
         for (int m3 = 0; m3 < K::M3T; ++m3)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3)
-                    XR[xoff + (16 * m3 + r) * XCS + n * WTW] = fmaf(mk[n], acc3[m3][n][r], xr[n][m3][r]);
+                if (!WIDE || 16 * m3 + 16 <= CP || 4 * g < CP - 16 * m3) {
+                    if constexpr (FCL) XR[xon + (16 * m3 + r) * XCS] = xr[n][m3][r] + acc3[m3][n][r];
+                    else XR[xon + (16 * m3 + r) * XCS] = fmaf(mk[n], acc3[m3][n][r], xr[n][m3][r]);
+                }
             }
+    }
+}
+template <int CP, int NT, int XCS = XRS>
+__device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
+                                              const float* __restrict__ MK, int lane_in, int n0,
+                                              const float (&P)[NT][3 * CP / 4]) {
+    const int none[NT] = {};
+    mlp_tile_regs_impl<CP, NT, XCS, false>(Wr, WS, XR, MK, lane_in, n0, none, P);
+}
+// mlp_tile_regs over gathered firing cells (stage_tile FCL): column n of lane (g, ci) is the cell at XR offset xc[n]
+template <int CP, int NT>
+__device__ __forceinline__ void mlp_cells_regs(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
+                                               int lane_in, const int (&xc)[NT], const float (&P)[NT][3 * CP / 4]) {
+    mlp_tile_regs_impl<CP, NT, XRS, true>(Wr, WS, XR, nullptr, lane_in, 0, xc, P);
 }
 
 // ---- UpdateNet on bf16 MFMA (bf16-storage kernels) -------------------------------------------------

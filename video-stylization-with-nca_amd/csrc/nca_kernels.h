@@ -126,6 +126,7 @@ size_t nca_cond_persist_xch_pairs(int B, int C, int H, int W);
 // query_only: only decide whether every tile gets a CU of its own on the current device (*fits)
 hipError_t nca_launch_cond_persist(const NcaCondPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
 int nca_get_cond_precision();
+void nca_set_cond_pc_dense(bool on);   // test hook: the fp32 producer/consumer step without firing-cell lists
 bool nca_cond_default_family();   // no test hook / environment override routes the ConditionedNCA step away from its default kernels
 
 struct NcaCondArgs {
