@@ -357,6 +357,176 @@ def cond_gate_influence(x0, goal_enc_padded, us, prm, alive_ch, k, thr=0.1, fire
     return region, count
 
 
+# --------------------------------------------------------------------------------------------------------------------------
+# Replay of a RECORDED ConditionedNCA history (the keep_history=True buffers of ncahip_cond_grow_fwd_*, include/ncahip.h):
+# states slot 0 = the grow's input, slot k >= 1 = the pending x'_{k-1} = x_{k-1} + r * out that step k-1 wrote; pre slot k (k >= 1)
+# = that step's pre mask alive(x_{k-1}).  The input of step k is in_0 = slot 0 and in_k = cond_resolve(slot k, pre slot k).  Each
+# step is re-evaluated from the RECORDED input, so every mask decision compares the same fp32 numbers on both sides and can be
+# demanded exactly, with no exclusion near the threshold: two free-running trajectories part for good at the first
+# near-threshold cell that resolves differently, one trajectory replayed step by step does not.
+#
+# Threshold trap: the kernels compare in fp32 -- max3x3(alpha) > 0.1f, clamp(u, 0, 1) < rate_f, clamp to [lo_f, hi_f].  A float64
+# comparison with Python's 0.1 calls a cell with pooled alpha == 0.1f (0.10000000149...) alive where the kernel does not.  Every
+# replay function therefore rounds thr, fire_rate, lo and hi to float32 first (_f32) and compares with that value promoted to the
+# working dtype; in fp32 this is exactly what the aten comparisons with the Python scalars did already.
+def _f32(v: float) -> float:
+    """v rounded to float32, as the kernels receive it (a float argument of the C ABI)"""
+    return float(np.float32(v))
+
+
+def _alive32(x: torch.Tensor, alive_ch: int, thr: float) -> torch.Tensor:
+    """[B,1,H,W] bool: max3x3(alpha) > float32(thr) (nca.py:152-163, kernel rounding); alive_ch < 0: every cell alive"""
+    if alive_ch < 0:
+        return torch.ones(x.shape[0], 1, x.shape[2], x.shape[3], dtype=torch.bool, device=x.device)
+    return F.max_pool2d(x[:, alive_ch:alive_ch + 1], kernel_size=3, stride=1, padding=1) > _f32(thr)
+
+
+def _mask4(m: torch.Tensor, like: torch.Tensor, alive_ch: int = 0) -> torch.Tensor:
+    """a recorded pre mask ([B,H,W] or [B,1,H,W], uint8 or bool) as [B,1,H,W] bool on like's device; alive_ch < 0: every cell
+    lives and the kernels read no mask (include/ncahip.h), so neither does the replay"""
+    if alive_ch < 0:
+        return torch.ones(like.shape[0], 1, like.shape[2], like.shape[3], dtype=torch.bool, device=like.device)
+    return m.reshape(like.shape[0], 1, like.shape[2], like.shape[3]).to(like.device) != 0
+
+
+def cond_resolve(x_pend: torch.Tensor, pre: torch.Tensor, alive_ch: int, thr: float = 0.1,
+                 lo: float = -10.0, hi: float = 10.0) -> torch.Tensor:
+    """ncahip_cond_finalize: clamp(x' * (pre & alive(x')), lo, hi) (nca.py:191-194) in x_pend's dtype; thr / lo / hi are
+    rounded to float32 (threshold trap above), so in float64 this is EXACTLY the fp32 result for fp32-representable x'."""
+    life = _mask4(pre, x_pend, alive_ch) & _alive32(x_pend, alive_ch, thr)
+    return torch.clamp(x_pend * life.to(x_pend.dtype), _f32(lo), _f32(hi))
+
+
+def _replay_parts(x_in, goal_pad, u, prm, alive_ch, thr, fire_rate):
+    """one step from the given input, the draws explicit: (pre, fire mask, perception, UpdateNet output, pending x');
+    weights and goal are taken in x_in's dtype"""
+    prm = {k: v.to(x_in.dtype) for k, v in prm.items() if k in _COND_TRAINED}
+    goal_pad = None if goal_pad is None else goal_pad.to(x_in.dtype)
+    pre = _alive32(x_in, alive_ch, thr)
+    rmask = (u.reshape(x_in.shape[0], 1, x_in.shape[2], x_in.shape[3]).float().clamp(0.0, 1.0) < _f32(fire_rate))
+    rmask = rmask.to(device=x_in.device, dtype=x_in.dtype)
+    z = x_in if goal_pad is None else x_in + goal_pad * pre.to(x_in.dtype)
+    p = cond_perceive(z, prm["perception_net.weight"])
+    out = cond_update_net(p, prm)
+    return pre, rmask, p, out, x_in + rmask * out
+
+
+def cond_replay_step(x_in: torch.Tensor, goal_pad: Optional[torch.Tensor], u: torch.Tensor, prm: Dict[str, torch.Tensor],
+                     alive_ch: int, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0):
+    """The step's (pre [B,1,H,W] bool, pending x' = x_in + r * out) from a given input x_in, in x_in's dtype (nca.py:181-189);
+    goal_pad None = no goal (goal_ch = 0).  ``u`` [B,1,H,W]: the uniforms, or 1 - mask for a bit-packed fire mask.  Thresholds
+    in float32 (threshold trap above).  lo / hi do not enter the pending state; they are accepted for a uniform signature."""
+    pre, _, _, _, pend = _replay_parts(x_in, goal_pad, u, prm, alive_ch, thr, fire_rate)
+    return pre, pend
+
+
+def cond_replay_forward(states: torch.Tensor, pre: torch.Tensor, x_final: Optional[torch.Tensor], goal_pad, us, prm,
+                        alive_ch: int, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0,
+                        dtype: torch.dtype = torch.float64):
+    """Walk a recorded history (states [T+1,B,C,H,W], pre [T+1,B,H,W]; any dtype and device) and yield, per step k, a dict
+
+        k, x_in  = in_k in ``dtype`` (slot 0; for k >= 1 cond_resolve(slot k, pre slot k)),
+        pre_ref  = alive(in_k)                 pre_got  = pre slot k+1 as [B,1,H,W] bool,
+        pend_ref = in_k + r * out(in_k)        pend_got = states slot k+1 in ``dtype``,
+        fire     = r as [B,1,H,W] bool,
+
+    then one last dict with k = T, x_in = in_T = cond_resolve(slot T, pre slot T) (x_final's reference) and x_final_got.
+    Only the current step lives in ``dtype``: no copy of the whole history is made."""
+    Tn = states.shape[0] - 1
+    for k in range(Tn):
+        x_in = states[0].to(dtype) if k == 0 else cond_resolve(states[k].to(dtype), pre[k], alive_ch, thr, lo, hi)
+        with torch.no_grad():
+            pre_ref, rmask, _, _, pend_ref = _replay_parts(x_in, goal_pad, us[k], prm, alive_ch, thr, fire_rate)
+        yield dict(k=k, x_in=x_in, pre_ref=pre_ref, pre_got=_mask4(pre[k + 1], x_in, alive_ch), pend_ref=pend_ref,
+                   pend_got=states[k + 1].to(dtype), fire=rmask > 0)
+    yield dict(k=Tn, x_in=cond_resolve(states[Tn].to(dtype), pre[Tn], alive_ch, thr, lo, hi),
+               x_final_got=None if x_final is None else x_final.to(dtype))
+
+
+_COND_TRAINED = ("perception_net.weight", "update_net.out.0.weight", "update_net.out.0.bias", "update_net.out.2.weight",
+                 "update_net.out.2.bias", "update_net.out.4.weight")
+
+
+def cond_replay_vjp_step(x_in: torch.Tensor, pend_slot: torch.Tensor, pre_slot: torch.Tensor, goal_pad, u, prm,
+                         g_next: torch.Tensor, alive_ch: int, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0,
+                         hi: float = 10.0):
+    """One step of the replay VJP: for in_{k+1} = clamp((in_k + r * out(in_k)) * life, lo, hi) with the recorded masks --
+    pre = pre slot k+1, post = alive(pend_slot = states slot k+1), neither carrying gradient -- and L = <g_next, in_{k+1}>,
+    returns (dL/d in_k, dL/d goal_pad (None without goal), {param: dL/dparam} in the reference layouts).  The clamp passes
+    gradient on the closed interval [lo, hi] (torch.clamp, as the kernels).  Everything in x_in's dtype."""
+    dt = x_in.dtype
+    x = x_in.detach().clone().requires_grad_(True)
+    g = None if goal_pad is None else goal_pad.detach().to(dt).clone().requires_grad_(True)
+    p = {k: prm[k].detach().to(dt).clone().requires_grad_(True) for k in _COND_TRAINED}
+    pre = _mask4(pre_slot, x, alive_ch).to(dt)
+    life = (_mask4(pre_slot, x, alive_ch) & _alive32(pend_slot.to(dt), alive_ch, thr)).to(dt)
+    rmask = (u.reshape(pre.shape).float().clamp(0.0, 1.0) < _f32(fire_rate)).to(device=x.device, dtype=dt)
+    z = x if g is None else x + g * pre
+    out = cond_update_net(cond_perceive(z, p["perception_net.weight"]), p)
+    nxt = torch.clamp((x + rmask * out) * life, _f32(lo), _f32(hi))
+    leaves = [x] + ([] if g is None else [g]) + [p[k] for k in _COND_TRAINED]
+    grads = torch.autograd.grad(nxt, leaves, grad_outputs=g_next.to(dt))
+    gx, rest = grads[0], grads[1:]
+    gg = None if g is None else rest[0]
+    return gx, gg, dict(zip(_COND_TRAINED, rest[0 if g is None else 1:]))
+
+
+def cond_replay_vjp(states: torch.Tensor, pre: torch.Tensor, goal_pad, us, prm, cot: torch.Tensor, alive_ch: int,
+                    thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0,
+                    dtype: torch.dtype = torch.float64, on_step=None):
+    """The chained VJP of L = <cot, x_final> along a recorded history (x_final = in_T): pre masks from the pre slots, post masks
+    alive(pending slot), masks without gradient, the clamp passing gradient on [lo, hi].  Returns (dL/dx0, dL/dgoal_pad or
+    None, {param: grad} in the reference layouts), all in ``dtype``.  ``on_step(k, in_k, g_next, result)``, if given, sees every
+    step's one-step VJP (cond_replay_vjp_step) on the way down, g_next = dL/d in_{k+1}.  Inputs are rebuilt slot by slot."""
+    Tn = states.shape[0] - 1
+    gk = cot.to(dtype)
+    gg_sum, gw_sum = None, None
+    for k in range(Tn - 1, -1, -1):
+        x_in = states[0].to(dtype) if k == 0 else cond_resolve(states[k].to(dtype), pre[k], alive_ch, thr, lo, hi)
+        r = cond_replay_vjp_step(x_in, states[k + 1], pre[k + 1], goal_pad, us[k], prm, gk, alive_ch, thr, fire_rate, lo, hi)
+        if on_step is not None:
+            on_step(k, x_in, gk, r)
+        gk, gg, gw = r
+        gg_sum = gg if gg_sum is None else gg_sum + gg
+        gw_sum = gw if gw_sum is None else {n: gw_sum[n] + gw[n] for n in gw}
+    return gk, gg_sum, gw_sum
+
+
+def cond_replay_gates(x_in: torch.Tensor, pend_slot: torch.Tensor, pre_slot: torch.Tensor, goal_pad, u, prm, alive_ch: int,
+                      k: float, thr: float = 0.1, fire_rate: float = 0.5):
+    """Gradient-carrying ReLU gates (fired, pre & post alive with the recorded masks) of one replayed step whose relative margin
+    |pre-activation| / (sum |w| |in| + |b|) is below k (cond_gate_influence's measure): ([B,1,H,W] cells holding one, count [B])."""
+    w1, b1 = (prm[n].to(x_in.dtype) for n in ("update_net.out.0.weight", "update_net.out.0.bias"))
+    w2, b2 = (prm[n].to(x_in.dtype) for n in ("update_net.out.2.weight", "update_net.out.2.bias"))
+    with torch.no_grad():
+        _, rmask, p, _, _ = _replay_parts(x_in, goal_pad, u, prm, alive_ch, thr, fire_rate)
+        carries = (rmask > 0) & _mask4(pre_slot, x_in, alive_ch) & _alive32(pend_slot.to(x_in.dtype), alive_ch, thr)
+        pre1 = _conv1x1(p, w1, b1)
+        near1 = (pre1.abs() < k * _conv1x1(p.abs(), w1.abs(), b1.abs())) & carries
+        h1 = F.relu(pre1)
+        pre2 = _conv1x1(h1, w2, b2)
+        near2 = (pre2.abs() < k * _conv1x1(h1, w2.abs(), b2.abs())) & carries
+    cells = near1.any(1, keepdim=True) | near2.any(1, keepdim=True)
+    return cells, near1.flatten(1).sum(1) + near2.flatten(1).sum(1)
+
+
+def cond_replay_gate_region(states: torch.Tensor, pre: torch.Tensor, goal_pad, us, prm, alive_ch: int, k: float,
+                            thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0,
+                            dtype: torch.dtype = torch.float64):
+    """cond_gate_influence for a recorded history: a gradient-carrying gate within relative margin k of zero at step t moves
+    dL/dx0 and dL/dgoal within Chebyshev distance t + 1 of its cell.  Returns (region [B,1,H,W] bool, gate count per item [B])."""
+    Tn = states.shape[0] - 1
+    B, _, H, W = states.shape[1:]
+    region = torch.zeros(B, 1, H, W, dtype=torch.bool, device=states.device)
+    count = torch.zeros(B, dtype=torch.long, device=states.device)
+    for t in range(Tn):
+        x_in = states[0].to(dtype) if t == 0 else cond_resolve(states[t].to(dtype), pre[t], alive_ch, thr, lo, hi)
+        cells, n = cond_replay_gates(x_in, states[t + 1], pre[t + 1], goal_pad, us[t], prm, alive_ch, k, thr, fire_rate)
+        count += n.to(count.device)
+        region |= F.max_pool2d(cells.float(), 2 * (t + 1) + 1, 1, t + 1).to(region.device) > 0
+    return region, count
+
+
 def dynca_gate_margin(x0, cond, us, prm, pad_mode, update_rate=0.5, scales=(0,)):
     """As cond_gate_margin for the DyNCA step (one hidden layer, dynca.py:126-133): per batch item, min over steps, updated
     cells (m = 1) and hidden units of |w1 y + b1| / (|w1| |y| + |b1|)."""

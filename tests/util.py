@@ -41,6 +41,30 @@ def grad_close(got: torch.Tensor, ref: torch.Tensor, l2: float = 1e-3, cap: floa
     return float(d.norm() / ref.norm().clamp_min(1e-12)) < l2 and float(d.abs().max() / ref.abs().max().clamp_min(1e-12)) < cap
 
 
+REPLAY_TOL = 1e-5   # one replayed fp32 step against float64 from the same input: max(1, max|ref|) * REPLAY_TOL per element
+
+
+def replay_step_check(rec, tol: float = REPLAY_TOL):
+    """Per-cell verdict on one step record of nca_oracle.cond_replay_forward, nothing excluded: (a) the recorded pre mask equals
+    alive(in_k) exactly, (b) a cell that does not fire keeps in_k by value (the firing-cell-list contract, include/ncahip.h),
+    (c) a cell that fires is within tol * max(1, max|pend_ref|) of the reference.  Returns (bad [B,1,H,W] bool, worst errors
+    {'pre': mismatched cells, 'keep': changed non-firing cells, 'fire': worst relative error of a firing cell})."""
+    fire = rec["fire"]
+    pre_bad = rec["pre_got"] != rec["pre_ref"]
+    got, ref = rec["pend_got"], rec["pend_ref"]
+    keep_bad = (got != rec["x_in"]).any(1, keepdim=True) & ~fire
+    d = ((got - ref).abs() / max(1.0, float(ref.abs().max()))).amax(1, keepdim=True)
+    fire_bad = ~(d <= tol) & fire                     # NaN fails
+    worst = float(d[fire].max()) if bool(fire.any()) else 0.0
+    return pre_bad | keep_bad | fire_bad, {"pre": int(pre_bad.sum()), "keep": int(keep_bad.sum()), "fire": worst}
+
+
+def near_threshold(x: torch.Tensor, alive_ch: int = 3, thr: float = 0.1, eps: float = 1e-4) -> torch.Tensor:
+    """[B,1,H,W]: cells whose 3x3-pooled alpha lies within eps of float32(thr), the value the kernels compare with"""
+    pooled = torch.nn.functional.max_pool2d(x[:, alive_ch:alive_ch + 1].double(), 3, 1, 1)
+    return (pooled - float(np.float32(thr))).abs() < eps
+
+
 # relative margin below which a ReLU gate may resolve differently under two fp32 summation orders: 16 ulp of the term-magnitude
 # bound (a 49..97-term fp32 dot product differs between orders by a few ulp of that bound)
 GATE_K = 1e-6
