@@ -459,6 +459,37 @@ int ncahip_debug_persist_drop_tiles(int n);
 int ncahip_pack_fire_mask_u32(const float *u, uint32_t *bits, int T, int B, int H, int W, float rate, int mode,
                               ncahip_stream_t stream);
 
+/* ---- relaxed-EMD part of the OT appearance loss -----------------------------------------------------------------------
+ * EncoderConditioning/loss/appearance_loss.py:149-174 for one style layer and a batch: with x_i the N sampled feature vectors of
+ * the style target and y_j those of generated image b,
+ *     d_ij = 1 - <x_i, y_j> / (|x_i| + 1e-10) / (|y_j| + 1e-10),     remd[b] = max(mean_i min_j d_ij, mean_j min_i d_ij).
+ * The N x N distances exist only in registers, forwards and backwards.  All fp32.  Covered: c a multiple of 4 up to 512,
+ * 1 <= N <= 1024, 1 <= B <= 65535; NCAHIP_ERANGE otherwise.  Results are bit-reproducible from run to run (no atomics).
+ *
+ * ncahip_ot_gather_f32: t [1, c, HW] (target, shared by the batch) and g [B, c, HW] -> x, y [B, N, c] (row n of sample b = the
+ *   feature vector at position idx[b, n]) and the norms xn, yn [B, N] = sqrt(sum v^2).  idx [B, N] int32, positions in [0, HW);
+ *   NULL = every position in order (then N == HW).
+ * ncahip_ot_gather_bwd_f32: its adjoint for g: dg [B, c, HW] [.., idx[b, n]] = dy [b, n, ..].  Positions of a sample must be distinct;
+ *   with idx != NULL the caller zeroes dg first (only the sampled positions are written).
+ * ncahip_ot_remd_fwd_f32: rmin [B, N] = min_j d_ij with rarg = its argmin, cmin / carg the same over i, remd [B], and branch [B]:
+ *   0 = the row mean won the max, 1 = the column mean, 2 = they are equal.  Ties of a minimum resolve to the lowest index.  x, y and
+ *   the workspace (ncahip_ot_workspace bytes: column-minimum partials, combined in a fixed order) 16-byte aligned.
+ * ncahip_ot_remd_bwd_f32: dy [B, N, c] = g_remd[b] * d remd[b] / d y (x is the constant target: no gradient), through the argmins of
+ *   the winning branch (both, halved, when branch == 2, as torch.maximum does); the norms are functions of x and y here:
+ *   d d_ij / d y_j = -xh / s + <xh, y_j> y_j / (|y_j| s^2), xh = x_i / (|x_i| + 1e-10), s = |y_j| + 1e-10; for |y_j| = 0 the second
+ *   term is taken as 0. */
+size_t ncahip_ot_workspace(int B, int N, int c);
+int ncahip_ot_gather_f32(const float *t, const float *g, const int32_t *idx, float *x, float *y, float *xn, float *yn,
+                         int B, int c, int HW, int N, ncahip_stream_t stream);
+int ncahip_ot_gather_bwd_f32(const float *dy, const int32_t *idx, float *dg, int B, int c, int HW, int N,
+                             ncahip_stream_t stream);
+int ncahip_ot_remd_fwd_f32(const float *x, const float *y, const float *xn, const float *yn, float *rmin, int32_t *rarg,
+                           float *cmin, int32_t *carg, float *remd, int32_t *branch, int B, int N, int c,
+                           void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+int ncahip_ot_remd_bwd_f32(const float *x, const float *y, const float *xn, const float *yn, const int32_t *rarg,
+                           const int32_t *carg, const int32_t *branch, const float *g_remd, float *dy, int B, int N, int c,
+                           ncahip_stream_t stream);
+
 /* The [B,1,H,W] uniforms the kernels draw for (seed, step) when u == NULL (for tests/tools). */
 int ncahip_philox_uniform_f32(float *u, int B, int H, int W, uint64_t seed, uint64_t step,
                               ncahip_stream_t stream);

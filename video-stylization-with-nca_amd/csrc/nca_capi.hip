@@ -784,6 +784,66 @@ int ncahip_gram_rows_f32(const float* a, int ma, const float* b1, int nb1, const
                                            accumulate != 0), "gram_rows");
 }
 
+// ---- relaxed-EMD part of the OT appearance loss (nca_ot.hip) ---------------------------------------------------------
+namespace {
+constexpr int kOtMaxC = 512, kOtMaxN = 1024, kOtMaxB = 65535;
+int check_ot(const char* what, int B, int N, int c) {
+    if (B <= 0) return fail(NCAHIP_EINVAL, "%s: bad size B=%d", what, B);
+    if (c <= 0 || (c & 3) != 0 || c > kOtMaxC) return fail(NCAHIP_ERANGE, "%s: c=%d must be a multiple of 4 in [4, %d]", what, c, kOtMaxC);
+    if (N < 1 || N > kOtMaxN) return fail(NCAHIP_ERANGE, "%s: N=%d outside [1, %d]", what, N, kOtMaxN);
+    if (B > kOtMaxB) return fail(NCAHIP_ERANGE, "%s: B=%d exceeds %d", what, B, kOtMaxB);
+    return 0;
+}
+bool ot_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+}  // namespace
+
+size_t ncahip_ot_workspace(int B, int N, int c) {
+    if (B <= 0 || B > kOtMaxB || N < 1 || N > kOtMaxN || c <= 0 || (c & 3) != 0 || c > kOtMaxC) return 0;
+    return (size_t)nca_ot_bands(N) * B * N * (sizeof(float) + sizeof(int32_t));
+}
+
+int ncahip_ot_gather_f32(const float* t, const float* g, const int32_t* idx, float* x, float* y, float* xn, float* yn, int B, int c,
+                         int HW, int N, ncahip_stream_t stream) {
+    if (!t || !g || !x || !y || !xn || !yn) return fail(NCAHIP_EINVAL, "ot_gather: null pointer");
+    if (int rc = check_ot("ot_gather", B, N, c)) return rc;
+    if (HW < N || (size_t)B * c * HW >= ((size_t)1 << 40)) return fail(NCAHIP_EINVAL, "ot_gather: bad size HW=%d (N=%d positions)", HW, N);
+    if (!idx && N != HW) return fail(NCAHIP_EINVAL, "ot_gather: idx == NULL means every position (N == HW), got N=%d HW=%d", N, HW);
+    if (x == y || (const float*)x == t || (const float*)x == g || (const float*)y == t || (const float*)y == g || xn == yn)
+        return fail(NCAHIP_EINVAL, "ot_gather: outputs must not alias each other or the inputs");
+    return hip_result(nca_launch_ot_gather(t, g, idx, x, y, xn, yn, B, c, HW, N, (hipStream_t)stream), "ot_gather");
+}
+
+int ncahip_ot_gather_bwd_f32(const float* dy, const int32_t* idx, float* dg, int B, int c, int HW, int N, ncahip_stream_t stream) {
+    if (!dy || !dg) return fail(NCAHIP_EINVAL, "ot_gather_bwd: null pointer");
+    if (int rc = check_ot("ot_gather_bwd", B, N, c)) return rc;
+    if (HW < N || (size_t)B * c * HW >= ((size_t)1 << 40)) return fail(NCAHIP_EINVAL, "ot_gather_bwd: bad size HW=%d (N=%d positions)", HW, N);
+    if (!idx && N != HW) return fail(NCAHIP_EINVAL, "ot_gather_bwd: idx == NULL means every position (N == HW), got N=%d HW=%d", N, HW);
+    if (dy == dg) return fail(NCAHIP_EINVAL, "ot_gather_bwd: dy and dg must not alias");
+    return hip_result(nca_launch_ot_scatter(dy, idx, dg, B, c, HW, N, (hipStream_t)stream), "ot_gather_bwd");
+}
+
+int ncahip_ot_remd_fwd_f32(const float* x, const float* y, const float* xn, const float* yn, float* rmin, int32_t* rarg, float* cmin,
+                           int32_t* carg, float* remd, int32_t* branch, int B, int N, int c, void* workspace, size_t workspace_bytes,
+                           ncahip_stream_t stream) {
+    if (!x || !y || !xn || !yn || !rmin || !rarg || !cmin || !carg || !remd || !branch || !workspace)
+        return fail(NCAHIP_EINVAL, "ot_remd_fwd: null pointer");
+    if (int rc = check_ot("ot_remd_fwd", B, N, c)) return rc;
+    if (rmin == cmin || rarg == carg || (const float*)rmin == xn || (const float*)rmin == yn || (const float*)cmin == xn || (const float*)cmin == yn)
+        return fail(NCAHIP_EINVAL, "ot_remd_fwd: outputs must not alias each other or the norms");
+    if (!ot_aligned(x) || !ot_aligned(y) || !ot_aligned(workspace)) return fail(NCAHIP_ERANGE, "ot_remd_fwd: x, y and workspace must be 16-byte aligned");
+    if (workspace_bytes < ncahip_ot_workspace(B, N, c)) return fail(NCAHIP_EINVAL, "ot_remd_fwd: workspace too small");
+    return hip_result(nca_launch_ot_remd_fwd(x, y, xn, yn, rmin, rarg, cmin, carg, remd, branch, B, N, c, workspace, (hipStream_t)stream), "ot_remd_fwd");
+}
+
+int ncahip_ot_remd_bwd_f32(const float* x, const float* y, const float* xn, const float* yn, const int32_t* rarg, const int32_t* carg,
+                           const int32_t* branch, const float* g_remd, float* dy, int B, int N, int c, ncahip_stream_t stream) {
+    if (!x || !y || !xn || !yn || !rarg || !carg || !branch || !g_remd || !dy) return fail(NCAHIP_EINVAL, "ot_remd_bwd: null pointer");
+    if (int rc = check_ot("ot_remd_bwd", B, N, c)) return rc;
+    if ((const float*)dy == x || (const float*)dy == y) return fail(NCAHIP_EINVAL, "ot_remd_bwd: dy must not alias x or y");
+    if (!ot_aligned(x) || !ot_aligned(y) || !ot_aligned(dy)) return fail(NCAHIP_ERANGE, "ot_remd_bwd: x, y and dy must be 16-byte aligned");
+    return hip_result(nca_launch_ot_remd_bwd(x, y, xn, yn, rarg, carg, branch, g_remd, dy, B, N, c, (hipStream_t)stream), "ot_remd_bwd");
+}
+
 size_t ncahip_cond_grow_bwd_workspace(int B, int C, int H, int W, int hidden) {
     if (!dims_ok(B, C, H, W) || hidden <= 0) return 0;
     const size_t n = (size_t)B * C * H * W * sizeof(float);

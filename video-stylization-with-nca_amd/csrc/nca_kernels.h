@@ -190,6 +190,15 @@ int nca_gram_grid(int B, int HW);
 hipError_t nca_launch_gram_rows(const float* a, int ma, const float* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                 float* out, float* ws, hipStream_t st, bool accumulate = false);
 hipError_t nca_launch_reduce_wp(const float* part, float* dst, int B, int C, int H, int W, hipStream_t st);
+// nca_ot.hip: relaxed-EMD part of the OT appearance loss (gather / normalise, N x N cosine distances reduced in registers, adjoints)
+int nca_ot_bands(int N);   // column-minimum partials per column (one per 32-row band)
+hipError_t nca_launch_ot_gather(const float* t, const float* g, const int* idx, float* x, float* y, float* xn, float* yn, int B, int c,
+                                int HW, int N, hipStream_t st);
+hipError_t nca_launch_ot_scatter(const float* dy, const int* idx, float* dg, int B, int c, int HW, int N, hipStream_t st);
+hipError_t nca_launch_ot_remd_fwd(const float* x, const float* y, const float* xn, const float* yn, float* rmin, int* rarg, float* cmin,
+                                  int* carg, float* remd, int* branch, int B, int N, int c, void* ws, hipStream_t st);
+hipError_t nca_launch_ot_remd_bwd(const float* x, const float* y, const float* xn, const float* yn, const int* rarg, const int* carg,
+                                  const int* branch, const float* gup, float* dy, int B, int N, int c, hipStream_t st);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);

@@ -188,3 +188,36 @@ def hip_perceive(x: torch.Tensor, pad_mode: str) -> torch.Tensor:
     if _needs_grad(x):
         return _HipPerceive.apply(x, pad_mode)
     return ops.dynca_perceive(x, pad_mode)
+
+
+# ------------------------------------------------------------------------------------ OT appearance loss
+class OTGather(torch.autograd.Function):
+    """(t [1,c,h,w], g [B,c,h,w], idx [B,N] int32 or None) -> X, Y [B,N,c], xn, yn [B,N] (ops.ot_gather).  Gradient to g only: the
+    target is a constant, and the norms are outputs for OTRelaxedEMD to read, not differentiable leaves."""
+
+    @staticmethod
+    def forward(ctx, t, g, idx):
+        x, y, xn, yn = ops.ot_gather(t, g, idx)
+        ctx.idx, ctx.hw = idx, (g.shape[2], g.shape[3])
+        ctx.mark_non_differentiable(x, xn, yn)
+        return x, y, xn, yn
+
+    @staticmethod
+    def backward(ctx, gx, gy, gxn, gyn):
+        return None, ops.ot_gather_backward(gy.contiguous(), ctx.idx, *ctx.hw), None
+
+
+class OTRelaxedEMD(torch.autograd.Function):
+    """(X, Y, xn, yn) -> remd [B] (ops.ot_remd).  Gradient to Y only, through the argmins of the branch that won the max; xn / yn
+    are treated as functions of X / Y inside the closed form (include/ncahip.h), not as separate leaves."""
+
+    @staticmethod
+    def forward(ctx, x, y, xn, yn):
+        r = ops.ot_remd(x, y, xn, yn)
+        ctx.save_for_backward(x, y, xn, yn, r["rarg"], r["carg"], r["branch"])
+        return r["remd"]
+
+    @staticmethod
+    def backward(ctx, g_remd):
+        x, y, xn, yn, rarg, carg, branch = ctx.saved_tensors
+        return None, ops.ot_remd_backward(x, y, xn, yn, rarg, carg, branch, g_remd.float().contiguous()), None, None

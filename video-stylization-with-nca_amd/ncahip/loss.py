@@ -178,10 +178,49 @@ def ot_loss_batched(target_feats, gen_feats, n_samples=1000):
     return total / B
 
 
+def ot_loss_fused(target_feats, gen_feats, n_samples=1000):
+    """ot_loss_batched with the relaxed-EMD part on this library's kernels (csrc/nca_ot.hip): the same index draws from numpy's
+    global stream in the same order (sample-major, layer-minor), one gather kernel per layer instead of expand / gather /
+    transpose, and the B x N x N cosine distances reduced to their row and column minima in registers, forwards and backwards
+    (the backward of a min is a gather through its argmin).  The moment term is `_moment_loss`'s arithmetic, batched, on the
+    X, Y the gather kernel produced.  CUDA float32 features only (no CPU fallback); c a multiple of 4 up to 512, N <= 1024.
+
+    The one place where the two paths differ on purpose: an all-zero generated feature vector.  In d d_ij / d y_j =
+    -xh / s + <xh, y_j> y_j / (|y_j| s^2) the second term is 0 / 0 at y_j = 0; torch's autograd of sqrt at 0 turns that into NaN
+    for the whole vector whenever a zero y_j sits on the winning branch, the kernel takes the term as 0 and returns the finite
+    first term.  Every finite case agrees with the torch path up to summation order."""
+    from .autograd import OTGather, OTRelaxedEMD
+    B = gen_feats[0].shape[0]
+    idx = [[None] * len(gen_feats) for _ in range(B)]
+    for b in range(B):                                     # the reference's draw order: sample-major, layer-minor
+        for li, t in enumerate(target_feats):
+            h, w = t.shape[2], t.shape[3]
+            if h > 32:
+                idx[b][li] = np.sort(np.random.choice(np.arange(h * w), size=n_samples, replace=False))
+    total = 0
+    for li, (t, g) in enumerate(zip(target_feats, gen_feats)):
+        ix = None
+        if idx[0][li] is not None:
+            ix = torch.as_tensor(np.stack([idx[b][li] for b in range(B)]).astype(np.int32)).to(g.device)    # [B, N]
+        x, y, xn, yn = OTGather.apply(t, g, ix)                                                      # [B, N, c]
+        remd = OTRelaxedEMD.apply(x, y, xn, yn)                                                      # [B]
+        mx, my = x.mean(1, keepdim=True), y.mean(1, keepdim=True)
+        xc, yc = x - mx, y - my
+        n = x.shape[1]
+        cx = torch.bmm(xc.transpose(1, 2), xc) / (n - 1)
+        cy = torch.bmm(yc.transpose(1, 2), yc) / (n - 1)
+        mom = (mx - my).abs().mean(dim=(1, 2)) + (cx - cy).abs().mean(dim=(1, 2))
+        total = total + (remd + mom).sum()
+    return total / B
+
+
 class Loss(nn.Module):
     def __init__(self, device, content_loss_weight=1.0, overflow_loss_weight=1.0, appearance_loss_weight=1.0,
-                 appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False):
+                 appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False, ot_impl="batched"):
         super().__init__()
+        if ot_impl not in ("batched", "fused"):
+            raise ValueError(f"ncahip.loss: unknown ot_impl={ot_impl!r} ('batched' or 'fused')")
+        self.ot_impl = ot_impl          # 'fused': the relaxed-EMD part of the OT term on this library's kernels (ot_loss_fused)
         self.device = device
         self.appearance_loss_type = appearance_loss_type
         self.appearance_loss_weight = appearance_loss_weight
@@ -227,7 +266,8 @@ class Loss(nn.Module):
             if "appearance" in self.loss_weights:
                 acc = 0
                 if self.appearance_loss_type == "OT":    # appearance_loss.py:212-220: mean over the batch
-                    acc = ot_loss_batched([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
+                    ot = ot_loss_fused if self.ot_impl == "fused" else ot_loss_batched
+                    acc = ot([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
                 elif self.appearance_loss_type == "Gram":   # :98-106
                     for l in STYLE_LAYERS:
                         acc = acc + (_gram(self.style_feats[l]) - _gram(gf[l])).square().mean()

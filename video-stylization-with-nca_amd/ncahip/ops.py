@@ -507,3 +507,64 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
                                             _p(out["w1"]), _p(out["b1"]), _p(out["w2"]), _p(out["b2"]), _p(ws), nbytes, _stream()),
           "dynca_nsteps_bwd" + sfx)
     return out
+
+
+# ---------------------------------------------------------------- relaxed-EMD part of the OT appearance loss (csrc/nca_ot.hip)
+def ot_gather(t: torch.Tensor, g: torch.Tensor, idx: Optional[torch.Tensor] = None):
+    """Feature vectors of one style layer at the sampled positions (ncahip_ot_gather_f32): t [1,c,h,w] the target's map, g [B,c,h,w]
+    the generated images', idx [B,N] int32 positions per sample (None: every position, N = h*w).  Returns X, Y [B,N,c] and the
+    norms xn, yn [B,N]."""
+    t, g = _dev(t, "t"), _dev(g, "g")
+    B, c, h, w = g.shape
+    assert t.shape == (1, c, h, w), (t.shape, g.shape)
+    if idx is not None:
+        idx = _dev(idx, "idx", torch.int32)
+        assert idx.dim() == 2 and idx.shape[0] == B
+    N = h * w if idx is None else idx.shape[1]
+    x, y = (torch.empty(B, N, c, device=g.device, dtype=torch.float32) for _ in range(2))
+    xn, yn = (torch.empty(B, N, device=g.device, dtype=torch.float32) for _ in range(2))
+    check(lib().ncahip_ot_gather_f32(_p(t), _p(g), _p(idx), _p(x), _p(y), _p(xn), _p(yn), B, c, h * w, N, _stream()), "ot_gather")
+    return x, y, xn, yn
+
+
+def ot_gather_backward(dy: torch.Tensor, idx: Optional[torch.Tensor], h: int, w: int) -> torch.Tensor:
+    """Adjoint of ot_gather for g: dy [B,N,c] scattered into dL/dg [B,c,h,w] (zero where nothing was sampled)."""
+    dy = _dev(dy, "dy")
+    B, N, c = dy.shape
+    if idx is not None:
+        idx = _dev(idx, "idx", torch.int32)
+        assert idx.shape == (B, N)
+    dg = (torch.zeros if idx is not None else torch.empty)(B, c, h, w, device=dy.device, dtype=torch.float32)
+    check(lib().ncahip_ot_gather_bwd_f32(_p(dy), _p(idx), _p(dg), B, c, h * w, N, _stream()), "ot_gather_bwd")
+    return dg
+
+
+def ot_remd(x: torch.Tensor, y: torch.Tensor, xn: torch.Tensor, yn: torch.Tensor):
+    """Relaxed EMD over cosine distances d_ij = 1 - <x_i,y_j> / (|x_i| + 1e-10) / (|y_j| + 1e-10) per sample
+    (ncahip_ot_remd_fwd_f32): returns dict remd [B], branch [B] (0 rows / 1 columns / 2 equal), rmin, rarg, cmin, carg [B,N]."""
+    x, y, xn, yn = _dev(x, "x"), _dev(y, "y"), _dev(xn, "xn"), _dev(yn, "yn")
+    B, N, c = x.shape
+    assert y.shape == (B, N, c) and xn.shape == (B, N) and yn.shape == (B, N)
+    dev, f32, i32 = x.device, torch.float32, torch.int32
+    out = {"remd": torch.empty(B, device=dev, dtype=f32), "branch": torch.empty(B, device=dev, dtype=i32),
+           "rmin": torch.empty(B, N, device=dev, dtype=f32), "rarg": torch.empty(B, N, device=dev, dtype=i32),
+           "cmin": torch.empty(B, N, device=dev, dtype=f32), "carg": torch.empty(B, N, device=dev, dtype=i32)}
+    nbytes = lib().ncahip_ot_workspace(B, N, c)
+    ws = _workspace(nbytes, dev)
+    check(lib().ncahip_ot_remd_fwd_f32(_p(x), _p(y), _p(xn), _p(yn), _p(out["rmin"]), _p(out["rarg"]), _p(out["cmin"]), _p(out["carg"]),
+                                       _p(out["remd"]), _p(out["branch"]), B, N, c, _p(ws), nbytes, _stream()), "ot_remd_fwd")
+    return out
+
+
+def ot_remd_backward(x: torch.Tensor, y: torch.Tensor, xn: torch.Tensor, yn: torch.Tensor, rarg: torch.Tensor, carg: torch.Tensor,
+                     branch: torch.Tensor, g_remd: torch.Tensor) -> torch.Tensor:
+    """dL/dy [B,N,c] of ot_remd given dL/dremd [B] (ncahip_ot_remd_bwd_f32); x is the constant target and gets no gradient."""
+    x, y, xn, yn = _dev(x, "x"), _dev(y, "y"), _dev(xn, "xn"), _dev(yn, "yn")
+    rarg, carg, branch = _dev(rarg, "rarg", torch.int32), _dev(carg, "carg", torch.int32), _dev(branch, "branch", torch.int32)
+    g_remd = _dev(g_remd, "g_remd")
+    B, N, c = x.shape
+    assert y.shape == (B, N, c) and g_remd.shape == (B,)
+    dy = torch.empty_like(y)
+    check(lib().ncahip_ot_remd_bwd_f32(_p(x), _p(y), _p(xn), _p(yn), _p(rarg), _p(carg), _p(branch), _p(g_remd), _p(dy), B, N, c,
+                                       _stream()), "ot_remd_bwd")
+    return dy
