@@ -490,6 +490,29 @@ int ncahip_ot_remd_bwd_f32(const float *x, const float *y, const float *xn, cons
                            const int32_t *carg, const int32_t *branch, const float *g_remd, float *dy, int B, int N, int c,
                            ncahip_stream_t stream);
 
+/* ---- moment-matching part of the OT appearance loss -------------------------------------------------------------------
+ * EncoderConditioning/loss/appearance_loss.py:176-192 for one style layer and a batch, on the x, y [B, N, c] that
+ * ncahip_ot_gather_f32 produces (x the constant target, y the generated image):
+ *     mom[b] = mean_k |mx_k - my_k| + mean_kl |Cx_kl - Cy_kl|,   mx = column means over the N rows,
+ *     Cx = (x - mx)^T (x - mx) / (N - 1) (unbiased, as in the reference), Cy likewise.
+ * The centred copies, the two c x c covariances and their difference exist only in LDS and registers.  All fp32.  Covered: c a
+ * multiple of 4 up to 512, 2 <= N <= 1024 (N = 1 divides by zero in the reference), 1 <= B <= 65535; NCAHIP_ERANGE otherwise.
+ * Null or aliased pointers: NCAHIP_EINVAL before any launch.  Results are bit-reproducible from run to run (no atomics).
+ *
+ * ncahip_ot_moment_fwd_f32: mom [B]; my [B, c] the column means of y (refined by one correction pass, so that the columns of
+ *   y - my sum to zero to rounding); sgn [B, c] = sign(mx - my) as -1 / 0 / +1 floats; S [B, c, c] int8 = sign(Cx - Cy), both
+ *   triangles.  x, y, my, sgn, S and the workspace (ncahip_ot_moment_workspace bytes: mx and the partial sums, combined in a
+ *   fixed order) 16-byte aligned.
+ * ncahip_ot_moment_bwd_f32: dy [B, N, c] += g_mom[b] * d mom[b] / d y (x gets no gradient), in closed form
+ *     dy[b, n, :] += g_mom[b] * (-sgn[b, :] / (c N) - 2 / ((N - 1) c^2) * (y[b, n, :] - my[b, :]) S[b]),   sign(0) = 0;
+ *   it ACCUMULATES into dy (plain read-modify-write, one owner per element): call it after ncahip_ot_remd_bwd_f32 has written the
+ *   same buffer, then scatter once.  y, my, S and dy 16-byte aligned. */
+size_t ncahip_ot_moment_workspace(int B, int N, int c);
+int ncahip_ot_moment_fwd_f32(const float *x, const float *y, float *mom, float *my, float *sgn, int8_t *S, int B, int N, int c,
+                             void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+int ncahip_ot_moment_bwd_f32(const float *y, const float *my, const float *sgn, const int8_t *S, const float *g_mom, float *dy,
+                             int B, int N, int c, ncahip_stream_t stream);
+
 /* The [B,1,H,W] uniforms the kernels draw for (seed, step) when u == NULL (for tests/tools). */
 int ncahip_philox_uniform_f32(float *u, int B, int H, int W, uint64_t seed, uint64_t step,
                               ncahip_stream_t stream);

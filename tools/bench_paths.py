@@ -14,10 +14,10 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
   video           B = 1 inference at 256^2 with the shipped video models' shapes, single- and two-scale
   trainer_default ConditionedNCATrainer at the reference's own defaults (C = 20, 64 x 64, batch 8, nca_steps [48, 96]): ms per iteration
   loss            the default objective (VGG16 features + batched OT + content + overflow) at 32 x 3 x 256^2, fp32 / bf16 features
-  loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched against fused alternating in one process:
-                  32 x 3 x 256^2 with bf16 features (configs[2]'s batch) and 8 x 3 x 64^2 (the reference's training shape)
-  loss_ot_batched / loss_ot_fused   the OT term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a kernel trace
-                  (not part of a run without names)
+  loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched, fused and fused_all alternating in one
+                  process: 32 x 3 x 256^2 with bf16 features (configs[2]'s batch) and 8 x 3 x 64^2 (the reference's training shape)
+  loss_ot_batched / loss_ot_fused / loss_ot_fused_all   the OT term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a
+                  kernel trace (not part of a run without names)
 """
 import json
 import os
@@ -50,6 +50,25 @@ def timed(fns, iters=10, warm=3):
         torch.cuda.synchronize()
         for i in range(len(fns)):
             res[i].append(ev[i].elapsed_time(ev[i + 1]))
+    return [statistics.median(r) for r in res], [min(r) for r in res]
+
+
+def timed_sync(fns, iters=10, warm=3):
+    """As `timed`, but every callable is timed on its own between two device synchronisations, on the host clock: for callables whose
+    host part outlasts their device part (the OT term draws its indices on the host) the events of `timed` would credit a callable
+    with the overlap of its host part and the device tail of the one before it, which depends on the order they run in."""
+    import time
+    for _ in range(warm):
+        for f in fns:
+            f()
+    res = [[] for _ in fns]
+    for _ in range(iters):
+        for i, f in enumerate(fns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            res[i].append((time.perf_counter() - t0) * 1e3)
     return [statistics.median(r) for r in res], [min(r) for r in res]
 
 
@@ -215,8 +234,16 @@ def loss_leg():
              miopen_benchmark=bool(torch.backends.cudnn.benchmark), wall_s_so_far=_time.perf_counter() - _t0)
 
 
+OT_IMPLS = ("batched", "fused", "fused_all")
+
+
+def _ot_fn(impl):
+    from ncahip import loss
+    return {"batched": loss.ot_loss_batched, "fused": loss.ot_loss_fused, "fused_all": loss.ot_loss_fused_all}[impl]
+
+
 def _ot_setup(B, S, dt):
-    """Loss modules of both OT variants on one style image, the objective's input dict, and the style / generated features the OT
+    """Loss modules of the three OT variants on one style image, the objective's input dict, and the style / generated features the OT
     term sees (the generated ones detached: leaves of their own, so the OT term's forward + backward can be timed alone)."""
     import warnings
     import numpy as np
@@ -225,7 +252,7 @@ def _ot_setup(B, S, dt):
     style = (np.random.RandomState(0).rand(S, S, 3) * 255).astype(np.uint8)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        L = {impl: Loss(dev, target_style_image=style, feature_dtype=dt, ot_impl=impl) for impl in ("batched", "fused")}
+        L = {impl: Loss(dev, target_style_image=style, feature_dtype=dt, ot_impl=impl) for impl in OT_IMPLS}
     gen = torch.rand(B, 3, S, S, device=dev, requires_grad=True)
     d = {"generated_images": gen, "nca_state": torch.rand(B, 16, S, S, device=dev) * 3 - 1.5, "target_images": torch.rand(B, 3, S, S, device=dev)}
     with torch.no_grad():
@@ -236,11 +263,11 @@ def _ot_setup(B, S, dt):
 
 
 def loss_ot_leg():
-    """ot_impl batched (the torch path) against fused (csrc/nca_ot.hip), alternating call by call in one process: (a) the whole
+    """ot_impl batched (the torch path) against fused (csrc/nca_ot.hip: relaxed EMD) and fused_all (+ csrc/nca_ot_moment.hip: the
+    moment term too), alternating call by call in one process: (a) the whole
     objective, forward + backward to the generated images, (b) the OT term alone on precomputed features, forward + backward to
-    the features.  Median of 10 after 3 warm-ups each."""
+    the features.  Median of 10 after 3 warm-ups each, host clock between device synchronisations (timed_sync)."""
     import numpy as np
-    from ncahip.loss import ot_loss_batched, ot_loss_fused
     for B, S, dt, name in ((32, 256, torch.bfloat16, "cfg3 batch, bf16 features"), (8, 64, torch.float32, "reference training shape, fp32 features")):
         L, d, gen, tf, gfl = _ot_setup(B, S, dt)
 
@@ -257,15 +284,14 @@ def loss_ot_leg():
                 fn(tf, gfl).backward()
             return f
         np.random.seed(0)
-        (wb, wf), (wbm, wfm) = timed([whole("batched"), whole("fused")], iters=10)
-        (tb, tfu), (tbm, tfm) = timed([term(ot_loss_batched), term(ot_loss_fused)], iters=10)
-        np.random.seed(1)
-        vb = float(ot_loss_batched(tf, gfl))
-        np.random.seed(1)
-        vf = float(ot_loss_fused(tf, gfl))
-        emit(path="loss_ot", shape=f"{B}x3x{S}x{S}", what=name, objective_ms_batched=wb, objective_ms_fused=wf, objective_min_ms_batched=wbm,
-             objective_min_ms_fused=wfm, ot_term_ms_batched=tb, ot_term_ms_fused=tfu, ot_term_min_ms_batched=tbm, ot_term_min_ms_fused=tfm,
-             ot_value_batched=vb, ot_value_fused=vf, layers=[list(t.shape[1:]) for t in tf])
+        w, wm = timed_sync([whole(impl) for impl in OT_IMPLS], iters=10)
+        t, tm = timed_sync([term(_ot_fn(impl)) for impl in OT_IMPLS], iters=10)
+        res = {}
+        for k, impl in enumerate(OT_IMPLS):
+            np.random.seed(1)
+            res.update({f"objective_ms_{impl}": w[k], f"objective_min_ms_{impl}": wm[k], f"ot_term_ms_{impl}": t[k],
+                        f"ot_term_min_ms_{impl}": tm[k], f"ot_value_{impl}": float(_ot_fn(impl)(tf, gfl))})
+        emit(path="loss_ot", shape=f"{B}x3x{S}x{S}", what=name, layers=[list(t.shape[1:]) for t in tf], **res)
         del L, d, gen, tf, gfl
         torch.cuda.empty_cache()
 
@@ -274,9 +300,8 @@ def loss_ot_trace_leg(impl, calls=5):
     """The OT term alone at 32 x 3 x 256^2, forward + backward, `calls` times with one variant and nothing else on the device after
     the features exist: run under a kernel trace, the per-call launch count is (kernel calls after set-up) / calls."""
     import numpy as np
-    from ncahip.loss import ot_loss_batched, ot_loss_fused
     _, _, _, tf, gfl = _ot_setup(32, 256, torch.bfloat16)
-    fn = ot_loss_fused if impl == "fused" else ot_loss_batched
+    fn = _ot_fn(impl)
     np.random.seed(0)
     torch.cuda.synchronize()
     emit(path="loss_ot_trace", impl=impl, calls=calls, marker="setup done")
@@ -413,7 +438,7 @@ def main(names):
         loss_leg()
     if allp or "loss_ot" in names:
         loss_ot_leg()
-    for impl in ("batched", "fused"):
+    for impl in OT_IMPLS:
         if "loss_ot_" + impl in names:
             loss_ot_trace_leg(impl)
     if allp or "video" in names:

@@ -844,6 +844,50 @@ int ncahip_ot_remd_bwd_f32(const float* x, const float* y, const float* xn, cons
     return hip_result(nca_launch_ot_remd_bwd(x, y, xn, yn, rarg, carg, branch, g_remd, dy, B, N, c, (hipStream_t)stream), "ot_remd_bwd");
 }
 
+// ---- moment-matching part of the OT appearance loss (nca_ot_moment.hip) ------------------------------------------------
+namespace {
+int check_ot_moment(const char* what, int B, int N, int c) {
+    if (int rc = check_ot(what, B, N, c)) return rc;
+    if (N < 2) return fail(NCAHIP_ERANGE, "%s: N=%d outside [2, %d] (the unbiased covariance divides by N - 1)", what, N, kOtMaxN);
+    return 0;
+}
+}  // namespace
+
+size_t ncahip_ot_moment_workspace(int B, int N, int c) {
+    if (B <= 0 || B > kOtMaxB || N < 2 || N > kOtMaxN || c <= 0 || (c & 3) != 0 || c > kOtMaxC) return 0;
+    const int nt = nca_ot_moment_tiles(c);
+    return (size_t)B * (c + nt + nt * (nt + 1) / 2) * sizeof(float);
+}
+
+int ncahip_ot_moment_fwd_f32(const float* x, const float* y, float* mom, float* my, float* sgn, int8_t* S, int B, int N, int c,
+                             void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!x || !y || !mom || !my || !sgn || !S || !workspace) return fail(NCAHIP_EINVAL, "ot_moment_fwd: null pointer");
+    if (int rc = check_ot_moment("ot_moment_fwd", B, N, c)) return rc;
+    const void* const in[2] = {x, y};
+    const void* const out[5] = {mom, my, sgn, S, workspace};
+    for (int a = 0; a < 5; ++a) {
+        for (int k = 0; k < 2; ++k)
+            if (out[a] == in[k]) return fail(NCAHIP_EINVAL, "ot_moment_fwd: outputs must not alias the inputs");
+        for (int k = a + 1; k < 5; ++k)
+            if (out[a] == out[k]) return fail(NCAHIP_EINVAL, "ot_moment_fwd: outputs must not alias each other");
+    }
+    if (!ot_aligned(x) || !ot_aligned(y) || !ot_aligned(my) || !ot_aligned(sgn) || !ot_aligned(S) || !ot_aligned(workspace))
+        return fail(NCAHIP_ERANGE, "ot_moment_fwd: x, y, my, sgn, S and workspace must be 16-byte aligned");
+    if (workspace_bytes < ncahip_ot_moment_workspace(B, N, c)) return fail(NCAHIP_EINVAL, "ot_moment_fwd: workspace too small");
+    return hip_result(nca_launch_ot_moment_fwd(x, y, mom, my, sgn, (signed char*)S, B, N, c, workspace, (hipStream_t)stream), "ot_moment_fwd");
+}
+
+int ncahip_ot_moment_bwd_f32(const float* y, const float* my, const float* sgn, const int8_t* S, const float* g_mom, float* dy, int B, int N,
+                             int c, ncahip_stream_t stream) {
+    if (!y || !my || !sgn || !S || !g_mom || !dy) return fail(NCAHIP_EINVAL, "ot_moment_bwd: null pointer");
+    if (int rc = check_ot_moment("ot_moment_bwd", B, N, c)) return rc;
+    if ((const float*)dy == y || (const float*)dy == my || (const float*)dy == sgn || (const void*)dy == (const void*)S || (const float*)dy == g_mom)
+        return fail(NCAHIP_EINVAL, "ot_moment_bwd: dy must not alias an input");
+    if (!ot_aligned(y) || !ot_aligned(my) || !ot_aligned(S) || !ot_aligned(dy))
+        return fail(NCAHIP_ERANGE, "ot_moment_bwd: y, my, S and dy must be 16-byte aligned");
+    return hip_result(nca_launch_ot_moment_bwd(y, my, sgn, (const signed char*)S, g_mom, dy, B, N, c, (hipStream_t)stream), "ot_moment_bwd");
+}
+
 size_t ncahip_cond_grow_bwd_workspace(int B, int C, int H, int W, int hidden) {
     if (!dims_ok(B, C, H, W) || hidden <= 0) return 0;
     const size_t n = (size_t)B * C * H * W * sizeof(float);

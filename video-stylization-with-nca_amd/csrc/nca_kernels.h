@@ -199,6 +199,12 @@ hipError_t nca_launch_ot_remd_fwd(const float* x, const float* y, const float* x
                                   int* carg, float* remd, int* branch, int B, int N, int c, void* ws, hipStream_t st);
 hipError_t nca_launch_ot_remd_bwd(const float* x, const float* y, const float* xn, const float* yn, const int* rarg, const int* carg,
                                   const int* branch, const float* gup, float* dy, int B, int N, int c, hipStream_t st);
+// nca_ot_moment.hip: moment-matching part of the OT appearance loss (means, covariance difference reduced to signs + partial sums, adjoint)
+int nca_ot_moment_tiles(int c);   // 64-channel tiles; the covariance kernel writes one partial per pair ti <= tj
+hipError_t nca_launch_ot_moment_fwd(const float* x, const float* y, float* mom, float* my, float* sgn, signed char* S, int B, int N, int c,
+                                    void* ws, hipStream_t st);
+hipError_t nca_launch_ot_moment_bwd(const float* y, const float* my, const float* sgn, const signed char* S, const float* gup, float* dy, int B,
+                                    int N, int c, hipStream_t st);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);

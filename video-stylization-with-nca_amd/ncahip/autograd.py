@@ -221,3 +221,26 @@ class OTRelaxedEMD(torch.autograd.Function):
     def backward(ctx, g_remd):
         x, y, xn, yn, rarg, carg, branch = ctx.saved_tensors
         return None, ops.ot_remd_backward(x, y, xn, yn, rarg, carg, branch, g_remd.float().contiguous()), None, None
+
+
+class OTLayerLoss(torch.autograd.Function):
+    """(t [1,c,h,w], g [B,c,h,w], idx [B,N] int32 or None) -> relaxed EMD + moment term per sample [B], every step on the library's
+    kernels: ops.ot_gather, ops.ot_remd, ops.ot_moment forwards; backwards ops.ot_remd_backward writes dY, ops.ot_moment_backward adds
+    its part to the same buffer, and one ops.ot_gather_backward scatters the sum.  Gradient to g only."""
+
+    @staticmethod
+    def forward(ctx, t, g, idx):
+        x, y, xn, yn = ops.ot_gather(t, g, idx)
+        r = ops.ot_remd(x, y, xn, yn)
+        m = ops.ot_moment(x, y)
+        ctx.idx, ctx.hw = idx, (g.shape[2], g.shape[3])
+        ctx.save_for_backward(x, y, xn, yn, r["rarg"], r["carg"], r["branch"], m["my"], m["sgn"], m["S"])
+        return r["remd"] + m["mom"]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, y, xn, yn, rarg, carg, branch, my, sgn, S = ctx.saved_tensors
+        gl = g_loss.float().contiguous()
+        dy = ops.ot_remd_backward(x, y, xn, yn, rarg, carg, branch, gl)
+        ops.ot_moment_backward(y, my, sgn, S, gl, dy)
+        return None, ops.ot_gather_backward(dy, ctx.idx, *ctx.hw), None

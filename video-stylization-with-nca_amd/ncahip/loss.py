@@ -214,13 +214,43 @@ def ot_loss_fused(target_feats, gen_feats, n_samples=1000):
     return total / B
 
 
+def ot_loss_fused_all(target_feats, gen_feats, n_samples=1000):
+    """ot_loss_fused with the moment term on this library's kernels as well (csrc/nca_ot_moment.hip): the same index draws from
+    numpy's global stream in the same order (sample-major, layer-minor); per layer the gather, the relaxed EMD and the moment term
+    (means, both covariances and their difference, reduced in registers to mean |Cx - Cy| and its signs) run on library kernels,
+    forwards and backwards, with one dY buffer and one scatter for both terms -- no torch matrix product anywhere.  CUDA float32
+    features only (no CPU fallback); c a multiple of 4 up to 512, 2 <= N <= 1024.
+
+    The zero-vector behaviour documented for ot_loss_fused carries over unchanged (it belongs to the relaxed EMD); the moment term
+    has no singularity.  Every finite case agrees with the torch path up to summation order."""
+    from .autograd import OTLayerLoss
+    B = gen_feats[0].shape[0]
+    idx = [[None] * len(gen_feats) for _ in range(B)]
+    for b in range(B):                                     # the reference's draw order: sample-major, layer-minor
+        for li, t in enumerate(target_feats):
+            h, w = t.shape[2], t.shape[3]
+            if h > 32:
+                idx[b][li] = np.sort(np.random.choice(np.arange(h * w), size=n_samples, replace=False))
+    per_layer = []
+    for li, (t, g) in enumerate(zip(target_feats, gen_feats)):
+        ix = None
+        if idx[0][li] is not None:
+            ix = torch.as_tensor(np.stack([idx[b][li] for b in range(B)]).astype(np.int32)).to(g.device)    # [B, N]
+        per_layer.append(OTLayerLoss.apply(t, g, ix))                                                # [B]
+    return torch.stack(per_layer).sum() / B
+
+
+_OT_IMPLS = {"batched": ot_loss_batched, "fused": ot_loss_fused, "fused_all": ot_loss_fused_all}
+
+
 class Loss(nn.Module):
     def __init__(self, device, content_loss_weight=1.0, overflow_loss_weight=1.0, appearance_loss_weight=1.0,
                  appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False, ot_impl="batched"):
         super().__init__()
-        if ot_impl not in ("batched", "fused"):
-            raise ValueError(f"ncahip.loss: unknown ot_impl={ot_impl!r} ('batched' or 'fused')")
-        self.ot_impl = ot_impl          # 'fused': the relaxed-EMD part of the OT term on this library's kernels (ot_loss_fused)
+        if ot_impl not in _OT_IMPLS:
+            raise ValueError(f"ncahip.loss: unknown ot_impl={ot_impl!r} ('batched', 'fused' or 'fused_all')")
+        self.ot_impl = ot_impl          # 'fused': the relaxed-EMD part of the OT term on this library's kernels (ot_loss_fused);
+                                        # 'fused_all': the moment term too (ot_loss_fused_all)
         self.device = device
         self.appearance_loss_type = appearance_loss_type
         self.appearance_loss_weight = appearance_loss_weight
@@ -266,8 +296,7 @@ class Loss(nn.Module):
             if "appearance" in self.loss_weights:
                 acc = 0
                 if self.appearance_loss_type == "OT":    # appearance_loss.py:212-220: mean over the batch
-                    ot = ot_loss_fused if self.ot_impl == "fused" else ot_loss_batched
-                    acc = ot([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
+                    acc = _OT_IMPLS[self.ot_impl]([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
                 elif self.appearance_loss_type == "Gram":   # :98-106
                     for l in STYLE_LAYERS:
                         acc = acc + (_gram(self.style_feats[l]) - _gram(gf[l])).square().mean()

@@ -568,3 +568,36 @@ def ot_remd_backward(x: torch.Tensor, y: torch.Tensor, xn: torch.Tensor, yn: tor
     check(lib().ncahip_ot_remd_bwd_f32(_p(x), _p(y), _p(xn), _p(yn), _p(rarg), _p(carg), _p(branch), _p(g_remd), _p(dy), B, N, c,
                                        _stream()), "ot_remd_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- moment-matching part of the OT appearance loss (csrc/nca_ot_moment.hip)
+def ot_moment(x: torch.Tensor, y: torch.Tensor):
+    """mean |mx - my| + mean |Cx - Cy| per sample (unbiased covariances) of x, y [B,N,c] as ot_gather returns them
+    (ncahip_ot_moment_fwd_f32): returns dict mom [B], and what the backward reads: my [B,c] the column means of y, sgn [B,c] =
+    sign(mx - my), S [B,c,c] int8 = sign(Cx - Cy)."""
+    x, y = _dev(x, "x"), _dev(y, "y")
+    B, N, c = x.shape
+    assert y.shape == (B, N, c)
+    dev, f32 = x.device, torch.float32
+    out = {"mom": torch.empty(B, device=dev, dtype=f32), "my": torch.empty(B, c, device=dev, dtype=f32),
+           "sgn": torch.empty(B, c, device=dev, dtype=f32), "S": torch.empty(B, c, c, device=dev, dtype=torch.int8)}
+    nbytes = lib().ncahip_ot_moment_workspace(B, N, c)
+    ws = _workspace(nbytes, dev)
+    check(lib().ncahip_ot_moment_fwd_f32(_p(x), _p(y), _p(out["mom"]), _p(out["my"]), _p(out["sgn"]), _p(out["S"]), B, N, c, _p(ws), nbytes,
+                                         _stream()), "ot_moment_fwd")
+    return out
+
+
+def ot_moment_backward(y: torch.Tensor, my: torch.Tensor, sgn: torch.Tensor, S: torch.Tensor, g_mom: torch.Tensor,
+                       dy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dL/dy [B,N,c] of ot_moment given dL/dmom [B] (ncahip_ot_moment_bwd_f32), ADDED to `dy` in place when one is given (the buffer
+    ot_remd_backward has just written) and to zeros otherwise; x is the constant target and gets no gradient."""
+    y, my, sgn, S, g_mom = _dev(y, "y"), _dev(my, "my"), _dev(sgn, "sgn"), _dev(S, "S", torch.int8), _dev(g_mom, "g_mom")
+    B, N, c = y.shape
+    assert my.shape == (B, c) and sgn.shape == (B, c) and S.shape == (B, c, c) and g_mom.shape == (B,)
+    if dy is None:
+        dy = torch.zeros_like(y)
+    else:
+        assert dy.shape == y.shape and dy.is_contiguous() and _dev(dy, "dy") is dy
+    check(lib().ncahip_ot_moment_bwd_f32(_p(y), _p(my), _p(sgn), _p(S), _p(g_mom), _p(dy), B, N, c, _stream()), "ot_moment_bwd")
+    return dy
