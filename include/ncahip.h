@@ -150,7 +150,9 @@ int ncahip_dynca_nsteps_fwd_f32(float *states, int ring, int T, const float *con
  *     y = ( perc(x) + up2( perc( down2(x) ) ) ) / 2,   down2 / up2 = F.interpolate(bilinear, align_corners=False) by 2.
  * Per step: one coarse pass (2x2 mean + fixed filters with F.pad(mode) on the coarse grid -> pc_scratch [B,4C,H/2,W/2]) and
  * the fused step kernel, which up-samples the coarse tile from LDS on the fly.  H and W even, C <= 16, fc <= 128
- * (NCAHIP_ERANGE otherwise: the Python layer then composes stencil + torch resampling).                                   */
+ * (NCAHIP_ERANGE otherwise: the Python layer then composes stencil + torch resampling).  NCAHIP_PAD_REFLECT needs a coarse
+ * grid of at least 2 x 2, i.e. H, W >= 4 (NCAHIP_EINVAL otherwise, from all four two-scale entry points: F.pad(mode="reflect")
+ * with pad 1 raises on a 1-wide axis, so the reference rejects such an input).                                            */
 int ncahip_dynca_step_fwd_ms_f32(const float *x_in, float *x_out, const float *cond, const float *u,
                                  const float *w1, const float *b1, const float *w2, const float *b2,
                                  int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
@@ -225,7 +227,8 @@ int ncahip_dynca_nsteps_bwd_bf16(const uint16_t *states, int T, const float *con
 /* The same backward through the TWO-SCALE steps of ncahip_dynca_nsteps_fwd_ms_f32 (training with perception_scales = [0, 1]:
  * ExtraChannels/fit_video_motion.py:129-130 defaults to it).  dL/dy splits evenly over the two levels: the fine level goes
  * through the stencil adjoint as before; the coarse level through the adjoint of the bilinear x2 up-sampling, the stencil
- * adjoint on the COARSE grid (pad mode resolved there) and the adjoint of the 2x2 mean.  Even H and W, C <= 16, fc <= 128.     */
+ * adjoint on the COARSE grid (pad mode resolved there) and the adjoint of the 2x2 mean.  Even H and W, C <= 16, fc <= 128;
+ * NCAHIP_PAD_REFLECT needs H, W >= 4 (NCAHIP_EINVAL otherwise, as in the forward).                                         */
 size_t ncahip_dynca_nsteps_bwd_ms_workspace(int B, int C, int H, int W, int fc, int c_cond);
 int ncahip_dynca_nsteps_bwd_ms_f32(const float *states, int T, const float *cond, const float *u,
                                    const float *w1, const float *b1, const float *w2, const float *b2,
@@ -410,7 +413,7 @@ int ncahip_dynca_nsteps_fwd_persist_f32(const float *x_in, float *x_out, int T, 
                                         void *workspace, size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream);
 /* The same for perception_scales = [0, 1] (every shipped video model; dynca.py:75-115): bit for bit what
  * ncahip_dynca_nsteps_fwd_ms_f32 computes.  Tiles additionally exchange the 2 x 2 means of their coarse cells within 2 of the
- * border; same workspace, epoch and coverage rules. */
+ * border; same workspace, epoch and coverage rules (NCAHIP_PAD_REFLECT with H < 4 or W < 4: NCAHIP_EINVAL, as there). */
 int ncahip_dynca_nsteps_fwd_persist_ms_f32(const float *x_in, float *x_out, int T, const float *cond, const float *u,
                                            const float *w1, const float *b1, const float *w2, const float *b2,
                                            int B, int C, int H, int W, int fc, int c_cond, int pad_mode,

@@ -123,3 +123,33 @@ def test_hot_path_refuses_cpu_tensors():
     from ncahip import ops, _capi
     with pytest.raises(_capi.NcaHipError):
         ops.dynca_perceive(torch.zeros(1, 4, 8, 8))
+
+
+@pytest.mark.parametrize("H,W", [(2, 8), (8, 2)])
+def test_two_scale_reflect_needs_a_2x2_coarse_grid(H, W):
+    """reflect padding with a 2-cell side: the coarse grid is 1 wide, where F.pad(mode='reflect') raises in the reference; the four
+    two-scale entry points refuse it with EINVAL before any launch, and accept the other pad modes' arguments up to that point"""
+    from ncahip import _capi
+    L = _capi.lib()
+    one, two, ws = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x2000), ctypes.c_void_p(0x4000)
+    REFLECT = _capi.PAD_MODES["reflect"]
+    calls = {
+        "step_fwd_ms": lambda pad: L.ncahip_dynca_step_fwd_ms_f32(one, two, None, None, one, one, one, one, 1, 12, H, W, 96, 0, pad, 0.5,
+                                                                  0, 0, one, None),
+        "nsteps_fwd_ms": lambda pad: L.ncahip_dynca_nsteps_fwd_ms_f32(one, 2, 1, None, None, one, one, one, one, 1, 12, H, W, 96, 0, pad,
+                                                                      0.5, 0, 0, one, None),
+        "nsteps_bwd_ms": lambda pad: L.ncahip_dynca_nsteps_bwd_ms_f32(one, 1, None, None, one, one, one, one, 1, 12, H, W, 96, 0, pad, 0.5,
+                                                                      0, 0, one, None, two, one, one, one, one, ws, 0, None),
+        "persist_ms": lambda pad: L.ncahip_dynca_nsteps_fwd_persist_ms_f32(one, two, 1, None, None, one, one, one, one, 1, 12, H, W, 96, 0,
+                                                                           pad, 0.5, 0, 0, ws, 1 << 20, 1, None),
+    }
+    for name in calls:
+        assert calls[name](REFLECT) == _capi.EINVAL, name
+        assert b"coarse grid" in L.ncahip_last_error(), (name, L.ncahip_last_error())
+    # the same arguments with replicate pass that check: the backward stops at its (empty) workspace, the persistent kernel at its
+    # shape coverage -- neither launches
+    assert calls["nsteps_bwd_ms"](_capi.PAD_MODES["replicate"]) == _capi.EINVAL and b"workspace" in L.ncahip_last_error()
+    assert calls["persist_ms"](_capi.PAD_MODES["replicate"]) == _capi.ERANGE
+    from ncahip import ops
+    assert not ops.two_scale_fused_ok(12, H, W, 96, "reflect") and ops.two_scale_fused_ok(12, H, W, 96, "replicate")
+    assert ops.two_scale_fused_ok(12, 4, 4, 96, "reflect")

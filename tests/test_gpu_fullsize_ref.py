@@ -440,18 +440,20 @@ def test_cond_plane_1024x4096_philox_vs_float64(ops):
 
 # ================================================================================================ DyNCA
 def _dynca_case(ops, case, prm, x0, cond, us, cot, pad, control=False, scales_two=False):
-    """free-running forward (every state, both kernel families) and dynca_nsteps_backward against float64 autograd"""
+    """free-running forward (every state, both kernel families) and dynca_nsteps_backward against float64 autograd; scales_two:
+    perception_scales = [0, 1] (the two-scale kernels against the oracle with scales=(0, 1))"""
+    sc = (0, 1) if scales_two else (0,)
     Tn = us.shape[0]
     p64 = _f64(prm)
     c64 = cond.double()
     w = _dyn_w(ops, prm, x0)
     with torch.no_grad():
-        refs = O.dynca_nsteps(x0.double(), c64, list(us), p64, pad, 0.5, collect=True)[1]
+        refs = O.dynca_nsteps(x0.double(), c64, list(us), p64, pad, 0.5, scales=sc, collect=True)[1]
     worst = 0.0
     for variant in (0, 1):
         ops.force_generic(variant)
         try:
-            out, states = ops.dynca_nsteps(x0, Tn, cond, us, w, pad, 0.5, keep_history=True)
+            out, states = ops.dynca_nsteps(x0, Tn, cond, us, w, pad, 0.5, keep_history=True, two_scale=scales_two)
             for t in range(Tn):
                 worst = max(worst, _rel(states[t + 1], refs[t]))
             if variant == 0:
@@ -461,34 +463,34 @@ def _dynca_case(ops, case, prm, x0, cond, us, cot, pad, control=False, scales_tw
             del out
         finally:
             ops.force_generic(0)
-    gr = ops.dynca_nsteps_backward(hist, cond, us, w, cot, None, Tn, pad, 0.5)
+    gr = ops.dynca_nsteps_backward(hist, cond, us, w, cot, None, Tn, pad, 0.5, two_scale=scales_two)
     ops.check_errors()
     _say(case + " fwd", err=worst, bound=REL_TOL)
     assert worst < REL_TOL, worst
     if control:
         key = "w2.weight"
         with torch.no_grad():
-            x1 = O.dynca_step(x0.double(), c64, us[0], p64, pad, 0.5, return_all=True)
+            x1 = O.dynca_step(x0.double(), c64, us[0], p64, pad, 0.5, sc, return_all=True)
             h = F.relu(O._conv1x1(x1["y"], p64["w1.weight"], p64["w1.bias"]))
             idx = _lever_entry(p64[key], h)
             del x1, h
-            bad = O.dynca_nsteps(x0.double(), c64, list(us), _f64(_perturbed(prm, key, idx)), pad, 0.5)
+            bad = O.dynca_nsteps(x0.double(), c64, list(us), _f64(_perturbed(prm, key, idx)), pad, 0.5, scales=sc)
         e = _rel(last, bad)
         _say(case + " fwd negative control", entry=f"{key}[{idx}]", err=e, bound=REL_TOL)
         assert e > REL_TOL, e
         del bad
     del refs
-    _, gx, gw = O.dynca_nsteps_loss_grads(x0.double(), c64, list(us), p64, pad, 0.5, cot.double())
-    region, cnt = O.dynca_gate_influence(x0.double(), c64, list(us), p64, pad, DYNCA_GATE_K)
+    _, gx, gw = O.dynca_nsteps_loss_grads(x0.double(), c64, list(us), p64, pad, 0.5, cot.double(), scales=sc)
+    region, cnt = O.dynca_gate_influence(x0.double(), c64, list(us), p64, pad, DYNCA_GATE_K, scales=sc)
     ok, nout, nin = grads_match_outside(gr["x0"], gx, region.cpu(), GTOL)
     ex = _err_outside(gr["x0"], gx, region)
     full = {k: (_rmax(gr[k], gw[n]), _rel2(gr[k], gw[n])) for k, n in DYNCA_NAMES.items()}
     del gx, gw, gr
     cq, quiet = _quiet_cot(cot, region, Tn, pad == "circular")
-    gq = ops.dynca_nsteps_backward(hist, cond, us, w, cq, None, Tn, pad, 0.5)
+    gq = ops.dynca_nsteps_backward(hist, cond, us, w, cq, None, Tn, pad, 0.5, two_scale=scales_two)
     ops.check_errors()
     del hist
-    eq = _dynca_grad_errs(gq, O.dynca_nsteps_loss_grads(x0.double(), c64, list(us), p64, pad, 0.5, cq.double()))
+    eq = _dynca_grad_errs(gq, O.dynca_nsteps_loss_grads(x0.double(), c64, list(us), p64, pad, 0.5, cq.double(), scales=sc))
     _say(case + " bwd", x0_outside_region=ex, bound=GTOL, gates_excluded=int(cnt.sum()), cells_excluded=int(region.sum()),
          x0_misses_inside=nin, full_cot_weights_max=max(v[0] for v in full.values()),
          full_cot_weights_l2=max(v[1] for v in full.values()), quiet_cot_cells_zeroed=int((~quiet).sum()),
@@ -500,7 +502,7 @@ def _dynca_case(ops, case, prm, x0, cond, us, cot, pad, control=False, scales_tw
         assert el2 < 1e-3 and emax < 1e-2, (k, emax, el2)
     if control:
         worst, which = _control(lambda q: _dynca_grad_errs(gq, O.dynca_nsteps_loss_grads(x0.double(), c64, list(us), _f64(q), pad, 0.5,
-                                                                                         cq.double())),
+                                                                                         cq.double(), scales=sc)),
                                 prm, list(DYNCA_NAMES.values()))
         _say(case + " bwd negative control", entry=which, err=worst, bound=GTOL)
         assert worst > GTOL, worst

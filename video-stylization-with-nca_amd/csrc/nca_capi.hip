@@ -61,6 +61,14 @@ int check_dynca(const void* x_in, const void* x_out, const void* cond, const voi
     return 0;
 }
 
+// two-scale perception: the fixed filters also run on the H/2 x W/2 grid with the pad mode resolved there, and F.pad(mode="reflect")
+// needs the pad (1) to be smaller than the dimension (the reference raises on a 1-wide coarse grid; nca_pad_index would clamp)
+int check_ms_reflect(int H, int W, int pad_mode) {
+    if (pad_mode == NCAHIP_PAD_REFLECT && (H < 4 || W < 4))
+        return fail(NCAHIP_EINVAL, "dynca two-scale step: reflect pad needs a coarse grid of at least 2 x 2 (H, W >= 4); H=%d W=%d gives %d x %d", H, W, H / 2, W / 2);
+    return 0;
+}
+
 int check_cond(const void* x_in, const void* x_out, const void* pre_out, const void* goal, const void* wp,
                const void* w1, const void* b1, const void* w2, const void* b2, const void* w3, int B, int C, int H,
                int W, int hidden, int goal_ch, int alive_ch, int max_c = kMaxC) {
@@ -248,6 +256,9 @@ static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, i
     if (T < 1 || !workspace) return fail(NCAHIP_EINVAL, "dynca nsteps persist: T >= 1 and a workspace required");
     if (epoch < 1 || epoch >= (1u << 20)) return fail(NCAHIP_EINVAL, "dynca nsteps persist: epoch must be in [1, 2^20) (zero the workspace and restart at 1 when it runs out)");
     if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;   // (refuses x_in == x_out)
+    if (two_scale) {
+        if (int rc = check_ms_reflect(H, W, pad_mode)) return rc;
+    }
     const size_t need = ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, c_cond);
     if (need == 0 || T >= 4096)
         return fail(NCAHIP_ERANGE, "dynca nsteps persist: shape not covered (C <= 16, fc <= 128, H %% 16 == 0, W %% 16 == 0, T < 4096); use ncahip_dynca_nsteps_fwd_f32");
@@ -345,8 +356,9 @@ int ncahip_edge_extractor_f32(const float* img, const float* k3, float* out, int
 }
 
 // ---- two-scale perception (perception_scales = [0, 1]): coarse pass + fused step with on-the-fly bilinear up-sampling --------
-static int check_ms(int C, int H, int W, int fc, const void* pc) {
+static int check_ms(int C, int H, int W, int fc, int pad_mode, const void* pc) {
     if (!pc) return fail(NCAHIP_EINVAL, "dynca two-scale step: pc_scratch required");
+    if (int rc = check_ms_reflect(H, W, pad_mode)) return rc;
     if ((H | W) & 1) return fail(NCAHIP_ERANGE, "dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)");
     if (C > kMaxC || fc > kMaxFc) return fail(NCAHIP_ERANGE, "dynca two-scale step: C=%d fc=%d exceeds (%d,%d)", C, fc, kMaxC, kMaxFc);
     return 0;
@@ -357,7 +369,7 @@ int ncahip_dynca_step_fwd_ms_f32(const float* x_in, float* x_out, const float* c
                                  int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step, float* pc_scratch,
                                  ncahip_stream_t stream) {
     if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (int rc = check_ms(C, H, W, fc, pc_scratch)) return rc;
+    if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = hip_result(nca_launch_dynca_coarse_perceive(x_in, pc_scratch, B, C, H, W, pad_mode, st), "dynca coarse perceive")) return rc;
     if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
@@ -373,7 +385,7 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* 
                                    ncahip_stream_t stream) {
     if (ring < 2 || T < 0) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
     if (int rc = check_dynca(states, states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (int rc = check_ms(C, H, W, fc, pc_scratch)) return rc;
+    if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
@@ -652,7 +664,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     if ((size_t)(128 > 4 * C ? 128 : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
     if (two_scale) {
-        if (int rc = check_ms(C, H, W, fc, workspace)) return rc;
+        if (int rc = check_ms(C, H, W, fc, pad_mode, workspace)) return rc;
     }
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;

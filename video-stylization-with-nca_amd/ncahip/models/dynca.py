@@ -124,9 +124,10 @@ class DyNCA(nn.Module):
 
     def _two_scale_fused(self, x) -> bool:
         """perception_scales == [0, 1] (every shipped video model; the default of fit_video_motion.py) on the fused two-scale
-        kernels, forward and backward: even sizes, C <= 16, fc <= 128, fp32 states."""
+        kernels, forward and backward: even sizes, C <= 16, fc <= 128, fp32 states; 'reflect' from H, W >= 4 (a 1-wide coarse grid
+        takes the composed path, whose coarse perception refuses it as F.pad does)."""
         return (list(self.perception_scales) == [0, 1] and x.dtype == torch.float32
-                and ops.two_scale_fused_ok(self.c_in, x.shape[2], x.shape[3], self.w1.out_channels))
+                and ops.two_scale_fused_ok(self.c_in, x.shape[2], x.shape[3], self.w1.out_channels, self.padding_mode))
 
     def _composed(self, x) -> bool:
         """True when the step runs as HIP stencil + device resampling + library GEMMs instead of the fused kernels:

@@ -249,8 +249,11 @@ persistent_steps = True     # dynca_nsteps: use the one-launch persistent kernel
 persistent_cond = False
 
 
-def two_scale_fused_ok(C: int, H: int, W: int, fc: int) -> bool:
-    """Shapes ncahip_dynca_*_fwd_ms_f32 covers (perception_scales = [0, 1] fused): even sizes, C <= 16, fc <= 128."""
+def two_scale_fused_ok(C: int, H: int, W: int, fc: int, pad_mode: str = "replicate") -> bool:
+    """Shapes ncahip_dynca_*_fwd_ms_f32 covers (perception_scales = [0, 1] fused): even sizes, C <= 16, fc <= 128; 'reflect' only
+    with a coarse grid of at least 2 x 2 (H, W >= 4: below that F.pad(mode="reflect") raises on the coarse level)."""
+    if pad_mode == "reflect" and (H < 4 or W < 4):
+        return False
     return H % 2 == 0 and W % 2 == 0 and C <= 16 and fc <= 128
 
 
