@@ -516,6 +516,41 @@ int ncahip_ot_moment_fwd_f32(const float *x, const float *y, float *mom, float *
 int ncahip_ot_moment_bwd_f32(const float *y, const float *my, const float *sgn, const int8_t *S, const float *g_mom, float *dy,
                              int B, int N, int c, ncahip_stream_t stream);
 
+/* ---- sliced-Wasserstein style loss ------------------------------------------------------------------------------------
+ * EncoderConditioning/loss/appearance_loss.py:109-140 for one level and a batch: source [B, c, n] and target [1, c, m] the
+ * flattened feature maps, proj [c, 32] the unit directions (drawn by the caller),
+ *     k[b, p, i] = sum_c source[b, c, i] proj[c, p],   s = k sorted ascending along i,   t = the target's keys [32, m] likewise,
+ *     loss = sum_{b, p, i} (s[b, p, i] - t[p, jmap[i]])^2          (a sum, not a mean),
+ * jmap [n] int32 the index map of F.interpolate(mode = "nearest") from m to n positions (the caller builds it; the kernels clamp it
+ * into [0, m)).  The stages are separate entry points.  All fp32.  Covered: c = 3 or a multiple of 4 up to 512, 1 <= n, m <= 65536,
+ * 1 <= B <= 1024, at most 65535 rows per sort call; NCAHIP_ERANGE otherwise, with the offending value in the message.  Null or
+ * aliased pointers and a short workspace: NCAHIP_EINVAL before any launch.  No atomics: results are bit-reproducible from run to
+ * run.  Non-finite inputs are outside the contract (a NaN key has no place in the order, a +inf key ties with the padding).
+ *
+ * ncahip_slw_workspace: bytes the loss forward and the backward need for (B, c, n, m) (host arithmetic: the larger of the
+ *   forward's partial sums, one per row and 4096 positions plus one per sample, and the backward's [B, 32, n] floats); 0 for a
+ *   shape outside the coverage.
+ * ncahip_slw_project_f32: ks [B, 32, n] and kt [32, m], source and target in one launch, exact fp32 products (fp32 MFMA for c a
+ *   multiple of 4, plain fma for c = 3).  source, target and proj 16-byte aligned.
+ * ncahip_slw_sort_f32: every row of keys [rows, n] sorted ascending IN PLACE, perm [rows, n] = the original position of each
+ *   sorted element.  Pairs are ordered by (key, original position), lowest position first on equal keys -- the order of a stable
+ *   sort; -0.0 and +0.0 are equal keys.  Any n in range, a power of two or not.
+ * ncahip_slw_loss_fwd_f32: loss [1] from sorted s [B, 32, n], sorted t [32, m] and jmap; partial sums per row in a fixed tree,
+ *   combined in index order.
+ * ncahip_slw_bwd_f32: dsource [B, c, n] = g_loss[0] * d loss / d source (target and proj get no gradient), in closed form:
+ *     dk[b, p, perm[b, p, i]] = 2 g_loss[0] (s[b, p, i] - t[p, jmap[i]]),   dsource[b, c, i] = sum_p proj[c, p] dk[b, p, i];
+ *   the residual is recomputed from s and t (nothing is kept by the forward), dk lives in the workspace.  perm must be a permutation
+ *   of [0, n) per row (what ncahip_slw_sort_f32 wrote); entries outside [0, n) are skipped. */
+size_t ncahip_slw_workspace(int B, int c, int n, int m);
+int ncahip_slw_project_f32(const float *source, const float *target, const float *proj, float *ks, float *kt, int B, int c, int n,
+                           int m, ncahip_stream_t stream);
+int ncahip_slw_sort_f32(float *keys, int32_t *perm, int rows, int n, ncahip_stream_t stream);
+int ncahip_slw_loss_fwd_f32(const float *s, const float *t, const int32_t *jmap, float *loss, int B, int n, int m,
+                            void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+int ncahip_slw_bwd_f32(const float *s, const float *t, const int32_t *jmap, const int32_t *perm, const float *proj,
+                       const float *g_loss, float *dsource, int B, int c, int n, int m, void *workspace, size_t workspace_bytes,
+                       ncahip_stream_t stream);
+
 /* The [B,1,H,W] uniforms the kernels draw for (seed, step) when u == NULL (for tests/tools). */
 int ncahip_philox_uniform_f32(float *u, int B, int H, int W, uint64_t seed, uint64_t step,
                               ncahip_stream_t stream);

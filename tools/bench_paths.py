@@ -18,6 +18,10 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
                   process: 32 x 3 x 256^2 with bf16 features (configs[2]'s batch) and 8 x 3 x 64^2 (the reference's training shape)
   loss_ot_batched / loss_ot_fused / loss_ot_fused_all   the OT term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a
                   kernel trace (not part of a run without names)
+  loss_slw        the objective with appearance_loss_type 'SlW' and its sliced-Wasserstein term alone (precomputed features, six levels),
+                  slw_impl torch and fused alternating in one process: 32 x 3 x 256^2 and 8 x 3 x 64^2, fp32 features
+  loss_slw_torch / loss_slw_fused   the sliced-Wasserstein term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a kernel
+                  trace (not part of a run without names)
 """
 import json
 import os
@@ -312,6 +316,86 @@ def loss_ot_trace_leg(impl, calls=5):
     torch.cuda.synchronize()
 
 
+SLW_IMPLS = ("torch", "fused")
+
+
+def _slw_setup(B, S):
+    """Loss modules of the two 'SlW' variants on one style image, the objective's input dict, and the six (source, target) levels the
+    term sees: the normalised image and the five style layers, flattened, the generated ones detached leaves of their own."""
+    import warnings
+    import numpy as np
+    from ncahip.loss import Loss, STYLE_LAYERS
+    dev = torch.device(DEV)
+    style = (np.random.RandomState(0).rand(S, S, 3) * 255).astype(np.uint8)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        L = {impl: Loss(dev, target_style_image=style, appearance_loss_type="SlW", slw_impl=impl) for impl in SLW_IMPLS}
+    gen = torch.rand(B, 3, S, S, device=dev, requires_grad=True)
+    d = {"generated_images": gen, "nca_state": torch.rand(B, 16, S, S, device=dev) * 3 - 1.5, "target_images": torch.rand(B, 3, S, S, device=dev)}
+    Lt = L["torch"]
+    flat = lambda f: f.reshape(f.shape[0], f.shape[1], -1)
+    norm = lambda im: (im - Lt.vgg.mean) / Lt.vgg.std
+    with torch.no_grad():
+        gf = Lt.vgg(gen, STYLE_LAYERS)
+        src = [flat(norm(gen))] + [flat(gf[l]) for l in STYLE_LAYERS]
+        tgt = [flat(norm(Lt.target_style_tensor))] + [flat(Lt.style_feats[l]) for l in STYLE_LAYERS]
+    src = [x.detach().clone().requires_grad_(True) for x in src]
+    return L, d, gen, src, tgt
+
+
+def _slw_term(impl, src, tgt):
+    from ncahip import loss
+    fn = loss._SLW_IMPLS[impl]
+
+    def f():
+        for x in src:
+            x.grad = None
+        total = sum(fn(x, y) for x, y in zip(src, tgt))
+        total.backward()
+        return total
+    return f
+
+
+def loss_slw_leg():
+    """slw_impl torch (einsum, torch.sort, autograd) against fused (csrc/nca_slw.hip), alternating call by call in one process: (a) the
+    whole objective with appearance_loss_type 'SlW', forward + backward to the generated images, (b) the sliced-Wasserstein term
+    alone on precomputed features (six levels), forward + backward to the features.  Median of 10 after 3 warm-ups each, host clock
+    between device synchronisations (timed_sync).  Both variants draw their projections from torch's CPU generator, seeded alike."""
+    for B, S, name in ((32, 256, "cfg3 batch, fp32 features"), (8, 64, "reference training shape, fp32 features")):
+        L, d, gen, src, tgt = _slw_setup(B, S)
+
+        def whole(impl):
+            def f():
+                gen.grad = None
+                L[impl](d)[0].backward()
+            return f
+        torch.manual_seed(0)
+        w, wm = timed_sync([whole(impl) for impl in SLW_IMPLS], iters=10)
+        t, tm = timed_sync([_slw_term(impl, src, tgt) for impl in SLW_IMPLS], iters=10)
+        res = {}
+        for k, impl in enumerate(SLW_IMPLS):
+            torch.manual_seed(1)
+            res.update({f"objective_ms_{impl}": w[k], f"objective_min_ms_{impl}": wm[k], f"slw_term_ms_{impl}": t[k],
+                        f"slw_term_min_ms_{impl}": tm[k], f"slw_value_{impl}": float(_slw_term(impl, src, tgt)())})
+        ops.check_errors()
+        emit(path="loss_slw", shape=f"{B}x3x{S}x{S}", what=name, levels=[[x.shape[1], x.shape[2], y.shape[2]] for x, y in zip(src, tgt)], **res)
+        del L, d, gen, src, tgt
+        torch.cuda.empty_cache()
+
+
+def loss_slw_trace_leg(impl, calls=5):
+    """The sliced-Wasserstein term alone at 32 x 3 x 256^2, forward + backward, `calls` times with one variant and nothing else on the
+    device after the features exist: run under a kernel trace, the per-call launch count is (kernel calls after set-up) / calls."""
+    _, _, _, src, tgt = _slw_setup(32, 256)
+    f = _slw_term(impl, src, tgt)
+    torch.manual_seed(0)
+    torch.cuda.synchronize()
+    emit(path="loss_slw_trace", impl=impl, calls=calls, marker="setup done")
+    for _ in range(calls):
+        f()
+    torch.cuda.synchronize()
+
+
 def trainer_default_leg():
     """ConditionedNCATrainer at the reference's OWN defaults (EncoderConditioning/train.py:30-50: default ConditionedNCA = C 20, 64 x 64
     targets, batch 8, nca_steps [48, 96] drawn per batch, pool 512, lr 2e-3): wall time per trainer iteration (two train_batch calls:
@@ -441,6 +525,11 @@ def main(names):
     for impl in OT_IMPLS:
         if "loss_ot_" + impl in names:
             loss_ot_trace_leg(impl)
+    if allp or "loss_slw" in names:
+        loss_slw_leg()
+    for impl in SLW_IMPLS:
+        if "loss_slw_" + impl in names:
+            loss_slw_trace_leg(impl)
     if allp or "video" in names:
         video_leg()
     if allp or "trainer_default" in names:

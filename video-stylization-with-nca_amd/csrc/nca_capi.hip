@@ -900,6 +900,73 @@ int ncahip_ot_moment_bwd_f32(const float* y, const float* my, const float* sgn, 
     return hip_result(nca_launch_ot_moment_bwd(y, my, sgn, (const signed char*)S, g_mom, dy, B, N, c, (hipStream_t)stream), "ot_moment_bwd");
 }
 
+// ---- sliced-Wasserstein style loss (nca_slw.hip) -------------------------------------------------------------------------
+namespace {
+constexpr int kSlwMaxC = 512, kSlwMaxLen = 65536, kSlwMaxB = 1024, kSlwMaxRows = 65535, kSlwDirs = 32;
+bool slw_c_ok(int c) { return c == 3 || (c >= 4 && (c & 3) == 0 && c <= kSlwMaxC); }
+int check_slw(const char* what, int B, int c, int n, int m) {
+    if (B <= 0) return fail(NCAHIP_EINVAL, "%s: bad size B=%d", what, B);
+    if (B > kSlwMaxB) return fail(NCAHIP_ERANGE, "%s: B=%d exceeds %d", what, B, kSlwMaxB);
+    if (!slw_c_ok(c)) return fail(NCAHIP_ERANGE, "%s: c=%d must be 3 or a multiple of 4 in [4, %d]", what, c, kSlwMaxC);
+    if (n < 1 || n > kSlwMaxLen) return fail(NCAHIP_ERANGE, "%s: n=%d outside [1, %d]", what, n, kSlwMaxLen);
+    if (m < 1 || m > kSlwMaxLen) return fail(NCAHIP_ERANGE, "%s: m=%d outside [1, %d]", what, m, kSlwMaxLen);
+    return 0;
+}
+}  // namespace
+
+size_t ncahip_slw_workspace(int B, int c, int n, int m) {
+    if (B <= 0 || B > kSlwMaxB || !slw_c_ok(c) || n < 1 || n > kSlwMaxLen || m < 1 || m > kSlwMaxLen) return 0;
+    const size_t dk = (size_t)B * kSlwDirs * n, part = (size_t)B * kSlwDirs * nca_slw_blocks(n) + B;   // the backward's dk; the forward's partials
+    return (dk > part ? dk : part) * sizeof(float);
+}
+
+int ncahip_slw_project_f32(const float* source, const float* target, const float* proj, float* ks, float* kt, int B, int c, int n, int m,
+                           ncahip_stream_t stream) {
+    if (!source || !target || !proj || !ks || !kt) return fail(NCAHIP_EINVAL, "slw_project: null pointer");
+    if (int rc = check_slw("slw_project", B, c, n, m)) return rc;
+    if (ks == kt || (const float*)ks == source || (const float*)ks == target || (const float*)ks == proj || (const float*)kt == source ||
+        (const float*)kt == target || (const float*)kt == proj)
+        return fail(NCAHIP_EINVAL, "slw_project: outputs must not alias each other or the inputs");
+    if (!ot_aligned(source) || !ot_aligned(target) || !ot_aligned(proj))
+        return fail(NCAHIP_ERANGE, "slw_project: source, target and proj must be 16-byte aligned");
+    return hip_result(nca_launch_slw_project(source, target, proj, ks, kt, B, c, n, m, (hipStream_t)stream), "slw_project");
+}
+
+int ncahip_slw_sort_f32(float* keys, int32_t* perm, int rows, int n, ncahip_stream_t stream) {
+    if (!keys || !perm) return fail(NCAHIP_EINVAL, "slw_sort: null pointer");
+    if (rows <= 0) return fail(NCAHIP_EINVAL, "slw_sort: bad size rows=%d", rows);
+    if (rows > kSlwMaxRows) return fail(NCAHIP_ERANGE, "slw_sort: rows=%d exceeds %d", rows, kSlwMaxRows);
+    if (n < 1 || n > kSlwMaxLen) return fail(NCAHIP_ERANGE, "slw_sort: n=%d outside [1, %d]", n, kSlwMaxLen);
+    if ((void*)keys == (void*)perm) return fail(NCAHIP_EINVAL, "slw_sort: keys and perm must not alias");
+    return hip_result(nca_launch_slw_sort(keys, perm, rows, n, (hipStream_t)stream), "slw_sort");
+}
+
+int ncahip_slw_loss_fwd_f32(const float* s, const float* t, const int32_t* jmap, float* loss, int B, int n, int m, void* workspace,
+                            size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!s || !t || !jmap || !loss || !workspace) return fail(NCAHIP_EINVAL, "slw_loss_fwd: null pointer");
+    if (int rc = check_slw("slw_loss_fwd", B, 4, n, m)) return rc;
+    if ((void*)loss == (void*)s || (void*)loss == (void*)t || (void*)loss == (void*)jmap || workspace == (void*)s || workspace == (void*)t ||
+        workspace == (void*)jmap || workspace == (void*)loss)
+        return fail(NCAHIP_EINVAL, "slw_loss_fwd: loss and workspace must not alias each other or the inputs");
+    if (((uintptr_t)workspace & 3u) != 0) return fail(NCAHIP_ERANGE, "slw_loss_fwd: workspace must be 4-byte aligned");
+    if (workspace_bytes < ncahip_slw_workspace(B, 4, n, m)) return fail(NCAHIP_EINVAL, "slw_loss_fwd: workspace too small");
+    return hip_result(nca_launch_slw_loss_fwd(s, t, jmap, loss, B, n, m, workspace, (hipStream_t)stream), "slw_loss_fwd");
+}
+
+int ncahip_slw_bwd_f32(const float* s, const float* t, const int32_t* jmap, const int32_t* perm, const float* proj, const float* g_loss,
+                       float* dsource, int B, int c, int n, int m, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!s || !t || !jmap || !perm || !proj || !g_loss || !dsource || !workspace) return fail(NCAHIP_EINVAL, "slw_bwd: null pointer");
+    if (int rc = check_slw("slw_bwd", B, c, n, m)) return rc;
+    const void* const in[6] = {s, t, jmap, perm, proj, g_loss};
+    for (int k = 0; k < 6; ++k)
+        if (in[k] == (const void*)dsource || in[k] == (const void*)workspace)
+            return fail(NCAHIP_EINVAL, "slw_bwd: dsource and workspace must not alias an input");
+    if ((void*)dsource == workspace) return fail(NCAHIP_EINVAL, "slw_bwd: dsource and workspace must not alias each other");
+    if (((uintptr_t)workspace & 3u) != 0) return fail(NCAHIP_ERANGE, "slw_bwd: workspace must be 4-byte aligned");
+    if (workspace_bytes < ncahip_slw_workspace(B, c, n, m)) return fail(NCAHIP_EINVAL, "slw_bwd: workspace too small");
+    return hip_result(nca_launch_slw_bwd(s, t, jmap, perm, proj, g_loss, dsource, B, c, n, m, workspace, (hipStream_t)stream), "slw_bwd");
+}
+
 size_t ncahip_cond_grow_bwd_workspace(int B, int C, int H, int W, int hidden) {
     if (!dims_ok(B, C, H, W) || hidden <= 0) return 0;
     const size_t n = (size_t)B * C * H * W * sizeof(float);

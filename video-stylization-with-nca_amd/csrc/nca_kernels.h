@@ -205,6 +205,14 @@ hipError_t nca_launch_ot_moment_fwd(const float* x, const float* y, float* mom, 
                                     void* ws, hipStream_t st);
 hipError_t nca_launch_ot_moment_bwd(const float* y, const float* my, const float* sgn, const signed char* S, const float* gup, float* dy, int B,
                                     int N, int c, hipStream_t st);
+// nca_slw.hip: sliced-Wasserstein style loss (projection onto 32 directions, segmented stable sort of (key, index) pairs, loss, adjoint)
+int nca_slw_blocks(int n);   // 4096-position blocks of a row: sort chunks, and loss partials per row
+hipError_t nca_launch_slw_project(const float* src, const float* tgt, const float* proj, float* ks, float* kt, int B, int c, int n, int m,
+                                  hipStream_t st);
+hipError_t nca_launch_slw_sort(float* keys, int* perm, int rows, int n, hipStream_t st);
+hipError_t nca_launch_slw_loss_fwd(const float* s, const float* t, const int* jmap, float* loss, int B, int n, int m, void* ws, hipStream_t st);
+hipError_t nca_launch_slw_bwd(const float* s, const float* t, const int* jmap, const int* perm, const float* proj, const float* gup, float* ds, int B,
+                              int c, int n, int m, void* ws, hipStream_t st);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);

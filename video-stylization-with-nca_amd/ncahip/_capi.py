@@ -82,13 +82,18 @@ SIGNATURES = {
     "ncahip_ot_moment_workspace": [_I, _I, _I],
     "ncahip_ot_moment_fwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P],
     "ncahip_ot_moment_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "ncahip_slw_workspace": [_I, _I, _I, _I],
+    "ncahip_slw_project_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ncahip_slw_sort_f32": [_P, _P, _I, _I, _P],
+    "ncahip_slw_loss_fwd_f32": [_P, _P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P],
+    "ncahip_slw_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_bwd_ms_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_persist_workspace": ctypes.c_size_t,
              "ncahip_cond_grow_persist_workspace": ctypes.c_size_t, "ncahip_ot_workspace": ctypes.c_size_t,
-             "ncahip_ot_moment_workspace": ctypes.c_size_t}
+             "ncahip_ot_moment_workspace": ctypes.c_size_t, "ncahip_slw_workspace": ctypes.c_size_t}
 
 _lib = None
 

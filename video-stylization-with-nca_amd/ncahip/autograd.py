@@ -244,3 +244,28 @@ class OTLayerLoss(torch.autograd.Function):
         dy = ops.ot_remd_backward(x, y, xn, yn, rarg, carg, branch, gl)
         ops.ot_moment_backward(y, my, sgn, S, gl, dy)
         return None, ops.ot_gather_backward(dy, ctx.idx, *ctx.hw), None
+
+
+# ------------------------------------------------------------------------------------ sliced-Wasserstein style loss
+class SlicedWasserstein(torch.autograd.Function):
+    """(source [B,c,n], target [1,c,m], proj [c,32], jmap [n] int32) -> sum of squared differences of the sorted projections (0-dim),
+    every step on the library's kernels: ops.slw_project, ops.slw_sort (one call for source and target when n == m), ops.slw_loss;
+    backwards ops.slw_backward.  Gradient to source only."""
+
+    @staticmethod
+    def forward(ctx, source, target, proj, jmap):
+        ks, kt = ops.slw_project(source, target, proj)
+        if ks.shape[-1] == kt.shape[-1]:                   # views of one buffer: one segmented sort of 32 B + 32 rows
+            both = ks._base
+            _, perm = ops.slw_sort(both)
+            perm = perm[:ks.shape[0]]
+        else:
+            _, perm = ops.slw_sort(ks)
+            ops.slw_sort(kt)
+        ctx.save_for_backward(ks, kt, jmap, perm, proj)
+        return ops.slw_loss(ks, kt, jmap)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        ks, kt, jmap, perm, proj = ctx.saved_tensors
+        return ops.slw_backward(ks, kt, jmap, perm, proj, g_loss.float().reshape(1).contiguous()), None, None, None

@@ -88,6 +88,36 @@ def _sliced_wasserstein(source, target, n_proj=32):
     return (ps - F.interpolate(pt, n, mode="nearest")).square().sum()
 
 
+def sliced_wasserstein_fused(source, target, n_proj=32):
+    """_sliced_wasserstein on this library's kernels (csrc/nca_slw.hip): the same torch.randn(ch, 32) draw on the CPU generator, so
+    torch's CPU RNG stream is left exactly where the torch path leaves it; projection, a stable segmented sort of (key, index)
+    pairs, the nearest resample of the target through a cached index map (F.interpolate applied to an arange), the sum of squares
+    and the closed-form backward (scatter through the sort's permutation, then proj . dk) all run as HIP kernels.  Only
+    n_proj == 32; CUDA float32 features only (no CPU fallback); c = 3 or a multiple of 4 up to 512.
+
+    A level whose rows are longer than 65 536 positions (source or target) is taken on the torch path, level by level, with the
+    projection already drawn: the sort kernels cover rows up to 65 536.  Non-finite features are outside the contract.  Equal
+    keys are ordered by position (a stable sort); the loss value does not depend on that order, the gradient's assignment of
+    equal keys does."""
+    from . import ops
+    from .autograd import SlicedWasserstein
+    if n_proj != ops.SLW_DIRECTIONS:
+        raise ValueError(f"ncahip.loss: sliced_wasserstein_fused covers n_proj == {ops.SLW_DIRECTIONS}, got {n_proj}")
+    ch, n = source.shape[-2:]
+    m = target.shape[-1]
+    proj = F.normalize(torch.randn(ch, n_proj), dim=0).to(source.device)
+    if n > ops.SLW_MAX_LEN or m > ops.SLW_MAX_LEN:
+        ps = torch.einsum("bcn,cp->bpn", source, proj).sort()[0]
+        pt = torch.einsum("bcn,cp->bpn", target, proj).sort()[0]
+        return (ps - F.interpolate(pt, n, mode="nearest")).square().sum()
+    if not source.is_cuda:
+        ops._dev(source, "source")                          # raises: no CPU fallback
+    return SlicedWasserstein.apply(source, target, proj, ops.slw_index_map(m, n, source.device))
+
+
+_SLW_IMPLS = {"torch": _sliced_wasserstein, "fused": sliced_wasserstein_fused}
+
+
 def _to_nchw(img) -> torch.Tensor:
     """appearance_loss.py:41-43 (torchvision ToTensor + unsqueeze): a PIL image or an H x W x C uint8 array becomes a
     [1,C,H,W] float tensor in [0,1]; float arrays are only transposed; a float tensor is taken as C x H x W (or N x C x H x W)
@@ -245,8 +275,12 @@ _OT_IMPLS = {"batched": ot_loss_batched, "fused": ot_loss_fused, "fused_all": ot
 
 class Loss(nn.Module):
     def __init__(self, device, content_loss_weight=1.0, overflow_loss_weight=1.0, appearance_loss_weight=1.0,
-                 appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False, ot_impl="batched"):
+                 appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False, ot_impl="batched",
+                 slw_impl="torch"):
         super().__init__()
+        if slw_impl not in _SLW_IMPLS:
+            raise ValueError(f"ncahip.loss: unknown slw_impl={slw_impl!r} ('torch' or 'fused')")
+        self.slw_impl = slw_impl        # 'fused': the 'SlW' term on this library's kernels (sliced_wasserstein_fused)
         if ot_impl not in _OT_IMPLS:
             raise ValueError(f"ncahip.loss: unknown ot_impl={ot_impl!r} ('batched', 'fused' or 'fused_all')")
         self.ot_impl = ot_impl          # 'fused': the relaxed-EMD part of the OT term on this library's kernels (ot_loss_fused);
@@ -305,7 +339,7 @@ class Loss(nn.Module):
                     norm = lambda im: (im - self.vgg.mean) / self.vgg.std
                     src = [flat(norm(gen))] + [flat(gf[l]) for l in STYLE_LAYERS]
                     tgt = [flat(norm(self.target_style_tensor))] + [flat(self.style_feats[l]) for l in STYLE_LAYERS]
-                    acc = sum(_sliced_wasserstein(x, y) for x, y in zip(src, tgt))
+                    acc = sum(_SLW_IMPLS[self.slw_impl](x, y) for x, y in zip(src, tgt))
                 terms["appearance"] = acc
             if "content" in self.loss_weights:
                 tgt_img = input_dict["target_images"]

@@ -604,3 +604,84 @@ def ot_moment_backward(y: torch.Tensor, my: torch.Tensor, sgn: torch.Tensor, S: 
         assert dy.shape == y.shape and dy.is_contiguous() and _dev(dy, "dy") is dy
     check(lib().ncahip_ot_moment_bwd_f32(_p(y), _p(my), _p(sgn), _p(S), _p(g_mom), _p(dy), B, N, c, _stream()), "ot_moment_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- sliced-Wasserstein style loss (csrc/nca_slw.hip)
+SLW_DIRECTIONS = 32
+SLW_MAX_LEN = 65536      # longest row the sort kernels take (include/ncahip.h)
+_SLW_MAPS = {}
+
+
+def slw_nearest_index(m: int, n: int) -> torch.Tensor:
+    """The index map j(i) of F.interpolate(mode="nearest") from m to n positions, as a CPU int32 tensor [n]: F.interpolate itself
+    applied to arange(m), so that it is the same map by construction (positions below 2^24 are exact in float32)."""
+    src = torch.arange(m, dtype=torch.float32).reshape(1, 1, m)
+    return torch.nn.functional.interpolate(src, n, mode="nearest").reshape(n).to(torch.int32)
+
+
+def slw_index_map(m: int, n: int, device) -> torch.Tensor:
+    """slw_nearest_index(m, n) on `device`, built once per (m, n, device)."""
+    device = torch.device(device)
+    key = (m, n, device.type, device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else -1))
+    jm = _SLW_MAPS.get(key)
+    if jm is None:
+        jm = _SLW_MAPS[key] = slw_nearest_index(m, n).to(device)
+    return jm
+
+
+def slw_project(source: torch.Tensor, target: torch.Tensor, proj: torch.Tensor):
+    """Keys of the sliced-Wasserstein loss (ncahip_slw_project_f32): source [B,c,n], target [1,c,m], proj [c,32] -> ks [B,32,n],
+    kt [1,32,m], k[b,p,i] = sum_c x[b,c,i] proj[c,p].  When n == m the two are views of one [(B+1),32,n] buffer, which slw_sort can
+    then take in one call."""
+    source, target, proj = _dev(source, "source"), _dev(target, "target"), _dev(proj, "proj")
+    B, c, n = source.shape
+    m = target.shape[2]
+    assert target.shape == (1, c, m) and proj.shape == (c, SLW_DIRECTIONS), (source.shape, target.shape, proj.shape)
+    if n == m:
+        both = torch.empty(B + 1, SLW_DIRECTIONS, n, device=source.device, dtype=torch.float32)
+        ks, kt = both[:B], both[B:]
+    else:
+        ks = torch.empty(B, SLW_DIRECTIONS, n, device=source.device, dtype=torch.float32)
+        kt = torch.empty(1, SLW_DIRECTIONS, m, device=source.device, dtype=torch.float32)
+    check(lib().ncahip_slw_project_f32(_p(source), _p(target), _p(proj), _p(ks), _p(kt), B, c, n, m, _stream()), "slw_project")
+    return ks, kt
+
+
+def slw_sort(keys: torch.Tensor):
+    """Sorts every row of keys [..., n] ascending IN PLACE (ncahip_slw_sort_f32) and returns (keys, perm): perm int32, the original
+    position of each sorted element; equal keys keep their original order, as with torch.sort(stable=True)."""
+    assert keys.is_contiguous() and _dev(keys, "keys") is keys
+    n = keys.shape[-1]
+    perm = torch.empty(keys.shape, device=keys.device, dtype=torch.int32)
+    check(lib().ncahip_slw_sort_f32(_p(keys), _p(perm), keys.numel() // n, n, _stream()), "slw_sort")
+    return keys, perm
+
+
+def slw_loss(s: torch.Tensor, t: torch.Tensor, jmap: torch.Tensor) -> torch.Tensor:
+    """sum (s[b,p,i] - t[p,jmap[i]])^2 over sorted keys s [B,32,n], t [1,32,m] (ncahip_slw_loss_fwd_f32): a 0-dim tensor."""
+    s, t, jmap = _dev(s, "s"), _dev(t, "t"), _dev(jmap, "jmap", torch.int32)
+    B, _, n = s.shape
+    m = t.shape[-1]
+    assert s.shape[1] == SLW_DIRECTIONS and t.numel() == SLW_DIRECTIONS * m and jmap.shape == (n,)
+    loss = torch.empty(1, device=s.device, dtype=torch.float32)
+    nbytes = lib().ncahip_slw_workspace(B, 4, n, m)
+    ws = _workspace(nbytes, s.device)
+    check(lib().ncahip_slw_loss_fwd_f32(_p(s), _p(t), _p(jmap), _p(loss), B, n, m, _p(ws), nbytes, _stream()), "slw_loss_fwd")
+    return loss[0]
+
+
+def slw_backward(s: torch.Tensor, t: torch.Tensor, jmap: torch.Tensor, perm: torch.Tensor, proj: torch.Tensor,
+                 g_loss: torch.Tensor) -> torch.Tensor:
+    """dL/dsource [B,c,n] of slw_loss(sort(project(source))) given dL/dloss (one float on the device) (ncahip_slw_bwd_f32): the
+    scaled residual scattered through perm, then proj . dk.  The target and proj get no gradient."""
+    s, t, jmap, perm = _dev(s, "s"), _dev(t, "t"), _dev(jmap, "jmap", torch.int32), _dev(perm, "perm", torch.int32)
+    proj, g_loss = _dev(proj, "proj"), _dev(g_loss, "g_loss")
+    B, _, n = s.shape
+    m, c = t.shape[-1], proj.shape[0]
+    assert perm.shape == s.shape and jmap.shape == (n,) and g_loss.numel() == 1 and proj.shape == (c, SLW_DIRECTIONS)
+    ds = torch.empty(B, c, n, device=s.device, dtype=torch.float32)
+    nbytes = lib().ncahip_slw_workspace(B, c, n, m)
+    ws = _workspace(nbytes, s.device)
+    check(lib().ncahip_slw_bwd_f32(_p(s), _p(t), _p(jmap), _p(perm), _p(proj), _p(g_loss), _p(ds), B, c, n, m, _p(ws), nbytes, _stream()),
+          "slw_bwd")
+    return ds
