@@ -41,7 +41,8 @@ def _both(ops, x, Tn, cond, us, w, pad, rate, **kw):
 
 
 @pytest.mark.parametrize("pad", ["replicate", "circular", "reflect", "constant"])
-@pytest.mark.parametrize("C,fc,cc,shape", [(12, 96, 3, (1, 64, 64)), (16, 128, 2, (2, 32, 96)), (8, 64, 0, (1, 16, 16)), (12, 96, 3, (1, 256, 256))])
+@pytest.mark.parametrize("C,fc,cc,shape", [(12, 96, 3, (1, 64, 64)), (16, 128, 2, (2, 32, 96)), (8, 64, 0, (1, 16, 16)), (12, 96, 3, (1, 256, 256)),
+                                          (16, 128, 0, (1, 16, 32)), (14, 112, 1, (1, 32, 16))])
 def test_persistent_equals_per_step_bit_for_bit(ops, pad, C, fc, cc, shape):
     B, H, W = shape
     gen = torch.Generator().manual_seed(C + H + len(pad))
@@ -61,7 +62,8 @@ def test_persistent_equals_per_step_bit_for_bit(ops, pad, C, fc, cc, shape):
 
 
 @pytest.mark.parametrize("pad", ["replicate", "circular", "reflect", "constant"])
-@pytest.mark.parametrize("C,fc,cc,shape", [(12, 96, 2, (1, 64, 64)), (16, 128, 3, (2, 32, 48)), (8, 64, 0, (1, 16, 16)), (12, 96, 2, (1, 256, 256))])
+@pytest.mark.parametrize("C,fc,cc,shape", [(12, 96, 2, (1, 64, 64)), (16, 128, 3, (2, 32, 48)), (8, 64, 0, (1, 16, 16)), (12, 96, 2, (1, 256, 256)),
+                                          (16, 128, 0, (1, 16, 32)), (14, 112, 1, (1, 32, 16))])
 def test_persistent_two_scale_equals_per_step_bit_for_bit(ops, pad, C, fc, cc, shape):
     """perception_scales = [0, 1] (every shipped video model): the one-launch kernel against coarse-perceive + fused step launches."""
     B, H, W = shape
@@ -70,6 +72,7 @@ def test_persistent_two_scale_equals_per_step_bit_for_bit(ops, pad, C, fc, cc, s
     x = (torch.rand(B, C, H, W, generator=gen) - 0.5).to(DEV)
     cond = (torch.rand(B, cc, H, W, generator=gen) * 2 - 1).to(DEV) if cc else None
     w = ops.DyncaWeights(prm["w1.weight"], prm["w1.bias"], prm["w2.weight"], prm["w2.bias"], x)
+    assert ops.lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, cc) > 0
     for Tn, mode in ((1, "u"), (6, "philox"), (2, "bits"), (19, "u")):
         us = None
         if mode != "philox":

@@ -245,8 +245,8 @@ int ncahip_dynca_nsteps_fwd_f32(float* states, int ring, int T, const float* con
 // ---- T steps in ONE launch for small grids (B = 1 video inference), nca_dynca_persist.hip -------------------------------------
 size_t ncahip_dynca_nsteps_persist_workspace(int B, int C, int H, int W, int fc, int c_cond) {
     if (!dims_ok(B, C, H, W) || !nca_dynca_persist_shape_ok(B, C, H, W, fc, c_cond)) return 0;
-    // abort word + the exchange: 2 parities x tiles x C x (60 fine ring cells + 48 coarse means) (value, tag) pairs
-    return 256 + align256((size_t)2 * nca_dynca_persist_tiles(B, H, W) * C * 108 * sizeof(unsigned long long));      // (sized for the two-scale exchange)
+    // abort word + the exchange: 2 parities x tiles x C x (fine ring cells + coarse means) (value, tag) pairs: sized for the two-scale exchange
+    return 256 + align256((size_t)2 * nca_dynca_persist_xch_pairs(B, C, H, W, true) * sizeof(unsigned long long));
 }
 
 static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, int T, const float* cond, const float* u, const float* w1,
@@ -271,7 +271,7 @@ static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, i
     hipStream_t st = (hipStream_t)stream;
     NcaDyncaPersistArgs a{x_in, x_out, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0,
                           (int*)workspace, epoch, (unsigned long long*)((char*)workspace + 256),
-                          (size_t)nca_dynca_persist_tiles(B, H, W) * C * (two_scale ? 108 : 60), nullptr, ubits ? 1 : 0};
+                          nca_dynca_persist_xch_pairs(B, C, H, W, two_scale), nullptr, ubits ? 1 : 0};
     bool fits = false;
     auto launch = two_scale ? nca_launch_dynca_persist_ms : nca_launch_dynca_persist;
     if (int rc = hip_result(launch(a, st, true, &fits), "dynca nsteps persist (occupancy)")) return rc;

@@ -23,6 +23,13 @@
 // The host side launches this only when every workgroup can be co-resident (occupancy x CUs >= tiles), H % 16 == 0, W % 16 == 0,
 // C <= 16, fc <= 128; anything else runs the per-step kernels (nca_step_fwd.hip).  Same arithmetic per cell in the same order as the
 // per-step kernel (perception from the LDS tile, exact-f32 MFMA chains with the same k order): bit-identical results.
+//
+// Two kernels live here: dynca_persist_kernel (single-scale) and dynca_persist_ms_kernel (two-scale).  What carries the bit-identity
+// contract exists ONCE, as persist_* helpers both call: the prologue (weight images, biases, conditioning, step-0 tile), the fire
+// masks, the MLP (both exact-f32 MFMA chains, ReLU), residual x mask with the state / ring stores, the hand-off between sync wave and
+// compute waves, the bounded-poll bookkeeping, and the host launcher.  What is per kernel is what really differs: the order in which a
+// tile's cells are visited (group_cell / group_cell_ms), the perception (plain / blended with the up-sampled coarse perception), the
+// sync wave's staging (register arrays / an LDS table + the coarse exchange) and the barrier schedule of a step.
 #include "nca_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -43,6 +50,8 @@ constexpr int kIW = PTW - 2;                               // interior width (14
 
 template <int CP, int FC, bool HAS_COND>
 struct PersistCfg {
+    static constexpr int CPAD = CP, FCPAD = FC;              // (for the shared helpers, which take the whole configuration)
+    static constexpr bool COND = HAS_COND;
     static constexpr int K1S = CP + (HAS_COND ? 1 : 0);
     static constexpr int M1T = FC / 16, K2S = FC / 4;
     static constexpr int OFF_W1 = 0;
@@ -100,31 +109,50 @@ __device__ __forceinline__ void group_cell(int j, int ci, int& r, int& q) {
     q = 1 + idx % kIW;
 }
 
-template <int CP, int FC, bool HAS_COND>
-__global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPersistArgs a) {
-    using K = PersistCfg<CP, FC, HAS_COND>;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const W1L = smem + K::OFF_W1;
-    float* const W2L = smem + K::OFF_W2;
-    float* const B1L = smem + K::OFF_B1;
-    float* const B2L = smem + K::OFF_B2;
-    float* const MK = smem + K::OFF_MK;
-    float* const CN = smem + K::OFF_CN;
-    int* const lflag = reinterpret_cast<int*>(smem + K::OFF_FLAG);
+// ---- shared by both kernels ---------------------------------------------------------------------------------------------------------
+// where a workgroup's tile sits
+struct PersistTile {
+    int tile, b, ty0, tx0, tiles_x, tiles_y;
+    size_t plane, cell0;     // H * W; linear index of the tile's first cell
+    unsigned tag0;           // (value, tag) pairs: tag = epoch * 4096 + step: stale pairs of earlier launches never match
+};
+__device__ __forceinline__ PersistTile persist_tile(const NcaDyncaPersistArgs& a) {
+    PersistTile G;
+    G.tiles_x = a.W / PTW, G.tiles_y = a.H / PTH;
+    G.tile = blockIdx.x, G.b = G.tile / (G.tiles_x * G.tiles_y);
+    G.ty0 = (G.tile / G.tiles_x) % G.tiles_y * PTH, G.tx0 = G.tile % G.tiles_x * PTW;
+    G.plane = (size_t)a.H * a.W;
+    G.cell0 = (size_t)G.b * G.plane + (size_t)G.ty0 * a.W + G.tx0;
+    G.tag0 = a.epoch << 12;
+    return G;
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ci = lane & 15;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int C = a.C, H = a.H, W = a.W, fc = a.fc, CC = a.c_cond, K1 = 4 * C + CC;
-    const size_t plane = (size_t)H * W;
-    const unsigned tag0 = a.epoch << 12;     // (value, tag) pairs: tag = epoch * 4096 + step: stale pairs of earlier launches never match
-    const int tiles_x = W / PTW, tiles_y = H / PTH;
-    const int tile = blockIdx.x, txi = tile % tiles_x, tyi = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int ty0 = tyi * PTH, tx0 = txi * PTW;
-    const size_t cell0 = (size_t)b * plane + (size_t)ty0 * W + tx0;     // linear index of the tile's first cell
+// fire mask of step t for the tile's 256 cells into MK[t & 1] (dynca.py:131): explicit uniforms, bit-packed masks, or Philox
+__device__ __forceinline__ void persist_fill_mask(const NcaDyncaPersistArgs& a, float* MK, size_t cell0, int t, int first, int stride) {
+    float* const mk = MK + (t & 1) * (PTH * PTW);
+    const size_t cells = (size_t)a.B * a.H * a.W;
+    for (int c = first; c < PTH * PTW; c += stride) {
+        const size_t cell = cell0 + (size_t)(c / PTW) * a.W + c % PTW;
+        float uu;
+        if (a.u) {
+            if (a.u_bits) uu = ((reinterpret_cast<const uint32_t*>(a.u)[(size_t)t * ((cells + 31) / 32) + (cell >> 5)] >> (unsigned)(cell & 31)) & 1u) ? 1.0f : 0.0f;
+            else uu = a.u[(size_t)t * cells + cell];
+        } else uu = nca_philox_cell(a.seed, a.step0 + (uint64_t)t, cell);
+        mk[c] = floorf(uu + a.rate);
+    }
+}
 
-    // ---- once per launch: A-operand weight images (same layouts and k order as dynca_step_fwd_kernel).  Two-phase gather: every
-    //      load of both images is requested before the first LDS write (one cold round trip for the prologue, not one per element)
+// once per launch (all 320 threads; the caller's barrier follows): weight images, biases, flags, conditioning tile, masks of step 0 and
+// the tile's cells at step 0.  Padded channels and padded hidden units are zero here and stay zero (persist_store)
+template <class K>
+__device__ __forceinline__ void persist_prologue(const NcaDyncaPersistArgs& a, float* smem, const PersistTile& G) {
+    constexpr int CP = K::CPAD;
+    const int tid = threadIdx.x, C = a.C, W = a.W, fc = a.fc, CC = a.c_cond, K1 = 4 * C + CC;
+    // A-operand weight images (same layouts and k order as dynca_step_fwd_kernel).  Two-phase gather: every load of both images is
+    // requested before the first LDS write (one cold round trip for the prologue, not one per element)
     {
+        float* const W1L = smem + K::OFF_W1;
+        float* const W2L = smem + K::OFF_W2;
         constexpr int N1 = K::M1T * K::K1S * 64, N2 = K::K2S * 64, U1 = (N1 + kPT - 1) / kPT, U2 = (N2 + kPT - 1) / kPT;
         float v1[U1], v2[U2];
 #pragma unroll
@@ -158,43 +186,185 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
         for (int u = 0; u < U2; ++u)
             if (tid + kPT * u < N2) W2L[tid + kPT * u] = v2[u];
     }
-    for (int idx = tid; idx < FC; idx += kPT) B1L[idx] = idx < fc ? a.b1[idx] : 0.0f;
-    if (tid < 16) B2L[tid] = tid < C ? a.b2[tid] : 0.0f;
-    if (tid < 4) lflag[tid] = 0;
-    if (HAS_COND) {
+    for (int idx = tid; idx < K::FCPAD; idx += kPT) smem[K::OFF_B1 + idx] = idx < fc ? a.b1[idx] : 0.0f;
+    if (tid < 16) smem[K::OFF_B2 + tid] = tid < C ? a.b2[tid] : 0.0f;
+    if (tid < 4) reinterpret_cast<int*>(smem + K::OFF_FLAG)[tid] = 0;
+    if (K::COND) {
         for (int i = tid; i < 4 * PTH * PTW; i += kPT) {
             const int cc = i / (PTH * PTW), c = i % (PTH * PTW);
-            CN[i] = cc < CC ? a.cond[((size_t)b * CC + cc) * plane + (size_t)(ty0 + c / PTW) * W + tx0 + c % PTW] : 0.0f;
+            smem[K::OFF_CN + i] = cc < CC ? a.cond[((size_t)G.b * CC + cc) * G.plane + (size_t)(G.ty0 + c / PTW) * W + G.tx0 + c % PTW] : 0.0f;
         }
     }
-    // fire mask of step t for the tile's 256 cells into MK[t & 1] (dynca.py:131): explicit uniforms, bit-packed masks, or Philox
-    auto fill_mask = [&](int t, int first, int stride) {
-        float* const mk = MK + (t & 1) * (PTH * PTW);
-        const size_t cells = (size_t)a.B * plane;
-        for (int c = first; c < PTH * PTW; c += stride) {
-            const size_t cell = cell0 + (size_t)(c / PTW) * W + c % PTW;
-            float uu;
-            if (a.u) {
-                if (a.u_bits) uu = ((reinterpret_cast<const uint32_t*>(a.u)[(size_t)t * ((cells + 31) / 32) + (cell >> 5)] >> (unsigned)(cell & 31)) & 1u) ? 1.0f : 0.0f;
-                else uu = a.u[(size_t)t * cells + cell];
-            } else uu = nca_philox_cell(a.seed, a.step0 + (uint64_t)t, cell);
-            mk[c] = floorf(uu + a.rate);
-        }
-    };
-    fill_mask(0, tid, kPT);
+    persist_fill_mask(a, smem + K::OFF_MK, G.cell0, 0, tid, kPT);
     // the tile's cells at step 0 (plain loads: written before the launch)
+    float* const Z0 = smem + K::OFF_Z;
+    const float* const xb = a.x_in + (size_t)G.b * C * G.plane;
+    for (int i = tid; i < CP * PTH * (PTW / 4); i += kPT) {
+        const int f4 = i % (PTW / 4), r = (i / (PTW / 4)) % PTH, ch = i / (PTH * (PTW / 4));
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (ch < C) v = *reinterpret_cast<const f32x4*>(xb + (size_t)ch * G.plane + (size_t)(G.ty0 + r) * W + G.tx0 + 4 * f4);
+        *reinterpret_cast<f32x4*>(Z0 + ch * PCS + (r + 1) * PRS + 4 + 4 * f4) = v;
+    }
+}
+
+// UpdateNet on NTP groups of 16 cells: acc2 = b2 + W2 relu(b1 + W1 P), both layers exact-f32 MFMA chains in the per-step kernel's k order
+template <class K, int NTP>
+__device__ __forceinline__ void persist_mlp(const float* smem, const float (&P)[NTP][K::K1S], int lane, int g, f32x4 (&acc2)[NTP], int dbg) {
+    const float* const W1L = smem + K::OFF_W1;
+    const float* const W2L = smem + K::OFF_W2;
+    const float* const B1L = smem + K::OFF_B1;
     {
-        float* const Z0 = smem + K::OFF_Z;
-        const float* const xb = a.x_in + (size_t)b * C * plane;
-        for (int i = tid; i < CP * PTH * (PTW / 4); i += kPT) {
-            const int f4 = i % (PTW / 4), r = (i / (PTW / 4)) % PTH, ch = i / (PTH * (PTW / 4));
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ch < C) v = *reinterpret_cast<const f32x4*>(xb + (size_t)ch * plane + (size_t)(ty0 + r) * W + tx0 + 4 * f4);
-            *reinterpret_cast<f32x4*>(Z0 + ch * PCS + (r + 1) * PRS + 4 + 4 * f4) = v;
+        const f32x4 bias = *reinterpret_cast<const f32x4*>(smem + K::OFF_B2 + 4 * g);
+#pragma unroll
+        for (int n = 0; n < NTP; ++n) acc2[n] = bias;
+    }
+    float wa1[K::K1S], wa2[4];
+    f32x4 bias1;
+    auto fetch = [&](int m) {
+        const float* const w1m = W1L + m * K::K1S * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < K::K1S; ++s) wa1[s] = w1m[s * 64];
+        const float* const w2m = W2L + (4 * m) * 64 + lane;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wa2[r] = w2m[r * 64];
+        bias1 = *reinterpret_cast<const f32x4*>(B1L + 16 * m + 4 * g);
+    };
+    fetch(0);
+#pragma unroll 1
+    for (int m = 0; m < ((dbg & 16) ? 0 : K::M1T); ++m) {
+        f32x4 acc1[NTP];
+#pragma unroll
+        for (int n = 0; n < NTP; ++n) acc1[n] = bias1;
+#pragma unroll
+        for (int s = 0; s < K::K1S; ++s)
+#pragma unroll
+            for (int n = 0; n < NTP; ++n) acc1[n] = nca_mfma(wa1[s], P[n][s], acc1[n]);
+        float w2c[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w2c[r] = wa2[r];
+        __builtin_amdgcn_sched_barrier(0);
+        if (m + 1 < K::M1T) fetch(m + 1);        // in flight across this tile's layer-2 MFMAs and the next chain
+        float h[NTP][4];
+#pragma unroll
+        for (int n = 0; n < NTP; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[n][r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int n = 0; n < NTP; ++n) acc2[n] = nca_mfma(w2c[r], h[n][r], acc2[n]);
+    }
+}
+
+// what a compute wave needs of step t (set up once per step, not once per phase: the phases' address arithmetic stays out of the MFMA
+// chains' registers)
+struct PersistStep {
+    int t;
+    bool last;            // the final step: the whole tile goes to x_out
+    const float* Zc;      // LDS tile of state t
+    float* Zn;            // LDS tile of state t + 1
+    const float* mkc;     // fire masks of step t
+    float* dst;           // this image's planes of x_out
+};
+template <class K>
+__device__ __forceinline__ PersistStep persist_step(const NcaDyncaPersistArgs& a, const PersistTile& G, float* smem, int t) {
+    PersistStep S;
+    S.t = t, S.last = t + 1 == a.T;
+    S.Zc = smem + K::OFF_Z + (t & 1) * (K::CPAD * PCS);
+    S.Zn = smem + K::OFF_Z + ((t + 1) & 1) * (K::CPAD * PCS);
+    S.mkc = smem + K::OFF_MK + (t & 1) * (PTH * PTW);
+    S.dst = a.x_out + (size_t)G.b * a.C * G.plane;
+    return S;
+}
+
+// residual + stochastic mask (dynca.py:131-133) for the cells (rr, qq) of step t: state t+1 -> the next step's LDS tile; ring cells (what
+// the neighbours read) -> the exchange every step, write-through, XCH_STRIDE pairs per channel and tile; everything -> memory at the
+// final step
+template <class K, int NTP, int XCH_STRIDE>
+__device__ __forceinline__ void persist_store(const NcaDyncaPersistArgs& a, const PersistTile& G, const PersistStep& S, int g,
+                                              const int (&rr)[NTP], const int (&qq)[NTP], const f32x4 (&acc2)[NTP]) {
+    constexpr int CP = K::CPAD;
+    const int C = a.C, t = S.t;
+#pragma unroll
+    for (int n = 0; n < NTP; ++n) {
+        const float mk = S.mkc[rr[n] * PTW + qq[n]];
+        const bool ring = rr[n] == 0 || rr[n] == PTH - 1 || qq[n] == 0 || qq[n] == PTW - 1;
+        const size_t o0 = (size_t)(G.ty0 + rr[n]) * a.W + G.tx0 + qq[n];
+        unsigned long long* const xd = a.xch + (size_t)((t + 1) & 1) * a.xch_words + (size_t)G.tile * C * XCH_STRIDE +
+                                       (ring ? ring_index(rr[n], qq[n]) : 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ch = 4 * g + r;
+            if (ch < CP) {
+                const int zo = ch * PCS + (rr[n] + 1) * PRS + qq[n] + 4;
+                const float xn = S.Zc[zo] + acc2[n][r] * mk;
+                S.Zn[zo] = ch < C ? xn : 0.0f;
+                if (ch < C && !(a.dbg & 2)) {
+                    if (S.last) S.dst[(size_t)ch * G.plane + o0] = xn;
+                    else if (ring) st_pair(xd + ch * XCH_STRIDE, xn, (int)(G.tag0 + (unsigned)(t + 1)));
+                }
+            }
         }
     }
+}
+
+// sync wave -> compute waves: the halo of state value - 1 is in the LDS tile (or, stop: give up).  LDS operations of a wave execute in
+// order: data, then the counter
+__device__ __forceinline__ void persist_post_halo(int* lflag, int lane, int value, bool stop) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (lane == 0) {
+        if (stop) __hip_atomic_store(lflag + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(lflag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+// compute waves: wait until the halo of state t is in the LDS tile (bounded poll of the sync wave's LDS counter); true = stop
+__device__ __forceinline__ bool persist_wait_halo(int* lflag, int t) {
+    int spins = 0;
+    while (__hip_atomic_load(lflag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return __hip_atomic_load(lflag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+}
+// sync wave, after a round of the neighbour poll that found stale pairs: true = give up (the bound is reached, or another workgroup has
+// raised the device-memory abort word -- the sticky error word itself is host-mapped: polling THAT is a PCIe read storm)
+__device__ __forceinline__ bool persist_poll_expired(const NcaDyncaPersistArgs& a, int lane, int& spins) {
+    bool give_up = ++spins >= (1 << 15);      // (uniform: every lane counts every round)
+    if ((spins & 31) == 0) give_up = give_up || __any(lane == 8 && (unsigned)__hip_atomic_load(a.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.epoch);
+    return give_up;
+}
+// a neighbour never delivered (not resident?): record it, tell every workgroup to drain
+__device__ __forceinline__ void persist_raise_abort(const NcaDyncaPersistArgs& a, int lane) {
+    if (lane == 0) {
+        if (a.err) __hip_atomic_fetch_or(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.flags, (int)a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// fine halo cell hc of 68 -> (r, q) in the 18 x 18 tile with halo: top row, bottom row, left column, right column
+__device__ __forceinline__ void fine_halo_cell(int hc, int& r, int& q) {
+    if (hc < PTW + 2) { r = 0; q = hc; }
+    else if (hc < 2 * (PTW + 2)) { r = PROWS - 1; q = hc - (PTW + 2); }
+    else if (hc < 2 * (PTW + 2) + PTH) { r = hc - 2 * (PTW + 2) + 1; q = 0; }
+    else { r = hc - 2 * (PTW + 2) - PTH + 1; q = PTW + 1; }
+}
+
+// ---- the single-scale kernel ----------------------------------------------------------------------------------------------------------
+template <int CP, int FC, bool HAS_COND>
+__global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPersistArgs a) {
+    using K = PersistCfg<CP, FC, HAS_COND>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const MK = smem + K::OFF_MK;
+    float* const CN = smem + K::OFF_CN;
+    int* const lflag = reinterpret_cast<int*>(smem + K::OFF_FLAG);
+
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ci = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = a.C, H = a.H, W = a.W;
+    const PersistTile G = persist_tile(a);
+    const int ty0 = G.ty0, tx0 = G.tx0;
+
+    persist_prologue<K>(a, smem, G);
     __syncthreads();
-    int* const abort_w = a.flags;   // device-memory abort word (the sticky error word itself is host-mapped: polling THAT is a PCIe read storm)
 
     if (wave == 4) {
         // =================================== sync wave: counters, halo, masks ================================================
@@ -205,14 +375,11 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
         for (int k = 0; k < K::NLD; ++k) {
             const int j = lane + 64 * k, hc = j % kHalo, ch = j / kHalo;
             int r, q;
-            if (hc < PTW + 2) { r = 0; q = hc; }
-            else if (hc < 2 * (PTW + 2)) { r = PROWS - 1; q = hc - (PTW + 2); }
-            else if (hc < 2 * (PTW + 2) + PTH) { r = hc - 2 * (PTW + 2) + 1; q = 0; }
-            else { r = hc - 2 * (PTW + 2) - PTH + 1; q = PTW + 1; }
+            fine_halo_cell(hc, r, q);
             const bool live = j < kHalo * CP;
             rz[k] = live ? ch * PCS + r * PRS + q + 3 : -1;
             const int sy = nca_pad_index(ty0 - 1 + r, H, a.pad_mode), sx = nca_pad_index(tx0 - 1 + q, W, a.pad_mode);
-            rsrc[k] = (live && ch < C && sy >= 0 && sx >= 0) ? (unsigned)((size_t)ch * plane + (size_t)sy * W + sx) : ~0u;
+            rsrc[k] = (live && ch < C && sy >= 0 && sx >= 0) ? (unsigned)((size_t)ch * G.plane + (size_t)sy * W + sx) : ~0u;
             // a pad-resolved source inside this tile (reflect / replicate at the image border: row 1, row 0 ...) is read from the LDS
             // tile itself -- interior cells are not in memory between the first and the last step (high bit = LDS offset)
             if (rsrc[k] != ~0u && sy >= ty0 && sy < ty0 + PTH && sx >= tx0 && sx < tx0 + PTW)
@@ -220,12 +387,10 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
             // the same source in the ring-exchange buffer (steps >= 1): [tile][channel][ring cell] pairs
             rxch[k] = ~0u;
             if (rsrc[k] != ~0u && !(rsrc[k] & 0x80000000u)) {
-                const int st_ = (b * tiles_y + sy / PTH) * tiles_x + sx / PTW;
+                const int st_ = (G.b * G.tiles_y + sy / PTH) * G.tiles_x + sx / PTW;
                 rxch[k] = (unsigned)((st_ * C + ch) * kRingCells + ring_index(sy % PTH, sx % PTW));
             }
         }
-        // the halo of state tt into LDS buffer tt & 1: `global` = the items that come from memory (neighbours' ring cells, coherent
-        // loads), else the items whose pad-resolved source is a cell of this tile (read from the LDS tile: needs it complete)
         // the halo of state tt into LDS buffer tt & 1.  global = the items that come from the neighbours: at tt = 0 plain loads of the
         // input state; later the ring-exchange pairs, re-read until every one carries step tt (bounded; false = gave up).
         // !global = the items whose pad-resolved source is a cell of this tile (read from the LDS tile: needs it complete).
@@ -246,7 +411,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
                 return true;
             }
             if (tt == 0) {
-                const float* const src = a.x_in + (size_t)b * C * plane;
+                const float* const src = a.x_in + (size_t)G.b * C * G.plane;
 #pragma unroll
                 for (int k = 0; k < K::NLD; ++k) hv[k] = rxch[k] != ~0u ? src[rsrc[k]] : 0.0f;
             } else {
@@ -255,15 +420,13 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
                     bool stale = false;
 #pragma unroll
                     for (int k = 0; k < K::NLD; ++k) {
-                        unsigned long long w = (unsigned long long)(tag0 + (unsigned)tt) << 32;
+                        unsigned long long w = (unsigned long long)(G.tag0 + (unsigned)tt) << 32;
                         if (rxch[k] != ~0u) w = ld_pair(xs + rxch[k]);
                         hv[k] = __uint_as_float((unsigned)w);
-                        stale = stale || (unsigned)(w >> 32) != tag0 + (unsigned)tt;
+                        stale = stale || (unsigned)(w >> 32) != G.tag0 + (unsigned)tt;
                     }
                     if (!__any(stale)) break;
-                    bool give_up = ++spins >= (1 << 15);      // (uniform: every lane counts every round)
-                    if ((spins & 31) == 0) give_up = give_up || __any(lane == 8 && (unsigned)__hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.epoch);
-                    if (give_up) return false;
+                    if (persist_poll_expired(a, lane, spins)) return false;
                     __builtin_amdgcn_s_sleep(1);
                 }
             }
@@ -274,50 +437,31 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
             }
             return true;
         };
-        auto post_halo = [&](int value, bool stop_) {   // LDS operations of a wave execute in order: data, then the counter
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            if (lane == 0) {
-                if (stop_) __hip_atomic_store(lflag + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_store(lflag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        };
         // state 0: everything is in memory / the LDS tile already
         stage_halo(0, true);
         stage_halo(0, false);
-        post_halo(1, false);
+        persist_post_halo(lflag, lane, 1, false);
         bool stop = false;
         for (int t = 0; t < a.T; ++t) {
             // the compute waves are in step t: ring first (its pairs go out early), then the interior.  Meanwhile: the neighbours'
             // rings of state t + 1 as soon as they arrive, into the OTHER LDS buffer's halo cells (nobody touches those in step t)
-            if (t + 1 < a.T) {
-                if (!(a.dbg & 1)) {
-                    stop = !stage_halo(t + 1, true);
-                    if (stop) {   // a neighbour never delivered (not resident?): record it, tell every workgroup to drain
-                        if (lane == 0) {
-                            if (a.err) __hip_atomic_fetch_or(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            __hip_atomic_store(abort_w, (int)a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                }
+            if (t + 1 < a.T && !(a.dbg & 1)) {
+                stop = !stage_halo(t + 1, true);
+                if (stop) persist_raise_abort(a, lane);
             }
             __syncthreads();      // step t's LDS tile (state t + 1) is complete
             if (t + 1 < a.T) {
                 if (!stop && !(a.dbg & 1)) stage_halo(t + 1, false);
-                post_halo(t + 2, stop);
+                persist_post_halo(lflag, lane, t + 2, stop);
             }
             if (stop) break;
         }
     } else {
         // =================================== compute waves ==================================================================
         for (int t = 0; t < a.T; ++t) {
-            float* const dst = a.x_out + (size_t)b * C * plane;      // (written at the final step only)
-            const float* const Zc = smem + K::OFF_Z + (t & 1) * (CP * PCS);
-            float* const Zn = smem + K::OFF_Z + ((t + 1) & 1) * (CP * PCS);
-            const float* const mkc = MK + (t & 1) * (PTH * PTW);
-            const bool last = t + 1 == a.T;
+            const PersistStep S = persist_step<K>(a, G, smem, t);
             // one phase = NTP groups of 16 cells: perception -> MLP on MFMA -> residual
-            auto phase = [&](auto ntp_tag, int j0, bool ack) {
+            auto phase = [&](auto ntp_tag, int j0) {
                 constexpr int NTP = decltype(ntp_tag)::value;
                 int rr[NTP], qq[NTP];
 #pragma unroll
@@ -325,7 +469,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
                 float P[NTP][K::K1S];
 #pragma unroll
                 for (int cq4 = 0; cq4 < CP / 4; ++cq4) {
-                    const float* const zc = Zc + (4 * cq4 + g) * PCS + 3;
+                    const float* const zc = S.Zc + (4 * cq4 + g) * PCS + 3;
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) {
                         float nbv[3][3];
@@ -339,92 +483,22 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
                         P[n][4 * cq4 + 3] = nca_laplacian(nbv);
                     }
                 }
-                if (HAS_COND) {
+                if constexpr (HAS_COND) {
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) P[n][CP] = CN[g * PTH * PTW + rr[n] * PTW + qq[n]];
                 }
                 f32x4 acc2[NTP];
-                {
-                    const f32x4 bias = *reinterpret_cast<const f32x4*>(B2L + 4 * g);
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n) acc2[n] = bias;
-                }
-                float wa1[K::K1S], wa2[4];
-                f32x4 bias1;
-                auto fetch = [&](int m) {
-                    const float* const w1m = W1L + m * K::K1S * 64 + lane;
-#pragma unroll
-                    for (int s = 0; s < K::K1S; ++s) wa1[s] = w1m[s * 64];
-                    const float* const w2m = W2L + (4 * m) * 64 + lane;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) wa2[r] = w2m[r * 64];
-                    bias1 = *reinterpret_cast<const f32x4*>(B1L + 16 * m + 4 * g);
-                };
-                fetch(0);
-#pragma unroll 1
-                for (int m = 0; m < ((a.dbg & 16) ? 0 : K::M1T); ++m) {
-                    f32x4 acc1[NTP];
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n) acc1[n] = bias1;
-#pragma unroll
-                    for (int s = 0; s < K::K1S; ++s)
-#pragma unroll
-                        for (int n = 0; n < NTP; ++n) acc1[n] = nca_mfma(wa1[s], P[n][s], acc1[n]);
-                    float w2c[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) w2c[r] = wa2[r];
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (m + 1 < K::M1T) fetch(m + 1);        // in flight across this tile's layer-2 MFMAs and the next chain
-                    float h[NTP][4];
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) h[n][r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                        for (int n = 0; n < NTP; ++n) acc2[n] = nca_mfma(w2c[r], h[n][r], acc2[n]);
-                }
-                // residual + stochastic mask (dynca.py:131-133): state t+1 -> the next step's LDS tile; ring cells (what the
-                // neighbours read) -> memory every step, write-through; everything -> memory at the final step
-#pragma unroll
-                for (int n = 0; n < NTP; ++n) {
-                    const float mk = mkc[rr[n] * PTW + qq[n]];
-                    const bool ring = rr[n] == 0 || rr[n] == PTH - 1 || qq[n] == 0 || qq[n] == PTW - 1;
-                    const size_t o0 = (size_t)(ty0 + rr[n]) * W + tx0 + qq[n];
-                    unsigned long long* const xd = a.xch + (size_t)((t + 1) & 1) * a.xch_words + (size_t)tile * C * kRingCells +
-                                                   (ring ? ring_index(rr[n], qq[n]) : 0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ch = 4 * g + r;
-                        if (ch < CP) {
-                            const int zo = ch * PCS + (rr[n] + 1) * PRS + qq[n] + 4;
-                            const float xn = Zc[zo] + acc2[n][r] * mk;
-                            Zn[zo] = ch < C ? xn : 0.0f;
-                            if (ch < C && !(a.dbg & 2)) {
-                                if (last) dst[(size_t)ch * plane + o0] = xn;
-                                else if (ring) st_pair(xd + ch * kRingCells, xn, (int)(tag0 + (unsigned)(t + 1)));
-                            }
-                        }
-                    }
-                }
+                persist_mlp<K, NTP>(smem, P, lane, g, acc2, a.dbg);
+                persist_store<K, NTP, kRingCells>(a, G, S, g, rr, qq, acc2);
             };
-            bool stop;
-            {   // the halo of state t is in the LDS tile (bounded poll of the sync wave's LDS counter)
-                int spins = 0;
-                while (__hip_atomic_load(lflag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(1);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                stop = __hip_atomic_load(lflag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
-            }
-            if (stop) break;
+            if (persist_wait_halo(lflag, t)) break;
             // the tile's border ring first (+ 4 left-over interior cells): its stores are what the neighbours wait for
-            if (!(a.dbg & 4)) phase(std::integral_constant<int, 1>{}, 12 + wave, false);
+            if (!(a.dbg & 4)) phase(std::integral_constant<int, 1>{}, 12 + wave);
             // the next step's fire masks: one cell per compute thread (in the sync wave -- four Philox evaluations per lane -- they
             // cost the SIMD it shares with compute wave 0 a microsecond per step)
-            if (!last && !(a.dbg & 8)) fill_mask(t + 1, tid, 256);
+            if (!S.last && !(a.dbg & 8)) persist_fill_mask(a, MK, G.cell0, t + 1, tid, 256);
             // the interior needs no halo and hides the exchange: ring pairs stored -> fetched by the neighbours
-            phase(std::integral_constant<int, 3>{}, 3 * wave, true);
+            phase(std::integral_constant<int, 3>{}, 3 * wave);
             __syncthreads();                    // Zn complete, Zc free
         }
         __builtin_amdgcn_s_waitcnt(0);   // the final step's stores (the whole tile)
@@ -479,10 +553,6 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
     using K = PersistCfg<CP, FC, HAS_COND>;
     using KM = PersistMsCfg<CP, FC, HAS_COND>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const W1L = smem + K::OFF_W1;
-    float* const W2L = smem + K::OFF_W2;
-    float* const B1L = smem + K::OFF_B1;
-    float* const B2L = smem + K::OFF_B2;
     float* const MK = smem + K::OFF_MK;
     float* const CN = smem + K::OFF_CN;
     float* const XC = smem + KM::OFF_XC;
@@ -491,85 +561,13 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
 
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ci = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int C = a.C, H = a.H, W = a.W, fc = a.fc, CC = a.c_cond, K1 = 4 * C + CC;
+    const int C = a.C, H = a.H, W = a.W;
     const int Hc = H >> 1, Wc = W >> 1;
-    const size_t plane = (size_t)H * W;
-    const unsigned tag0 = a.epoch << 12;
-    const int tiles_x = W / PTW, tiles_y = H / PTH;
-    const int tile = blockIdx.x, txi = tile % tiles_x, tyi = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int ty0 = tyi * PTH, tx0 = txi * PTW, cy0 = ty0 >> 1, cx0 = tx0 >> 1;
-    const size_t cell0 = (size_t)b * plane + (size_t)ty0 * W + tx0;
+    const PersistTile G = persist_tile(a);
+    const int ty0 = G.ty0, tx0 = G.tx0, cy0 = ty0 >> 1, cx0 = tx0 >> 1;
 
-    // ---- once per launch: weight images (as the single-scale kernel), conditioning, masks of step 0, the tile's cells -----------
-    {
-        constexpr int N1 = K::M1T * K::K1S * 64, N2 = K::K2S * 64, U1 = (N1 + kPT - 1) / kPT, U2 = (N2 + kPT - 1) / kPT;
-        float v1[U1], v2[U2];
-#pragma unroll
-        for (int u = 0; u < U1; ++u) {
-            const int idx = tid + kPT * u;
-            const int l = idx & 63, s_ = (idx >> 6) % K::K1S, m = (idx >> 6) / K::K1S;
-            const int gg = l >> 4, o = 16 * m + (l & 15);
-            long src = -1;
-            if (idx < N1 && o < fc) {
-                if (s_ < CP) {
-                    const int ch = (s_ & ~3) + gg;
-                    if (ch < C) src = (long)o * K1 + (s_ & 3) * C + ch;
-                } else if (gg < CC) src = (long)o * K1 + 4 * C + gg;
-            }
-            const float w = a.w1[src >= 0 ? src : 0];
-            v1[u] = src >= 0 ? w : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < U2; ++u) {
-            const int idx = tid + kPT * u;
-            const int l = idx & 63, s_ = idx >> 6;
-            const int gg = l >> 4, o = l & 15, k = 16 * (s_ >> 2) + 4 * gg + (s_ & 3);
-            const bool ok = idx < N2 && o < C && k < fc;
-            const float w = a.w2[ok ? (long)o * fc + k : 0];
-            v2[u] = ok ? w : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < U1; ++u)
-            if (tid + kPT * u < N1) W1L[tid + kPT * u] = v1[u];
-#pragma unroll
-        for (int u = 0; u < U2; ++u)
-            if (tid + kPT * u < N2) W2L[tid + kPT * u] = v2[u];
-    }
-    for (int idx = tid; idx < FC; idx += kPT) B1L[idx] = idx < fc ? a.b1[idx] : 0.0f;
-    if (tid < 16) B2L[tid] = tid < C ? a.b2[tid] : 0.0f;
-    if (tid < 4) lflag[tid] = 0;
-    if (HAS_COND) {
-        for (int i = tid; i < 4 * PTH * PTW; i += kPT) {
-            const int cc = i / (PTH * PTW), c = i % (PTH * PTW);
-            CN[i] = cc < CC ? a.cond[((size_t)b * CC + cc) * plane + (size_t)(ty0 + c / PTW) * W + tx0 + c % PTW] : 0.0f;
-        }
-    }
-    auto fill_mask = [&](int t, int first, int stride) {
-        float* const mk = MK + (t & 1) * (PTH * PTW);
-        const size_t cells = (size_t)a.B * plane;
-        for (int c = first; c < PTH * PTW; c += stride) {
-            const size_t cell = cell0 + (size_t)(c / PTW) * W + c % PTW;
-            float uu;
-            if (a.u) {
-                if (a.u_bits) uu = ((reinterpret_cast<const uint32_t*>(a.u)[(size_t)t * ((cells + 31) / 32) + (cell >> 5)] >> (unsigned)(cell & 31)) & 1u) ? 1.0f : 0.0f;
-                else uu = a.u[(size_t)t * cells + cell];
-            } else uu = nca_philox_cell(a.seed, a.step0 + (uint64_t)t, cell);
-            mk[c] = floorf(uu + a.rate);
-        }
-    };
-    fill_mask(0, tid, kPT);
-    {
-        float* const Z0 = smem + K::OFF_Z;
-        const float* const xb = a.x_in + (size_t)b * C * plane;
-        for (int i = tid; i < CP * PTH * (PTW / 4); i += kPT) {
-            const int f4 = i % (PTW / 4), r = (i / (PTW / 4)) % PTH, ch = i / (PTH * (PTW / 4));
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ch < C) v = *reinterpret_cast<const f32x4*>(xb + (size_t)ch * plane + (size_t)(ty0 + r) * W + tx0 + 4 * f4);
-            *reinterpret_cast<f32x4*>(Z0 + ch * PCS + (r + 1) * PRS + 4 + 4 * f4) = v;
-        }
-    }
+    persist_prologue<K>(a, smem, G);
     __syncthreads();
-    int* const abort_w = a.flags;
     // 2 x 2 mean of tile-local coarse cell (i, j) of channel ch from an LDS state tile -- upsample_bilinear2d's own expression for the
     // exact x1/2 case, as dynca_coarse_perceive_kernel evaluates it
     auto mean4 = [&](const float* Zt, int ch, int i, int j) -> float {
@@ -589,7 +587,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
         int* const TBL = reinterpret_cast<int*>(smem + KM::OFF_TBL);
         {
             float* const Z0 = smem + K::OFF_Z;
-            const float* const src = a.x_in + (size_t)b * C * plane;
+            const float* const src = a.x_in + (size_t)G.b * C * G.plane;
 #pragma unroll 1
             for (int k = 0; k < NIT; ++k) {
                 const bool coarse = k >= K::NLD;
@@ -598,10 +596,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                 if (!coarse) {
                     const int hc = j % kHalo, ch = j / kHalo;
                     int r, q;
-                    if (hc < PTW + 2) { r = 0; q = hc; }
-                    else if (hc < 2 * (PTW + 2)) { r = PROWS - 1; q = hc - (PTW + 2); }
-                    else if (hc < 2 * (PTW + 2) + PTH) { r = hc - 2 * (PTW + 2) + 1; q = 0; }
-                    else { r = hc - 2 * (PTW + 2) - PTH + 1; q = PTW + 1; }
+                    fine_halo_cell(hc, r, q);
                     if (j < kHalo * CP) {
                         const int dsto = ch * PCS + r * PRS + q + 3;
                         const int sy = nca_pad_index(ty0 - 1 + r, H, a.pad_mode), sx = nca_pad_index(tx0 - 1 + q, W, a.pad_mode);
@@ -612,8 +607,8 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                                 w1 = ch * PCS + (sy - ty0 + 1) * PRS + (sx - tx0) + 4;
                             } else {
                                 kind = 3;
-                                w1 = (((b * tiles_y + sy / PTH) * tiles_x + sx / PTW) * C + ch) * kXchMS + ring_index(sy % PTH, sx % PTW);
-                                Z0[dsto] = src[(size_t)ch * plane + (size_t)sy * W + sx];
+                                w1 = (((G.b * G.tiles_y + sy / PTH) * G.tiles_x + sx / PTW) * C + ch) * kXchMS + ring_index(sy % PTH, sx % PTW);
+                                Z0[dsto] = src[(size_t)ch * G.plane + (size_t)sy * W + sx];
                             }
                         }
                         if (kind == 1) { Z0[dsto] = 0.0f; Z0[CP * PCS + dsto] = 0.0f; }      // constant padding / padded channels: zero once, both buffers
@@ -635,8 +630,8 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                                 w1 = ch * XCS + (sy - cy0 + 2) * XCR + (sx - cx0) + 2;
                             } else {
                                 kind = 3;
-                                w1 = (((b * tiles_y + sy / 8) * tiles_x + sx / 8) * C + ch) * kXchMS + kRingCells + coarse_ring_index(sy % 8, sx % 8);
-                                const float* const p0 = src + (size_t)ch * plane + (size_t)(2 * sy) * W + 2 * sx;
+                                w1 = (((G.b * G.tiles_y + sy / 8) * G.tiles_x + sx / 8) * C + ch) * kXchMS + kRingCells + coarse_ring_index(sy % 8, sx % 8);
+                                const float* const p0 = src + (size_t)ch * G.plane + (size_t)(2 * sy) * W + 2 * sx;
                                 XC[dsto] = 0.5f * (0.5f * p0[0] + 0.5f * p0[1]) + 0.5f * (0.5f * p0[W] + 0.5f * p0[W + 1]);
                             }
                         }
@@ -669,7 +664,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
         auto stage_global = [&](int tt) -> bool {
             float* const Zt = smem + K::OFF_Z + (tt & 1) * (CP * PCS);
             const unsigned long long* const xs = a.xch + (size_t)(tt & 1) * a.xch_words;
-            const unsigned want = tag0 + (unsigned)tt;
+            const unsigned want = G.tag0 + (unsigned)tt;
             float hv[NIT];
             for (int spins = 0;;) {
                 bool stale = false;
@@ -682,9 +677,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                     stale = stale || (unsigned)(w >> 32) != want;
                 }
                 if (!__any(stale)) break;
-                bool give_up = ++spins >= (1 << 15);
-                if ((spins & 31) == 0) give_up = give_up || __any(lane == 8 && (unsigned)__hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.epoch);
-                if (give_up) return false;
+                if (persist_poll_expired(a, lane, spins)) return false;
                 __builtin_amdgcn_s_sleep(1);
             }
 #pragma unroll
@@ -697,16 +690,8 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
             }
             return true;
         };
-        auto post_halo = [&](int value, bool stop_) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            if (lane == 0) {
-                if (stop_) __hip_atomic_store(lflag + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_store(lflag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        };
         stage_own(0);
-        post_halo(1, false);
+        persist_post_halo(lflag, lane, 1, false);
         bool stop = false;
         for (int t = 0; t < a.T; ++t) {
             __syncthreads();      // barrier P: the compute waves have built the coarse perception of state t (XC is free again)
@@ -714,7 +699,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
             if (t + 1 < a.T && !(a.dbg & 1)) {
                 // this tile's coarse cells within 2 of its border, for the neighbours
                 const float* const Zn = smem + K::OFF_Z + ((t + 1) & 1) * (CP * PCS);
-                unsigned long long* const xd = a.xch + (size_t)((t + 1) & 1) * a.xch_words + (size_t)tile * C * kXchMS + kRingCells;
+                unsigned long long* const xd = a.xch + (size_t)((t + 1) & 1) * a.xch_words + (size_t)G.tile * C * kXchMS + kRingCells;
 #pragma unroll
                 for (int k = 0; k < KM::NPB; ++k) {
                     const int j = lane + 64 * k, kc = j % kCoarseRing, ch = j / kCoarseRing;
@@ -723,38 +708,24 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                     else if (kc < 32) { i = 6 + ((kc - 16) >> 3); jj = kc & 7; }
                     else if (kc < 40) { i = 2 + ((kc - 32) >> 1); jj = (kc - 32) & 1; }
                     else { i = 2 + ((kc - 40) >> 1); jj = 6 + ((kc - 40) & 1); }
-                    if (j < kCoarseRing * CP && ch < C) st_pair(xd + ch * kXchMS + kc, mean4(Zn, ch, i, jj), (int)(tag0 + (unsigned)(t + 1)));
+                    if (j < kCoarseRing * CP && ch < C) st_pair(xd + ch * kXchMS + kc, mean4(Zn, ch, i, jj), (int)(G.tag0 + (unsigned)(t + 1)));
                 }
                 // ... and the neighbours' data of state t + 1 as it arrives (fine ring -> the other LDS buffer's halo, coarse -> XC)
                 stop = !stage_global(t + 1);
-                if (stop && lane == 0) {
-                    if (a.err) __hip_atomic_fetch_or(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(abort_w, (int)a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                if (stop) persist_raise_abort(a, lane);
             }
             __syncthreads();      // barrier E: state t + 1 complete in LDS
             if (t + 1 < a.T) {
                 if (!stop && !(a.dbg & 1)) stage_own(t + 1);
-                post_halo(t + 2, stop);
+                persist_post_halo(lflag, lane, t + 2, stop);
             }
             if (stop) break;
         }
     } else {
         // =================================== compute waves =======================================================================
         for (int t = 0; t < a.T; ++t) {
-            float* const dst = a.x_out + (size_t)b * C * plane;
-            const float* const Zc = smem + K::OFF_Z + (t & 1) * (CP * PCS);
-            float* const Zn = smem + K::OFF_Z + ((t + 1) & 1) * (CP * PCS);
-            const float* const mkc = MK + (t & 1) * (PTH * PTW);
-            const bool last = t + 1 == a.T;
-            bool stop;
-            {
-                int spins = 0;
-                while (__hip_atomic_load(lflag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(1);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                stop = __hip_atomic_load(lflag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
-            }
-            if (stop) break;
+            const PersistStep S = persist_step<K>(a, G, smem, t);
+            if (persist_wait_halo(lflag, t)) break;
             // ---- coarse perception of state t on coarse cells -1 .. 8 (index-clamped at the image border), from xc -------------------
 #pragma unroll
             for (int k = 0; k < KM::NPC; ++k) {
@@ -783,7 +754,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                 float P[NTP][K::K1S];
 #pragma unroll
                 for (int cq4 = 0; cq4 < CP / 4; ++cq4) {
-                    const float* const zc = Zc + (4 * cq4 + g) * PCS + 3;
+                    const float* const zc = S.Zc + (4 * cq4 + g) * PCS + 3;
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) {
                         float nbv[3][3];
@@ -808,77 +779,16 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                         }
                     }
                 }
-                if (HAS_COND) {
+                if constexpr (HAS_COND) {
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) P[n][CP] = CN[g * PTH * PTW + rr[n] * PTW + qq[n]];
                 }
                 f32x4 acc2[NTP];
-                {
-                    const f32x4 bias = *reinterpret_cast<const f32x4*>(B2L + 4 * g);
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n) acc2[n] = bias;
-                }
-                float wa1[K::K1S], wa2[4];
-                f32x4 bias1;
-                auto fetch = [&](int m) {
-                    const float* const w1m = W1L + m * K::K1S * 64 + lane;
-#pragma unroll
-                    for (int s_ = 0; s_ < K::K1S; ++s_) wa1[s_] = w1m[s_ * 64];
-                    const float* const w2m = W2L + (4 * m) * 64 + lane;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) wa2[r] = w2m[r * 64];
-                    bias1 = *reinterpret_cast<const f32x4*>(B1L + 16 * m + 4 * g);
-                };
-                fetch(0);
-#pragma unroll 1
-                for (int m = 0; m < K::M1T; ++m) {
-                    f32x4 acc1[NTP];
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n) acc1[n] = bias1;
-#pragma unroll
-                    for (int s_ = 0; s_ < K::K1S; ++s_)
-#pragma unroll
-                        for (int n = 0; n < NTP; ++n) acc1[n] = nca_mfma(wa1[s_], P[n][s_], acc1[n]);
-                    float w2c[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) w2c[r] = wa2[r];
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (m + 1 < K::M1T) fetch(m + 1);
-                    float h[NTP][4];
-#pragma unroll
-                    for (int n = 0; n < NTP; ++n)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) h[n][r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                        for (int n = 0; n < NTP; ++n) acc2[n] = nca_mfma(w2c[r], h[n][r], acc2[n]);
-                }
-#pragma unroll
-                for (int n = 0; n < NTP; ++n) {
-                    const float mk = mkc[rr[n] * PTW + qq[n]];
-                    const bool ring = rr[n] == 0 || rr[n] == PTH - 1 || qq[n] == 0 || qq[n] == PTW - 1;
-                    const size_t o0 = (size_t)(ty0 + rr[n]) * W + tx0 + qq[n];
-                    unsigned long long* const xd = a.xch + (size_t)((t + 1) & 1) * a.xch_words + (size_t)tile * C * kXchMS +
-                                                   (ring ? ring_index(rr[n], qq[n]) : 0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ch = 4 * g + r;
-                        if (ch < CP) {
-                            const int zo = ch * PCS + (rr[n] + 1) * PRS + qq[n] + 4;
-                            const float xn = Zc[zo] + acc2[n][r] * mk;
-                            Zn[zo] = ch < C ? xn : 0.0f;
-                            if (ch < C) {
-                                if (last) dst[(size_t)ch * plane + o0] = xn;
-                                else if (ring) st_pair(xd + ch * kXchMS, xn, (int)(tag0 + (unsigned)(t + 1)));
-                            }
-                        }
-                    }
-                }
+                persist_mlp<K, NTP>(smem, P, lane, g, acc2, a.dbg);
+                persist_store<K, NTP, kXchMS>(a, G, S, g, rr, qq, acc2);
             };
             phase(std::integral_constant<int, 3>{}, 3 * wave);      // the 192-cell border band: what the neighbours' next step needs
-            if (!last) fill_mask(t + 1, tid, 256);
+            if (!S.last) persist_fill_mask(a, MK, G.cell0, t + 1, tid, 256);
             __syncthreads();      // barrier A
             phase(std::integral_constant<int, 1>{}, 12 + wave);     // the 8 x 8 centre, under the exchange
             __syncthreads();      // barrier E
@@ -887,40 +797,21 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
     }
 }
 
-template <int CP, int FC, bool HAS_COND>
-hipError_t launch_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    using KM = PersistMsCfg<CP, FC, HAS_COND>;
-    auto kern = dynca_persist_ms_kernel<CP, FC, HAS_COND>;
-    const size_t lds = (size_t)KM::LDS_FLOATS * sizeof(float) > 81 * 1024 ? (size_t)KM::LDS_FLOATS * sizeof(float) : (size_t)81 * 1024;
-    static NcaLdsAttr attr;
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
-    const int ntiles = a.B * (a.H / PTH) * (a.W / PTW);
-    static std::atomic<int> occ[kNcaMaxDevices];
-    int per_cu = occ[nca_device_index()].load(std::memory_order_relaxed);
-    if (per_cu == 0) {
-        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), kPT, lds); e != hipSuccess) return e;
-        occ[nca_device_index()].store(per_cu > 0 ? per_cu : -1, std::memory_order_relaxed);
-    }
-    *fits = (long)per_cu * nca_cu_count() >= ntiles;
-    if (!*fits || query_only) return hipSuccess;
-    const int grid = g_drop_tiles > 0 && g_drop_tiles < ntiles ? ntiles - g_drop_tiles : ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kPT), lds, st, a);
-    return hipGetLastError();
-}
-
-template <int CP, int FC, bool HAS_COND>
-hipError_t launch_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    using K = PersistCfg<CP, FC, HAS_COND>;
-    auto kern = dynca_persist_kernel<CP, FC, HAS_COND>;
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+// One launcher for every instantiation of both kernels; the LDS attribute and the occupancy cache are statics of launch_persist<KERN>,
+// i.e. per kernel instantiation.
+template <auto KERN>
+hipError_t launch_persist(int lds_floats, const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
+    const void* const kern = reinterpret_cast<const void*>(KERN);
     // more than half a CU's LDS: ONE workgroup per CU (two tiles on one CU would share its matrix pipes while another CU idles)
-    const size_t lds = (size_t)K::LDS_FLOATS * sizeof(float) > 81 * 1024 ? (size_t)K::LDS_FLOATS * sizeof(float) : (size_t)81 * 1024;
+    const size_t lds = (size_t)lds_floats * sizeof(float) > 81 * 1024 ? (size_t)lds_floats * sizeof(float) : (size_t)81 * 1024;
     static NcaLdsAttr attr;
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
+    if (hipError_t e = attr.ensure(kern, lds); e != hipSuccess) return e;
     const int ntiles = a.B * (a.H / PTH) * (a.W / PTW);
     static std::atomic<int> occ[kNcaMaxDevices];     // workgroups per CU of this instantiation (queried once per device)
     int per_cu = occ[nca_device_index()].load(std::memory_order_relaxed);
     if (per_cu == 0) {
-        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), kPT, lds); e != hipSuccess) return e;
+        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kPT, lds); e != hipSuccess) return e;
         occ[nca_device_index()].store(per_cu > 0 ? per_cu : -1, std::memory_order_relaxed);
     }
     *fits = (long)per_cu * nca_cu_count() >= ntiles;      // every workgroup must be resident at once (neighbours wait for each other)
@@ -928,8 +819,29 @@ hipError_t launch_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool que
     // test hook (ncahip_debug_persist_drop_tiles): launch only the first tiles -- the others' neighbours never hear from them, their
     // bounded polls expire, the launch drains and the sticky error word carries bit 1: what a non-resident workgroup looks like
     const int grid = g_drop_tiles > 0 && g_drop_tiles < ntiles ? ntiles - g_drop_tiles : ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kPT), lds, st, a);
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(kPT), lds, st, a);
     return hipGetLastError();
+}
+
+template <bool MS, int CP, int FC, bool HAS_COND>
+hipError_t launch_cfg(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
+    if constexpr (MS) return launch_persist<dynca_persist_ms_kernel<CP, FC, HAS_COND>>(PersistMsCfg<CP, FC, HAS_COND>::LDS_FLOATS, a, st, query_only, fits);
+    else return launch_persist<dynca_persist_kernel<CP, FC, HAS_COND>>(PersistCfg<CP, FC, HAS_COND>::LDS_FLOATS, a, st, query_only, fits);
+}
+
+int persist_dbg() {
+    static const int dbg = getenv("NCAHIP_PERSIST_DBG") ? atoi(getenv("NCAHIP_PERSIST_DBG")) : 0;
+    return dbg;
+}
+
+template <bool MS>
+hipError_t dispatch_persist(const NcaDyncaPersistArgs& a_in, hipStream_t st, bool query_only, bool* fits) {
+    NcaDyncaPersistArgs a = a_in;
+    a.err = nca_error_word_device();
+    a.dbg = persist_dbg();
+    const bool small = a.C <= 12 && a.fc <= 96;
+    if (a.c_cond > 0) return small ? launch_cfg<MS, 12, 96, true>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, true>(a, st, query_only, fits);
+    return small ? launch_cfg<MS, 12, 96, false>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, false>(a, st, query_only, fits);
 }
 
 }  // namespace
@@ -940,23 +852,13 @@ bool nca_dynca_persist_shape_ok(int B, int C, int H, int W, int fc, int c_cond) 
            (long)B * (H / PTH) * (W / PTW) <= 4096 && (size_t)C * H * W < ((size_t)1 << 31);
 }
 int nca_dynca_persist_tiles(int B, int H, int W) { return B * (H / PTH) * (W / PTW); }
-
-hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a_in, hipStream_t st, bool query_only, bool* fits) {
-    NcaDyncaPersistArgs a = a_in;
-    a.err = nca_error_word_device();
-    static const int dbg = getenv("NCAHIP_PERSIST_DBG") ? atoi(getenv("NCAHIP_PERSIST_DBG")) : 0;
-    a.dbg = dbg;
-    const bool small = a.C <= 12 && a.fc <= 96;
-    if (a.c_cond > 0) return small ? launch_persist_ms<12, 96, true>(a, st, query_only, fits) : launch_persist_ms<16, 128, true>(a, st, query_only, fits);
-    return small ? launch_persist_ms<12, 96, false>(a, st, query_only, fits) : launch_persist_ms<16, 128, false>(a, st, query_only, fits);
+size_t nca_dynca_persist_xch_pairs(int B, int C, int H, int W, bool two_scale) {
+    return (size_t)nca_dynca_persist_tiles(B, H, W) * C * (two_scale ? kXchMS : kRingCells);
 }
 
-hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a_in, hipStream_t st, bool query_only, bool* fits) {
-    NcaDyncaPersistArgs a = a_in;
-    a.err = nca_error_word_device();
-    static const int dbg = getenv("NCAHIP_PERSIST_DBG") ? atoi(getenv("NCAHIP_PERSIST_DBG")) : 0;
-    a.dbg = dbg;
-    const bool small = a.C <= 12 && a.fc <= 96;
-    if (a.c_cond > 0) return small ? launch_persist<12, 96, true>(a, st, query_only, fits) : launch_persist<16, 128, true>(a, st, query_only, fits);
-    return small ? launch_persist<12, 96, false>(a, st, query_only, fits) : launch_persist<16, 128, false>(a, st, query_only, fits);
+hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
+    return dispatch_persist<false>(a, st, query_only, fits);
+}
+hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
+    return dispatch_persist<true>(a, st, query_only, fits);
 }

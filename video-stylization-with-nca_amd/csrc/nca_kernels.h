@@ -88,11 +88,14 @@ struct NcaDyncaPersistArgs {
     unsigned* err;       // sticky error word (bit 1: a neighbour poll expired)
     int u_bits;
     int dbg;             // diagnostic knobs (NCAHIP_PERSIST_DBG, timing experiments only -- results are then NOT valid): bit 0 no neighbour
-                         // polls / halo loads, bit 1 no state stores, bit 2 no ring phase, bit 3 no mask refill, bit 4 no MFMA chains
+                         // polls / halo loads, bit 1 no state stores, bit 2 no ring phase, bit 3 no mask refill, bit 4 no MFMA chains.
+                         // The single-scale kernel honours all five; the two-scale kernel bits 0, 1 and 4 (1 and 4 sit in shared code)
 };
 void nca_set_persist_drop_tiles(int n);   // test hook: the persistent launch leaves out its last n tiles (their neighbours' polls expire)
 bool nca_dynca_persist_shape_ok(int B, int C, int H, int W, int fc, int c_cond);
 int nca_dynca_persist_tiles(int B, int H, int W);
+// (value, tag) pairs per parity of the ring exchange: tiles x C x 60 fine ring cells (+ 48 coarse means: two_scale)
+size_t nca_dynca_persist_xch_pairs(int B, int C, int H, int W, bool two_scale);
 // query_only: only decide whether every workgroup can be co-resident on the current device (*fits)
 hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
 // two-scale perception (perception_scales = [0, 1]): exchanges 108 pairs per channel and tile (60 fine ring cells + 48 coarse means)
