@@ -537,27 +537,84 @@ def test_dynca_wide_hidden_forward(ops, C, fc, cc):
     assert rel_err(got1.cpu(), ref1) < REL_TOL
 
 
-@pytest.mark.parametrize("ma,nb1,nb2,B,H,W", [(128, 64, 3, 2, 16, 24), (96, 48, 3, 3, 9, 13), (16, 128, 0, 2, 16, 24),
-                                               (12, 96, 0, 1, 7, 5), (64, 80, 0, 1, 64, 64), (32, 100, 0, 2, 10, 10)])
-def test_gram_rows(ops, ma, nb1, nb2, B, H, W):
-    """ncahip_gram_rows_f32 (the DyNCA weight-gradient products, cell axis as K) against a float64 contraction: row counts
-    that do not fill the 16-row tiles, cell counts that do not fill the 64-cell chunks, the two-tensor B operand."""
+def _gram_inputs(ma, nb1, nb2, B, H, W, positive_a=False):
     g = torch.Generator().manual_seed(ma + nb1)
     a = torch.randn(B, ma, H, W, generator=g)
+    if positive_a:                                        # non-zero mean: the row sums carry signal
+        a = F.relu(a) + 0.1
     b1 = torch.randn(B, nb1, H, W, generator=g)
     b2 = torch.randn(B, nb2, H, W, generator=g) if nb2 else None
+    return a.to(DEV), b1.to(DEV), None if b2 is None else b2.to(DEV)
+
+
+def _gram_rows_check(ops, a, b1, b2, tol_prod=1e-5, tol_rs=1e-5):
+    """products and row sums of ops.gram_rows against a float64 contraction (bounds relative to the largest reference entry), the
+    fixed summation order, and the accumulate mode: products AND the row-sum tail of the caller's vector"""
+    ma, nb = a.shape[1], b1.shape[1] + (0 if b2 is None else b2.shape[1])
     bb = b1 if b2 is None else torch.cat([b1, b2], dim=1)
     ref = torch.einsum("bihw,bjhw->ij", a.double(), bb.double())
-    prod, rsum = ops.gram_rows(a.to(DEV), b1.to(DEV), None if b2 is None else b2.to(DEV))
+    prod, rsum = ops.gram_rows(a, b1, b2)
     scale = float(ref.abs().max())
-    assert float((prod.cpu().double() - ref).abs().max()) <= 1e-5 * scale
+    assert float((prod.double() - ref).abs().max()) <= tol_prod * scale
     rs_ref = a.double().sum(dim=(0, 2, 3))
-    assert float((rsum.cpu().double() - rs_ref).abs().max()) <= 1e-5 * max(1.0, float(rs_ref.abs().max()))
-    prod2, _ = ops.gram_rows(a.to(DEV), b1.to(DEV), None if b2 is None else b2.to(DEV))
-    assert torch.equal(prod, prod2)                      # fixed summation order
-    acc = torch.ones(ma * (nb1 + nb2) + ma, device=DEV)   # accumulate mode adds to the caller's vector
-    ops.gram_rows(a.to(DEV), b1.to(DEV), None if b2 is None else b2.to(DEV), out=acc)
-    assert torch.allclose(acc[:ma * (nb1 + nb2)].view(ma, -1), prod + 1.0, rtol=0, atol=1e-5 * scale)
+    rs_scale = max(1.0, float(rs_ref.abs().max()))
+    assert float((rsum.double() - rs_ref).abs().max()) <= tol_rs * rs_scale
+    prod2, rsum2 = ops.gram_rows(a, b1, b2)
+    assert torch.equal(prod, prod2) and torch.equal(rsum, rsum2)   # fixed summation order
+    acc = torch.ones(ma * nb + ma, device=DEV)            # accumulate mode adds to the caller's vector
+    ops.gram_rows(a, b1, b2, out=acc)
+    assert torch.allclose(acc[:ma * nb].view(ma, -1), prod + 1.0, rtol=0, atol=1e-5 * scale)
+    assert torch.allclose(acc[ma * nb:], rsum + 1.0, rtol=0, atol=1e-5 * rs_scale)
+    return ref, rs_ref
+
+
+@pytest.mark.parametrize("ma,nb1,nb2,B,H,W", [(128, 64, 3, 2, 16, 24), (96, 48, 3, 3, 9, 13), (16, 128, 0, 2, 16, 24),
+                                               (12, 96, 0, 1, 7, 5), (64, 80, 0, 1, 64, 64), (32, 100, 0, 2, 10, 10),
+                                               (5, 3, 0, 1, 1, 1), (40, 64, 3, 1, 1, 1), (1, 1, 0, 2, 3, 5)])
+def test_gram_rows(ops, ma, nb1, nb2, B, H, W):
+    """ncahip_gram_rows_f32 (the DyNCA weight-gradient products, cell axis as K) against a float64 contraction: row counts
+    that do not fill the 16-row tiles, cell counts that do not fill the 64-cell chunks, the two-tensor B operand; a single cell
+    (HW = 1, B = 1) and a single row against a single row (ma = nb = 1)."""
+    _gram_rows_check(ops, *_gram_inputs(ma, nb1, nb2, B, H, W))
+
+
+# (ma, nb1, nb2): <2,9>, <1,9>, the small-ma fall-through to <1,9> (ma <= 32 but nb > 128), and nb = 144 = 16 NB_T, where the ones
+# column does not fit and the vector-add form must be taken even when NCAHIP_GRAM_ONES=1 asks for it
+GRAM_WIDE = [(128, 128, 3), (40, 80, 4), (8, 128, 4), (128, 141, 3)]
+
+
+@pytest.mark.parametrize("ma,nb1,nb2,B,H,W,ones", [(*s, 3, 9, 13, o) for s in GRAM_WIDE for o in (None, "0", "1")] +
+                         [(128, 64, 3, 2, 16, 24, "1")])       # nb = 67 (<2,5>): the ones column is not its default
+def test_gram_rows_row_sum_forms(ops, monkeypatch, ma, nb1, nb2, B, H, W, ones):
+    """gram_rows_kernel<*,9,true> and both forms of the row sums (vector adds beside the MFMAs / one more B column of ones): the
+    launcher reads NCAHIP_GRAM_ONES per launch (tools/ab_gram.py relies on that), unset = the template's default"""
+    if ones is None:
+        monkeypatch.delenv("NCAHIP_GRAM_ONES", raising=False)
+    else:
+        monkeypatch.setenv("NCAHIP_GRAM_ONES", ones)
+    _gram_rows_check(ops, *_gram_inputs(ma, nb1, nb2, B, H, W, positive_a=True))
+
+
+def test_gram_rows_grid_stride(ops):
+    """more chunks than workgroups: the grid-stride loop with the next chunk prefetched.  The grid is min(chunks, 2 CUs); ten
+    workgroups take a second chunk, HW is no multiple of 64.  A dropped or doubled chunk moves a row sum by 1 / 500.  K = B HW is
+    about 3e4 here, so the bound is ten times the error of the plain fp32 torch contraction of the same inputs against float64, or
+    1e-5, whichever is larger (the convention of tests/test_gpu_slw.py and tests/test_gpu_ot_moment.py)."""
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    B, ma, nb, HW = 2, 16, 20, 64 * (cus + 4) + 37
+    assert B * ((HW + 63) // 64) > 2 * cus and HW % 64 != 0
+    a, b1, _ = _gram_inputs(ma, nb, 0, B, 1, HW, positive_a=True)
+    ref = torch.einsum("bihw,bjhw->ij", a.double(), b1.double())
+    rs_ref = a.double().sum(dim=(0, 2, 3))
+    e_prod = float((torch.einsum("bihw,bjhw->ij", a, b1).double() - ref).abs().max()) / float(ref.abs().max())
+    e_rs = float((a.sum(dim=(0, 2, 3)).double() - rs_ref).abs().max()) / float(rs_ref.abs().max())
+    tol_prod, tol_rs = max(10 * e_prod, 1e-5), max(10 * e_rs, 1e-5)
+    prod, rsum = ops.gram_rows(a, b1)
+    g_prod = float((prod.double() - ref).abs().max()) / float(ref.abs().max())
+    g_rs = float((rsum.double() - rs_ref).abs().max()) / float(rs_ref.abs().max())
+    print(f"\ngram_rows grid stride, {B * ((HW + 63) // 64)} chunks on {2 * cus} workgroups: products {g_prod:.2e} (fp32 torch "
+          f"{e_prod:.2e}, bound {tol_prod:.2e}), row sums {g_rs:.2e} (fp32 torch {e_rs:.2e}, bound {tol_rs:.2e})")
+    _gram_rows_check(ops, a, b1, None, tol_prod, tol_rs)
 
 
 @pytest.mark.parametrize("C,fc,cc,H,W", [(16, 128, 3, 24, 40), (12, 96, 0, 13, 36), (8, 64, 2, 9, 20)])
