@@ -448,6 +448,47 @@ int ncahip_cond_grow_fwd_persist_f32(float *states, uint8_t *pre, int ring, int 
  * (The persistent ConditionedNCA grow does not take it.) */
 int ncahip_debug_persist_drop_tiles(int n);
 
+/* ---- a whole clip per call: frame front end, DyNCA steps, image output -------------------------------------------------
+ * ConditioneDyNCA/utils/misc/video_utils.py:50-83 (`save_video`): for every target frame, steps_per_frame times
+ * { forward_nsteps(h, step_n, cond_img = grey(frame)); emit clip(rgb, -1, 1) * 0.5 + 0.5 }, the state carried across frames.
+ * Three entry points: the conditioning of all frames of a call in one pass, one output image from a state, and the driver that
+ * enqueues the existing step entry points and the image output for F frames.  Nothing here synchronises.
+ *
+ * Formats of frames in and images out: */
+#define NCAHIP_CLIP_F32_NCHW 0   /* float32, channels first: frames [F,B,3,H,W] in network range [-1, 1]; images [B,c_out,H,W] in [0, 1] */
+#define NCAHIP_CLIP_U8_NHWC  1   /* uint8, channels last (what decoders and encoders use): frames [F,B,H,W,3]; images [B,H,W,c_out]     */
+/* ncahip_clip_cond: cond [F,B,3,H,W] = EdgeExtractor(grey(frame)) (dynca.py:204-213; k3 [3][9], zero padding and apply_tanh as
+ *   ncahip_edge_extractor_f32), grey = gray_r * r + gray_g * g + gray_b * b: (1/3, 1/3, 1/3) is the reference's RGBToGrayscale
+ *   (utils/misc/preprocess_texture.py:178-179, the channel mean), (0.2989, 0.587, 0.114) the ITU-R 601 luma.  uint8 frames are
+ *   widened as preprocess_texture.py:28, :54: v = float(u8) / 255.0f (a true division), then v * 2 - 1.  Every input pixel is read once
+ *   per workgroup (16 x 64 tile + halo in LDS).  ncahip_clip_cond_workspace: bytes of cond (host arithmetic; 0 for a non-positive size).
+ * ncahip_clip_emit: img = (clamp(2 * state[:, :c_out], -1, 1) + 1) / 2 (video_utils.py:78-81, dynca.py:140-141), bit for bit the torch
+ *   expression; uint8 output = (uint8_t)(img * 255.0f), truncating as VideoWriter.add's np.uint8 (video_utils.py:26).  1 <= c_out <= 4,
+ *   c_out <= C.
+ * ncahip_dynca_clip_f32: for f in 0..F-1, j in 0..steps_per_frame-1, n = f * steps_per_frame + j: step_n DyNCA steps on the state with
+ *   cond[f] (c_cond = 3), then image n = ncahip_clip_emit(state) into images + n * (one image).
+ *   states: 2 slots of B*C*H*W floats; slot 0 holds the state on entry and on return, slot 1 is scratch.
+ *   u: NULL = in-kernel Philox, call n uses steps step0 + n * step_n ...; bit-packed masks (seed == NCAHIP_SEED_U_IS_BITS) or float
+ *   uniforms of all F * steps_per_frame * step_n steps laid end to end.
+ *   two_scale != 0: perception_scales = [0, 1] (the _ms_ entry points; pc_scratch [B,4C,H/2,W/2] required).
+ *   The steps are the library's existing entry points, unchanged: with persist_ws != NULL each call n first goes to
+ *   ncahip_dynca_nsteps_fwd_persist_f32 / _ms_f32 with epoch epoch0 + n (persist_ws as that entry point documents; NCAHIP_EINVAL when
+ *   epoch0 < 1 or epoch0 + F * steps_per_frame >= 2^20); from its first NCAHIP_ERANGE on, and always with persist_ws == NULL, the calls
+ *   run on ncahip_dynca_nsteps_fwd_f32 / _ms_f32 with ring 2 over `states`.  What those entry points cover, this one covers, with their
+ *   bits; what they refuse, it refuses with their code.
+ *   Arguments are checked on the host before anything is enqueued (null or overlapping buffers, F, steps_per_frame, step_n <= 0, c_out,
+ *   an unknown format, the epoch range: NCAHIP_EINVAL; shapes the step entry points refuse: their code); a set sticky error word refuses
+ *   the call with NCAHIP_EDEVICE, as the grow drivers do; the driver stops enqueuing at the first failing launch and returns its code. */
+size_t ncahip_clip_cond_workspace(int F, int B, int H, int W);
+int ncahip_clip_cond(const void *frames, int frame_fmt, const float *k3, float gray_r, float gray_g, float gray_b, int apply_tanh,
+                     float *cond, int F, int B, int H, int W, ncahip_stream_t stream);
+int ncahip_clip_emit(const float *state, void *img, int img_fmt, int B, int C, int c_out, int H, int W, ncahip_stream_t stream);
+int ncahip_dynca_clip_f32(float *states, const float *cond, void *images, int img_fmt, int F, int steps_per_frame, int step_n,
+                          const float *u, const float *w1, const float *b1, const float *w2, const float *b2,
+                          int B, int C, int c_out, int H, int W, int fc, int pad_mode, int two_scale, float update_rate,
+                          uint64_t seed, uint64_t step0, float *pc_scratch, void *persist_ws, size_t persist_bytes,
+                          unsigned epoch0, ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

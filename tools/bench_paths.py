@@ -12,6 +12,9 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
   dynca_train     DyNCA forward with history + backward (the C driver): C=16/fc=128, C=12/fc=96, C=32/fc=256 at 2x512^2
   big             working sets beyond the 256 MiB Infinity Cache: perception stencil and fused fp32 step at B=64
   video           B = 1 inference at 256^2 with the shipped video models' shapes, single- and two-scale
+  video_clip      a 64-frame clip at 256^2, B = 1, step_n = 8, edge conditioning, Philox masks (C = 12 / fc = 96 and C = 16 / fc = 128,
+                  single- and two-scale): the per-frame generator synthesize_video consumed to the end against stylize_clip with
+                  float32 frames in / float32 images out and uint8 in / uint8 out; host clock around a device synchronise
   trainer_default ConditionedNCATrainer at the reference's own defaults (C = 20, 64 x 64, batch 8, nca_steps [48, 96]): ms per iteration
   loss            the default objective (VGG16 features + batched OT + content + overflow) at 32 x 3 x 256^2, fp32 / bf16 features
   loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched, fused and fused_all alternating in one
@@ -486,6 +489,43 @@ def video_leg():
                  per_step_launch_us_per_step=res["per_step"][0] / T * 1e3, frac_f32_mfma=256 * 256 * T * flops / ms / 1e9 / 157.3)
 
 
+def video_clip_leg():
+    """What a user does with a trained model: a clip in, a stylised clip out (utils/misc/video_utils.py:50-83).  (a) the Python
+    generator ncahip.video.synthesize_video, one frame at a time; (b) ncahip.video.stylize_clip, float32 [F,3,H,W] in, float32 out;
+    (c) stylize_clip, uint8 [F,H,W,3] in, uint8 out.  Frames live on the device; every call seeds the state anew, so each timed call
+    does the same work.  The host part of (a) outlasts its device part, so each call is timed on the host clock between two device
+    synchronisations (timed_sync): median of 10 after 3 warm-ups."""
+    from ncahip import video
+    from ncahip.models.dynca import DyNCA
+    n_frames, step_n, S = 64, 8, 256
+    for C, fc in ((12, 96), (16, 128)):
+        for two in (False, True):
+            torch.manual_seed(0)
+            m = DyNCA(C, 3, fc_dim=fc, padding_mode="circular", conditioning="edges", edge_transform="tanh",
+                      perception_scales=[0, 1] if two else [0], device=torch.device(DEV))
+            m.mask_rng, m.mask_seed = "philox", 1
+            gen = torch.Generator().manual_seed(0)
+            u8 = torch.randint(0, 256, (n_frames, S, S, 3), generator=gen, dtype=torch.uint8).to(DEV)
+            f32 = (u8.float() / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2).contiguous()
+            frame_list = list(f32)
+
+            def loop():
+                for _ in video.synthesize_video(m, frame_list, step_n=step_n):
+                    pass
+
+            fns, names = [loop], ["synthesize_video"]
+            if hasattr(video, "stylize_clip"):
+                fns += [lambda: video.stylize_clip(m, f32, step_n=step_n), lambda: video.stylize_clip(m, u8, step_n=step_n, out_dtype=torch.uint8)]
+                names += ["stylize_clip_f32", "stylize_clip_u8"]
+            med, mn = timed_sync(fns)
+            ops.check_errors()
+            res = {n: dict(us_per_frame=a / n_frames * 1e3, min_us_per_frame=b / n_frames * 1e3, frames_per_s=n_frames / a * 1e3)
+                   for n, a, b in zip(names, med, mn)}
+            ratios = {n + "_over_synthesize_video": res[n]["us_per_frame"] / res["synthesize_video"]["us_per_frame"] for n in names[1:]}
+            emit(path="video_clip", C=C, fc=fc, two_scale=two, HW=[S, S], frames=n_frames, step_n=step_n, masks="philox",
+                 route=getattr(getattr(video, "stylize_clip", None), "last_path", None), **res, **ratios)
+
+
 def main(names):
     allp = not names
     if allp or "cond_train" in names:
@@ -532,6 +572,8 @@ def main(names):
             loss_slw_trace_leg(impl)
     if allp or "video" in names:
         video_leg()
+    if allp or "video_clip" in names:
+        video_clip_leg()
     if allp or "trainer_default" in names:
         trainer_default_leg()
 

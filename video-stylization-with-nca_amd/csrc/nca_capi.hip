@@ -402,6 +402,124 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* 
     return 0;
 }
 
+// ---- a whole clip per call (video_utils.py:50-83): conditioning of every frame, the existing step entry points, image output ----
+static bool clip_fmt_ok(int fmt) { return fmt == NCAHIP_CLIP_F32_NCHW || fmt == NCAHIP_CLIP_U8_NHWC; }
+static size_t clip_fmt_bytes(int fmt) { return fmt == NCAHIP_CLIP_U8_NHWC ? 1 : sizeof(float); }
+static bool clip_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + bn && pb < pa + an;
+}
+
+size_t ncahip_clip_cond_workspace(int F, int B, int H, int W) {
+    if (F <= 0 || !dims_ok(B, 3, H, W)) return 0;
+    return (size_t)F * B * 3 * H * W * sizeof(float);
+}
+
+int ncahip_clip_cond(const void* frames, int frame_fmt, const float* k3, float gray_r, float gray_g, float gray_b, int apply_tanh, float* cond,
+                     int F, int B, int H, int W, ncahip_stream_t stream) {
+    if (!frames || !k3 || !cond) return fail(NCAHIP_EINVAL, "clip_cond: null pointer");
+    if (!clip_fmt_ok(frame_fmt)) return fail(NCAHIP_EINVAL, "clip_cond: unknown frame format %d", frame_fmt);
+    if (F <= 0 || !dims_ok(B, 3, H, W) || (size_t)F * B > 0x7fffffffu) return fail(NCAHIP_EINVAL, "clip_cond: bad size");
+    const size_t px = (size_t)F * B * 3 * H * W;
+    if (clip_overlap(frames, px * clip_fmt_bytes(frame_fmt), cond, px * sizeof(float)) || clip_overlap(k3, 27 * sizeof(float), cond, px * sizeof(float)))
+        return fail(NCAHIP_EINVAL, "clip_cond: cond overlaps an input");
+    if (frame_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)frames & 3) != 0) return fail(NCAHIP_EINVAL, "clip_cond: float32 frames must be 4-byte aligned");
+    return hip_result(nca_launch_clip_cond(frames, frame_fmt == NCAHIP_CLIP_U8_NHWC, k3, gray_r, gray_g, gray_b, apply_tanh != 0, cond, F * B, H, W,
+                                           (hipStream_t)stream), "clip_cond");
+}
+
+static int check_clip_emit(const void* state, const void* img, int img_fmt, int B, int C, int c_out, int H, int W) {
+    if (!state || !img) return fail(NCAHIP_EINVAL, "clip emit: null pointer");
+    if (!clip_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
+    if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit: bad size");
+    if (c_out < 1 || c_out > 4 || c_out > C) return fail(NCAHIP_EINVAL, "clip emit: c_out=%d must be in 1..4 and at most C=%d", c_out, C);
+    if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit: float32 images must be 4-byte aligned");
+    return 0;
+}
+
+int ncahip_clip_emit(const float* state, void* img, int img_fmt, int B, int C, int c_out, int H, int W, ncahip_stream_t stream) {
+    if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W)) return rc;
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt)))
+        return fail(NCAHIP_EINVAL, "clip emit: the image overlaps the state");
+    return hip_result(nca_launch_clip_emit(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit");
+}
+
+int ncahip_dynca_clip_f32(float* states, const float* cond, void* images, int img_fmt, int F, int steps_per_frame, int step_n, const float* u,
+                          const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int c_out, int H, int W, int fc,
+                          int pad_mode, int two_scale, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, void* persist_ws,
+                          size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream) {
+    constexpr int c_cond = 3;
+    // host-side checks: nothing is enqueued before all of them have passed
+    if (!cond) return fail(NCAHIP_EINVAL, "dynca clip: null pointer");
+    if (int rc = check_clip_emit(states, images, img_fmt, B, C, c_out, H, W)) return rc;
+    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "dynca clip: F, steps_per_frame and step_n must be positive");
+    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
+    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "dynca clip: F * steps_per_frame * step_n must stay below 2^31");
+    const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W, cslot = (size_t)B * c_cond * H * W;
+    const size_t ibytes = (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt);
+    if (clip_overlap(states, 2 * slot * sizeof(float), cond, (size_t)F * cslot * sizeof(float)) ||
+        clip_overlap(states, 2 * slot * sizeof(float), images, (size_t)calls * ibytes) ||
+        clip_overlap(cond, (size_t)F * cslot * sizeof(float), images, (size_t)calls * ibytes))
+        return fail(NCAHIP_EINVAL, "dynca clip: states, cond and images must not overlap");
+    if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
+        return fail(NCAHIP_EINVAL, "dynca clip: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)");
+    // what the per-step entry point refuses for this shape, the clip refuses with its code (T = 0: every check, no launch)
+    if (int rc = two_scale ? ncahip_dynca_nsteps_fwd_ms_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, pc_scratch, stream)
+                           : ncahip_dynca_nsteps_fwd_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, stream))
+        return rc;
+    if (persist_ws) {
+        const size_t need = ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, c_cond);
+        if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "dynca clip: persistent workspace too small");
+    }
+    if (int rc = device_error_rc("dynca clip")) return rc;
+
+    const bool ubits = u_is_bits(u, seed), u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
+    hipStream_t st = (hipStream_t)stream;
+    bool persist = persist_ws != nullptr;
+    int cur = 0;   // the slot that holds the state
+    for (int n = 0; n < (int)calls; ++n) {
+        const float* const cf = cond + (size_t)(n / steps_per_frame) * cslot;
+        const int t0 = n * step_n;                                  // first step of this call within `u`
+        const uint64_t s0 = step0 + (uint64_t)t0;
+        bool done = false;
+        if (persist) {
+            auto fn = two_scale ? ncahip_dynca_nsteps_fwd_persist_ms_f32 : ncahip_dynca_nsteps_fwd_persist_f32;
+            const int rc = fn(states + (size_t)cur * slot, states + (size_t)(cur ^ 1) * slot, step_n, cf, u_at(u, ubits, t0, uslot), w1, b1, w2, b2, B, C,
+                              H, W, fc, c_cond, pad_mode, update_rate, seed, s0, persist_ws, persist_bytes, epoch0 + (unsigned)n, stream);
+            if (rc == 0) {
+                cur ^= 1;
+                done = true;
+            } else if (rc == NCAHIP_ERANGE) {
+                persist = false;   // not covered (shape, alignment, residency): this call and the rest run on the per-step kernels
+            } else {
+                return rc;
+            }
+        }
+        if (!done) {
+            int T = step_n, t = t0;
+            if (cur == 1) {   // the ring of the n-step entry point starts at slot 0: one single step brings the state there
+                if (int rc = two_scale ? ncahip_dynca_step_fwd_ms_f32(states + slot, states, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond,
+                                                                      pad_mode, update_rate, seed, step0 + (uint64_t)t, pc_scratch, stream)
+                                       : ncahip_dynca_step_fwd_f32(states + slot, states, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond,
+                                                                   pad_mode, update_rate, seed, step0 + (uint64_t)t, stream))
+                    return rc;
+                --T, ++t;
+            }
+            if (int rc = two_scale ? ncahip_dynca_nsteps_fwd_ms_f32(states, 2, T, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                                                                    update_rate, seed, step0 + (uint64_t)t, pc_scratch, stream)
+                                   : ncahip_dynca_nsteps_fwd_f32(states, 2, T, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                                                                 update_rate, seed, step0 + (uint64_t)t, stream))
+                return rc;
+            cur = T & 1;
+        }
+        if (int rc = hip_result(nca_launch_clip_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, B, C, c_out, H, W, st), "dynca clip (emit)"))
+            return rc;
+    }
+    if (cur == 1)   // the state returns in slot 0
+        return hip_result(hipMemcpyAsync(states, states + slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "dynca clip (state copy)");
+    return 0;
+}
+
 int ncahip_cond_step_fwd_f32(const float* x_in, const uint8_t* pre_in, float* x_out, uint8_t* pre_out,
                              const float* goal, int goal_ch, const float* u, const float* wp, const float* w1,
                              const float* b1, const float* w2, const float* b2, const float* w3, int B, int C, int H,

@@ -1,0 +1,201 @@
+// nca_clip.hip -- the two ends of clip stylisation (ConditioneDyNCA/utils/misc/video_utils.py:50-83) around the DyNCA steps:
+//   clip_cond_kernel   frames of one call -> cond [F,B,3,H,W]: grey, then EdgeExtractor (dynca.py:204-213) in one pass
+//   clip_emit_kernel   state [B,C,H,W] -> one output image (video_utils.py:78-81), float32 NCHW or uint8 NHWC
+#include "nca_kernels.h"
+
+namespace {
+
+constexpr int kTileW = 64, kTileH = 16;                  // output pixels per workgroup: one wave per 4 rows, one lane per column
+constexpr int kHaloW = kTileW + 2, kHaloH = kTileH + 2;  // grey tile with its one-cell halo
+constexpr int kRawDwords = (3 * kHaloW + 3 + 3) / 4 + 1; // aligned dwords that cover one halo row of uint8 RGB (198 bytes at any phase)
+
+// uint8 -> network range as the reference's preprocessing (preprocess_texture.py:28, :54): a true division, then v * 2 - 1
+__device__ __forceinline__ float clip_widen_u8(unsigned v) {
+    const float f = __fdiv_rn((float)v, 255.0f);
+    return __fsub_rn(__fmul_rn(f, 2.0f), 1.0f);
+}
+
+// One workgroup = one 16 x 64 tile of one image.  The grey tile (+ halo, zero outside the image) is staged in LDS, so every input
+// pixel is read once per workgroup; a lane then walks 4 output rows of its column keeping the 3 x 3 window rows in registers.
+// U8: the halo rows' bytes come in as aligned dwords (4 bytes per lane) and are unpacked from LDS.
+template <bool U8>
+__global__ __launch_bounds__(256) void clip_cond_kernel(const void* __restrict__ frames, const float* __restrict__ k3, float wr, float wg,
+                                                        float wb, int do_tanh, float* __restrict__ cond, int N, int H, int W, int tiles_x,
+                                                        int tiles_y) {
+    __shared__ float grey[kHaloH][kHaloW + 1];
+    __shared__ unsigned raw[U8 ? kHaloH : 1][U8 ? kRawDwords : 1];
+    const int tid = threadIdx.x;
+    const size_t blk = blockIdx.x;
+    const int tx = (int)(blk % tiles_x), ty = (int)((blk / tiles_x) % tiles_y);
+    const size_t n = blk / ((size_t)tiles_x * tiles_y);   // image index f * B + b
+    if (n >= (size_t)N) return;
+    const int x0 = tx * kTileW, y0 = ty * kTileH;
+    const size_t plane = (size_t)H * W;
+    // columns of the halo tile that lie inside the image: [cx0, cx1) in image coordinates
+    const int cx0 = max(x0 - 1, 0), cx1 = min(x0 + kTileW + 1, W);
+
+    if (U8) {
+        const unsigned char* const base = static_cast<const unsigned char*>(frames);
+        const size_t total = (size_t)N * plane * 3;
+        const uintptr_t mis = (uintptr_t)base & 3;         // the dwords are aligned in memory, whatever the tensor's own alignment
+        for (int i = tid; i < kHaloH * kRawDwords; i += 256) {
+            const int r = i / kRawDwords, d = i % kRawDwords;
+            const int y = y0 - 1 + r;
+            if (y < 0 || y >= H) continue;
+            const size_t first = (n * plane + (size_t)y * W + cx0) * 3;          // first byte of the row segment
+            const size_t last = first + (size_t)(cx1 - cx0) * 3;                 // one past its last byte
+            const ptrdiff_t a0 = (ptrdiff_t)((first + mis) & ~(size_t)3) - (ptrdiff_t)mis;   // aligned start, as an offset from base (>= -3)
+            const ptrdiff_t a = a0 + 4 * (ptrdiff_t)d;
+            if (a >= (ptrdiff_t)last) continue;
+            unsigned v;
+            if (a >= 0 && (size_t)a + 4 <= total) {
+                v = *reinterpret_cast<const unsigned*>(base + a);
+            } else {   // the dword straddles an end of the tensor: only its bytes inside
+                v = 0u;
+                for (int k = 0; k < 4; ++k)
+                    if (a + k >= 0 && (size_t)(a + k) < total) v |= (unsigned)base[a + k] << (8 * k);
+            }
+            raw[r][d] = v;
+        }
+        __syncthreads();
+        const unsigned char* const rb = reinterpret_cast<const unsigned char*>(&raw[0][0]);
+        for (int i = tid; i < kHaloH * kHaloW; i += 256) {
+            const int r = i / kHaloW, c = i % kHaloW;
+            const int y = y0 - 1 + r, x = x0 - 1 + c;
+            float g = 0.0f;
+            if (y >= 0 && y < H && x >= cx0 && x < cx1) {
+                const size_t first = (n * plane + (size_t)y * W + cx0) * 3;
+                const int off = (int)((first + mis) & 3) + 3 * (x - cx0);        // byte of this pixel within the staged row
+                const unsigned char* const p = rb + (size_t)r * kRawDwords * 4 + off;
+                g = wr * clip_widen_u8(p[0]) + wg * clip_widen_u8(p[1]) + wb * clip_widen_u8(p[2]);
+            }
+            grey[r][c] = g;
+        }
+    } else {
+        const float* const ib = static_cast<const float*>(frames) + n * 3 * plane;
+        for (int i = tid; i < kHaloH * kHaloW; i += 256) {
+            const int r = i / kHaloW, c = i % kHaloW;
+            const int y = y0 - 1 + r, x = x0 - 1 + c;
+            float g = 0.0f;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const size_t o = (size_t)y * W + x;
+                g = wr * ib[o] + wg * ib[plane + o] + wb * ib[2 * plane + o];
+            }
+            grey[r][c] = g;
+        }
+    }
+    __syncthreads();
+
+    float k[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) k[i] = k3[i];
+    const int col = tid & 63, row0 = (tid >> 6) * 4;
+    const int x = x0 + col;
+    float w0[3], w1[3], w2[3];   // window rows y - 1, y, y + 1
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        w0[j] = grey[row0][col + j];
+        w1[j] = grey[row0 + 1][col + j];
+    }
+    float* const ob = cond + n * 3 * plane;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int y = y0 + row0 + r;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) w2[j] = grey[row0 + r + 2][col + j];
+        if (x < W && y < H) {
+#pragma unroll
+            for (int f = 0; f < 3; ++f) {
+                float acc = 0.0f;   // tap order of ncahip_edge_extractor_f32
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc = fmaf(k[f * 9 + j], w0[j], acc);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc = fmaf(k[f * 9 + 3 + j], w1[j], acc);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc = fmaf(k[f * 9 + 6 + j], w2[j], acc);
+                ob[(size_t)f * plane + (size_t)y * W + x] = do_tanh ? tanhf(acc) : acc;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            w0[j] = w1[j];
+            w1[j] = w2[j];
+        }
+    }
+}
+
+// img = (clamp(2 x, -1, 1) + 1) / 2, in the reference's order of operations (NaN passes through, as torch.clamp)
+__device__ __forceinline__ float clip_image_value(float x) {
+    float v = __fmul_rn(x, 2.0f);
+    v = v < -1.0f ? -1.0f : v;
+    v = v > 1.0f ? 1.0f : v;
+    return __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);
+}
+
+__global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restrict__ x, float* __restrict__ img, int B, int C, int c_out,
+                                                            size_t plane) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (size_t)B * c_out * plane) return;
+    const size_t p = id % plane, c = (id / plane) % c_out, b = id / (plane * c_out);
+    img[id] = clip_image_value(x[(b * C + c) * plane + p]);
+}
+
+// uint8 NHWC: a lane owns 4 consecutive pixels of the flattened [B*H*W] axis = CO dwords, stored whole (bytes only for the last, partial
+// group or an output that is not 4-byte aligned).  (uint8_t)(img * 255): truncation, as np.uint8 in VideoWriter.add.
+template <int CO>
+__global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, int B, int C,
+                                                           size_t plane, int aligned) {
+    const size_t grp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t npix = (size_t)B * plane, q0 = grp * 4;
+    if (q0 >= npix) return;
+    unsigned char px[4 * CO];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const size_t q = q0 + i < npix ? q0 + i : npix - 1;
+        const size_t b = q / plane, p = q % plane;
+#pragma unroll
+        for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_image_value(x[(b * C + c) * plane + p]), 255.0f);
+    }
+    unsigned char* const o = img + q0 * CO;
+    if (aligned && q0 + 4 <= npix) {
+#pragma unroll
+        for (int d = 0; d < CO; ++d)
+            reinterpret_cast<unsigned*>(o)[d] = (unsigned)px[4 * d] | (unsigned)px[4 * d + 1] << 8 | (unsigned)px[4 * d + 2] << 16 | (unsigned)px[4 * d + 3] << 24;
+    } else {
+        const size_t nb = (q0 + 4 <= npix ? 4 : npix - q0) * CO;
+        for (size_t i = 0; i < nb; ++i) o[i] = px[i];
+    }
+}
+
+}  // namespace
+
+hipError_t nca_launch_clip_cond(const void* frames, bool u8, const float* k3, float wr, float wg, float wb, int do_tanh, float* cond, int N, int H,
+                                int W, hipStream_t st) {
+    const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
+    const size_t blocks = (size_t)N * tiles_x * tiles_y;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    if (u8) hipLaunchKernelGGL(clip_cond_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, frames, k3, wr, wg, wb, do_tanh, cond, N, H, W, tiles_x, tiles_y);
+    else hipLaunchKernelGGL(clip_cond_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, frames, k3, wr, wg, wb, do_tanh, cond, N, H, W, tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+hipError_t nca_launch_clip_emit(const float* state, void* img, bool u8, int B, int C, int c_out, int H, int W, hipStream_t st) {
+    const size_t plane = (size_t)H * W;
+    if (!u8) {
+        const size_t n = (size_t)B * c_out * plane;
+        hipLaunchKernelGGL(clip_emit_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img, B, C, c_out, plane);
+        return hipGetLastError();
+    }
+    const size_t groups = ((size_t)B * plane + 3) / 4;
+    const dim3 grid((unsigned)((groups + 255) / 256));
+    const int aligned = ((uintptr_t)img & 3) == 0;
+    unsigned char* const o = (unsigned char*)img;
+    switch (c_out) {
+        case 1: hipLaunchKernelGGL(clip_emit_u8_kernel<1>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
+        case 2: hipLaunchKernelGGL(clip_emit_u8_kernel<2>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
+        case 3: hipLaunchKernelGGL(clip_emit_u8_kernel<3>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
+        case 4: hipLaunchKernelGGL(clip_emit_u8_kernel<4>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}

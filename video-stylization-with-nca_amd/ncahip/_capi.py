@@ -87,13 +87,19 @@ SIGNATURES = {
     "ncahip_slw_sort_f32": [_P, _P, _I, _I, _P],
     "ncahip_slw_loss_fwd_f32": [_P, _P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P],
     "ncahip_slw_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P],
+    "ncahip_clip_cond_workspace": [_I, _I, _I, _I],
+    "ncahip_clip_cond": [_P, _I, _P, _F, _F, _F, _I, _P, _I, _I, _I, _I, _P],
+    "ncahip_clip_emit": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ncahip_dynca_clip_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P,
+                              ctypes.c_size_t, ctypes.c_uint, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_bwd_ms_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_persist_workspace": ctypes.c_size_t,
              "ncahip_cond_grow_persist_workspace": ctypes.c_size_t, "ncahip_ot_workspace": ctypes.c_size_t,
-             "ncahip_ot_moment_workspace": ctypes.c_size_t, "ncahip_slw_workspace": ctypes.c_size_t}
+             "ncahip_ot_moment_workspace": ctypes.c_size_t, "ncahip_slw_workspace": ctypes.c_size_t,
+             "ncahip_clip_cond_workspace": ctypes.c_size_t}
 
 _lib = None
 
@@ -104,6 +110,7 @@ class NcaHipError(RuntimeError):
 
 EINVAL, ERANGE, EDEVICE = -1, -2, 100001     # include/ncahip.h return codes
 SEED_U_IS_BITS = 0x5354494255     # include/ncahip.h NCAHIP_SEED_U_IS_BITS: `u` holds bit-packed fire masks
+CLIP_F32_NCHW, CLIP_U8_NHWC = 0, 1     # include/ncahip.h NCAHIP_CLIP_*: frame / image formats of the clip entry points
 
 
 def lib():

@@ -46,17 +46,19 @@ def _workspace(nbytes: int, device: torch.device) -> torch.Tensor:
 _PERSIST_WS = {}
 
 
-def _persist_workspace(nbytes: int, device: torch.device):
+def _persist_workspace(nbytes: int, device: torch.device, count: int = 1):
     """(workspace, epoch) for ncahip_dynca_nsteps_fwd_persist_f32: a dedicated tensor per (device, stream, size), zeroed when it is
     created and whenever its epoch counter runs out; every call gets the next epoch (the library never clears the workspace: the
-    exchanged pairs are tagged epoch * 4096 + step)."""
+    exchanged pairs are tagged epoch * 4096 + step).  count: the number of consecutive epochs the caller will consume, epoch ..
+    epoch + count - 1 (ncahip_dynca_clip_f32 uses one per persistent launch)."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(), nbytes)
     ent = _PERSIST_WS.get(key)
-    if ent is None or ent[1] >= (1 << 20) - 2:
+    if ent is None or ent[1] + count > (1 << 20) - 2:
         ent = [torch.zeros(nbytes, device=device, dtype=torch.uint8), 0]
         _PERSIST_WS[key] = ent
-    ent[1] += 1
-    return ent[0], ent[1]
+    first = ent[1] + 1
+    ent[1] += count
+    return ent[0], first
 
 
 def release_workspaces() -> None:
@@ -301,6 +303,82 @@ def dynca_nsteps(x: torch.Tensor, T: int, cond: Optional[torch.Tensor], us: Opti
                                                            _p(w.b2), B, C, H, W, w.fc, c_cond, PAD_MODES[pad_mode],
                                                            update_rate, seed, step0, _stream()), "dynca_nsteps_fwd_" + sfx)
     return states[T % ring], states
+
+
+# ------------------------------------------------------------------------------------ a whole clip per call
+GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0),       # the reference's RGBToGrayscale (preprocess_texture.py:178-179)
+                "luma": (0.2989, 0.587, 0.114)}                  # ITU-R 601, what ncahip.video.rgb_to_grayscale computes
+
+
+def _clip_fmt(dtype) -> int:
+    if dtype == torch.float32:
+        return _capi.CLIP_F32_NCHW
+    if dtype == torch.uint8:
+        return _capi.CLIP_U8_NHWC
+    raise TypeError(f"ncahip: clip frames / images are float32 (channels first) or uint8 (channels last), got {dtype}")
+
+
+def clip_cond(frames: torch.Tensor, k3: torch.Tensor, gray="mean", apply_tanh: bool = True) -> torch.Tensor:
+    """frames [F,B,3,H,W] float32 in [-1, 1] or [F,B,H,W,3] uint8 -> cond [F,B,3,H,W] = EdgeExtractor(grey(frame)) in one launch
+    (ncahip_clip_cond).  gray: 'mean', 'luma' or three weights; k3: the EdgeExtractor's three 3 x 3 filters."""
+    fmt = _clip_fmt(frames.dtype)
+    frames = _dev(frames, "frames", frames.dtype)
+    if fmt == _capi.CLIP_U8_NHWC:
+        F_, B, H, W, three = frames.shape
+    else:
+        F_, B, three, H, W = frames.shape
+    assert three == 3, tuple(frames.shape)
+    wr, wg, wb = GRAY_WEIGHTS[gray] if isinstance(gray, str) else gray
+    k3 = _w(k3.reshape(-1), "k3", frames)
+    assert k3.numel() == 27
+    cond = torch.empty(F_, B, 3, H, W, device=frames.device, dtype=torch.float32)
+    assert cond.numel() * 4 == lib().ncahip_clip_cond_workspace(F_, B, H, W)
+    check(lib().ncahip_clip_cond(_p(frames), fmt, _p(k3), wr, wg, wb, int(apply_tanh), _p(cond), F_, B, H, W, _stream()), "clip_cond")
+    return cond
+
+
+def _clip_images(n: int, B: int, c_out: int, H: int, W: int, out_dtype, device) -> torch.Tensor:
+    if _clip_fmt(out_dtype) == _capi.CLIP_U8_NHWC:
+        return torch.empty(n, B, H, W, c_out, device=device, dtype=torch.uint8)
+    return torch.empty(n, B, c_out, H, W, device=device, dtype=torch.float32)
+
+
+def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32) -> torch.Tensor:
+    """State [B,C,H,W] -> (clamp(2 x[:, :c_out], -1, 1) + 1) / 2 as float32 [B,c_out,H,W], or truncated to uint8 [B,H,W,c_out]."""
+    x = _dev(x, "x")
+    B, C, H, W = x.shape
+    img = _clip_images(1, B, c_out, H, W, out_dtype, x.device)[0]
+    check(lib().ncahip_clip_emit(_p(x), _p(img), _clip_fmt(out_dtype), B, C, c_out, H, W, _stream()), "clip_emit")
+    return img
+
+
+def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], w: DyncaWeights, steps_per_frame: int, step_n: int,
+               c_out: int = 3, pad_mode: str = "replicate", update_rate: float = 0.5, seed: int = 0, step0: int = 0,
+               two_scale: bool = False, out_dtype=torch.float32):
+    """The video loop over the F frames of cond [F,B,3,H,W] in one C call (ncahip_dynca_clip_f32): per frame steps_per_frame times
+    {step_n DyNCA steps, one image}.  us: None (Philox: seed, step0), or the masks / uniforms of all F * steps_per_frame * step_n steps.
+    Returns (images [F * steps_per_frame, B, c_out, H, W] float32 or [.., B, H, W, c_out] uint8, final state [B,C,H,W])."""
+    x = _dev(x, "x")
+    B, C, H, W = x.shape
+    cond = _dev(cond, "cond")
+    F_ = cond.shape[0]
+    assert cond.shape == (F_, B, 3, H, W), (tuple(cond.shape), tuple(x.shape))
+    calls = F_ * steps_per_frame
+    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
+    assert w.c == C and w.k1 == 4 * C + 3, (w.c, w.k1, C)
+    states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
+    states[0].copy_(x)
+    images = _clip_images(calls, B, c_out, H, W, out_dtype, x.device)
+    pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
+    ws, nbytes, epoch = None, 0, 0
+    if persistent_steps:
+        nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, 3)
+        if nbytes and calls < (1 << 20) - 2:
+            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
+    check(lib().ncahip_dynca_clip_f32(_p(states), _p(cond), _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n, _p(us), _p(w.w1),
+                                      _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode], int(two_scale), update_rate,
+                                      seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "dynca_clip")
+    return images, states[0]
 
 
 # ------------------------------------------------------------------------------------ ConditionedNCA

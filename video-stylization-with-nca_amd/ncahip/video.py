@@ -10,7 +10,8 @@ import torch
 
 
 def rgb_to_grayscale(x: torch.Tensor) -> torch.Tensor:
-    """ITU-R 601 luma as torchvision's rgb_to_grayscale (the reference's RGBToGrayscale): [B,3,H,W] -> [B,1,H,W]."""
+    """ITU-R 601 luma as torchvision's rgb_to_grayscale (the reference's RGBToGrayscale): [B,3,H,W] -> [B,1,H,W].
+    (preprocess_texture.py:178-179 takes the channel mean instead: stylize_clip offers both and defaults to the mean.)"""
     r, g, b = x.unbind(dim=-3)
     return (0.2989 * r + 0.587 * g + 0.114 * b).unsqueeze(-3)
 
@@ -20,7 +21,8 @@ def synthesize_video(nca_model, frames: Iterable[torch.Tensor], step_n: int = 8,
                      size=None, state: Optional[torch.Tensor] = None) -> Iterator[torch.Tensor]:
     """Yields one [3,H,W] image in [0,1] per (frame, k): video_utils.py:66-83.  `frames`: tensors [3,H,W] in [-1,1] on
     the model's device (the reference's preprocess_video output, one time slice each).  The NCA state persists across
-    frames; pass `state` to continue a previous call."""
+    frames; pass `state` to continue a previous call.
+    (stylize_clip runs a whole clip per call; it conditions on the channel-mean grey by default, this loop on the luma.)"""
     h = state
     for frame in frames:
         frame = frame.to(nca_model.device)
@@ -32,3 +34,96 @@ def synthesize_video(nca_model, frames: Iterable[torch.Tensor], step_n: int = 8,
             h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond)
             yield (rgb[0].clamp(-1.0, 1.0) + 1.0) / 2.0
     synthesize_video.last_state = h
+
+
+def _gray(x: torch.Tensor, gray: str) -> torch.Tensor:
+    """[B,3,H,W] -> [B,1,H,W]: 'mean' = the reference's RGBToGrayscale (preprocess_texture.py:178-179), 'luma' = rgb_to_grayscale."""
+    if gray == "mean":
+        return x.mean(dim=-3, keepdim=True)
+    if gray == "luma":
+        return rgb_to_grayscale(x)
+    raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
+
+
+def _widen(frames: torch.Tensor) -> torch.Tensor:
+    """[n,H,W,3] uint8 -> [n,3,H,W] float32 in [-1, 1], as the reference's preprocessing (preprocess_texture.py:28, :54)."""
+    return (frames.float() / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2).contiguous()
+
+
+def _clip_route(nca_model, h: torch.Tensor) -> bool:
+    """True when ncahip_dynca_clip_f32 covers the model: edge conditioning, perception_scales [0] or the fused [0, 1], an fp32
+    state on the GPU."""
+    if getattr(nca_model, "conditioning", None) != "edges" or not h.is_cuda or h.dtype != torch.float32 or h.shape[0] != 1:
+        return False
+    scales = list(getattr(nca_model, "perception_scales", [0]))
+    return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
+
+
+@torch.no_grad()
+def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
+                 gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32):
+    """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
+
+    frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
+    [F*steps_per_frame,3,H,W] float32 in [0, 1], or [F*steps_per_frame,H,W,3] uint8 (truncated, as VideoWriter.add) with
+    out_dtype=torch.uint8, on the model's device.  state: None seeds as synthesize_video does; pass the returned state to continue.
+    gray: 'mean' (the reference's RGBToGrayscale, the default) or 'luma' (what synthesize_video conditions on).
+
+    Models with edge conditioning and perception_scales [0] or the fused [0, 1] run frames_per_call frames per C call
+    (ncahip_clip_cond, then ncahip_dynca_clip_f32: the library's step kernels and the image output, no Python per frame); the result
+    does not depend on frames_per_call.  The fire masks follow the model's mask_rng exactly as forward_nsteps draws them.  Anything else
+    (other conditioning or scale sets, non-fp32 state, CPU tensors) runs a Python loop over forward_nsteps with the chosen grey.
+    stylize_clip.last_path records the route: 'clip' or 'loop'."""
+    from . import ops
+    if gray not in ops.GRAY_WEIGHTS:
+        raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+    u8_in = frames.dtype == torch.uint8
+    if frames.dim() != 4 or frames.shape[-1 if u8_in else 1] != 3 or not (u8_in or frames.dtype == torch.float32):
+        raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
+    n_frames = frames.shape[0]
+    hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
+    k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
+    dev = nca_model.device
+    h = state if state is not None else nca_model.seed(1, size=(ww, hh))
+    fused = _clip_route(nca_model, h) and torch.device(dev).type == "cuda"
+    stylize_clip.last_path = "clip" if fused else "loop"
+    outs = []
+    if fused:
+        layer = nca_model.cond_layer
+        bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
+        do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
+        w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
+        rate, two = 0.5, list(nca_model.perception_scales) == [0, 1]
+        for f0 in range(0, n_frames, per_call):
+            chunk = frames[f0:f0 + per_call].to(dev).unsqueeze(1)                 # [n,1,3,H,W] or [n,1,H,W,3]
+            n = chunk.shape[0]
+            cond = ops.clip_cond(chunk, bank, gray, do_tanh)
+            us = None
+            if nca_model.mask_rng != "philox":     # the loop's own draws, call by call (DyNCA._draw): the generator ends where it would
+                us = torch.cat([ops.draw_fire_masks(1, hh, ww, step_n, rate, "dynca", h.device) for _ in range(n * k)])
+            imgs, h = ops.dynca_clip(h, cond, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
+                                     nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
+            nca_model._mask_step += n * k * step_n
+            outs.append(imgs[:, 0])
+    else:
+        for f0 in range(0, n_frames, per_call):
+            chunk = frames[f0:f0 + per_call].to(dev)
+            chunk = _widen(chunk) if u8_in else chunk
+            for i in range(chunk.shape[0]):
+                cond = _gray(chunk[i:i + 1], gray)
+                for _ in range(k):
+                    h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond)
+                    img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
+                    outs.append((img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img)
+    if outs:
+        images = torch.cat(outs)
+    else:
+        c = getattr(nca_model, "c_out", 3)
+        images = torch.empty((0, hh, ww, c) if out_dtype == torch.uint8 else (0, c, hh, ww), dtype=out_dtype, device=dev)
+    stylize_clip.last_state = h
+    return images, h
+
+
+stylize_clip.last_path = None
