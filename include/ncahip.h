@@ -79,7 +79,12 @@ int ncahip_cond_precision(int mode);
  * bit 4 = the matrix kernel walks whole super-tiles on small grids as well (by default a grid with fewer super-tiles than half
  * the CUs gives each workgroup half a super-tile; with this bit its summation order equals the one-launch form's bit for bit);
  * bit 5 = the fp32 producer/consumer ConditionedNCA step runs perception and UpdateNet on every cell, as before firing-cell lists
- * (by default it runs them on the cells that fire only; same values, see ncahip_cond_step_fwd_f32).
+ * (by default it runs them on the cells that fire only; same values, see ncahip_cond_step_fwd_f32);
+ * bit 6 = the firing-cell lists of that step pad every wave tile's last group of 16 cells (by default, for C <= 16, a consumer
+ * wave carries the cells of a partial group across the tiles it owns and runs UpdateNet on them once 16 have come together;
+ * same bits for every cell; C > 16 always pads, so the bit changes nothing there);
+ * bits 8-15 = a cap on the number of workgroups of a producer/consumer step launch, 0 = no cap (a small grid then gives every
+ * workgroup many rounds: what the tests of bit 6's default need; never faster).
  * Any bit set also keeps ncahip_cond_grow_fwd_persist_f32 from running (it returns NCAHIP_ERANGE). */
 int ncahip_debug_force_generic(int on);
 

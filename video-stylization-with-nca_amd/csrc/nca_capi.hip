@@ -173,6 +173,8 @@ int ncahip_debug_force_generic(int on) {
     nca_set_bwd_variant((on & 8) ? 3 : 0);   // bit 3: ConditionedNCA backward kernel A in the form that is NOT the mode's default (one launch <-> front + matrix)
     nca_set_bwd_fm_nosplit((on & 16) != 0);  // bit 4: the matrix kernel walks whole super-tiles on small grids too (its summation order then equals the one-launch form's)
     nca_set_cond_pc_dense((on & 32) != 0);   // bit 5: the fp32 producer/consumer step runs every cell (no firing-cell lists)
+    nca_set_cond_pc_nocarry((on & 64) != 0); // bit 6: firing-cell lists pad every tile's last group (no carry across a pair's tiles)
+    nca_set_cond_pc_wg_cap((on >> 8) & 255); // bits 8-15: at most this many workgroups per producer/consumer step launch (0: no cap)
     return 0;
 }
 

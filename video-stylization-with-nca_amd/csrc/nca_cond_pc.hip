@@ -70,10 +70,15 @@ struct PCfg {
 // FC: the producer compacts the tile's firing cells into a list (stage_tile FCL) and the consumer runs perception and UpdateNet
 // on those cells only, in groups of 16 MFMA columns (two groups per pass, one for an odd last group).  x' = x + fire * out
 // (nca.py:189): a cell that does not fire keeps its resolved state, which XR already holds -- store_tile is unchanged.
-template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false>
+// CARRY (narrow carve): a tile's last, partial group is not padded to 16 columns.  Its cells get their perception and are
+// parked in the consumer's carry (FireCarry, on the dead W1 / W2 images); UpdateNet runs when 16 parked cells have come
+// together, whichever tiles of the pair they came from, and once more, padded, after the pair's last round.  Only the consumer
+// wave changes: hand-off, round counters, tile buffers and the producer are those of the kernel without the carry.
+template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false, bool CARRY = false>
 __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const NcaCondArgs a) {
     static_assert(!SPLIT || ST::BYTES == 4, "bf16x3 emulation is an option of the fp32-storage kernel");
     static_assert(!FC || (ST::BYTES == 4 && !SPLIT), "firing-cell lists: the exact-f32 fp32-storage consumer");
+    static_assert(!CARRY || (FC && CP <= 16), "the carry: firing-cell lists on the narrow carve");
     constexpr bool BF = ST::BYTES == 2;   // bf16 storage: UpdateNet on bf16 MFMA (operands rounded from the same LDS image)
     using K = WCfg<CP>;
     using PK = PCfg<CP>;
@@ -198,13 +203,15 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     MlpRegs<CP> Wr;        // exact-f32 operands (f32 storage)
     MlpRegsBf<CP> Wb;      // bf16 operands (bf16 storage)
     MlpRegsSplit<CP> Ws;   // bf16 hi/lo operand pairs (fp32 storage, ncahip_cond_precision(1))
-    auto consume = [&](const WTile& t, int which) {
-        if (!t.valid) return;
-        const TileLds L = lds_of(which);
+    // CARRY: number of parked cells (wave-uniform) and the consumer's carry, on the W1 / W2 images (nothing without CARRY)
+    constexpr int kCarrySize = [] { if constexpr (CARRY) return FireCarry<CP>::SIZE; else return 0; }();
+    [[maybe_unused]] int carry_n = 0;
+    [[maybe_unused]] float* const CR = smem + pair * kCarrySize;
+    // FC: ng full groups of 16 listed cells of tile L, two per pass and one for an odd last one.  Without the carry ng counts the
+    // partial last group too: its padding entries (kFirePad) compute on a real cell and write XR's padding column.
+    auto fire_groups = [&]([[maybe_unused]] const TileLds& L, [[maybe_unused]] int ng) {
         if constexpr (FC) {
-            // groups of 16 listed cells; padding entries (kFirePad) compute on a real cell and write XR's padding column
             const int* const FL = reinterpret_cast<const int*>(L.MK);
-            const int ng = (__builtin_amdgcn_readfirstlane(*L.NF) + 15) >> 4;
             auto cells = [&](auto nt, int gi) {
                 constexpr int NTC = decltype(nt)::value;
                 int zc[NTC], xc[NTC];
@@ -225,6 +232,97 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
 #pragma unroll 1
             for (; gi + 2 <= ng; gi += 2) cells(std::integral_constant<int, 2>{}, gi);
             if (gi < ng) cells(std::integral_constant<int, 1>{}, gi);
+        }
+    };
+    // flush (CARRY only): after the pair's last round -- no tile, one padded group on what the carry still holds
+    auto consume = [&](const WTile& t, int which, [[maybe_unused]] bool flush) {
+        if (!flush && !t.valid) return;
+        const TileLds L = lds_of(which);
+        if constexpr (CARRY) {
+            using KC = FireCarry<CP>;
+            const int* const FL = reinterpret_cast<const int*>(L.MK);
+            int q = 0, rem = 0;
+            if (!flush) {
+                const int nf = __builtin_amdgcn_readfirstlane(*L.NF);
+                q = nf >> 4;
+                rem = nf & 15;
+                fire_groups(L, q);   // the full groups, as without the carry
+            }
+            // the lane's own places in the carry: derived here, from an opaque lane id, so that nothing of it is kept in
+            // registers through the full groups above
+            int lane_c = lane;
+            asm volatile("" : "+v"(lane_c));
+            float* const CP_ = CR + KC::OFF_P + lane_c;
+            float* const CX = CR + KC::OFF_X;
+            int* const CPIX = reinterpret_cast<int*>(CR + KC::OFF_PIX) + lane_c;
+            int* const CBAT = reinterpret_cast<int*>(CR + KC::OFF_BAT) + lane_c;
+            const int g = (lane_c >> 4) & 3, col = lane_c & 15;
+            float P1[1][K::K1S];
+            bool has = false, run = flush;   // has: this lane's column took a remainder cell of this tile; run: a carry group is due
+            int xcell = 0, pix = 0;
+            // lane (g, col) moves channel rows 4g..4g+3 of its cell between the tile's XR and its slot of the carry
+            auto park_x = [&]() {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) CX[(4 * g + k) * KC::XCS + col] = L.XR[(4 * g + k) * XRS + xcell];
+                *CPIX = pix;
+                *CBAT = t.b;
+            };
+            if (!flush) {
+                if (rem > 0) {
+                    // remainder entry e -> MFMA column (carry_n + e) mod 16: behind the parked cells, wrapping to column 0
+                    const int e = (col - carry_n) & 15;
+                    has = e < rem;
+                    const int ent = has ? FL[16 * q + e] : kFirePad;
+                    const int zc[1] = {ent & 0xFFFF};
+                    xcell = ent >> 16;
+                    pix = __mul24(t.ty0 + (xcell >> 4), W) + t.tx0 + (xcell & 15);
+                    perceive_cells_pipe<CP, 1>(smem, L.Z, lane, zc, P1);
+                    if (carry_n + rem >= 16) {
+                        run = true;
+                    } else {
+                        if (has) {
+#pragma unroll
+                            for (int s_ = 0; s_ < K::K1S; ++s_) CP_[s_ * 64] = P1[0][s_];
+                            park_x();
+                        }
+                        carry_n += rem;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int s_ = 0; s_ < K::K1S; ++s_) P1[0][s_] = 0.0f;
+            }
+            if (run) {
+                // columns < carry_n hold parked cells; the others took this tile's remainder cells (flush: nothing, they compute
+                // on zeros and are not stored).  A remainder cell that wrapped into a parked column swaps its P in and waits.
+                const bool old = col < carry_n;
+                if (old) {
+#pragma unroll
+                    for (int s_ = 0; s_ < K::K1S; ++s_) {
+                        const float parked = CP_[s_ * 64];
+                        if (has) CP_[s_ * 64] = P1[0][s_];
+                        P1[0][s_] = parked;
+                    }
+                } else if (has) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) CX[(4 * g + k) * KC::XCS + col] = L.XR[(4 * g + k) * XRS + xcell];
+                }
+                const int xc1[1] = {col};
+                mlp_cells_regs<CP, 1, KC::XCS>(Wr, smem, CX, lane, xc1, P1);
+                // this tile's cells go back into its XR (store_tile below writes them); the parked ones go to x_out from here,
+                // after the tile stores of the rounds they came from (those wrote their state before the update) have completed
+                if (!old && has) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) L.XR[(4 * g + k) * XRS + xcell] = CX[(4 * g + k) * KC::XCS + col];
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                store_carry<CP, EXACT, kNtStore>(a, CX, lane, old, *CPIX, *CBAT);
+                if (old && has) park_x();
+                carry_n = flush ? 0 : carry_n + rem - 16;
+            }
+            if (flush) return;
+        } else if constexpr (FC) {
+            fire_groups(L, (__builtin_amdgcn_readfirstlane(*L.NF) + 15) >> 4);
         } else {
             constexpr int NT = 2;
 #pragma unroll 1
@@ -302,7 +400,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         post(0, 0);
         NCA_KSTAMP(1);
         __syncthreads();              // weight image complete, counters initialised
-        if constexpr (PK::WIDE) __syncthreads();   // ... and moved into the consumers' registers: the second buffers may overwrite it
+        if constexpr (PK::WIDE || CARRY) __syncthreads();   // ... and moved into the consumers' registers: the second buffers (wide carve) / the carries may overwrite it
         NCA_KSTAMP(2);
         while (pos.k + 1 < n_rounds) {
             const Pos pn = advance(pos);
@@ -328,7 +426,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         if constexpr (SPLIT) load_weights_split_lds<CP>(smem, lane, Ws);
         else if constexpr (BF) load_weights_bf16_lds<CP>(smem, lane, Wb);   // same image, rounded to bf16 operand pairs
         else mlp_load_regs<CP>(smem, lane, Wr);
-        if constexpr (PK::WIDE) {
+        if constexpr (PK::WIDE || CARRY) {
             static_assert(!PK::WIDE || !SPLIT, "wide carve: the exact-f32 and the bf16 consumer");
             __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the image reads have landed
             __syncthreads();
@@ -341,7 +439,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
 #ifdef NCA_STAMPS
             if (a.seed != 0xD1A7ull)  // diagnostic knob: idle consumers
 #endif
-            consume(cur, which);
+            consume(cur, which, false);
             if (tile_no == 2) NCA_KSTAMP(5);
             post(1, pos.k);
             if (tile_no == 2) NCA_KSTAMP(6);
@@ -351,33 +449,46 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
             which ^= 1;
             ++tile_no;
         }
+        if constexpr (CARRY) {
+            if (carry_n > 0) consume(cur, which, true);
+        }
         NCA_KSTAMP(3);
     }
 }
 
-template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false>
+int g_pc_wg_cap = 0;       // test hook (ncahip_debug_force_generic bits 8-15): at most this many workgroups per step launch (0: no cap)
+template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false>
 hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     using PK = PCfg<CP>;
-    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC>;
+    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC, CARRY>;
     const size_t lds = (size_t)PK::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
     const int cus = nca_cu_count();
     const int nst = a.B * ((a.W + 15) / 16) * ((a.H + 15) / 16);
-    hipLaunchKernelGGL(kern, dim3(nst < cus ? nst : cus), dim3(kThreadsW), lds, st, a);
+    int nwg = nst < cus ? nst : cus;
+    if (g_pc_wg_cap > 0 && nwg > g_pc_wg_cap) nwg = g_pc_wg_cap;
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(kThreadsW), lds, st, a);
     return hipGetLastError();
 }
 
 bool g_pc_dense = false;   // test hook (ncahip_debug_force_generic bit 5): the exact-f32 consumer runs every cell
-// the exact-f32, fp32-storage step: firing-cell lists unless the test hook asks for the dense consumer
+bool g_pc_nocarry = false; // test hook (bit 6): firing-cell lists with every tile's last group padded (no carry across tiles)
+// the exact-f32, fp32-storage step: firing-cell lists (narrow carve: with the carry) unless a test hook asks otherwise
 template <int CP, bool EXACT>
 hipError_t launch_cond_pc_f32(const NcaCondArgs& a, hipStream_t st) {
-    return g_pc_dense ? launch_cond_pc<CP, EXACT, StF32, false, false>(a, st) : launch_cond_pc<CP, EXACT, StF32, false, true>(a, st);
+    if (g_pc_dense) return launch_cond_pc<CP, EXACT, StF32, false, false>(a, st);
+    if constexpr (CP <= 16) {
+        if (!g_pc_nocarry) return launch_cond_pc<CP, EXACT, StF32, false, true, true>(a, st);
+    }
+    return launch_cond_pc<CP, EXACT, StF32, false, true>(a, st);
 }
 
 }  // namespace
 
 void nca_set_cond_pc_dense(bool on) { g_pc_dense = on; }
+void nca_set_cond_pc_nocarry(bool on) { g_pc_nocarry = on; }
+void nca_set_cond_pc_wg_cap(int n) { g_pc_wg_cap = n > 0 ? n : 0; }
 
 // W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_step_fwd.hip dispatch) guarantees it.
 extern "C" void nca_debug_set_stamp_buffer_pc(void* p);

@@ -974,11 +974,33 @@ __device__ __forceinline__ void mlp_tile_regs(const MlpRegs<CP>& Wr, const float
     mlp_tile_regs_impl<CP, NT, XCS, false>(Wr, WS, XR, MK, lane_in, n0, none, P);
 }
 // mlp_tile_regs over gathered firing cells (stage_tile FCL): column n of lane (g, ci) is the cell at XR offset xc[n]
-template <int CP, int NT>
+// (XCS: channel-row stride of XR -- a wave tile's XR by default, FireCarry::XCS for a pair's carry)
+template <int CP, int NT, int XCS = XRS>
 __device__ __forceinline__ void mlp_cells_regs(const MlpRegs<CP>& Wr, const float* __restrict__ WS, float* __restrict__ XR,
                                                int lane_in, const int (&xc)[NT], const float (&P)[NT][3 * CP / 4]) {
-    mlp_tile_regs_impl<CP, NT, XRS, true>(Wr, WS, XR, nullptr, lane_in, 0, xc, P);
+    mlp_tile_regs_impl<CP, NT, XCS, true>(Wr, WS, XR, nullptr, lane_in, 0, xc, P);
 }
+
+// Carry of a consumer wave (nca_cond_pc.hip, CARRY): up to 15 firing cells whose perception is done and whose UpdateNet waits
+// for a full group of 16 MFMA columns.  Slot = MFMA column ci.  Every array is indexed so that lane (g, ci) only ever touches
+// its own elements -- the carry is a per-lane parking area, no lane reads what another lane wrote:
+//   P [K1S][64]       perception vector of the slot's cell, element s of lane (g, ci) -- the layout mlp_cells_regs consumes
+//   X [16*M3T][XCS]   resolved state column of the slot's cell (channel rows 4g..4g+3 belong to lane (g, ci)); rows >= CP
+//                     are scratch, as in a tile's XR
+//   PIX, BAT [64]     where the cell lives in x_out: cell index gy*W + gx and batch item (one copy per lane)
+template <int CP>
+struct FireCarry {
+    using F = WCfg<CP>;
+    static constexpr int XCS = 20;   // 16 slots + padding; 4 * XCS % 32 == 16 as for XRS
+    static constexpr int OFF_P = 0;
+    static constexpr int OFF_X = OFF_P + F::K1S * 64;
+    static constexpr int OFF_PIX = OFF_X + 16 * F::M3T * XCS;
+    static constexpr int OFF_BAT = OFF_PIX + 64;
+    static constexpr int SIZE = OFF_BAT + 64;
+    static_assert((4 * XCS) % 32 == 16, "bank layout");
+    static_assert(F::M3T == 1, "narrow carve only");
+    static_assert(4 * SIZE <= F::OFF_W3, "four carries fit on the W1 / W2 images, below W3");
+};
 
 // ---- UpdateNet on bf16 MFMA (bf16-storage kernels) -------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -1226,6 +1248,36 @@ __device__ __forceinline__ void store_tile(const NcaCondArgs& a, const WTile& t,
         const int ch = 4 * k + q4;
         const f32x4 v = ld4(XR + ch * XRS + row * WTW + 4 * ff);
         if (ok && ch < C) ST::template st4<WT ? 16 : 0>(ro, vo, 4u * k * plane4, v);
+    }
+}
+
+// The carry's finished cells out (fp32 storage): lane (g, ci) with `act` set stores channels 4g..4g+3 of the cell in slot ci
+// from the carry's state columns CX to x_out, 4 bytes each -- the values, (absent) conversion and cache policy of store_tile.
+// The cells of a carry may belong to different batch items and a buffer resource is wave-uniform: one round per distinct item.
+template <int CP, bool EXACT, bool WT>
+__device__ __forceinline__ void store_carry(const NcaCondArgs& a, const float* __restrict__ CX, int lane_in, bool act, int pix, int bat) {
+    const int C = EXACT ? CP : a.C;
+    const unsigned plane = (unsigned)(a.H * a.W);
+    unsigned plane4 = plane * 4u;
+    asm volatile("" : "+s"(plane4));   // see issue_loads
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
+    const int g = (lane >> 4) & 3, ci = lane & 15;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = CX[(4 * g + k) * FireCarry<CP>::XCS + ci];
+    const unsigned vo = (unsigned)pix * 4u + nca_mul_u32((unsigned)(4 * g), plane4);
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(act);
+    while (todo) {
+        const int bu = __builtin_amdgcn_readlane(bat, __builtin_ctzll(todo));
+        const bool mine = act && bat == bu;
+        const __amdgpu_buffer_rsrc_t ro = nca_rsrc(reinterpret_cast<char*>(a.x_out) + (size_t)bu * C * plane * 4u);
+        if (mine) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < C) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[k]), ro, (int)vo, (int)((unsigned)k * plane4), WT ? 16 : 0);
+        }
+        todo &= ~__builtin_amdgcn_ballot_w64(mine);
     }
 }
 

@@ -130,6 +130,8 @@ size_t nca_cond_persist_xch_pairs(int B, int C, int H, int W);
 hipError_t nca_launch_cond_persist(const NcaCondPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
 int nca_get_cond_precision();
 void nca_set_cond_pc_dense(bool on);   // test hook: the fp32 producer/consumer step without firing-cell lists
+void nca_set_cond_pc_nocarry(bool on); // test hook: firing-cell lists without the carry of partial groups across tiles
+void nca_set_cond_pc_wg_cap(int n);    // test hook: cap on the workgroups of a producer/consumer step launch (0: none)
 bool nca_cond_default_family();   // no test hook / environment override routes the ConditionedNCA step away from its default kernels
 
 struct NcaCondArgs {

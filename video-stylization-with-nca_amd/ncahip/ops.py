@@ -84,7 +84,8 @@ def _w(t: torch.Tensor, name: str, like: torch.Tensor) -> torch.Tensor:
 
 def force_generic(on) -> None:
     """Test hook (see ncahip.h): True/1 = generic any-shape kernels, 2 = symmetric wave-private ConditionedNCA
-    kernel, 32 = fp32 producer/consumer step without firing-cell lists, False/0 = defaults."""
+    kernel, 32 = fp32 producer/consumer step without firing-cell lists, 64 = firing-cell lists without the carry across
+    tiles, n << 8 = at most n workgroups per producer/consumer step launch, False/0 = defaults."""
     lib().ncahip_debug_force_generic(int(on))
 
 
