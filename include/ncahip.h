@@ -494,6 +494,36 @@ int ncahip_dynca_clip_f32(float *states, const float *cond, void *images, int im
                           uint64_t seed, uint64_t step0, float *pc_scratch, void *persist_ws, size_t persist_bytes,
                           unsigned epoch0, ncahip_stream_t stream);
 
+/* ---- a whole clip per call, extra-channel models: the grey frame is the LAST state channel ----------------------------------
+ * ExtraChannels/utils/misc/video_utils.py:66-82: for every target frame, steps_per_frame times
+ * { h = cat(h, grey(frame)); state, rgb = forward_nsteps(h, step_n); h = state[:, :-1]; emit clip(rgb, -1, 1) * 0.5 + 0.5 }.  The model
+ * has C = c_in channels, the last one the conditioning image, which evolves with the rest during a call and is replaced before the
+ * next; its cond map is the positional encoding (CPE, c_cond = 2, the same for every frame) or none.  Formats as above.
+ * ncahip_clip_gray: gray [F,B,H,W] = gray_r * r + gray_g * g + gray_b * b of every frame of a call in one launch; weights and the
+ *   widening of uint8 frames as ncahip_clip_cond, whose loader it shares (aligned dwords at any alignment of the tensor and any W * 3).
+ * ncahip_clip_emit_inject: one launch for the two things that happen between two calls.  img != NULL: img = ncahip_clip_emit(state), the
+ *   same bits.  gray != NULL: state[:, C-1] = gray [B,H,W].  The image reads channels below c_out, the plane goes to channel C-1:
+ *   1 <= c_out <= 4 and c_out <= C-1.  img == NULL: inject only (before the first call); gray == NULL: emit only; both NULL:
+ *   NCAHIP_EINVAL.  State, image and plane must not overlap.
+ * ncahip_dynca_clip_xc_f32: ncahip_dynca_clip_f32 for these models.  For call n = f * steps_per_frame + j: channel C-1 of the current
+ *   state is replaced by gray[f] (before EVERY call, the repeats j > 0 included, as the reference's cat does), then step_n steps run
+ *   with cond, then image n is written.  A clip is one inject launch, then per call the step launch(es) and one emit + inject launch.
+ *   gray: [F,B,H,W], from ncahip_clip_gray.  cond: ONE map [B,c_cond,H,W] for all frames, c_cond = 2; or NULL with c_cond = 0.
+ *   states, u, two_scale, pc_scratch, persist_ws / epoch0, the routes (persistent entry points, per-step ring from the first NCAHIP_ERANGE
+ *   on), the host-side checks, the sticky error word and the return codes: as ncahip_dynca_clip_f32, with which it shares its body.  In
+ *   addition NCAHIP_EINVAL for gray == NULL, c_cond other than 0 or 2, a cond pointer that does not match c_cond, c_out > C-1, and gray
+ *   overlapping states, cond or images.  On return slot 0 of states holds all C channels, the last one the extra channel as the last
+ *   call's steps left it: dropping it (h = state[:, :-1]) is the caller's job. */
+int ncahip_clip_gray(const void *frames, int frame_fmt, float gray_r, float gray_g, float gray_b, float *gray, int F, int B, int H, int W,
+                     ncahip_stream_t stream);
+int ncahip_clip_emit_inject(float *state, void *img, int img_fmt, const float *gray, int B, int C, int c_out, int H, int W,
+                            ncahip_stream_t stream);
+int ncahip_dynca_clip_xc_f32(float *states, const float *gray, const float *cond, int c_cond, void *images, int img_fmt, int F,
+                             int steps_per_frame, int step_n, const float *u, const float *w1, const float *b1, const float *w2,
+                             const float *b2, int B, int C, int c_out, int H, int W, int fc, int pad_mode, int two_scale,
+                             float update_rate, uint64_t seed, uint64_t step0, float *pc_scratch, void *persist_ws,
+                             size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

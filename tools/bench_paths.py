@@ -15,6 +15,9 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
   video_clip      a 64-frame clip at 256^2, B = 1, step_n = 8, edge conditioning, Philox masks (C = 12 / fc = 96 and C = 16 / fc = 128,
                   single- and two-scale): the per-frame generator synthesize_video consumed to the end against stylize_clip with
                   float32 frames in / float32 images out and uint8 in / uint8 out; host clock around a device synchronise
+  video_clip_xc   the same clip with the ExtraChannels default model (C = 16 / fc = 128 / CPE, two- and single-scale), whose grey frame is
+                  the last state channel: (a) the hand loop over forward_nsteps (cat, call, slice) against stylize_clip (b) float32 ->
+                  float32 and (c) uint8 -> uint8, the three measured twice over (a b c a b c) so that the spread of (a) is on record
   trainer_default ConditionedNCATrainer at the reference's own defaults (C = 20, 64 x 64, batch 8, nca_steps [48, 96]): ms per iteration
   loss            the default objective (VGG16 features + batched OT + content + overflow) at 32 x 3 x 256^2, fp32 / bf16 features
   loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched, fused and fused_all alternating in one
@@ -526,6 +529,42 @@ def video_clip_leg():
                  route=getattr(getattr(video, "stylize_clip", None), "last_path", None), **res, **ratios)
 
 
+def video_clip_xc_leg():
+    """video_clip_leg for the extra-channel family (ExtraChannels/utils/misc/video_utils.py:66-82; fit_video_motion.py's default model).
+    (a) the reference's loop by hand: per frame h = cat(h, mean grey), forward_nsteps, h = state[:, :-1], one image; (b) stylize_clip
+    float32 in / float32 out; (c) uint8 in / uint8 out.  Frames on the device, every call seeds anew, host clock between two device
+    synchronisations, median of 10 after 3 warm-ups; two passes over (a, b, c): the two (a) figures give the session's spread."""
+    from ncahip import video
+    from ncahip.models.dynca_extra import DyNCA
+    n_frames, step_n, S, C, fc = 64, 8, 256, 16, 128
+    for two in (True, False):
+        torch.manual_seed(0)
+        m = DyNCA(C, 3, fc_dim=fc, padding_mode="circular", pos_emb="CPE", perception_scales=[0, 1] if two else [0], device=torch.device(DEV))
+        m.mask_rng, m.mask_seed = "philox", 1
+        gen = torch.Generator().manual_seed(0)
+        u8 = torch.randint(0, 256, (n_frames, S, S, 3), generator=gen, dtype=torch.uint8).to(DEV)
+        f32 = (u8.float() / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2).contiguous()
+
+        @torch.no_grad()
+        def loop():
+            h = m.seed(1, size=(S, S))
+            for f in range(n_frames):
+                state, rgb = m.forward_nsteps(torch.cat((h, f32[f:f + 1].mean(1, keepdim=True)), 1), step_n)
+                h = state[:, :-1]
+                (rgb.clamp(-1.0, 1.0) + 1.0) / 2.0
+
+        fns = [loop, lambda: video.stylize_clip(m, f32, step_n=step_n), lambda: video.stylize_clip(m, u8, step_n=step_n, out_dtype=torch.uint8)]
+        names = ["hand_loop", "stylize_clip_f32", "stylize_clip_u8"]
+        for run in (1, 2):
+            med, mn = timed_sync(fns)
+            ops.check_errors()
+            res = {n: dict(us_per_frame=a / n_frames * 1e3, min_us_per_frame=b / n_frames * 1e3, frames_per_s=n_frames / a * 1e3)
+                   for n, a, b in zip(names, med, mn)}
+            ratios = {n + "_over_hand_loop": res[n]["us_per_frame"] / res["hand_loop"]["us_per_frame"] for n in names[1:]}
+            emit(path="video_clip_xc", run=run, C=C, fc=fc, two_scale=two, HW=[S, S], frames=n_frames, step_n=step_n, masks="philox",
+                 route=video.stylize_clip.last_path, **res, **ratios)
+
+
 def main(names):
     allp = not names
     if allp or "cond_train" in names:
@@ -574,6 +613,8 @@ def main(names):
         video_leg()
     if allp or "video_clip" in names:
         video_clip_leg()
+    if allp or "video_clip_xc" in names:
+        video_clip_xc_leg()
     if allp or "trainer_default" in names:
         trainer_default_leg()
 

@@ -430,8 +430,8 @@ int ncahip_clip_cond(const void* frames, int frame_fmt, const float* k3, float g
                                            (hipStream_t)stream), "clip_cond");
 }
 
-static int check_clip_emit(const void* state, const void* img, int img_fmt, int B, int C, int c_out, int H, int W) {
-    if (!state || !img) return fail(NCAHIP_EINVAL, "clip emit: null pointer");
+static int check_clip_emit(const void* state, const void* img, int img_fmt, int B, int C, int c_out, int H, int W, bool need_img = true) {
+    if (!state || (need_img && !img)) return fail(NCAHIP_EINVAL, "clip emit: null pointer");
     if (!clip_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
     if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit: bad size");
     if (c_out < 1 || c_out > 4 || c_out > C) return fail(NCAHIP_EINVAL, "clip emit: c_out=%d must be in 1..4 and at most C=%d", c_out, C);
@@ -443,44 +443,87 @@ int ncahip_clip_emit(const float* state, void* img, int img_fmt, int B, int C, i
     if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W)) return rc;
     if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt)))
         return fail(NCAHIP_EINVAL, "clip emit: the image overlaps the state");
-    return hip_result(nca_launch_clip_emit(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit");
+    // without a grey plane the launcher only reads the state
+    return hip_result(nca_launch_clip_emit_inject(const_cast<float*>(state), img, img_fmt == NCAHIP_CLIP_U8_NHWC, nullptr, B, C, c_out, H, W,
+                                                  (hipStream_t)stream), "clip_emit");
 }
 
-int ncahip_dynca_clip_f32(float* states, const float* cond, void* images, int img_fmt, int F, int steps_per_frame, int step_n, const float* u,
-                          const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int c_out, int H, int W, int fc,
-                          int pad_mode, int two_scale, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, void* persist_ws,
-                          size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream) {
-    constexpr int c_cond = 3;
+int ncahip_clip_gray(const void* frames, int frame_fmt, float gray_r, float gray_g, float gray_b, float* gray, int F, int B, int H, int W,
+                     ncahip_stream_t stream) {
+    if (!frames || !gray) return fail(NCAHIP_EINVAL, "clip_gray: null pointer");
+    if (!clip_fmt_ok(frame_fmt)) return fail(NCAHIP_EINVAL, "clip_gray: unknown frame format %d", frame_fmt);
+    if (F <= 0 || !dims_ok(B, 3, H, W) || (size_t)F * B > 0x7fffffffu) return fail(NCAHIP_EINVAL, "clip_gray: bad size");
+    const size_t px = (size_t)F * B * H * W;
+    if (clip_overlap(frames, 3 * px * clip_fmt_bytes(frame_fmt), gray, px * sizeof(float))) return fail(NCAHIP_EINVAL, "clip_gray: gray overlaps the frames");
+    if (frame_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)frames & 3) != 0) return fail(NCAHIP_EINVAL, "clip_gray: float32 frames must be 4-byte aligned");
+    return hip_result(nca_launch_clip_gray(frames, frame_fmt == NCAHIP_CLIP_U8_NHWC, gray_r, gray_g, gray_b, gray, F * B, H, W, (hipStream_t)stream),
+                      "clip_gray");
+}
+
+// c_out of a model whose last state channel is the conditioning image: the image never reads that channel
+static int check_extra_channel(const char* who, int C, int c_out) {
+    if (c_out > C - 1) return fail(NCAHIP_EINVAL, "%s: c_out=%d reaches the extra channel (channel C-1 = %d holds the grey frame: c_out <= C-1)", who, c_out, C - 1);
+    return 0;
+}
+
+int ncahip_clip_emit_inject(float* state, void* img, int img_fmt, const float* gray, int B, int C, int c_out, int H, int W, ncahip_stream_t stream) {
+    if (!img && !gray) return fail(NCAHIP_EINVAL, "clip emit_inject: neither an image nor a grey plane (null pointer for both halves)");
+    if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W, false)) return rc;
+    if (int rc = check_extra_channel("clip emit_inject", C, c_out)) return rc;
+    const size_t sbytes = (size_t)B * C * H * W * sizeof(float), gbytes = (size_t)B * H * W * sizeof(float);
+    const size_t ibytes = (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt);
+    if ((img && clip_overlap(state, sbytes, img, ibytes)) || (gray && clip_overlap(state, sbytes, gray, gbytes)) ||
+        (img && gray && clip_overlap(img, ibytes, gray, gbytes)))
+        return fail(NCAHIP_EINVAL, "clip emit_inject: state, image and grey plane must not overlap");
+    return hip_result(nca_launch_clip_emit_inject(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, gray, B, C, c_out, H, W, (hipStream_t)stream),
+                      "clip_emit_inject");
+}
+
+// The body of the two clip drivers.  gray == NULL: ncahip_dynca_clip_f32 (cond [F] maps, one per frame).  gray != NULL:
+// ncahip_dynca_clip_xc_f32 (one cond map or none for all frames; gray[f] replaces state channel C-1 before every call).
+static int dynca_clip_impl(const char* who, float* states, const float* gray, const float* cond, int c_cond, bool cond_per_frame, void* images,
+                           int img_fmt, int F, int steps_per_frame, int step_n, const float* u, const float* w1, const float* b1, const float* w2,
+                           const float* b2, int B, int C, int c_out, int H, int W, int fc, int pad_mode, int two_scale, float update_rate,
+                           uint64_t seed, uint64_t step0, float* pc_scratch, void* persist_ws, size_t persist_bytes, unsigned epoch0,
+                           ncahip_stream_t stream) {
     // host-side checks: nothing is enqueued before all of them have passed
-    if (!cond) return fail(NCAHIP_EINVAL, "dynca clip: null pointer");
     if (int rc = check_clip_emit(states, images, img_fmt, B, C, c_out, H, W)) return rc;
-    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "dynca clip: F, steps_per_frame and step_n must be positive");
+    if (gray) {
+        if (int rc = check_extra_channel(who, C, c_out)) return rc;
+    }
+    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
     const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
-    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "dynca clip: F * steps_per_frame * step_n must stay below 2^31");
+    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
     const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W, cslot = (size_t)B * c_cond * H * W;
     const size_t ibytes = (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt);
-    if (clip_overlap(states, 2 * slot * sizeof(float), cond, (size_t)F * cslot * sizeof(float)) ||
-        clip_overlap(states, 2 * slot * sizeof(float), images, (size_t)calls * ibytes) ||
-        clip_overlap(cond, (size_t)F * cslot * sizeof(float), images, (size_t)calls * ibytes))
-        return fail(NCAHIP_EINVAL, "dynca clip: states, cond and images must not overlap");
+    const size_t sbytes = 2 * slot * sizeof(float), cbytes = (cond_per_frame ? (size_t)F : 1) * cslot * sizeof(float);
+    const size_t gbytes = (size_t)F * uslot * sizeof(float);
+    if ((cond && clip_overlap(states, sbytes, cond, cbytes)) || clip_overlap(states, sbytes, images, (size_t)calls * ibytes) ||
+        (cond && clip_overlap(cond, cbytes, images, (size_t)calls * ibytes)) ||
+        (gray && (clip_overlap(states, sbytes, gray, gbytes) || clip_overlap(gray, gbytes, images, (size_t)calls * ibytes) ||
+                  (cond && clip_overlap(gray, gbytes, cond, cbytes)))))
+        return fail(NCAHIP_EINVAL, "%s: states, %scond and images must not overlap", who, gray ? "gray, " : "");
     if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
-        return fail(NCAHIP_EINVAL, "dynca clip: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)");
+        return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
     // what the per-step entry point refuses for this shape, the clip refuses with its code (T = 0: every check, no launch)
     if (int rc = two_scale ? ncahip_dynca_nsteps_fwd_ms_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, pc_scratch, stream)
                            : ncahip_dynca_nsteps_fwd_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, stream))
         return rc;
     if (persist_ws) {
         const size_t need = ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, c_cond);
-        if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "dynca clip: persistent workspace too small");
+        if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "%s: persistent workspace too small", who);
     }
-    if (int rc = device_error_rc("dynca clip")) return rc;
+    if (int rc = device_error_rc(who)) return rc;
 
     const bool ubits = u_is_bits(u, seed), u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
     hipStream_t st = (hipStream_t)stream;
     bool persist = persist_ws != nullptr;
     int cur = 0;   // the slot that holds the state
+    if (gray) {    // the first frame's grey; every later one goes in with the image of the call before it
+        if (int rc = hip_result(nca_launch_clip_emit_inject(states, nullptr, false, gray, B, C, c_out, H, W, st), "dynca clip (inject)")) return rc;
+    }
     for (int n = 0; n < (int)calls; ++n) {
-        const float* const cf = cond + (size_t)(n / steps_per_frame) * cslot;
+        const float* const cf = cond_per_frame ? cond + (size_t)(n / steps_per_frame) * cslot : cond;
         const int t0 = n * step_n;                                  // first step of this call within `u`
         const uint64_t s0 = step0 + (uint64_t)t0;
         bool done = false;
@@ -514,12 +557,36 @@ int ncahip_dynca_clip_f32(float* states, const float* cond, void* images, int im
                 return rc;
             cur = T & 1;
         }
-        if (int rc = hip_result(nca_launch_clip_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, B, C, c_out, H, W, st), "dynca clip (emit)"))
+        // image n and, in the same launch, the grey of the call that follows (the repeats j > 0 of a frame included: the channel has
+        // evolved); after the last call the channel stays as the steps left it
+        const float* const gnext = gray && n + 1 < (int)calls ? gray + (size_t)((n + 1) / steps_per_frame) * uslot : nullptr;
+        if (int rc = hip_result(nca_launch_clip_emit_inject(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, gnext, B, C, c_out, H, W, st),
+                                "dynca clip (emit)"))
             return rc;
     }
     if (cur == 1)   // the state returns in slot 0
         return hip_result(hipMemcpyAsync(states, states + slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "dynca clip (state copy)");
     return 0;
+}
+
+int ncahip_dynca_clip_f32(float* states, const float* cond, void* images, int img_fmt, int F, int steps_per_frame, int step_n, const float* u,
+                          const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int c_out, int H, int W, int fc,
+                          int pad_mode, int two_scale, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, void* persist_ws,
+                          size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream) {
+    if (!cond) return fail(NCAHIP_EINVAL, "dynca clip: null pointer");
+    return dynca_clip_impl("dynca clip", states, nullptr, cond, 3, true, images, img_fmt, F, steps_per_frame, step_n, u, w1, b1, w2, b2, B, C, c_out, H, W,
+                           fc, pad_mode, two_scale, update_rate, seed, step0, pc_scratch, persist_ws, persist_bytes, epoch0, stream);
+}
+
+int ncahip_dynca_clip_xc_f32(float* states, const float* gray, const float* cond, int c_cond, void* images, int img_fmt, int F, int steps_per_frame,
+                             int step_n, const float* u, const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int c_out,
+                             int H, int W, int fc, int pad_mode, int two_scale, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch,
+                             void* persist_ws, size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream) {
+    if (!gray) return fail(NCAHIP_EINVAL, "dynca clip xc: null pointer");
+    if (c_cond != 0 && c_cond != 2) return fail(NCAHIP_EINVAL, "dynca clip xc: c_cond=%d must be 0 (no cond map) or 2 (CPE)", c_cond);
+    if ((c_cond == 2) != (cond != nullptr)) return fail(NCAHIP_EINVAL, "dynca clip xc: cond pointer / c_cond mismatch");
+    return dynca_clip_impl("dynca clip xc", states, gray, cond, c_cond, false, images, img_fmt, F, steps_per_frame, step_n, u, w1, b1, w2, b2, B, C, c_out,
+                           H, W, fc, pad_mode, two_scale, update_rate, seed, step0, pc_scratch, persist_ws, persist_bytes, epoch0, stream);
 }
 
 int ncahip_cond_step_fwd_f32(const float* x_in, const uint8_t* pre_in, float* x_out, uint8_t* pre_out,

@@ -1,6 +1,9 @@
 // nca_clip.hip -- the two ends of clip stylisation (ConditioneDyNCA/utils/misc/video_utils.py:50-83) around the DyNCA steps:
 //   clip_cond_kernel   frames of one call -> cond [F,B,3,H,W]: grey, then EdgeExtractor (dynca.py:204-213) in one pass
 //   clip_emit_kernel   state [B,C,H,W] -> one output image (video_utils.py:78-81), float32 NCHW or uint8 NHWC
+// and, for the models that carry the grey frame as their last state channel (ExtraChannels/utils/misc/video_utils.py:66-82):
+//   clip_gray_kernel   frames of one call -> grey [F,B,H,W]
+//   the emit kernels with INJ: the image as above and, in the same launch, a grey plane written over state channel C - 1
 #include "nca_kernels.h"
 
 namespace {
@@ -13,6 +16,44 @@ constexpr int kRawDwords = (3 * kHaloW + 3 + 3) / 4 + 1; // aligned dwords that 
 __device__ __forceinline__ float clip_widen_u8(unsigned v) {
     const float f = __fdiv_rn((float)v, 255.0f);
     return __fsub_rn(__fmul_rn(f, 2.0f), 1.0f);
+}
+
+// uint8 RGB rows into LDS as memory-aligned dwords: ROWS row segments (image rows y_first .. y_first + ROWS - 1 of image n, columns
+// [cx0, cx1), at most kHaloW of them) of a [N,H,W,3] tensor of `total` bytes, kRawDwords dwords per staged row.  The dwords are aligned in
+// memory, whatever the tensor's own alignment or W * 3; one that straddles an end of the tensor is assembled from its bytes inside.
+template <int ROWS>
+__device__ __forceinline__ void clip_stage_u8_rows(const unsigned char* base, size_t total, size_t n, size_t plane, int H, int W, int y_first,
+                                                   int cx0, int cx1, unsigned* raw, int tid) {
+    const uintptr_t mis = (uintptr_t)base & 3;
+    for (int i = tid; i < ROWS * kRawDwords; i += 256) {
+        const int r = i / kRawDwords, d = i % kRawDwords;
+        const int y = y_first + r;
+        if (y < 0 || y >= H) continue;
+        const size_t first = (n * plane + (size_t)y * W + cx0) * 3;          // first byte of the row segment
+        const size_t last = first + (size_t)(cx1 - cx0) * 3;                 // one past its last byte
+        const ptrdiff_t a0 = (ptrdiff_t)((first + mis) & ~(size_t)3) - (ptrdiff_t)mis;   // aligned start, as an offset from base (>= -3)
+        const ptrdiff_t a = a0 + 4 * (ptrdiff_t)d;
+        if (a >= (ptrdiff_t)last) continue;
+        unsigned v;
+        if (a >= 0 && (size_t)a + 4 <= total) {
+            v = *reinterpret_cast<const unsigned*>(base + a);
+        } else {   // the dword straddles an end of the tensor: only its bytes inside
+            v = 0u;
+            for (int k = 0; k < 4; ++k)
+                if (a + k >= 0 && (size_t)(a + k) < total) v |= (unsigned)base[a + k] << (8 * k);
+        }
+        raw[r * kRawDwords + d] = v;
+    }
+}
+
+// grey of pixel (y, x) of image n from the rows clip_stage_u8_rows staged (r: its staged row, cx0: the first staged column)
+__device__ __forceinline__ float clip_staged_u8_grey(const unsigned char* base, const unsigned* raw, int r, size_t n, size_t plane, int W, int y,
+                                                     int x, int cx0, float wr, float wg, float wb) {
+    const uintptr_t mis = (uintptr_t)base & 3;
+    const size_t first = (n * plane + (size_t)y * W + cx0) * 3;
+    const int off = (int)((first + mis) & 3) + 3 * (x - cx0);            // byte of this pixel within the staged row
+    const unsigned char* const p = reinterpret_cast<const unsigned char*>(raw) + (size_t)r * kRawDwords * 4 + off;
+    return wr * clip_widen_u8(p[0]) + wg * clip_widen_u8(p[1]) + wb * clip_widen_u8(p[2]);
 }
 
 // One workgroup = one 16 x 64 tile of one image.  The grey tile (+ halo, zero outside the image) is staged in LDS, so every input
@@ -36,39 +77,13 @@ __global__ __launch_bounds__(256) void clip_cond_kernel(const void* __restrict__
 
     if (U8) {
         const unsigned char* const base = static_cast<const unsigned char*>(frames);
-        const size_t total = (size_t)N * plane * 3;
-        const uintptr_t mis = (uintptr_t)base & 3;         // the dwords are aligned in memory, whatever the tensor's own alignment
-        for (int i = tid; i < kHaloH * kRawDwords; i += 256) {
-            const int r = i / kRawDwords, d = i % kRawDwords;
-            const int y = y0 - 1 + r;
-            if (y < 0 || y >= H) continue;
-            const size_t first = (n * plane + (size_t)y * W + cx0) * 3;          // first byte of the row segment
-            const size_t last = first + (size_t)(cx1 - cx0) * 3;                 // one past its last byte
-            const ptrdiff_t a0 = (ptrdiff_t)((first + mis) & ~(size_t)3) - (ptrdiff_t)mis;   // aligned start, as an offset from base (>= -3)
-            const ptrdiff_t a = a0 + 4 * (ptrdiff_t)d;
-            if (a >= (ptrdiff_t)last) continue;
-            unsigned v;
-            if (a >= 0 && (size_t)a + 4 <= total) {
-                v = *reinterpret_cast<const unsigned*>(base + a);
-            } else {   // the dword straddles an end of the tensor: only its bytes inside
-                v = 0u;
-                for (int k = 0; k < 4; ++k)
-                    if (a + k >= 0 && (size_t)(a + k) < total) v |= (unsigned)base[a + k] << (8 * k);
-            }
-            raw[r][d] = v;
-        }
+        clip_stage_u8_rows<kHaloH>(base, (size_t)N * plane * 3, n, plane, H, W, y0 - 1, cx0, cx1, &raw[0][0], tid);
         __syncthreads();
-        const unsigned char* const rb = reinterpret_cast<const unsigned char*>(&raw[0][0]);
         for (int i = tid; i < kHaloH * kHaloW; i += 256) {
             const int r = i / kHaloW, c = i % kHaloW;
             const int y = y0 - 1 + r, x = x0 - 1 + c;
             float g = 0.0f;
-            if (y >= 0 && y < H && x >= cx0 && x < cx1) {
-                const size_t first = (n * plane + (size_t)y * W + cx0) * 3;
-                const int off = (int)((first + mis) & 3) + 3 * (x - cx0);        // byte of this pixel within the staged row
-                const unsigned char* const p = rb + (size_t)r * kRawDwords * 4 + off;
-                g = wr * clip_widen_u8(p[0]) + wg * clip_widen_u8(p[1]) + wb * clip_widen_u8(p[2]);
-            }
+            if (y >= 0 && y < H && x >= cx0 && x < cx1) g = clip_staged_u8_grey(base, &raw[0][0], r, n, plane, W, y, x, cx0, wr, wg, wb);
             grey[r][c] = g;
         }
     } else {
@@ -132,19 +147,26 @@ __device__ __forceinline__ float clip_image_value(float x) {
     return __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);
 }
 
-__global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restrict__ x, float* __restrict__ img, int B, int C, int c_out,
-                                                            size_t plane) {
+// One launch for both halves of the step between two calls of an extra-channel clip: EMIT writes the image of x[:, :c_out] into img,
+// INJ copies the plane gray [B,H,W] over channel C - 1 of the same state (xlast = x + (C - 1) * plane; c_out <= C - 1, so the two halves
+// touch different channels).  EMIT alone is the image output of the edge family.
+template <bool EMIT, bool INJ>
+__global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restrict__ x, float* __restrict__ img, float* __restrict__ xlast,
+                                                            const float* __restrict__ gray, int B, int C, int c_out, size_t plane) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= (size_t)B * c_out * plane) return;
-    const size_t p = id % plane, c = (id / plane) % c_out, b = id / (plane * c_out);
-    img[id] = clip_image_value(x[(b * C + c) * plane + p]);
+    const size_t nc = (EMIT ? (size_t)c_out : 0) + (INJ ? 1 : 0);
+    if (id >= (size_t)B * nc * plane) return;
+    const size_t p = id % plane, c = (id / plane) % nc, b = id / (plane * nc);
+    if (INJ && c == nc - 1) xlast[b * C * plane + p] = gray[b * plane + p];
+    else img[INJ ? (b * c_out + c) * plane + p : id] = clip_image_value(x[(b * C + c) * plane + p]);
 }
 
 // uint8 NHWC: a lane owns 4 consecutive pixels of the flattened [B*H*W] axis = CO dwords, stored whole (bytes only for the last, partial
-// group or an output that is not 4-byte aligned).  (uint8_t)(img * 255): truncation, as np.uint8 in VideoWriter.add.
-template <int CO>
-__global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, int B, int C,
-                                                           size_t plane, int aligned) {
+// group or an output that is not 4-byte aligned).  (uint8_t)(img * 255): truncation, as np.uint8 in VideoWriter.add.  INJ as above, for
+// the lane's pixels.
+template <int CO, bool INJ>
+__global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
+                                                           const float* __restrict__ gray, int B, int C, size_t plane, int aligned) {
     const size_t grp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t npix = (size_t)B * plane, q0 = grp * 4;
     if (q0 >= npix) return;
@@ -155,6 +177,7 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
         const size_t b = q / plane, p = q % plane;
 #pragma unroll
         for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_image_value(x[(b * C + c) * plane + p]), 255.0f);
+        if (INJ && q0 + i < npix) xlast[b * C * plane + p] = gray[q];
     }
     unsigned char* const o = img + q0 * CO;
     if (aligned && q0 + 4 <= npix) {
@@ -164,6 +187,39 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
     } else {
         const size_t nb = (q0 + 4 <= npix ? 4 : npix - q0) * CO;
         for (size_t i = 0; i < nb; ++i) o[i] = px[i];
+    }
+}
+
+// grey [N,H,W] of N = F*B frames, one 16 x 64 tile per workgroup and no halo.  U8: the tile's rows come in through clip_stage_u8_rows, the
+// loader of clip_cond_kernel; float32 planes are read in place (every pixel once, coalesced), so no LDS there.
+template <bool U8>
+__global__ __launch_bounds__(256) void clip_gray_kernel(const void* __restrict__ frames, float wr, float wg, float wb, float* __restrict__ gray,
+                                                        int N, int H, int W, int tiles_x, int tiles_y) {
+    __shared__ unsigned raw[U8 ? kTileH : 1][U8 ? kRawDwords : 1];
+    const int tid = threadIdx.x;
+    const size_t blk = blockIdx.x;
+    const int tx = (int)(blk % tiles_x), ty = (int)((blk / tiles_x) % tiles_y);
+    const size_t n = blk / ((size_t)tiles_x * tiles_y);
+    if (n >= (size_t)N) return;
+    const int x0 = tx * kTileW, y0 = ty * kTileH;
+    const size_t plane = (size_t)H * W;
+    const int cx1 = min(x0 + kTileW, W);
+    if (U8) {
+        clip_stage_u8_rows<kTileH>(static_cast<const unsigned char*>(frames), (size_t)N * plane * 3, n, plane, H, W, y0, x0, cx1, &raw[0][0], tid);
+        __syncthreads();
+    }
+    for (int i = tid; i < kTileH * kTileW; i += 256) {
+        const int r = i / kTileW, y = y0 + r, x = x0 + i % kTileW;
+        if (y >= H || x >= W) continue;
+        const size_t o = (size_t)y * W + x;
+        float g;
+        if (U8) {
+            g = clip_staged_u8_grey(static_cast<const unsigned char*>(frames), &raw[0][0], r, n, plane, W, y, x, x0, wr, wg, wb);
+        } else {
+            const float* const ib = static_cast<const float*>(frames) + n * 3 * plane;
+            g = wr * ib[o] + wg * ib[plane + o] + wb * ib[2 * plane + o];
+        }
+        gray[n * plane + o] = g;
     }
 }
 
@@ -179,11 +235,33 @@ hipError_t nca_launch_clip_cond(const void* frames, bool u8, const float* k3, fl
     return hipGetLastError();
 }
 
-hipError_t nca_launch_clip_emit(const float* state, void* img, bool u8, int B, int C, int c_out, int H, int W, hipStream_t st) {
+hipError_t nca_launch_clip_gray(const void* frames, bool u8, float wr, float wg, float wb, float* gray, int N, int H, int W, hipStream_t st) {
+    const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
+    const size_t blocks = (size_t)N * tiles_x * tiles_y;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    if (u8) hipLaunchKernelGGL(clip_gray_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, frames, wr, wg, wb, gray, N, H, W, tiles_x, tiles_y);
+    else hipLaunchKernelGGL(clip_gray_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, frames, wr, wg, wb, gray, N, H, W, tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+template <int CO>
+static void clip_launch_emit_u8(bool inj, dim3 grid, hipStream_t st, const float* x, unsigned char* o, float* xlast, const float* gray, int B, int C,
+                                size_t plane, int aligned) {
+    if (inj) hipLaunchKernelGGL((clip_emit_u8_kernel<CO, true>), grid, dim3(256), 0, st, x, o, xlast, gray, B, C, plane, aligned);
+    else hipLaunchKernelGGL((clip_emit_u8_kernel<CO, false>), grid, dim3(256), 0, st, x, o, xlast, gray, B, C, plane, aligned);
+}
+
+hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const float* gray, int B, int C, int c_out, int H, int W, hipStream_t st) {
     const size_t plane = (size_t)H * W;
-    if (!u8) {
-        const size_t n = (size_t)B * c_out * plane;
-        hipLaunchKernelGGL(clip_emit_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img, B, C, c_out, plane);
+    if (!img && !gray) return hipErrorInvalidValue;
+    if (gray && c_out > C - 1) return hipErrorInvalidValue;
+    float* const xlast = state + (size_t)(C - 1) * plane;
+    if (!img || !u8) {
+        const size_t n = (size_t)B * ((img ? c_out : 0) + (gray ? 1 : 0)) * plane;
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (!img) hipLaunchKernelGGL((clip_emit_f32_kernel<false, true>), grid, dim3(256), 0, st, state, (float*)nullptr, xlast, gray, B, C, c_out, plane);
+        else if (gray) hipLaunchKernelGGL((clip_emit_f32_kernel<true, true>), grid, dim3(256), 0, st, state, (float*)img, xlast, gray, B, C, c_out, plane);
+        else hipLaunchKernelGGL((clip_emit_f32_kernel<true, false>), grid, dim3(256), 0, st, state, (float*)img, xlast, gray, B, C, c_out, plane);
         return hipGetLastError();
     }
     const size_t groups = ((size_t)B * plane + 3) / 4;
@@ -191,10 +269,10 @@ hipError_t nca_launch_clip_emit(const float* state, void* img, bool u8, int B, i
     const int aligned = ((uintptr_t)img & 3) == 0;
     unsigned char* const o = (unsigned char*)img;
     switch (c_out) {
-        case 1: hipLaunchKernelGGL(clip_emit_u8_kernel<1>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
-        case 2: hipLaunchKernelGGL(clip_emit_u8_kernel<2>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
-        case 3: hipLaunchKernelGGL(clip_emit_u8_kernel<3>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
-        case 4: hipLaunchKernelGGL(clip_emit_u8_kernel<4>, grid, dim3(256), 0, st, state, o, B, C, plane, aligned); break;
+        case 1: clip_launch_emit_u8<1>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
+        case 2: clip_launch_emit_u8<2>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
+        case 3: clip_launch_emit_u8<3>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
+        case 4: clip_launch_emit_u8<4>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

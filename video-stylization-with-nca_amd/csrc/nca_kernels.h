@@ -219,10 +219,13 @@ hipError_t nca_launch_slw_loss_fwd(const float* s, const float* t, const int* jm
 hipError_t nca_launch_slw_bwd(const float* s, const float* t, const int* jmap, const int* perm, const float* proj, const float* gup, float* ds, int B,
                               int c, int n, int m, void* ws, hipStream_t st);
 // nca_clip.hip: the two ends of clip stylisation.  frames: N = F*B images, float32 [N,3,H,W] or (u8) uint8 [N,H,W,3] -> cond [N,3,H,W];
-// state [B,C,H,W] -> image float32 [B,c_out,H,W] or (u8) uint8 [B,H,W,c_out], c_out in 1..4
+// state [B,C,H,W] -> image float32 [B,c_out,H,W] or (u8) uint8 [B,H,W,c_out], c_out in 1..4; frames -> grey [N,H,W]
 hipError_t nca_launch_clip_cond(const void* frames, bool u8, const float* k3, float wr, float wg, float wb, int do_tanh, float* cond, int N, int H,
                                 int W, hipStream_t st);
-hipError_t nca_launch_clip_emit(const float* state, void* img, bool u8, int B, int C, int c_out, int H, int W, hipStream_t st);
+hipError_t nca_launch_clip_gray(const void* frames, bool u8, float wr, float wg, float wb, float* gray, int N, int H, int W, hipStream_t st);
+// one launch: the image of state[:, :c_out] (img != nullptr) and the plane gray [B,H,W] over state[:, C-1] (gray != nullptr, c_out <= C-1);
+// the state is only read without a grey plane
+hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const float* gray, int B, int C, int c_out, int H, int W, hipStream_t st);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);

@@ -92,6 +92,10 @@ SIGNATURES = {
     "ncahip_clip_emit": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "ncahip_dynca_clip_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P,
                               ctypes.c_size_t, ctypes.c_uint, _P],
+    "ncahip_clip_gray": [_P, _I, _F, _F, _F, _P, _I, _I, _I, _I, _P],
+    "ncahip_clip_emit_inject": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "ncahip_dynca_clip_xc_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P,
+                                 _P, ctypes.c_size_t, ctypes.c_uint, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,

@@ -382,6 +382,73 @@ def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], 
     return images, states[0]
 
 
+def clip_gray(frames: torch.Tensor, gray="mean") -> torch.Tensor:
+    """frames [F,B,3,H,W] float32 in [-1, 1] or [F,B,H,W,3] uint8 -> grey [F,B,H,W] float32 in one launch (ncahip_clip_gray): what the
+    extra-channel models take as their last state channel.  gray: 'mean', 'luma' or three weights."""
+    fmt = _clip_fmt(frames.dtype)
+    frames = _dev(frames, "frames", frames.dtype)
+    if fmt == _capi.CLIP_U8_NHWC:
+        F_, B, H, W, three = frames.shape
+    else:
+        F_, B, three, H, W = frames.shape
+    assert three == 3, tuple(frames.shape)
+    wr, wg, wb = GRAY_WEIGHTS[gray] if isinstance(gray, str) else gray
+    out = torch.empty(F_, B, H, W, device=frames.device, dtype=torch.float32)
+    check(lib().ncahip_clip_gray(_p(frames), fmt, wr, wg, wb, _p(out), F_, B, H, W, _stream()), "clip_gray")
+    return out
+
+
+def clip_emit_inject(state: torch.Tensor, c_out: int = 3, gray_plane: Optional[torch.Tensor] = None, out_dtype=torch.float32,
+                     emit: bool = True) -> Optional[torch.Tensor]:
+    """One launch (ncahip_clip_emit_inject): the image of state[:, :c_out] as clip_emit (emit=True; returned) and gray_plane [B,H,W]
+    written over state[:, C-1] IN PLACE (gray_plane given).  c_out <= C-1.  emit=False: inject only, returns None."""
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float32 or not state.is_contiguous():
+        raise _capi.NcaHipError("ncahip: `state` must be a contiguous float32 CUDA (ROCm) tensor -- it is written in place")
+    B, C, H, W = state.shape
+    if gray_plane is not None:
+        gray_plane = _dev(gray_plane, "gray_plane")
+        assert gray_plane.numel() == B * H * W, (tuple(gray_plane.shape), tuple(state.shape))
+    img = _clip_images(1, B, c_out, H, W, out_dtype, state.device)[0] if emit else None
+    check(lib().ncahip_clip_emit_inject(_p(state), _p(img), _clip_fmt(out_dtype), _p(gray_plane), B, C, c_out, H, W, _stream()), "clip_emit_inject")
+    return img
+
+
+def dynca_clip_xc(x: torch.Tensor, gray: torch.Tensor, cond: Optional[torch.Tensor], us: Optional[torch.Tensor], w: DyncaWeights,
+                  steps_per_frame: int, step_n: int, c_out: int = 3, pad_mode: str = "replicate", update_rate: float = 0.5, seed: int = 0,
+                  step0: int = 0, two_scale: bool = False, out_dtype=torch.float32):
+    """dynca_clip for the models whose last state channel is the grey frame (ncahip_dynca_clip_xc_f32): over the F frames of gray
+    [F,B,H,W], per frame steps_per_frame times {state[:, -1] = gray[f], step_n DyNCA steps with cond, one image}.  x: the state with all
+    C = w.c channels, or with C - 1 (the reference's `h`: the last channel is written before the first call anyway).  cond: ONE map
+    [B,2,H,W] (CPE) for all frames, or None.  us as dynca_clip.  Returns (images, final state [B,C,H,W] with the evolved last channel)."""
+    x = _dev(x, "x")
+    B, cx, H, W = x.shape
+    C = w.c
+    gray = _dev(gray, "gray")
+    F_ = gray.shape[0]
+    assert gray.shape == (F_, B, H, W) and cx in (C - 1, C), (tuple(gray.shape), tuple(x.shape), C)
+    c_cond = 0 if cond is None else 2
+    if cond is not None:
+        cond = _dev(cond, "cond")
+        assert cond.shape == (B, 2, H, W), tuple(cond.shape)
+    calls = F_ * steps_per_frame
+    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
+    assert w.k1 == 4 * C + c_cond, (w.c, w.k1, c_cond)
+    states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
+    states[0, :, :cx].copy_(x)
+    images = _clip_images(calls, B, c_out, H, W, out_dtype, x.device)
+    pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
+    ws, nbytes, epoch = None, 0, 0
+    if persistent_steps:
+        nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, c_cond)
+        if nbytes and calls < (1 << 20) - 2:
+            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
+    check(lib().ncahip_dynca_clip_xc_f32(_p(states), _p(gray), _p(cond), c_cond, _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n,
+                                         _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode],
+                                         int(two_scale), update_rate, seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch,
+                                         _stream()), "dynca_clip_xc")
+    return images, states[0]
+
+
 # ------------------------------------------------------------------------------------ ConditionedNCA
 class CondWeights:
     """perception_net.weight [3C,1,3,3]; update_net.out.{0,2,4} weights/biases (nca.py:40-46,99-107)."""

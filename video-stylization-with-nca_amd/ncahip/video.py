@@ -3,6 +3,10 @@
 Reference: ConditioneDyNCA/utils/misc/video_utils.py:50-83 (`save_video`): seed once, then for every target frame run
 `steps_per_frame` x `forward_nsteps(h, step_n, cond_img=gray(frame))` and emit `clip(rgb, -1, 1) * 0.5 + 0.5`.  Video
 decoding / encoding (moviepy, cv2) is outside the hot path: frames come in and go out as tensors.
+
+stylize_clip also serves the ExtraChannels family (ncahip.models.dynca_extra.DyNCA), whose loop
+(ExtraChannels/utils/misc/video_utils.py:66-82) appends the grey frame to the state as its last channel before every call and
+drops it again after.
 """
 from typing import Iterable, Iterator, Optional
 
@@ -59,6 +63,21 @@ def _clip_route(nca_model, h: torch.Tensor) -> bool:
     return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
 
 
+def _extra_channels(nca_model) -> bool:
+    """True for the ExtraChannels family: the grey frame is the model's last state channel, not a cond_img."""
+    from .models import dynca_extra
+    return isinstance(nca_model, dynca_extra.DyNCA)
+
+
+def _clip_route_xc(nca_model, h: torch.Tensor) -> bool:
+    """True when ncahip_dynca_clip_xc_f32 covers an extra-channel model: perception_scales [0] or the fused [0, 1], an fp32 state on
+    the GPU, one sample."""
+    if not h.is_cuda or h.dtype != torch.float32 or h.shape[0] != 1:
+        return False
+    scales = list(nca_model.perception_scales)
+    return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
+
+
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                  gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32):
@@ -73,7 +92,13 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     (ncahip_clip_cond, then ncahip_dynca_clip_f32: the library's step kernels and the image output, no Python per frame); the result
     does not depend on frames_per_call.  The fire masks follow the model's mask_rng exactly as forward_nsteps draws them.  Anything else
     (other conditioning or scale sets, non-fp32 state, CPU tensors) runs a Python loop over forward_nsteps with the chosen grey.
-    stylize_clip.last_path records the route: 'clip' or 'loop'."""
+    stylize_clip.last_path records the route: 'clip' or 'loop'.
+
+    Extra-channel models (ncahip.models.dynca_extra.DyNCA; ExtraChannels/utils/misc/video_utils.py:66-82): per (frame, k) the grey frame
+    becomes the last state channel, forward_nsteps runs, the channel is dropped again.  `state` in and out is the reference's `h` with
+    c_in - 1 channels (anything else: ValueError).  perception_scales [0] or the fused [0, 1] with an fp32 state run frames_per_call
+    frames per C call (ncahip_clip_gray, then ncahip_dynca_clip_xc_f32 with the model's positional encoding); anything else runs that
+    loop in Python."""
     from . import ops
     if gray not in ops.GRAY_WEIGHTS:
         raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
@@ -86,25 +111,36 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
+    extra = _extra_channels(nca_model)
+    if extra and state is not None and (state.dim() != 4 or state.shape[1] != nca_model.c_in - 1):
+        raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
     h = state if state is not None else nca_model.seed(1, size=(ww, hh))
-    fused = _clip_route(nca_model, h) and torch.device(dev).type == "cuda"
+    fused = (_clip_route_xc(nca_model, h) if extra else _clip_route(nca_model, h)) and torch.device(dev).type == "cuda"
     stylize_clip.last_path = "clip" if fused else "loop"
     outs = []
     if fused:
-        layer = nca_model.cond_layer
-        bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
-        do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
         w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
         rate, two = 0.5, list(nca_model.perception_scales) == [0, 1]
+        if extra:
+            pos = nca_model._cond(h.new_empty(1, nca_model.c_in, hh, ww))        # CPE (or None): a function of the shape alone
+        else:
+            layer = nca_model.cond_layer
+            bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
+            do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
         for f0 in range(0, n_frames, per_call):
             chunk = frames[f0:f0 + per_call].to(dev).unsqueeze(1)                 # [n,1,3,H,W] or [n,1,H,W,3]
             n = chunk.shape[0]
-            cond = ops.clip_cond(chunk, bank, gray, do_tanh)
+            cond = ops.clip_gray(chunk, gray) if extra else ops.clip_cond(chunk, bank, gray, do_tanh)
             us = None
             if nca_model.mask_rng != "philox":     # the loop's own draws, call by call (DyNCA._draw): the generator ends where it would
                 us = torch.cat([ops.draw_fire_masks(1, hh, ww, step_n, rate, "dynca", h.device) for _ in range(n * k)])
-            imgs, h = ops.dynca_clip(h, cond, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
-                                     nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
+            if extra:                              # h keeps c_in - 1 channels: the driver's last channel is the grey frame
+                imgs, x = ops.dynca_clip_xc(h, cond, pos, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
+                                            nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
+                h = x[:, :-1]
+            else:
+                imgs, h = ops.dynca_clip(h, cond, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
+                                         nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
             nca_model._mask_step += n * k * step_n
             outs.append(imgs[:, 0])
     else:
@@ -114,7 +150,11 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
             for i in range(chunk.shape[0]):
                 cond = _gray(chunk[i:i + 1], gray)
                 for _ in range(k):
-                    h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond)
+                    if extra:       # the grey frame as the last state channel, dropped again after the call
+                        x, rgb = nca_model.forward_nsteps(torch.cat((h, cond.to(h.dtype)), 1), step_n)
+                        h = x[:, :-1]
+                    else:
+                        h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond)
                     img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
                     outs.append((img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img)
     if outs:
