@@ -592,6 +592,27 @@ int ncahip_ot_moment_fwd_f32(const float *x, const float *y, float *mom, float *
 int ncahip_ot_moment_bwd_f32(const float *y, const float *my, const float *sgn, const int8_t *S, const float *g_mom, float *dy,
                              int B, int N, int c, ncahip_stream_t stream);
 
+/* ---- position sampler of the OT appearance loss ------------------------------------------------------------------------
+ * EncoderConditioning/loss/appearance_loss.py:200-203 draws, per (sample, layer larger than 32 x 32),
+ * np.sort(np.random.choice(np.arange(h * w), n, replace = False)) on the host.  This is the same kind of draw on the device, from
+ * a keyed stream of its own (NOT numpy's: the positions differ from the reference's, the distribution does not).  A row is one
+ * (call, layer, sample) triple with a 64-bit id `row`; for position p in [0, HW)
+ *     words = philox4x32_10(counter = (p >> 2, row_lo, row_hi, 0x4F5453 'OTS'), key = (seed_lo, seed_hi)),
+ *     key(p) = words[p & 3] >> (32 - key_bits),
+ * and the row's result is the n positions with the smallest (key, p) in lexicographic order, written in ascending p.  With
+ * distinct keys every n-subset is equally likely.  Equal keys are broken by position, which matters only for a tie exactly at the
+ * threshold: with key_bits = 32 (production) that has probability about HW * 2^-32 per row -- the documented deviation from an
+ * exactly uniform subset.  key_bits < 32 shortens the keys and makes ties common (it exercises the tie path; not for training).
+ *
+ * ncahip_ot_sample_idx: idx [rows, n] int32; row r uses the id row0 + r (64-bit arithmetic: the high word is used).  One
+ *   workgroup per row: a radix select of the n-th smallest key (8-bit digits, keys regenerated from Philox in every pass), then
+ *   an ordered compaction; no atomics on global memory, nothing shared between rows, bit-reproducible.  Covered: 1 <= n <= 1024
+ *   (the gather's limit), n <= HW <= 2^20, 1 <= rows <= 65535, 1 <= key_bits <= 32.  A null pointer, a non-positive size, n > HW
+ *   or key_bits out of range: NCAHIP_EINVAL; n > 1024, HW > 2^20 or rows > 65535: NCAHIP_ERANGE; both before any launch, with
+ *   the offending value in the message.  Refuses with NCAHIP_EDEVICE while the device error word is set. */
+int ncahip_ot_sample_idx(int32_t *idx, int rows, int HW, int n, uint64_t seed, uint64_t row0, int key_bits,
+                         ncahip_stream_t stream);
+
 /* ---- sliced-Wasserstein style loss ------------------------------------------------------------------------------------
  * EncoderConditioning/loss/appearance_loss.py:109-140 for one level and a batch: source [B, c, n] and target [1, c, m] the
  * flattened feature maps, proj [c, 32] the unit directions (drawn by the caller),

@@ -24,6 +24,10 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
                   process: 32 x 3 x 256^2 with bf16 features (configs[2]'s batch) and 8 x 3 x 64^2 (the reference's training shape)
   loss_ot_batched / loss_ot_fused / loss_ot_fused_all   the OT term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a
                   kernel trace (not part of a run without names)
+  loss_ot_index   the OT term alone (ot_impl fused_all, precomputed features at 32 x 3 x 256^2: layers of 65 536 / 16 384 / 4 096
+                  positions sampled, n = 1000) with ot_index_rng numpy and philox alternating in one process (numpy / philox / numpy /
+                  philox): host time until the term returns, host clock between two synchronisations around forward + backward, and
+                  the three sampler launches' own device time
   loss_slw        the objective with appearance_loss_type 'SlW' and its sliced-Wasserstein term alone (precomputed features, six levels),
                   slw_impl torch and fused alternating in one process: 32 x 3 x 256^2 and 8 x 3 x 64^2, fp32 features
   loss_slw_torch / loss_slw_fused   the sliced-Wasserstein term alone at 32 x 3 x 256^2, one variant, 5 calls: the workload of a kernel
@@ -322,6 +326,55 @@ def loss_ot_trace_leg(impl, calls=5):
     torch.cuda.synchronize()
 
 
+def loss_ot_index_leg():
+    """Where the OT term's sampled positions come from: Loss(ot_impl="fused_all") with ot_index_rng "numpy" (np.random.choice per
+    (sample, layer) on the host, one upload per layer) against "philox" (ops.ot_sample_idx: one launch per sampled layer), on
+    precomputed features of BASELINE configs[2]'s batch.  Four runs in one process, numpy / philox / numpy / philox, so that the
+    numpy leg's own run-to-run difference is on record; each the median of 10 after 3 warm-ups of (a) host ms until ot_term returns,
+    nothing synchronised, and (b) host ms between two device synchronisations around forward + backward.  Then the three sampler
+    launches alone between two events."""
+    import time
+    import numpy as np
+    from ncahip.loss import Loss
+    B, S, n = 32, 256, 1000
+    _, _, _, tf, gfl = _ot_setup(B, S, torch.bfloat16)
+    dev = torch.device(DEV)
+    sampled = [t.shape[2] * t.shape[3] for t in tf if t.shape[2] > 32]
+    np.random.seed(0)
+    for run, rng in enumerate(("numpy", "philox", "numpy", "philox")):
+        L = Loss(dev, content_loss_weight=0.0, appearance_loss_weight=0.0, ot_impl="fused_all", ot_index_rng=rng, ot_index_seed=1)
+        ret, both = [], []
+        for it in range(13):
+            for g in gfl:
+                g.grad = None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            v = L.ot_term(tf, gfl)
+            t1 = time.perf_counter()
+            v.backward()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if it >= 3:
+                ret.append((t1 - t0) * 1e3)
+                both.append((t2 - t0) * 1e3)
+        emit(path="loss_ot_index", run=run, ot_index_rng=rng, shape=f"{B}x3x{S}x{S}", sampled_positions=sampled, n=n,
+             host_return_ms=statistics.median(ret), host_return_min_ms=min(ret), fwd_bwd_sync_ms=statistics.median(both),
+             fwd_bwd_sync_min_ms=min(both), ot_value=float(v.detach()))
+    dts = []
+    for it in range(13):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for li, hw in enumerate(sampled):
+            ops.ot_sample_idx(B, hw, n, 1, (it << 24) | (li << 16), device=dev)
+        e1.record()
+        torch.cuda.synchronize()
+        if it >= 3:
+            dts.append(e0.elapsed_time(e1))
+    emit(path="loss_ot_index", what="the three sampler launches alone (events around them)", rows=B, sampled_positions=sampled, n=n,
+         sampler_device_ms=statistics.median(dts), sampler_device_min_ms=min(dts))
+
+
 SLW_IMPLS = ("torch", "fused")
 
 
@@ -604,6 +657,8 @@ def main(names):
     for impl in OT_IMPLS:
         if "loss_ot_" + impl in names:
             loss_ot_trace_leg(impl)
+    if allp or "loss_ot_index" in names:
+        loss_ot_index_leg()
     if allp or "loss_slw" in names:
         loss_slw_leg()
     for impl in SLW_IMPLS:

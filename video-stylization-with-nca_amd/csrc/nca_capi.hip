@@ -1087,6 +1087,20 @@ int ncahip_ot_moment_bwd_f32(const float* y, const float* my, const float* sgn, 
     return hip_result(nca_launch_ot_moment_bwd(y, my, sgn, (const signed char*)S, g_mom, dy, B, N, c, (hipStream_t)stream), "ot_moment_bwd");
 }
 
+// ---- position sampler of the OT appearance loss (nca_ot_sample.hip) ------------------------------------------------------
+int ncahip_ot_sample_idx(int32_t* idx, int rows, int HW, int n, uint64_t seed, uint64_t row0, int key_bits, ncahip_stream_t stream) {
+    constexpr int kSmpMaxHW = 1 << 20;
+    if (!idx) return fail(NCAHIP_EINVAL, "ot_sample_idx: null pointer");
+    if (rows <= 0 || HW <= 0 || n <= 0) return fail(NCAHIP_EINVAL, "ot_sample_idx: bad size rows=%d HW=%d n=%d", rows, HW, n);
+    if (n > HW) return fail(NCAHIP_EINVAL, "ot_sample_idx: n=%d exceeds HW=%d (positions are drawn without replacement)", n, HW);
+    if (key_bits < 1 || key_bits > 32) return fail(NCAHIP_EINVAL, "ot_sample_idx: key_bits=%d outside [1, 32]", key_bits);
+    if (n > kOtMaxN) return fail(NCAHIP_ERANGE, "ot_sample_idx: n=%d outside [1, %d]", n, kOtMaxN);
+    if (HW > kSmpMaxHW) return fail(NCAHIP_ERANGE, "ot_sample_idx: HW=%d exceeds %d", HW, kSmpMaxHW);
+    if (rows > kOtMaxB) return fail(NCAHIP_ERANGE, "ot_sample_idx: rows=%d exceeds %d", rows, kOtMaxB);
+    if (int rc = device_error_rc("ot_sample_idx")) return rc;
+    return hip_result(nca_launch_ot_sample(idx, rows, HW, n, seed, row0, key_bits, (hipStream_t)stream), "ot_sample_idx");
+}
+
 // ---- sliced-Wasserstein style loss (nca_slw.hip) -------------------------------------------------------------------------
 namespace {
 constexpr int kSlwMaxC = 512, kSlwMaxLen = 65536, kSlwMaxB = 1024, kSlwMaxRows = 65535, kSlwDirs = 32;

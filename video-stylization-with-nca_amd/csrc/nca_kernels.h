@@ -210,6 +210,9 @@ hipError_t nca_launch_ot_moment_fwd(const float* x, const float* y, float* mom, 
                                     void* ws, hipStream_t st);
 hipError_t nca_launch_ot_moment_bwd(const float* y, const float* my, const float* sgn, const signed char* S, const float* gup, float* dy, int B,
                                     int N, int c, hipStream_t st);
+// nca_ot_sample.hip: the OT loss's position sampler (keyed Philox draws, radix select of the n smallest, ordered compaction); one
+// workgroup per row, idx [rows, n]
+hipError_t nca_launch_ot_sample(int* idx, int rows, int HW, int n, uint64_t seed, uint64_t row0, int key_bits, hipStream_t st);
 // nca_slw.hip: sliced-Wasserstein style loss (projection onto 32 directions, segmented stable sort of (key, index) pairs, loss, adjoint)
 int nca_slw_blocks(int n);   // 4096-position blocks of a row: sort chunks, and loss partials per row
 hipError_t nca_launch_slw_project(const float* src, const float* tgt, const float* proj, float* ks, float* kt, int B, int c, int n, int m,

@@ -82,6 +82,7 @@ SIGNATURES = {
     "ncahip_ot_moment_workspace": [_I, _I, _I],
     "ncahip_ot_moment_fwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P],
     "ncahip_ot_moment_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "ncahip_ot_sample_idx": [_P, _I, _I, _I, _U64, _U64, _I, _P],
     "ncahip_slw_workspace": [_I, _I, _I, _I],
     "ncahip_slw_project_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "ncahip_slw_sort_f32": [_P, _P, _I, _I, _P],

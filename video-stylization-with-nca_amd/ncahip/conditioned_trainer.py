@@ -104,6 +104,8 @@ class ConditionedNCATrainer(NCATrainer):
             torch.manual_seed(ncadist.rank_seed(base + 1))              # fire masks drawn with torch.rand_like (nca.py:172)
             if hasattr(nca, "mask_seed"):
                 nca.mask_seed = ncadist.rank_seed(int(nca.mask_seed) + 1)   # ... or in-kernel Philox
+            if getattr(self.loss, "ot_index_rng", None) == "philox":
+                self.loss.ot_index_seed = ncadist.rank_seed(int(self.loss.ot_index_seed))   # OT positions differ per rank too
 
     # ------------------------------------------------------------------------------------------------ sampling
     def sample_targets(self, sampled_indices):

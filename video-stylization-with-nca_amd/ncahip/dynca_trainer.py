@@ -36,6 +36,8 @@ class DyNCATrainer:
         self.inject_seed_step, self.reseed_offset = inject_seed_step, reseed_offset
         self.pool_size = ncadist.shard_size(pool_size)
         ncadist.broadcast_parameters(model)    # data parallel: every replica starts from rank 0's weights (no-op in one process)
+        if ncadist.world_size() > 1 and getattr(loss_fn, "ot_index_rng", None) == "philox":
+            loss_fn.ot_index_seed = ncadist.rank_seed(int(loss_fn.ot_index_seed))   # ncahip.loss.Loss: the ranks sample different positions
         with torch.no_grad():
             self.pool = model.seed(self.pool_size, size=size).to(self.device)
         self.optimizer = torch.optim.Adam(model.parameters(), lr=lr)

@@ -172,23 +172,46 @@ def ot_loss_single(target_feats, gen_feats, n_samples=1000):
     return loss
 
 
-def ot_loss_batched(target_feats, gen_feats, n_samples=1000):
-    """The batch mean of ot_loss_single (appearance_loss.py:212-220) without the per-sample Python loop: the sub-sampling
-    indices are drawn sample by sample, layer by layer, exactly as the loop would draw them from numpy's global stream; the
-    cosine-distance, nearest-neighbour and covariance products then run as batched GEMMs over all samples of a layer."""
-    B = gen_feats[0].shape[0]
-    idx = [[None] * len(gen_feats) for _ in range(B)]
+def _ot_layer_indices(target_feats, B, n_samples, device, np_dtype, idx_source=None):
+    """The sampled positions of every style layer for a batch of B: per layer None (a map of 32 x 32 or smaller: every position)
+    or an integer tensor [B, n_samples] on `device`, ascending per row.  idx_source None: drawn from numpy's global stream exactly
+    as the reference's loop draws them (sample-major, layer-minor), as `np_dtype`.  Otherwise idx_source(li, B, HW, n, device)
+    supplies each sampled layer's tensor and numpy's stream is not touched."""
+    sampled = [t.shape[2] > 32 for t in target_feats]
+    if idx_source is not None:
+        out = []
+        for li, t in enumerate(target_feats):
+            ix = idx_source(li, B, t.shape[2] * t.shape[3], n_samples, device) if sampled[li] else None
+            if ix is not None and (tuple(ix.shape) != (B, n_samples) or ix.device.type != torch.device(device).type or ix.dtype.is_floating_point):
+                raise ValueError(f"ncahip.loss: idx_source returned {tuple(ix.shape)} {ix.dtype} on {ix.device} for layer {li}; "
+                                 f"an integer tensor [{B}, {n_samples}] on {device} is required")
+            out.append(ix)
+        return out
+    idx = [[None] * len(target_feats) for _ in range(B)]
     for b in range(B):                                     # the reference's draw order: sample-major, layer-minor
         for li, t in enumerate(target_feats):
-            h, w = t.shape[2], t.shape[3]
-            if h > 32:
-                idx[b][li] = np.sort(np.random.choice(np.arange(h * w), size=n_samples, replace=False))
+            if sampled[li]:
+                idx[b][li] = np.sort(np.random.choice(np.arange(t.shape[2] * t.shape[3]), size=n_samples, replace=False))
+    return [torch.as_tensor(np.stack([idx[b][li] for b in range(B)]).astype(np_dtype, copy=False)).to(device) if sampled[li] else None
+            for li in range(len(target_feats))]
+
+
+def ot_loss_batched(target_feats, gen_feats, n_samples=1000, idx_source=None):
+    """The batch mean of ot_loss_single (appearance_loss.py:212-220) without the per-sample Python loop: the sub-sampling
+    indices are drawn sample by sample, layer by layer, exactly as the loop would draw them from numpy's global stream; the
+    cosine-distance, nearest-neighbour and covariance products then run as batched GEMMs over all samples of a layer.
+
+    idx_source (here and in ot_loss_fused / ot_loss_fused_all): None, or a callable (li, B, HW, n, device) -> integer tensor [B, n]
+    on `device`, ascending per row, that supplies the sampled positions of layer li instead; no np.random call is then made
+    (Loss(ot_index_rng="philox") passes the keyed sampler of ops.ot_sample_idx)."""
+    B = gen_feats[0].shape[0]
+    idx = _ot_layer_indices(target_feats, B, n_samples, target_feats[0].device, np.int64, idx_source)
     total = 0
     for li, (t, g) in enumerate(zip(target_feats, gen_feats)):
         c = t.shape[1]
         tv, gv = t.reshape(1, c, -1), g.reshape(B, c, -1)
-        if idx[0][li] is not None:
-            ix = torch.as_tensor(np.stack([idx[b][li] for b in range(B)]), device=t.device)          # [B, N]
+        if idx[li] is not None:
+            ix = idx[li].long()                                                                      # [B, N]
             gv = torch.gather(gv, 2, ix[:, None, :].expand(B, c, -1))
             tv = tv.expand(B, c, -1).gather(2, ix[:, None, :].expand(B, c, -1))
         else:
@@ -208,7 +231,7 @@ def ot_loss_batched(target_feats, gen_feats, n_samples=1000):
     return total / B
 
 
-def ot_loss_fused(target_feats, gen_feats, n_samples=1000):
+def ot_loss_fused(target_feats, gen_feats, n_samples=1000, idx_source=None):
     """ot_loss_batched with the relaxed-EMD part on this library's kernels (csrc/nca_ot.hip): the same index draws from numpy's
     global stream in the same order (sample-major, layer-minor), one gather kernel per layer instead of expand / gather /
     transpose, and the B x N x N cosine distances reduced to their row and column minima in registers, forwards and backwards
@@ -221,17 +244,10 @@ def ot_loss_fused(target_feats, gen_feats, n_samples=1000):
     first term.  Every finite case agrees with the torch path up to summation order."""
     from .autograd import OTGather, OTRelaxedEMD
     B = gen_feats[0].shape[0]
-    idx = [[None] * len(gen_feats) for _ in range(B)]
-    for b in range(B):                                     # the reference's draw order: sample-major, layer-minor
-        for li, t in enumerate(target_feats):
-            h, w = t.shape[2], t.shape[3]
-            if h > 32:
-                idx[b][li] = np.sort(np.random.choice(np.arange(h * w), size=n_samples, replace=False))
+    idx = _ot_layer_indices(target_feats, B, n_samples, gen_feats[0].device, np.int32, idx_source)
     total = 0
     for li, (t, g) in enumerate(zip(target_feats, gen_feats)):
-        ix = None
-        if idx[0][li] is not None:
-            ix = torch.as_tensor(np.stack([idx[b][li] for b in range(B)]).astype(np.int32)).to(g.device)    # [B, N]
+        ix = None if idx[li] is None else idx[li].to(torch.int32)                                    # [B, N]
         x, y, xn, yn = OTGather.apply(t, g, ix)                                                      # [B, N, c]
         remd = OTRelaxedEMD.apply(x, y, xn, yn)                                                      # [B]
         mx, my = x.mean(1, keepdim=True), y.mean(1, keepdim=True)
@@ -244,7 +260,7 @@ def ot_loss_fused(target_feats, gen_feats, n_samples=1000):
     return total / B
 
 
-def ot_loss_fused_all(target_feats, gen_feats, n_samples=1000):
+def ot_loss_fused_all(target_feats, gen_feats, n_samples=1000, idx_source=None):
     """ot_loss_fused with the moment term on this library's kernels as well (csrc/nca_ot_moment.hip): the same index draws from
     numpy's global stream in the same order (sample-major, layer-minor); per layer the gather, the relaxed EMD and the moment term
     (means, both covariances and their difference, reduced in registers to mean |Cx - Cy| and its signs) run on library kernels,
@@ -255,17 +271,10 @@ def ot_loss_fused_all(target_feats, gen_feats, n_samples=1000):
     has no singularity.  Every finite case agrees with the torch path up to summation order."""
     from .autograd import OTLayerLoss
     B = gen_feats[0].shape[0]
-    idx = [[None] * len(gen_feats) for _ in range(B)]
-    for b in range(B):                                     # the reference's draw order: sample-major, layer-minor
-        for li, t in enumerate(target_feats):
-            h, w = t.shape[2], t.shape[3]
-            if h > 32:
-                idx[b][li] = np.sort(np.random.choice(np.arange(h * w), size=n_samples, replace=False))
+    idx = _ot_layer_indices(target_feats, B, n_samples, gen_feats[0].device, np.int32, idx_source)
     per_layer = []
     for li, (t, g) in enumerate(zip(target_feats, gen_feats)):
-        ix = None
-        if idx[0][li] is not None:
-            ix = torch.as_tensor(np.stack([idx[b][li] for b in range(B)]).astype(np.int32)).to(g.device)    # [B, N]
+        ix = None if idx[li] is None else idx[li].to(torch.int32)                                    # [B, N]
         per_layer.append(OTLayerLoss.apply(t, g, ix))                                                # [B]
     return torch.stack(per_layer).sum() / B
 
@@ -276,8 +285,22 @@ _OT_IMPLS = {"batched": ot_loss_batched, "fused": ot_loss_fused, "fused_all": ot
 class Loss(nn.Module):
     def __init__(self, device, content_loss_weight=1.0, overflow_loss_weight=1.0, appearance_loss_weight=1.0,
                  appearance_loss_type="OT", target_style_image=None, feature_dtype=torch.float32, channels_last=False, ot_impl="batched",
-                 slw_impl="torch"):
+                 slw_impl="torch", ot_index_rng="numpy", ot_index_seed=0):
+        """ot_index_rng: where the OT term's sampled positions come from (layers larger than 32 x 32, 1000 positions per sample).
+        'numpy' (default): np.random.choice on numpy's global stream, draw for draw as the reference.  'philox': the keyed sampler
+        of ops.ot_sample_idx (csrc/nca_ot_sample.hip), one launch per sampled layer -- on the device for CUDA features, its numpy
+        mirror for CPU features.  The loss then NO LONGER CONSUMES numpy's global stream: a seeded trainer run draws a different
+        pool and target sequence than with 'numpy', because the draws that used to sit between the trainer's own are gone.  That is
+        the point (the draws leave the host and the shared stream), and the reason it is opt-in.  The sampled positions are a
+        function of the plain attributes ot_index_seed, ot_index_call (starts at 0, +1 per evaluated OT term; set it to resume a
+        run) and ot_index_offset (default 0; the first sample's number, for callers that split a batch): sample b of layer li
+        (index into STYLE_LAYERS) uses the row id (ot_index_call << 24) | (li << 16) | (ot_index_offset + b).  None of them is part
+        of state_dict.  Works with every ot_impl; does nothing for 'Gram' / 'SlW'."""
         super().__init__()
+        if ot_index_rng not in ("numpy", "philox"):
+            raise ValueError(f"ncahip.loss: unknown ot_index_rng={ot_index_rng!r} ('numpy' or 'philox')")
+        self.ot_index_rng = ot_index_rng
+        self.ot_index_seed, self.ot_index_call, self.ot_index_offset = int(ot_index_seed), 0, 0
         if slw_impl not in _SLW_IMPLS:
             raise ValueError(f"ncahip.loss: unknown slw_impl={slw_impl!r} ('torch' or 'fused')")
         self.slw_impl = slw_impl        # 'fused': the 'SlW' term on this library's kernels (sliced_wasserstein_fused)
@@ -314,6 +337,29 @@ class Loss(nn.Module):
         s = input_dict["nca_state"]
         return (s - s.clamp(-1.0, 1.0)).abs().mean()
 
+    def _ot_idx_source(self):
+        """The idx_source of this evaluation of the OT term (None: numpy's global stream)."""
+        if self.ot_index_rng == "numpy":
+            return None
+        from . import ops
+        seed, call, offset = int(self.ot_index_seed), int(self.ot_index_call), int(self.ot_index_offset)
+
+        def source(li, B, HW, n, device):
+            assert 0 <= offset and offset + B <= 65536, f"ot_index_offset + B = {offset + B} exceeds the 16 bits of a row id"
+            row0 = (call << 24) | (li << 16) | offset
+            if torch.device(device).type == "cuda":
+                return ops.ot_sample_idx(B, HW, n, seed, row0, device=device)
+            return torch.from_numpy(ops.ot_sample_idx_host(B, HW, n, seed, row0))
+        return source
+
+    def ot_term(self, target_feats, gen_feats):
+        """The OT appearance term (appearance_loss.py:212-220: mean over the batch) of per-layer feature lists, with this object's
+        ot_impl and index source; counts the evaluation in ot_index_call."""
+        acc = _OT_IMPLS[self.ot_impl](target_feats, gen_feats, idx_source=self._ot_idx_source())
+        if self.ot_index_rng != "numpy":
+            self.ot_index_call += 1
+        return acc
+
     def forward(self, input_dict, return_summary=True):
         loss, log = 0, {}
         terms = {}
@@ -330,7 +376,7 @@ class Loss(nn.Module):
             if "appearance" in self.loss_weights:
                 acc = 0
                 if self.appearance_loss_type == "OT":    # appearance_loss.py:212-220: mean over the batch
-                    acc = _OT_IMPLS[self.ot_impl]([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
+                    acc = self.ot_term([self.style_feats[l] for l in STYLE_LAYERS], [gf[l] for l in STYLE_LAYERS])
                 elif self.appearance_loss_type == "Gram":   # :98-106
                     for l in STYLE_LAYERS:
                         acc = acc + (_gram(self.style_feats[l]) - _gram(gf[l])).square().mean()

@@ -4,6 +4,7 @@ has no CPU fallback (the CPU restatement lives in oracle/ and is test infrastruc
 import re
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -750,6 +751,62 @@ def ot_moment_backward(y: torch.Tensor, my: torch.Tensor, sgn: torch.Tensor, S: 
         assert dy.shape == y.shape and dy.is_contiguous() and _dev(dy, "dy") is dy
     check(lib().ncahip_ot_moment_bwd_f32(_p(y), _p(my), _p(sgn), _p(S), _p(g_mom), _p(dy), B, N, c, _stream()), "ot_moment_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- position sampler of the OT appearance loss (csrc/nca_ot_sample.hip)
+_U64_MASK = (1 << 64) - 1
+_OT_SAMPLE_DOMAIN = 0x4F5453     # 'OTS': the fourth counter word (include/ncahip.h)
+
+
+def ot_sample_idx(rows: int, HW: int, n: int, seed: int, row0: int, key_bits: int = 32, device="cuda") -> torch.Tensor:
+    """The OT loss's sampled positions, drawn on the device (ncahip_ot_sample_idx): int32 [rows, n]; row r holds, in ascending
+    order, the n positions of [0, HW) with the smallest (key, position), the keys being Philox words keyed by `seed` and the
+    64-bit row id row0 + r.  Enqueued on the current stream of `device`; nothing synchronises.  key_bits < 32 shortens the keys
+    (ties become common: the tie path's test hook)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _capi.NcaHipError("ncahip: ot_sample_idx runs on a CUDA (ROCm) device -- ot_sample_idx_host is the numpy mirror")
+    with torch.cuda.device(dev):
+        out = torch.empty(max(int(rows), 0), max(int(n), 0), device=dev, dtype=torch.int32)
+        check(lib().ncahip_ot_sample_idx(_p(out), int(rows), int(HW), int(n), int(seed) & _U64_MASK, int(row0) & _U64_MASK, int(key_bits),
+                                         _stream()), "ot_sample_idx")
+    return out
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 on numpy uint32 arrays (csrc/nca_common.h nca_philox4x32_10, restated)."""
+    m0, m1, s32 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(32)
+    for r in range(10):
+        p0, p1 = m0 * c0.astype(np.uint64), m1 * c2.astype(np.uint64)           # 32 x 32 -> 64 bits: no overflow
+        ka, kb = np.uint32((k0 + r * 0x9E3779B9) & 0xFFFFFFFF), np.uint32((k1 + r * 0xBB67AE85) & 0xFFFFFFFF)
+        c0, c1, c2, c3 = (p1 >> s32).astype(np.uint32) ^ c1 ^ ka, p1.astype(np.uint32), (p0 >> s32).astype(np.uint32) ^ c3 ^ kb, p0.astype(np.uint32)
+    return c0, c1, c2, c3
+
+
+def ot_sample_idx_host(rows: int, HW: int, n: int, seed: int, row0: int, key_bits: int = 32, device=None):
+    """ot_sample_idx evaluated with numpy: the same definition (include/ncahip.h), bit for bit, as a numpy int32 array [rows, n].
+    What the loss uses for CPU features, and what the tests hold the kernel against.  `device` is accepted and ignored."""
+    rows, HW, n, key_bits = int(rows), int(HW), int(n), int(key_bits)
+    if rows < 1 or n < 1 or n > HW or HW > (1 << 20) or not 1 <= key_bits <= 32:
+        raise ValueError(f"ncahip: ot_sample_idx_host: rows={rows} HW={HW} n={n} key_bits={key_bits} outside 1 <= n <= HW <= 2^20, 1 <= key_bits <= 32")
+    seed, row0 = int(seed) & _U64_MASK, int(row0) & _U64_MASK
+    groups = (HW + 3) // 4
+    grp = np.arange(groups, dtype=np.uint32)[None, :]
+    pos = np.arange(4 * groups, dtype=np.uint64)[None, :]
+    out = np.empty((rows, n), dtype=np.int32)
+    step = max(1, (1 << 22) // (4 * groups))                  # rows per block: at most 4 M keys in flight
+    for r0 in range(0, rows, step):
+        ids = [(row0 + r) & _U64_MASK for r in range(r0, min(rows, r0 + step))]
+        lo = np.array([i & 0xFFFFFFFF for i in ids], dtype=np.uint32)[:, None]
+        hi = np.array([i >> 32 for i in ids], dtype=np.uint32)[:, None]
+        shape = (len(ids), groups)
+        w = _philox4x32_10(np.broadcast_to(grp, shape), np.broadcast_to(lo, shape), np.broadcast_to(hi, shape),
+                           np.full(shape, _OT_SAMPLE_DOMAIN, dtype=np.uint32), seed & 0xFFFFFFFF, seed >> 32)
+        key = np.stack(w, axis=2).reshape(len(ids), 4 * groups) >> np.uint32(32 - key_bits)           # key[r, 4 g + j] = words[j]
+        comp = ((key.astype(np.uint64) << np.uint64(20)) | pos)[:, :HW]                              # (key, p) as one integer: p < 2^20
+        take = np.partition(comp, n - 1, axis=1)[:, :n] & np.uint64((1 << 20) - 1)
+        out[r0:r0 + len(ids)] = np.sort(take, axis=1).astype(np.int32)
+    return out
 
 
 # ---------------------------------------------------------------- sliced-Wasserstein style loss (csrc/nca_slw.hip)
