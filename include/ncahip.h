@@ -524,6 +524,47 @@ int ncahip_dynca_clip_xc_f32(float *states, const float *gray, const float *cond
                              float update_rate, uint64_t seed, uint64_t step0, float *pc_scratch, void *persist_ws,
                              size_t persist_bytes, unsigned epoch0, ncahip_stream_t stream);
 
+/* ---- a whole clip per call, ConditionedNCA: fused encoder, grow per frame, image output ------------------------------------------
+ * EncoderConditioning/visualisation.ipynb (ConditionedNCAVisualizer.loop with button_fn: the state is carried, the goal image changes):
+ * for every frame, steps_per_frame times { state = grow(state, step_n, frame); emit clamp(state[:, :3], 0, 1) } (trainer.py:36-39,
+ * utils/utils.py:34-35).  Formats as above, except that float32 frames are ToTensor output in [0, 1] and are used as they are, and uint8
+ * frames are widened as float(u8) / 255.0f (a true division) with no * 2 - 1.  Nothing here synchronises.
+ * ncahip_clip_encode: goal [F,B,E,H,W] = ImageEncoder(frame) (encoder.py:37-57) for every frame of a call in ONE launch, inference only:
+ *   gray = mean over the ch channels; feat [3+ch] = [sobel_x(gray) | sobel_y(gray) | laplacian(gray) | blur5x5(img[c])], zero padding, k3 [3][9]
+ *   and k5 [25] as ncahip_image_encoder_front_f32; h1 = relu(conv3x3(feat, w1 [E,3+ch,3,3]) + b1 [E]), zero padding; goal = conv3x3(h1,
+ *   w2 [E,E,3,3]), zero padding (h1 counts as 0 outside the image), no bias.  float32 frames [F,B,ch,H,W] with ch <= 4, uint8 frames
+ *   [F,B,H,W,3] (ch == 3; any alignment, any W * 3); 1 <= E <= 32; any H, W >= 1; NCAHIP_ERANGE otherwise.  Null, overlapping, non-positive or
+ *   unknown-format arguments: NCAHIP_EINVAL.  All checked before the launch.  One workgroup per 16 x 16 output tile: the image tile with a
+ *   4-cell halo, feat on tile + 2 and h1 on tile + 1 live in LDS; both convolutions run on the exact-f32 MFMA (16 x 16 x 4) as implicit GEMMs
+ *   per tap.  No workspace beyond goal: ncahip_clip_encode_workspace returns its bytes (host arithmetic; 0 for a non-positive size).
+ * ncahip_clip_emit_unit: img = clamp(state[:, :3], 0, 1), bit for bit the torch expression on the device (NaN passes through); float32
+ *   [B,3,H,W], or uint8 [B,H,W,3] = (uint8_t)(img * 255.0f), truncating.  C >= 3.
+ * ncahip_cond_clip_f32: for f in 0..F-1, j in 0..steps_per_frame-1, n = f * steps_per_frame + j: step_n ConditionedNCA steps and the finalize
+ *   on the state with goal[f] (goal [F,B,goal_ch,H,W], from ncahip_clip_encode), then image n = ncahip_clip_emit_unit(state) into
+ *   images + n * (one image).  Host code over the existing grow drivers; no step kernel of its own.
+ *   states: 4 slots of B*C*H*W floats.  Slot 0 holds the state on entry and on return; slots 1..3 are scratch.  Between calls the driver keeps
+ *   the state in slot 0 or 2: a persistent call reads one and writes the other; a per-step call runs the ring of that slot and the next one
+ *   and finalizes into the slot it started from (step_n odd) or into the other of slots 0 / 2 (step_n even: x_final must not be the pending
+ *   slot).  No copy per call n; one device-to-device copy at the end when the state ended in slot 2.  pre: 2 slots of B*H*W bytes, scratch.
+ *   u: NULL = in-kernel Philox, call n uses steps step0 + n * step_n ...; bit-packed masks (seed == NCAHIP_SEED_U_IS_BITS) or float uniforms
+ *   of all F * steps_per_frame * step_n steps laid end to end.
+ *   With persist_ws != NULL each call n first goes to ncahip_cond_grow_fwd_persist_f32 (ring 2) with epoch epoch0 + n (persist_ws as that
+ *   entry point documents; NCAHIP_EINVAL when epoch0 < 1 or epoch0 + F * steps_per_frame >= 2^20); from its first NCAHIP_ERANGE on (float
+ *   uniforms included), and always with persist_ws == NULL, the calls run on ncahip_cond_grow_fwd_f32 with ring 2.  What those entry points
+ *   cover, this one covers, with their bits; what they refuse, it refuses with their code.
+ *   Arguments are checked on the host before anything is enqueued (null or overlapping buffers, F, steps_per_frame, step_n <= 0, C < 3, an
+ *   unknown format, the epoch range: NCAHIP_EINVAL; shapes the grow drivers refuse: their code); then a set sticky error word refuses the call
+ *   with NCAHIP_EDEVICE; the driver stops enqueuing at the first failing launch and returns its code. */
+size_t ncahip_clip_encode_workspace(int F, int B, int E, int H, int W);
+int ncahip_clip_encode(const void *frames, int frame_fmt, const float *k3, const float *k5, const float *w1, const float *b1, const float *w2,
+                       float *goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream);
+int ncahip_clip_emit_unit(const float *state, void *img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream);
+int ncahip_cond_clip_f32(float *states, uint8_t *pre, const float *goal, int goal_ch, void *images, int img_fmt, int F, int steps_per_frame,
+                         int step_n, const float *u, const float *wp, const float *w1, const float *b1, const float *w2, const float *b2,
+                         const float *w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                         float clamp_hi, uint64_t seed, uint64_t step0, void *persist_ws, size_t persist_bytes, unsigned epoch0,
+                         ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

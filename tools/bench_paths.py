@@ -18,6 +18,10 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
   video_clip_xc   the same clip with the ExtraChannels default model (C = 16 / fc = 128 / CPE, two- and single-scale), whose grey frame is
                   the last state channel: (a) the hand loop over forward_nsteps (cat, call, slice) against stylize_clip (b) float32 ->
                   float32 and (c) uint8 -> uint8, the three measured twice over (a b c a b c) so that the spread of (a) is on record
+  video_clip_cond the same clip with the reference's default ConditionedNCA (C = 20, E = 16, hidden 64), every frame the goal of its own
+                  8 steps: (a) the hand loop over nca.grow + torch.clamp against stylize_clip_conditioned (b) float32 -> float32 and
+                  (c) uint8 -> uint8, measured twice over (a b c a b c), with ops.persistent_cond off and on; then the encoder alone,
+                  ImageEncoder.forward (front pass + MIOpen) against ops.clip_encode, for 8 frames at 256^2 and 1 frame at 64^2
   trainer_default ConditionedNCATrainer at the reference's own defaults (C = 20, 64 x 64, batch 8, nca_steps [48, 96]): ms per iteration
   loss            the default objective (VGG16 features + batched OT + content + overflow) at 32 x 3 x 256^2, fp32 / bf16 features
   loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched, fused and fused_all alternating in one
@@ -618,6 +622,80 @@ def video_clip_xc_leg():
                  route=video.stylize_clip.last_path, **res, **ratios)
 
 
+def video_clip_cond_leg():
+    """video_clip_leg for ConditionedNCA (EncoderConditioning/visualisation.ipynb: the goal switched while the state runs).  (a) the loop by
+    hand: per frame state = nca.grow(state, step_n, frame[None]), clamp(state[:, :3], 0, 1); (b) stylize_clip_conditioned float32 in /
+    float32 out; (c) uint8 in / uint8 out.  Frames on the device, a dense state (alive everywhere) so that every step does real work, host
+    clock between two device synchronisations, median of 10 after 3 warm-ups; two passes over (a, b, c): the two (a) figures give the
+    session's spread.  At 256^2 the persistent grow needs all 256 CUs: a poll that expires is reported, not retried."""
+    from ncahip import video
+    from ncahip.nca import ConditionedNCA
+    n_frames, step_n, S = 64, 8, 256
+    torch.manual_seed(0)
+    m = ConditionedNCA(target_shape=(3, S, S)).to(DEV)
+    with torch.no_grad():
+        m.update_net.out[4].weight.mul_(0.3)
+    m.mask_rng, m.mask_seed = "philox", 1
+    gen = torch.Generator().manual_seed(0)
+    u8 = torch.randint(0, 256, (n_frames, S, S, 3), generator=gen, dtype=torch.uint8).to(DEV)
+    f32 = (u8.float() / 255.0).permute(0, 3, 1, 2).contiguous()
+    x0 = torch.rand(1, m.num_channels, S, S, generator=gen) * 0.5
+    x0[:, 3] = 1.0
+    x0 = x0.to(DEV)
+
+    @torch.no_grad()
+    def loop():
+        state = x0
+        for f in range(n_frames):
+            state = m.grow(state, step_n, f32[f:f + 1])
+            torch.clamp(state[:, :3], 0.0, 1.0)
+
+    fns = [loop, lambda: video.stylize_clip_conditioned(m, f32, step_n=step_n, state=x0),
+           lambda: video.stylize_clip_conditioned(m, u8, step_n=step_n, state=x0, out_dtype=torch.uint8)]
+    names = ["hand_loop", "stylize_clip_conditioned_f32", "stylize_clip_conditioned_u8"]
+    keep = ops.persistent_cond
+    try:
+        for persistent in (False, True):
+            ops.persistent_cond = persistent
+            if persistent:      # one grow first: if its polls expire here, the clip legs (64 launches each) are not started
+                try:
+                    with torch.no_grad():
+                        m.grow(x0, step_n, f32[:1])
+                    ops.check_errors()
+                except Exception as e:
+                    emit(path="video_clip_cond", persistent_cond=True, error="probe grow: " + str(e)[:300])
+                    break
+            for run in (1, 2):
+                try:
+                    med, mn = timed_sync(fns)
+                    ops.check_errors()
+                except Exception as e:      # a bounded poll of the persistent grow expired (another process holds CUs): on record, no retry
+                    emit(path="video_clip_cond", run=run, persistent_cond=persistent, error=str(e)[:300])
+                    try:
+                        ops.check_errors()
+                    except Exception:
+                        pass
+                    break
+                res = {n: dict(us_per_frame=a / n_frames * 1e3, min_us_per_frame=b / n_frames * 1e3, frames_per_s=n_frames / a * 1e3)
+                       for n, a, b in zip(names, med, mn)}
+                ratios = {n + "_over_hand_loop": res[n]["us_per_frame"] / res["hand_loop"]["us_per_frame"] for n in names[1:]}
+                emit(path="video_clip_cond", run=run, persistent_cond=persistent, C=m.num_channels, E=m.num_hidden_channels, HW=[S, S],
+                     frames=n_frames, step_n=step_n, masks="philox", route=video.stylize_clip_conditioned.last_path, **res, **ratios)
+    finally:
+        ops.persistent_cond = keep
+    # the encoder alone: the module's forward (HIP front pass, two MIOpen convolutions, bias, ReLU) against the one fused launch
+    for n, s in ((8, 256), (1, 64)):
+        fr = f32[:n, :, :s, :s].contiguous()
+        with torch.no_grad():
+            enc_fns = [lambda: m.encoder(fr), lambda: ops.clip_encode(fr.unsqueeze(1), m.encoder)]
+            for run in (1, 2):
+                med, mn = timed_sync(enc_fns)
+                emit(path="video_clip_cond_encoder", run=run, frames=n, HW=[s, s], E=m.num_hidden_channels,
+                     module_forward_us=med[0] * 1e3, module_forward_min_us=mn[0] * 1e3, clip_encode_us=med[1] * 1e3, clip_encode_min_us=mn[1] * 1e3,
+                     clip_encode_over_module=med[1] / med[0])
+    ops.check_errors()
+
+
 def main(names):
     allp = not names
     if allp or "cond_train" in names:
@@ -670,6 +748,8 @@ def main(names):
         video_clip_leg()
     if allp or "video_clip_xc" in names:
         video_clip_xc_leg()
+    if allp or "video_clip_cond" in names:
+        video_clip_cond_leg()
     if allp or "trainer_default" in names:
         trainer_default_leg()
 

@@ -714,6 +714,118 @@ int ncahip_cond_grow_fwd_f32(float* states, uint8_t* pre, int ring, int T, float
                                                alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize");
 }
 
+// ---- a whole clip per call, ConditionedNCA (EncoderConditioning/visualisation.ipynb: the goal switched while the state runs) ----------
+size_t ncahip_clip_encode_workspace(int F, int B, int E, int H, int W) {
+    if (F <= 0 || !dims_ok(B, E, H, W)) return 0;
+    return (size_t)F * B * E * H * W * sizeof(float);
+}
+
+int ncahip_clip_encode(const void* frames, int frame_fmt, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                       float* goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream) {
+    if (!frames || !k3 || !k5 || !w1 || !b1 || !w2 || !goal) return fail(NCAHIP_EINVAL, "clip_encode: null pointer");
+    if (!clip_fmt_ok(frame_fmt)) return fail(NCAHIP_EINVAL, "clip_encode: unknown frame format %d", frame_fmt);
+    if (F <= 0 || ch <= 0 || E <= 0 || !dims_ok(B, 1, H, W) || (size_t)F * B > 0x7fffffffu) return fail(NCAHIP_EINVAL, "clip_encode: bad size");
+    if (ch > 4 || E > 32) return fail(NCAHIP_ERANGE, "clip_encode: ch=%d E=%d exceeds (4, 32)", ch, E);
+    if (frame_fmt == NCAHIP_CLIP_U8_NHWC && ch != 3) return fail(NCAHIP_ERANGE, "clip_encode: uint8 frames have 3 channels, got ch=%d", ch);
+    const size_t px = (size_t)F * B * H * W;
+    if ((size_t)F * B * ((H + 15) / 16) * ((W + 15) / 16) > 0x7fffffffu) return fail(NCAHIP_ERANGE, "clip_encode: more than 2^31 tiles of 16 x 16 in one launch");
+    const size_t gbytes = px * E * sizeof(float), fbytes = px * ch * clip_fmt_bytes(frame_fmt);
+    const size_t k1 = (size_t)(3 + ch);
+    if (clip_overlap(frames, fbytes, goal, gbytes) || clip_overlap(k3, 27 * sizeof(float), goal, gbytes) || clip_overlap(k5, 25 * sizeof(float), goal, gbytes) ||
+        clip_overlap(w1, E * k1 * 9 * sizeof(float), goal, gbytes) || clip_overlap(b1, E * sizeof(float), goal, gbytes) ||
+        clip_overlap(w2, (size_t)E * E * 9 * sizeof(float), goal, gbytes))
+        return fail(NCAHIP_EINVAL, "clip_encode: goal overlaps an input");
+    if (frame_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)frames & 3) != 0) return fail(NCAHIP_EINVAL, "clip_encode: float32 frames must be 4-byte aligned");
+    return hip_result(nca_launch_clip_encode(frames, frame_fmt == NCAHIP_CLIP_U8_NHWC, k3, k5, w1, b1, w2, goal, F * B, ch, E, H, W, (hipStream_t)stream),
+                      "clip_encode");
+}
+
+static int check_clip_emit_unit(const void* state, const void* img, int img_fmt, int B, int C, int H, int W) {
+    if (!state || !img) return fail(NCAHIP_EINVAL, "clip emit_unit: null pointer");
+    if (!clip_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit_unit: unknown image format %d", img_fmt);
+    if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit_unit: bad size");
+    if (C < 3) return fail(NCAHIP_EINVAL, "clip emit_unit: the image is state[:, :3], C=%d has fewer than 3 channels", C);
+    if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: float32 images must be 4-byte aligned");
+    return 0;
+}
+
+int ncahip_clip_emit_unit(const float* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
+    if (int rc = check_clip_emit_unit(state, img, img_fmt, B, C, H, W)) return rc;
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, (size_t)B * 3 * H * W * clip_fmt_bytes(img_fmt)))
+        return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
+    return hip_result(nca_launch_clip_emit_unit(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, H, W, (hipStream_t)stream), "clip_emit_unit");
+}
+
+// The driver keeps the state in slot 0 or slot 2 of `states` (cur).  A persistent call reads slot cur and writes slot cur ^ 2.  A per-step call
+// runs the ring {cur, cur + 1}: after step_n steps the pending state lies in slot cur + (step_n & 1); the finalize writes the resolved state
+// to slot cur when step_n is odd (the input is dead by then) and to slot cur ^ 2 when it is even (x_final must not be the pending slot).
+int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
+                         int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                         float clamp_hi, uint64_t seed, uint64_t step0, void* persist_ws, size_t persist_bytes, unsigned epoch0,
+                         ncahip_stream_t stream) {
+    const char* const who = "cond clip";
+    // host-side checks: nothing is enqueued before all of them have passed
+    if (!pre || !goal) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
+    if (int rc = check_clip_emit_unit(states, images, img_fmt, B, C, H, W)) return rc;
+    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
+    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
+    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
+    // the checks of the grow drivers (ncahip_cond_grow_fwd_f32 takes no T = 0, so they are shared as functions): their codes
+    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwd)) return rc;
+    const bool ubits = u_is_bits(u, seed), u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
+    if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
+    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W, gslot = (size_t)B * goal_ch * H * W;
+    const size_t ibytes = (size_t)B * 3 * H * W * clip_fmt_bytes(img_fmt);
+    const size_t sbytes = 4 * slot * sizeof(float), pbytes = 2 * pslot, gbytes = (size_t)F * gslot * sizeof(float), abytes = (size_t)calls * ibytes;
+    if (clip_overlap(states, sbytes, goal, gbytes) || clip_overlap(states, sbytes, images, abytes) || clip_overlap(states, sbytes, pre, pbytes) ||
+        clip_overlap(goal, gbytes, images, abytes) || clip_overlap(goal, gbytes, pre, pbytes) || clip_overlap(images, abytes, pre, pbytes))
+        return fail(NCAHIP_EINVAL, "%s: states, pre, goal and images must not overlap", who);
+    if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
+        return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
+    if (persist_ws) {
+        const size_t need = ncahip_cond_grow_persist_workspace(B, C, H, W, hidden, goal_ch);
+        if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "%s: persistent workspace too small", who);
+    }
+    if (int rc = device_error_rc(who)) return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    bool persist = persist_ws != nullptr;
+    int cur = 0;   // the slot that holds the state: 0 or 2
+    for (int n = 0; n < (int)calls; ++n) {
+        const float* const gf = goal + (size_t)(n / steps_per_frame) * gslot;
+        const int t0 = n * step_n;                                  // first step of this call within `u`
+        const uint64_t s0 = step0 + (uint64_t)t0;
+        float* const in = states + (size_t)cur * slot;
+        bool done = false;
+        if (persist) {
+            const int rc = ncahip_cond_grow_fwd_persist_f32(in, nullptr, 2, step_n, states + (size_t)(cur ^ 2) * slot, gf, goal_ch, u_at(u, ubits, t0, pslot),
+                                                            wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi,
+                                                            seed, s0, persist_ws, persist_bytes, epoch0 + (unsigned)n, stream);
+            if (rc == 0) {
+                cur ^= 2;
+                done = true;
+            } else if (rc == NCAHIP_ERANGE) {
+                persist = false;   // not covered (shape, masks, alignment, residency): this call and the rest run on the per-step kernels
+            } else {
+                return rc;
+            }
+        }
+        if (!done) {
+            const int out = (step_n & 1) ? cur : cur ^ 2;
+            if (int rc = ncahip_cond_grow_fwd_f32(in, pre, 2, step_n, states + (size_t)out * slot, gf, goal_ch, u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2,
+                                                  w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, s0, stream))
+                return rc;
+            cur = out;
+        }
+        if (int rc = hip_result(nca_launch_clip_emit_unit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, B, C, H, W, st), "cond clip (emit)"))
+            return rc;
+    }
+    if (cur != 0)   // the state returns in slot 0: the one copy of a call
+        return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "cond clip (state copy)");
+    return 0;
+}
+
 // ---- bf16 state storage for the DyNCA step (same kernel, exact f32 compute, RNE on store) ----------------------
 int ncahip_dynca_step_fwd_bf16(const uint16_t* x_in, uint16_t* x_out, const float* cond, const float* u, const float* w1,
                                const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,

@@ -5,12 +5,13 @@
 //   clip_gray_kernel   frames of one call -> grey [F,B,H,W]
 //   the emit kernels with INJ: the image as above and, in the same launch, a grey plane written over state channel C - 1
 #include "nca_kernels.h"
+#include "nca_clip_u8.h"
 
 namespace {
 
 constexpr int kTileW = 64, kTileH = 16;                  // output pixels per workgroup: one wave per 4 rows, one lane per column
 constexpr int kHaloW = kTileW + 2, kHaloH = kTileH + 2;  // grey tile with its one-cell halo
-constexpr int kRawDwords = (3 * kHaloW + 3 + 3) / 4 + 1; // aligned dwords that cover one halo row of uint8 RGB (198 bytes at any phase)
+static_assert(kHaloW <= kClipStageCols, "a halo row must fit the staged row of nca_clip_u8.h");
 
 // uint8 -> network range as the reference's preprocessing (preprocess_texture.py:28, :54): a true division, then v * 2 - 1
 __device__ __forceinline__ float clip_widen_u8(unsigned v) {
@@ -18,41 +19,10 @@ __device__ __forceinline__ float clip_widen_u8(unsigned v) {
     return __fsub_rn(__fmul_rn(f, 2.0f), 1.0f);
 }
 
-// uint8 RGB rows into LDS as memory-aligned dwords: ROWS row segments (image rows y_first .. y_first + ROWS - 1 of image n, columns
-// [cx0, cx1), at most kHaloW of them) of a [N,H,W,3] tensor of `total` bytes, kRawDwords dwords per staged row.  The dwords are aligned in
-// memory, whatever the tensor's own alignment or W * 3; one that straddles an end of the tensor is assembled from its bytes inside.
-template <int ROWS>
-__device__ __forceinline__ void clip_stage_u8_rows(const unsigned char* base, size_t total, size_t n, size_t plane, int H, int W, int y_first,
-                                                   int cx0, int cx1, unsigned* raw, int tid) {
-    const uintptr_t mis = (uintptr_t)base & 3;
-    for (int i = tid; i < ROWS * kRawDwords; i += 256) {
-        const int r = i / kRawDwords, d = i % kRawDwords;
-        const int y = y_first + r;
-        if (y < 0 || y >= H) continue;
-        const size_t first = (n * plane + (size_t)y * W + cx0) * 3;          // first byte of the row segment
-        const size_t last = first + (size_t)(cx1 - cx0) * 3;                 // one past its last byte
-        const ptrdiff_t a0 = (ptrdiff_t)((first + mis) & ~(size_t)3) - (ptrdiff_t)mis;   // aligned start, as an offset from base (>= -3)
-        const ptrdiff_t a = a0 + 4 * (ptrdiff_t)d;
-        if (a >= (ptrdiff_t)last) continue;
-        unsigned v;
-        if (a >= 0 && (size_t)a + 4 <= total) {
-            v = *reinterpret_cast<const unsigned*>(base + a);
-        } else {   // the dword straddles an end of the tensor: only its bytes inside
-            v = 0u;
-            for (int k = 0; k < 4; ++k)
-                if (a + k >= 0 && (size_t)(a + k) < total) v |= (unsigned)base[a + k] << (8 * k);
-        }
-        raw[r * kRawDwords + d] = v;
-    }
-}
-
 // grey of pixel (y, x) of image n from the rows clip_stage_u8_rows staged (r: its staged row, cx0: the first staged column)
 __device__ __forceinline__ float clip_staged_u8_grey(const unsigned char* base, const unsigned* raw, int r, size_t n, size_t plane, int W, int y,
                                                      int x, int cx0, float wr, float wg, float wb) {
-    const uintptr_t mis = (uintptr_t)base & 3;
-    const size_t first = (n * plane + (size_t)y * W + cx0) * 3;
-    const int off = (int)((first + mis) & 3) + 3 * (x - cx0);            // byte of this pixel within the staged row
-    const unsigned char* const p = reinterpret_cast<const unsigned char*>(raw) + (size_t)r * kRawDwords * 4 + off;
+    const unsigned char* const p = clip_staged_u8_pixel(base, raw, r, n, plane, W, y, x, cx0);
     return wr * clip_widen_u8(p[0]) + wg * clip_widen_u8(p[1]) + wb * clip_widen_u8(p[2]);
 }
 
@@ -147,10 +117,18 @@ __device__ __forceinline__ float clip_image_value(float x) {
     return __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);
 }
 
+// img = clamp(x, 0, 1) as torch.clamp evaluates it on the device (EncoderConditioning/trainer.py:36-39): NaN passes through, then
+// min(max(x, 0), 1)
+__device__ __forceinline__ float clip_unit_value(float x) { return x != x ? x : fminf(fmaxf(x, 0.0f), 1.0f); }
+
+// UNIT selects the image definition: false = clip_image_value (the DyNCA families), true = clip_unit_value (ConditionedNCA)
+template <bool UNIT>
+__device__ __forceinline__ float clip_emit_value(float x) { return UNIT ? clip_unit_value(x) : clip_image_value(x); }
+
 // One launch for both halves of the step between two calls of an extra-channel clip: EMIT writes the image of x[:, :c_out] into img,
 // INJ copies the plane gray [B,H,W] over channel C - 1 of the same state (xlast = x + (C - 1) * plane; c_out <= C - 1, so the two halves
 // touch different channels).  EMIT alone is the image output of the edge family.
-template <bool EMIT, bool INJ>
+template <bool EMIT, bool INJ, bool UNIT = false>
 __global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restrict__ x, float* __restrict__ img, float* __restrict__ xlast,
                                                             const float* __restrict__ gray, int B, int C, int c_out, size_t plane) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,13 +136,13 @@ __global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restr
     if (id >= (size_t)B * nc * plane) return;
     const size_t p = id % plane, c = (id / plane) % nc, b = id / (plane * nc);
     if (INJ && c == nc - 1) xlast[b * C * plane + p] = gray[b * plane + p];
-    else img[INJ ? (b * c_out + c) * plane + p : id] = clip_image_value(x[(b * C + c) * plane + p]);
+    else img[INJ ? (b * c_out + c) * plane + p : id] = clip_emit_value<UNIT>(x[(b * C + c) * plane + p]);
 }
 
 // uint8 NHWC: a lane owns 4 consecutive pixels of the flattened [B*H*W] axis = CO dwords, stored whole (bytes only for the last, partial
 // group or an output that is not 4-byte aligned).  (uint8_t)(img * 255): truncation, as np.uint8 in VideoWriter.add.  INJ as above, for
 // the lane's pixels.
-template <int CO, bool INJ>
+template <int CO, bool INJ, bool UNIT = false>
 __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
                                                            const float* __restrict__ gray, int B, int C, size_t plane, int aligned) {
     const size_t grp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
         const size_t q = q0 + i < npix ? q0 + i : npix - 1;
         const size_t b = q / plane, p = q % plane;
 #pragma unroll
-        for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_image_value(x[(b * C + c) * plane + p]), 255.0f);
+        for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_emit_value<UNIT>(x[(b * C + c) * plane + p]), 255.0f);
         if (INJ && q0 + i < npix) xlast[b * C * plane + p] = gray[q];
     }
     unsigned char* const o = img + q0 * CO;
@@ -275,5 +253,21 @@ hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const f
         case 4: clip_launch_emit_u8<4>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ConditionedNCA's image: clamp(state[:, :3], 0, 1) through the same two kernels (float32 NCHW, or uint8 NHWC with a lane owning four pixels)
+hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
+    const size_t plane = (size_t)H * W;
+    if (!img || C < 3) return hipErrorInvalidValue;
+    if (!u8) {
+        const size_t n = (size_t)B * 3 * plane;
+        hipLaunchKernelGGL((clip_emit_f32_kernel<true, false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img,
+                           (float*)nullptr, (const float*)nullptr, B, C, 3, plane);
+        return hipGetLastError();
+    }
+    const size_t groups = ((size_t)B * plane + 3) / 4;
+    hipLaunchKernelGGL((clip_emit_u8_kernel<3, false, true>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, state, (unsigned char*)img,
+                       (float*)nullptr, (const float*)nullptr, B, C, plane, ((uintptr_t)img & 3) == 0 ? 1 : 0);
     return hipGetLastError();
 }

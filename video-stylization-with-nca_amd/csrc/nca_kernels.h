@@ -229,6 +229,12 @@ hipError_t nca_launch_clip_gray(const void* frames, bool u8, float wr, float wg,
 // one launch: the image of state[:, :c_out] (img != nullptr) and the plane gray [B,H,W] over state[:, C-1] (gray != nullptr, c_out <= C-1);
 // the state is only read without a grey plane
 hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const float* gray, int B, int C, int c_out, int H, int W, hipStream_t st);
+// ConditionedNCA's image clamp(state[:, :3], 0, 1): float32 [B,3,H,W] or (u8) uint8 [B,H,W,3]; C >= 3
+hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st);
+// nca_encoder.hip: ImageEncoder.forward of N = F*B frames in one launch: float32 [N,ch,H,W] (ch <= 4) or (u8) uint8 [N,H,W,3] -> goal [N,E,H,W],
+// E <= 32; w1 [E,3+ch,3,3], b1 [E], w2 [E,E,3,3]; hipErrorInvalidValue outside that range
+hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                                  float* goal, int N, int ch, int E, int H, int W, hipStream_t st);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);

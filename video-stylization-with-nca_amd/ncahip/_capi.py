@@ -97,6 +97,11 @@ SIGNATURES = {
     "ncahip_clip_emit_inject": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     "ncahip_dynca_clip_xc_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P,
                                  _P, ctypes.c_size_t, ctypes.c_uint, _P],
+    "ncahip_clip_encode_workspace": [_I, _I, _I, _I, _I],
+    "ncahip_clip_encode": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ncahip_clip_emit_unit": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "ncahip_cond_clip_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _U64, _U64,
+                             _P, ctypes.c_size_t, ctypes.c_uint, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
@@ -104,7 +109,8 @@ _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ct
              "ncahip_dynca_nsteps_bwd_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_persist_workspace": ctypes.c_size_t,
              "ncahip_cond_grow_persist_workspace": ctypes.c_size_t, "ncahip_ot_workspace": ctypes.c_size_t,
              "ncahip_ot_moment_workspace": ctypes.c_size_t, "ncahip_slw_workspace": ctypes.c_size_t,
-             "ncahip_clip_cond_workspace": ctypes.c_size_t}
+             "ncahip_clip_cond_workspace": ctypes.c_size_t,
+             "ncahip_clip_encode_workspace": ctypes.c_size_t}
 
 _lib = None
 

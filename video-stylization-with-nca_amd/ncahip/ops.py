@@ -564,6 +564,81 @@ def cond_grow(x: torch.Tensor, T: int, goal: Optional[torch.Tensor], us: Optiona
     return out, states, pre
 
 
+def encoder_clip_ok(encoder) -> bool:
+    """True for an ImageEncoder that ncahip_clip_encode covers: the drop-in class itself (not a subclass with its own forward), at most 4
+    image channels, an embedding of at most 32 channels, the reference's `embed` (3 x 3 conv with bias, ReLU, 3 x 3 conv without)."""
+    from .encoder import ImageEncoder
+    if type(encoder) is not ImageEncoder:
+        return False
+    e0, e2 = encoder.embed[0], encoder.embed[2]
+    E, ch = e0.out_channels, encoder.channels
+    return (1 <= ch <= 4 and 1 <= E <= 32 and e0.bias is not None and e2.bias is None and tuple(e0.weight.shape) == (E, 3 + ch, 3, 3)
+            and tuple(e2.weight.shape) == (E, E, 3, 3) and e0.padding == (1, 1) and e2.padding == (1, 1))
+
+
+def clip_encode(frames: torch.Tensor, encoder_module) -> torch.Tensor:
+    """frames [F,B,ch,H,W] float32 in [0, 1] or [F,B,H,W,3] uint8 -> goal [F,B,E,H,W] = encoder_module(frame) for every frame in one launch
+    (ncahip_clip_encode: fixed filters, 3 x 3 conv + bias + ReLU, 3 x 3 conv, on the exact-f32 MFMA).  Inference only: no gradient.
+    encoder_module: an ncahip.encoder.ImageEncoder that encoder_clip_ok accepts (anything else raises: there is no fallback here)."""
+    if not encoder_clip_ok(encoder_module):
+        raise _capi.NcaHipError("ncahip: clip_encode covers ncahip.encoder.ImageEncoder with at most 4 image channels and an embedding of at most 32")
+    fmt = _clip_fmt(frames.dtype)
+    frames = _dev(frames, "frames", frames.dtype)
+    if fmt == _capi.CLIP_U8_NHWC:
+        F_, B, H, W, ch = frames.shape
+    else:
+        F_, B, ch, H, W = frames.shape
+    enc = encoder_module
+    assert ch == enc.channels, (tuple(frames.shape), enc.channels)
+    E = enc.embed[0].out_channels
+    k3 = _w(torch.cat((enc.sobel_x.weight, enc.sobel_y.weight, enc.laplacian.weight), dim=0).reshape(-1), "k3", frames)
+    k5 = _w(enc.gaussian_blur.weight.reshape(-1), "k5", frames)
+    w1, b1, w2 = _w(enc.embed[0].weight, "embed.0.weight", frames), _w(enc.embed[0].bias, "embed.0.bias", frames), _w(enc.embed[2].weight, "embed.2.weight", frames)
+    goal = torch.empty(F_, B, E, H, W, device=frames.device, dtype=torch.float32)
+    assert goal.numel() * 4 == lib().ncahip_clip_encode_workspace(F_, B, E, H, W)
+    check(lib().ncahip_clip_encode(_p(frames), fmt, _p(k3), _p(k5), _p(w1), _p(b1), _p(w2), _p(goal), F_, B, ch, E, H, W, _stream()), "clip_encode")
+    return goal
+
+
+def clip_emit_unit(state: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
+    """State [B,C,H,W] -> clamp(state[:, :3], 0, 1) as float32 [B,3,H,W], or truncated to uint8 [B,H,W,3] (ncahip_clip_emit_unit)."""
+    x = _dev(state, "state")
+    B, C, H, W = x.shape
+    img = _clip_images(1, B, 3, H, W, out_dtype, x.device)[0]
+    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), _clip_fmt(out_dtype), B, C, H, W, _stream()), "clip_emit_unit")
+    return img
+
+
+def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w: CondWeights, steps_per_frame: int, step_n: int,
+              alive_ch: int = 3, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0, seed: int = 0, step0: int = 0,
+              out_dtype=torch.float32):
+    """The ConditionedNCA clip loop over the F frames of goal [F,B,E,H,W] in one C call (ncahip_cond_clip_f32): per frame steps_per_frame times
+    {grow(state, step_n) with goal[f], one image clamp(state[:, :3], 0, 1)}.  us: None (Philox: seed, step0), or the masks / uniforms of all
+    F * steps_per_frame * step_n steps.  With persistent_cond the calls go to the one-launch grow where it applies.
+    Returns (images [F * steps_per_frame, B, 3, H, W] float32 or [.., B, H, W, 3] uint8, final state [B,C,H,W])."""
+    x = _dev(x, "x")
+    B, C, H, W = x.shape
+    goal = _dev(goal, "goal")
+    F_, gch = goal.shape[0], goal.shape[2]
+    assert goal.shape == (F_, B, gch, H, W) and 0 < gch <= C, (tuple(goal.shape), tuple(x.shape))
+    calls = F_ * steps_per_frame
+    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
+    assert w.c == C
+    states = torch.empty(4, B, C, H, W, device=x.device, dtype=torch.float32)
+    states[0].copy_(x)
+    pre = torch.empty(2, B, H, W, device=x.device, dtype=torch.uint8)
+    images = _clip_images(calls, B, 3, H, W, out_dtype, x.device)
+    ws, nbytes, epoch = None, 0, 0
+    if persistent_cond and not torch.cuda.is_current_stream_capturing():
+        nbytes = lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch)
+        if nbytes and calls < (1 << 20) - 2:
+            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
+    check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n, _p(us),
+                                     _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
+                                     lo, hi, seed, step0, _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "cond_clip")
+    return images, states[0]
+
+
 def cond_grow_backward(states: torch.Tensor, pre: torch.Tensor, goal: Optional[torch.Tensor], us: Optional[torch.Tensor],
                        w: CondWeights, g_final: torch.Tensor, T: int, alive_ch: int = 3, thr: float = 0.1,
                        fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0, seed: int = 0, step0: int = 0):

@@ -167,3 +167,93 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
 
 
 stylize_clip.last_path = None
+
+
+def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
+    """clamp(state[:, :3], 0, 1) (trainer.py:36-39, utils/utils.py:34-35), float32 [B,3,H,W] or truncated to uint8 [B,H,W,3]."""
+    img = torch.clamp(state[:, :3].float(), 0.0, 1.0)
+    return (img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img
+
+
+@torch.no_grad()
+def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
+                             warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8):
+    """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
+    loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
+    goal of its own steps:
+
+        for frame in frames, steps_per_frame times:  state = nca.grow(state, step_n, frame[None]);  image = clamp(state[:, :3], 0, 1)
+
+    frames: [F,3,H,W] float32 in [0, 1] (ToTensor output) or [F,H,W,3] uint8, on the host or the device.  images:
+    [F*steps_per_frame,3,H,W] float32 in [0, 1], or [F*steps_per_frame,H,W,3] uint8 (truncated) with out_dtype=torch.uint8, on the model's
+    device.  state: None starts from nca.generate_seed(1, size=H) (H == W required then); pass the returned state to continue.
+    warmup_steps: extra steps on frame 0's goal before the first image (a seed needs tens of steps to grow).
+
+    An fp32 state on the GPU with one sample and an ImageEncoder the fused kernel covers run frames_per_call frames per C call
+    (ncahip_clip_encode for the goals of the chunk -- 34 MB at 8 x 256^2, E = 16 --, then ncahip_cond_clip_f32: the library's grow drivers and
+    the image output, no Python per frame); the result does not depend on frames_per_call.  The fire masks are drawn exactly as
+    ConditionedNCA._draw draws them per grow call, in order, and _mask_step advances as in the loop.  Anything else (a custom encoder, a bf16
+    state) runs the loop above in Python.  stylize_clip_conditioned.last_path records the route: 'clip' or 'loop'."""
+    from . import ops
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+    u8_in = frames.dtype == torch.uint8
+    if frames.dim() != 4 or frames.shape[-1 if u8_in else 1] != 3 or not (u8_in or frames.dtype == torch.float32):
+        raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
+    if nca.num_target_channels != 3:
+        raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
+    n_frames = frames.shape[0]
+    hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
+    if state is not None and (state.dim() != 4 or state.shape[1] != nca.num_channels or tuple(state.shape[2:]) != (hh, ww)):
+        raise ValueError(f"state must be [B,{nca.num_channels},{hh},{ww}] (nca.num_channels channels, the frames' size), got {tuple(state.shape)}")
+    if state is None and hh != ww:
+        raise ValueError(f"state=None seeds a square grid (generate_seed(1, size=H)): frames are {hh} x {ww}; pass a state")
+    k, step_n, warm, per_call = int(steps_per_frame), int(step_n), int(warmup_steps), max(1, int(frames_per_call))
+    if k < 1 or step_n < 1 or warm < 0:
+        raise ValueError("steps_per_frame and step_n must be positive and warmup_steps non-negative")
+    dev = next(nca.parameters()).device
+    h = (nca.generate_seed(1, size=hh) if state is None else state).to(dev)
+    fused = h.is_cuda and h.dtype == torch.float32 and h.shape[0] == 1 and ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3
+    stylize_clip_conditioned.last_path = "clip" if fused else "loop"
+
+    def unit(chunk):      # frames of a chunk as the module takes them: [n,3,H,W] float32 in [0, 1]
+        return (chunk.float() / 255.0).permute(0, 3, 1, 2).contiguous() if u8_in else chunk
+
+    outs = []
+    if fused:
+        h = h.contiguous()
+        w = nca._weights(h)
+        draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(h, steps)      # noqa: E731
+        args = (nca._alive_ch(), nca.alpha_living_threshold, nca.cell_fire_rate, -10.0, 10.0)
+        for f0 in range(0, n_frames, per_call):
+            chunk = frames[f0:f0 + per_call].to(dev).unsqueeze(1)                 # [n,1,3,H,W] or [n,1,H,W,3]
+            n = chunk.shape[0]
+            goal = ops.clip_encode(chunk, nca.encoder)
+            if f0 == 0 and warm > 0:
+                h, _, _ = ops.cond_grow(h, warm, goal[0], draw(warm), w, *args, nca.mask_seed, nca._mask_step)
+                nca._mask_step += warm
+            us = None
+            if nca.mask_rng != "philox":           # the loop's own draws, grow call by grow call: the generator ends where it would
+                us = torch.cat([draw(step_n) for _ in range(n * k)])
+            imgs, h = ops.cond_clip(h, goal, us, w, k, step_n, *args, nca.mask_seed, nca._mask_step, out_dtype=out_dtype)
+            nca._mask_step += n * k * step_n
+            outs.append(imgs[:, 0])
+    else:
+        for f0 in range(0, n_frames, per_call):
+            chunk = unit(frames[f0:f0 + per_call].to(dev))
+            for i in range(chunk.shape[0]):
+                goal_img = chunk[i:i + 1]
+                if f0 == 0 and i == 0 and warm > 0:
+                    h = nca.grow(h, warm, goal_img)
+                for _ in range(k):
+                    h = nca.grow(h, step_n, goal_img)
+                    outs.append(_unit_image(h, out_dtype))
+    if outs:
+        images = torch.cat(outs)
+    else:
+        images = torch.empty((0, hh, ww, 3) if out_dtype == torch.uint8 else (0, 3, hh, ww), dtype=out_dtype, device=dev)
+    stylize_clip_conditioned.last_state = h
+    return images, h
+
+
+stylize_clip_conditioned.last_path = None
