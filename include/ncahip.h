@@ -565,6 +565,47 @@ int ncahip_cond_clip_f32(float *states, uint8_t *pre, const float *goal, int goa
                          float clamp_hi, uint64_t seed, uint64_t step0, void *persist_ws, size_t persist_bytes, unsigned epoch0,
                          ncahip_stream_t stream);
 
+/* ---- a whole clip per call, decoder-sized frames: crop + resize of uint8 frames, bit for bit Pillow's 8-bit Image.resize -------------
+ * A decoder delivers 1080p or 720p uint8 frames; the models run at 128^2 .. 512^2.  The reference shrinks on the host with Pillow:
+ * preprocess_style_image (ConditioneDyNCA/utils/misc/preprocess_texture.py:9-33: symmetric centre cut, then Image.resize = bicubic) and
+ * load_image (EncoderConditioning/utils/utils.py:5-25: square crop, then resize(..., Image.LANCZOS)).  Pillow's 8-bit resize is an integer
+ * algorithm, reproduced here exactly.  The resize sees only the cropped image: `in` below is the cropped length, tap indices count from
+ * the crop's first pixel and end at its last.
+ * The arithmetic, per axis, for input length in, output length out and a filter f of support s (C double throughout; (int) truncates):
+ *   NCAHIP_RESIZE_BICUBIC: s = 2, a = -0.5; |x| < 1: ((a + 2)|x| - (a + 3))|x|^2 + 1; |x| < 2: (((|x| - 5)|x| + 8)|x| - 4) a; else 0
+ *   NCAHIP_RESIZE_LANCZOS: s = 3; sinc(x) sinc(x / 3) on -3 <= x < 3 (sinc(x) = sin(pi x) / (pi x), 1 at 0); else 0
+ *   scale = in / out; fs = max(scale, 1); sup = s * fs; ksize = 2 * ceil(sup) + 1 (the row width of the table)
+ *   output index i: center = (i + 0.5) * scale; xmin = max((int)(center - sup + 0.5), 0); n = min((int)(center + sup + 0.5), in) - xmin;
+ *     w[j] = f((j + xmin - center + 0.5) * (1 / fs)) for j < n (Pillow multiplies by the reciprocal; so does the builder);
+ *     w[j] /= sum(w) (summed in index order) when the sum is not 0;
+ *     k[j] = (int)(w[j] * 2^22 + 0.5) for w[j] >= 0, (int)(w[j] * 2^22 - 0.5) otherwise; k[j] = 0 for n <= j < ksize
+ *   a pass: out = clamp((2^21 + sum_{j < n} px[xmin + j] * k[j]) >> 22, 0, 255) per channel, int32 accumulation, arithmetic shift.
+ *   The horizontal pass runs first and writes a uint8 image [crop_h, out_w, 3]; the vertical pass reads that image.
+ * ncahip_resize_ksize: ksize of (in, out, filter); host arithmetic.  in, out <= 0 or an unknown filter: NCAHIP_EINVAL.
+ * ncahip_resize_tables: fills k [out, ksize] and bounds [out, 2] = (xmin, n) in CALLER (host) memory; plain host code with floating-point
+ *   contraction off, no GPU call -- usable on a machine without a GPU.  ksize must be ncahip_resize_ksize's value (NCAHIP_EINVAL
+ *   otherwise).  Checks per row 255 * sum|k| + 2^21 < 2^31 and |k| < 2^23 (what the passes' int32 / 24-bit arithmetic needs; the largest
+ *   sum|k| observed is 1.56 * 2^22): NCAHIP_ERANGE if a row breaks it.  This is the only implementation of the table arithmetic.
+ * ncahip_clip_resize_u8: src [N,H,W,3] uint8 (any alignment, any W * 3) -> dst [N,out_h,out_w,3] uint8; the crop is columns
+ *   x0 .. x0 + crop_w - 1 and rows y0 .. y0 + crop_h - 1 of every frame.  kx / bx: the tables of (crop_w -> out_w) and ky / by those of
+ *   (crop_h -> out_h), copied to DEVICE memory, row widths ksize_x / ksize_y.  workspace: ncahip_clip_resize_workspace(N, crop_h, out_w) =
+ *   N * crop_h * out_w * 3 bytes of device memory for the intermediate image.  Two launches for all N frames: the horizontal pass (a
+ *   workgroup = a band of rows x a block of output columns; coefficient rows and the source row segments in LDS, the latter as
+ *   memory-aligned dwords; a loop over the runtime tap count) and the vertical pass (a lane per 4 output bytes of a row when out_w * 3 and
+ *   the buffers are 4-byte aligned, else per byte; coefficients wave-uniform).  The tables are not trusted with addresses: (xmin, n) of
+ *   every row is cut to the crop before the tap loop, so a wrong table gives wrong pixels and never a read outside the frame.  Nothing
+ *   synchronises.  NCAHIP_ERANGE: H, W, out_h or out_w above 16384, ksize_x or ksize_y above 2048, a crop outside the frame, a null or
+ *   not 4-byte aligned table or workspace.  NCAHIP_EINVAL: null src / dst, a non-positive size, a short workspace, overlapping
+ *   src / dst / workspace.  All checked before the first launch.  Same size and no crop: the tables are the identity, dst = src. */
+#define NCAHIP_RESIZE_BICUBIC 0
+#define NCAHIP_RESIZE_LANCZOS 1
+int ncahip_resize_ksize(int in, int out, int filter);
+int ncahip_resize_tables(int in, int out, int filter, int32_t *k, int32_t *bounds, int ksize);
+size_t ncahip_clip_resize_workspace(int N, int crop_h, int out_w);
+int ncahip_clip_resize_u8(const uint8_t *src, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t *kx,
+                          const int32_t *bx, int ksize_x, const int32_t *ky, const int32_t *by, int ksize_y, uint8_t *dst, int out_h,
+                          int out_w, void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

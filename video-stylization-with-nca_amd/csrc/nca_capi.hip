@@ -826,6 +826,58 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
     return 0;
 }
 
+// ---- decoder-sized uint8 frames: crop + Pillow-exact resize before the clip front ends (nca_resize.hip) ----------------------------
+static bool resize_filter_ok(int filter) { return filter == NCAHIP_RESIZE_BICUBIC || filter == NCAHIP_RESIZE_LANCZOS; }
+constexpr int kResizeMaxDim = 16384, kResizeMaxKsize = 2048;
+
+int ncahip_resize_ksize(int in, int out, int filter) {
+    if (in <= 0 || out <= 0) return fail(NCAHIP_EINVAL, "resize_ksize: bad size in=%d out=%d", in, out);
+    if (!resize_filter_ok(filter)) return fail(NCAHIP_EINVAL, "resize_ksize: unknown filter %d", filter);
+    const int ks = nca_resize_ksize(in, out, filter);
+    if (ks < 0) return fail(NCAHIP_ERANGE, "resize_ksize: the table row of in=%d out=%d does not fit an int", in, out);
+    return ks;
+}
+
+int ncahip_resize_tables(int in, int out, int filter, int32_t* k, int32_t* bounds, int ksize) {
+    if (!k || !bounds) return fail(NCAHIP_EINVAL, "resize_tables: null pointer");
+    const int ks = ncahip_resize_ksize(in, out, filter);
+    if (ks < 0) return ks;
+    if (ksize != ks) return fail(NCAHIP_EINVAL, "resize_tables: ksize=%d, but ncahip_resize_ksize(%d, %d, %d) = %d", ksize, in, out, filter, ks);
+    if (const int row = nca_resize_build_tables(in, out, filter, k, bounds, ksize))
+        return fail(NCAHIP_ERANGE, "resize_tables: row %d of in=%d out=%d breaks the int32 bound of a pass (255 * sum|k| + 2^21 < 2^31, |k| < 2^23)",
+                    row - 1, in, out);
+    return 0;
+}
+
+size_t ncahip_clip_resize_workspace(int N, int crop_h, int out_w) {
+    if (N <= 0 || crop_h <= 0 || out_w <= 0) return 0;
+    return (size_t)N * crop_h * out_w * 3;
+}
+
+int ncahip_clip_resize_u8(const uint8_t* src, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t* kx, const int32_t* bx,
+                          int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst, int out_h, int out_w, void* workspace,
+                          size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!src || !dst) return fail(NCAHIP_EINVAL, "clip_resize: null pointer");
+    if (N <= 0 || H <= 0 || W <= 0 || crop_w <= 0 || crop_h <= 0 || out_h <= 0 || out_w <= 0 || ksize_x <= 0 || ksize_y <= 0)
+        return fail(NCAHIP_EINVAL, "clip_resize: bad size");
+    if (H > kResizeMaxDim || W > kResizeMaxDim || out_h > kResizeMaxDim || out_w > kResizeMaxDim)
+        return fail(NCAHIP_ERANGE, "clip_resize: H=%d W=%d out_h=%d out_w=%d exceeds %d", H, W, out_h, out_w, kResizeMaxDim);
+    if (ksize_x > kResizeMaxKsize || ksize_y > kResizeMaxKsize)
+        return fail(NCAHIP_ERANGE, "clip_resize: table width ksize_x=%d ksize_y=%d exceeds %d", ksize_x, ksize_y, kResizeMaxKsize);
+    if (x0 < 0 || y0 < 0 || crop_w > W - x0 || crop_h > H - y0)
+        return fail(NCAHIP_ERANGE, "clip_resize: crop (x0=%d, y0=%d, w=%d, h=%d) lies outside the %d x %d frame", x0, y0, crop_w, crop_h, H, W);
+    if (!kx || !bx || !ky || !by || (((uintptr_t)kx | (uintptr_t)bx | (uintptr_t)ky | (uintptr_t)by) & 3) != 0)
+        return fail(NCAHIP_ERANGE, "clip_resize: null or misaligned table (int32, 4-byte aligned)");
+    if (!workspace || ((uintptr_t)workspace & 3) != 0) return fail(NCAHIP_ERANGE, "clip_resize: null or misaligned workspace (4-byte aligned)");
+    const size_t need = ncahip_clip_resize_workspace(N, crop_h, out_w);
+    if (workspace_bytes < need) return fail(NCAHIP_EINVAL, "clip_resize: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    const size_t sbytes = (size_t)N * H * W * 3, dbytes = (size_t)N * out_h * out_w * 3;
+    if (clip_overlap(src, sbytes, dst, dbytes) || clip_overlap(src, sbytes, workspace, need) || clip_overlap(dst, dbytes, workspace, need))
+        return fail(NCAHIP_EINVAL, "clip_resize: frames, output and workspace must not overlap");
+    return hip_result(nca_launch_clip_resize(src, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h, out_w,
+                                             (unsigned char*)workspace, (hipStream_t)stream), "clip_resize");
+}
+
 // ---- bf16 state storage for the DyNCA step (same kernel, exact f32 compute, RNE on store) ----------------------
 int ncahip_dynca_step_fwd_bf16(const uint16_t* x_in, uint16_t* x_out, const float* cond, const float* u, const float* w1,
                                const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,

@@ -236,6 +236,17 @@ hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int
 hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
                                   float* goal, int N, int ch, int E, int H, int W, hipStream_t st);
 
+// nca_resize.hip: crop + Pillow-exact 8-bit resize of N uint8 frames [N,H,W,3] -> [N,out_h,out_w,3]: horizontal pass into tmp
+// [N,ch,out_w,3], vertical pass into dst.  kx [out_w,ksize_x] / bx [out_w,2] and ky [out_h,ksize_y] / by [out_h,2]: device tables as
+// nca_resize_build_tables fills them for (cw -> out_w) and (ch -> out_h)
+hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx, const int* bx,
+                                  int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
+                                  unsigned char* tmp, hipStream_t st);
+// host only (no GPU call): table row width (-1: does not fit an int), and the tables of one axis; filter 0 = bicubic, 1 = Lanczos.  The
+// builder returns 0, or the 1-based row that breaks an integer bound of the passes
+int nca_resize_ksize(int in, int out, int filter);
+int nca_resize_build_tables(int in, int out, int filter, int32_t* k, int32_t* bounds, int ksize);
+
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_step_fwd(const NcaCondArgs& a, hipStream_t st);

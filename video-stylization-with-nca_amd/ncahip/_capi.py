@@ -102,6 +102,10 @@ SIGNATURES = {
     "ncahip_clip_emit_unit": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ncahip_cond_clip_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _U64, _U64,
                              _P, ctypes.c_size_t, ctypes.c_uint, _P],
+    "ncahip_resize_ksize": [_I, _I, _I],
+    "ncahip_resize_tables": [_I, _I, _I, _P, _P, _I],
+    "ncahip_clip_resize_workspace": [_I, _I, _I],
+    "ncahip_clip_resize_u8": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, ctypes.c_size_t, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
@@ -110,7 +114,7 @@ _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ct
              "ncahip_cond_grow_persist_workspace": ctypes.c_size_t, "ncahip_ot_workspace": ctypes.c_size_t,
              "ncahip_ot_moment_workspace": ctypes.c_size_t, "ncahip_slw_workspace": ctypes.c_size_t,
              "ncahip_clip_cond_workspace": ctypes.c_size_t,
-             "ncahip_clip_encode_workspace": ctypes.c_size_t}
+             "ncahip_clip_encode_workspace": ctypes.c_size_t, "ncahip_clip_resize_workspace": ctypes.c_size_t}
 
 _lib = None
 
@@ -122,6 +126,7 @@ class NcaHipError(RuntimeError):
 EINVAL, ERANGE, EDEVICE = -1, -2, 100001     # include/ncahip.h return codes
 SEED_U_IS_BITS = 0x5354494255     # include/ncahip.h NCAHIP_SEED_U_IS_BITS: `u` holds bit-packed fire masks
 CLIP_F32_NCHW, CLIP_U8_NHWC = 0, 1     # include/ncahip.h NCAHIP_CLIP_*: frame / image formats of the clip entry points
+RESIZE_FILTERS = {"bicubic": 0, "lanczos": 1}     # include/ncahip.h NCAHIP_RESIZE_*
 
 
 def lib():

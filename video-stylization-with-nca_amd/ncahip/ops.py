@@ -63,9 +63,10 @@ def _persist_workspace(nbytes: int, device: torch.device, count: int = 1):
 
 
 def release_workspaces() -> None:
-    """Drop the cached workspaces (they are re-created on the next use)."""
+    """Drop the cached workspaces and the device copies of the resize tables (they are re-created on the next use)."""
     _WS_CACHE.clear()
     _PERSIST_WS.clear()
+    _RESIZE_TABLES_DEV.clear()
 
 
 def _state_dtype(x: torch.Tensor):
@@ -826,6 +827,128 @@ def ot_moment_backward(y: torch.Tensor, my: torch.Tensor, sgn: torch.Tensor, S: 
         assert dy.shape == y.shape and dy.is_contiguous() and _dev(dy, "dy") is dy
     check(lib().ncahip_ot_moment_bwd_f32(_p(y), _p(my), _p(sgn), _p(S), _p(g_mom), _p(dy), B, N, c, _stream()), "ot_moment_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- crop + resize of uint8 clip frames (csrc/nca_resize.hip)
+RESIZE_MAX_DIM, RESIZE_MAX_KSIZE = 16384, 2048      # what ncahip_clip_resize_u8 takes (include/ncahip.h)
+_RESIZE_TABLES = {}          # (in, out, resample) -> (k, bounds), numpy, read-only
+_RESIZE_TABLES_DEV = {}      # (in, out, resample, device) -> (k, bounds), device copies
+
+
+def _resize_filter(resample) -> int:
+    if resample not in _capi.RESIZE_FILTERS:
+        raise ValueError(f"resample must be 'bicubic' or 'lanczos', got {resample!r}")
+    return _capi.RESIZE_FILTERS[resample]
+
+
+def resize_tables(n_in: int, n_out: int, resample: str = "bicubic"):
+    """One axis's tables of Pillow's 8-bit resize (include/ncahip.h), from the library's host builder ncahip_resize_tables -- the only
+    implementation of that arithmetic; no GPU involved.  Returns numpy int32 (k [n_out, ksize], bounds [n_out, 2] = (xmin, n)):
+    output i = clamp((2^21 + sum_{j < n} px[xmin + j] * k[i, j]) >> 22, 0, 255).  Cached; the arrays are read-only."""
+    filt = _resize_filter(resample)
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_tables: lengths must be positive, got in={n_in} out={n_out}")
+    key = (n_in, n_out, resample)
+    tab = _RESIZE_TABLES.get(key)
+    if tab is None:
+        ksize = lib().ncahip_resize_ksize(n_in, n_out, filt)
+        if ksize < 0:
+            check(ksize, "resize_ksize")
+        k = np.empty((n_out, ksize), dtype=np.int32)
+        bounds = np.empty((n_out, 2), dtype=np.int32)
+        check(lib().ncahip_resize_tables(n_in, n_out, filt, k.ctypes.data, bounds.ctypes.data, ksize), "resize_tables")
+        k.setflags(write=False)
+        bounds.setflags(write=False)
+        tab = _RESIZE_TABLES[key] = (k, bounds)
+    return tab
+
+
+def _resize_tables_dev(n_in: int, n_out: int, resample: str, device: torch.device):
+    key = (int(n_in), int(n_out), resample, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    tab = _RESIZE_TABLES_DEV.get(key)
+    if tab is None:
+        k, bounds = resize_tables(n_in, n_out, resample)
+        tab = _RESIZE_TABLES_DEV[key] = (torch.from_numpy(k.copy()).to(device), torch.from_numpy(bounds.copy()).to(device))
+    return tab
+
+
+def _resize_args(shape, size, crop):
+    """(N, H, W, out_h, out_w, (x0, y0, w, h)) of a clip_resize call, validated."""
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"frames must be [N,H,W,3] uint8, got {tuple(shape)}")
+    N, H, W = int(shape[0]), int(shape[1]), int(shape[2])
+    try:
+        out_h, out_w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (out_h, out_w), got {size!r}") from None
+    if N < 1 or H < 1 or W < 1 or out_h < 1 or out_w < 1:
+        raise ValueError(f"clip_resize: frames {tuple(shape)} and size {(out_h, out_w)} must be positive")
+    if crop is None:
+        box = (0, 0, W, H)
+    else:
+        try:
+            box = tuple(int(v) for v in crop)
+        except (TypeError, ValueError):
+            raise ValueError(f"crop must be None or a box (x0, y0, w, h), got {crop!r}") from None
+        if len(box) != 4:
+            raise ValueError(f"crop must be None or a box (x0, y0, w, h), got {crop!r}")
+    x0, y0, cw, ch = box
+    if cw < 1 or ch < 1 or x0 < 0 or y0 < 0 or x0 + cw > W or y0 + ch > H:
+        raise ValueError(f"crop box (x0, y0, w, h) = {box} lies outside the {H} x {W} frame or is empty")
+    return N, H, W, out_h, out_w, box
+
+
+def _clip_resize_launch(frames: torch.Tensor, box, tx, ty, out: torch.Tensor, ws: torch.Tensor) -> None:
+    """ncahip_clip_resize_u8 on tensors as they are: frames [N,H,W,3] and out [N,out_h,out_w,3] uint8 and dense, tx = (kx, bx),
+    ty = (ky, by) int32 on the device, ws the workspace."""
+    N, H, W, _ = frames.shape
+    _, out_h, out_w, _ = out.shape
+    x0, y0, cw, ch = box
+    check(lib().ncahip_clip_resize_u8(_p(frames), N, H, W, x0, y0, cw, ch, _p(tx[0]), _p(tx[1]), tx[0].shape[1], _p(ty[0]), _p(ty[1]),
+                                      ty[0].shape[1], _p(out), out_h, out_w, _p(ws), ws.numel() * ws.element_size(), _stream()), "clip_resize")
+
+
+def clip_resize(frames: torch.Tensor, size, crop=None, resample: str = "bicubic") -> torch.Tensor:
+    """frames [N,H,W,3] uint8 on the device -> [N,out_h,out_w,3] uint8: crop = None or a box (x0, y0, w, h) in pixels, then Pillow's
+    8-bit Image.resize to size = (out_h, out_w) with resample 'bicubic' or 'lanczos', bit for bit (ncahip_clip_resize_u8: two launches
+    for all N frames).  The tables come from resize_tables; their device copies are cached per (in, out, resample, device)."""
+    _resize_filter(resample)
+    frames = _dev(frames, "frames", torch.uint8)
+    N, H, W, out_h, out_w, box = _resize_args(frames.shape, size, crop)
+    with torch.cuda.device(frames.device):
+        tx = _resize_tables_dev(box[2], out_w, resample, frames.device)
+        ty = _resize_tables_dev(box[3], out_h, resample, frames.device)
+        out = torch.empty(N, out_h, out_w, 3, device=frames.device, dtype=torch.uint8)
+        ws = _workspace(lib().ncahip_clip_resize_workspace(N, box[3], out_w), frames.device)
+        _clip_resize_launch(frames, box, tx, ty, out, ws)
+    return out
+
+
+def _resize_pass_host(img: np.ndarray, k: np.ndarray, bounds: np.ndarray, axis: int) -> np.ndarray:
+    """One pass over `axis` of a uint8 array: out[i] = clamp((2^21 + sum_j img[xmin + j] * k[i, j]) >> 22, 0, 255), int32 arithmetic."""
+    img = np.moveaxis(img, axis, -1).astype(np.int32)
+    out = np.empty(img.shape[:-1] + (k.shape[0],), dtype=np.uint8)
+    for i in range(k.shape[0]):
+        x, n = int(bounds[i, 0]), int(bounds[i, 1])
+        acc = img[..., x:x + n] @ k[i, :n] + np.int32(1 << 21)           # int32: the builder checked the bound
+        out[..., i] = np.clip(acc >> 22, 0, 255)
+    return np.moveaxis(out, -1, axis)
+
+
+def clip_resize_host(frames, size, crop=None, resample: str = "bicubic"):
+    """clip_resize evaluated with numpy on the same tables (resize_tables): the definition in code, bit for bit Pillow's and the kernel's
+    result, and the route for CPU tensors.  frames: a uint8 tensor or numpy array [N,H,W,3]; returns the same kind, on the host."""
+    _resize_filter(resample)
+    as_tensor = isinstance(frames, torch.Tensor)
+    arr = frames.detach().cpu().numpy() if as_tensor else np.asarray(frames)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"ncahip: `frames` must be uint8, got {arr.dtype}")
+    N, H, W, out_h, out_w, (x0, y0, cw, ch) = _resize_args(arr.shape, size, crop)
+    arr = arr[:, y0:y0 + ch, x0:x0 + cw]
+    arr = _resize_pass_host(arr, *resize_tables(cw, out_w, resample), axis=2)        # horizontal first; uint8 in between
+    arr = np.ascontiguousarray(_resize_pass_host(arr, *resize_tables(ch, out_h, resample), axis=1))
+    return torch.from_numpy(arr) if as_tensor else arr
 
 
 # ---------------------------------------------------------------- position sampler of the OT appearance loss (csrc/nca_ot_sample.hip)

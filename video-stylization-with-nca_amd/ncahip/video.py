@@ -7,6 +7,9 @@ decoding / encoding (moviepy, cv2) is outside the hot path: frames come in and g
 stylize_clip also serves the ExtraChannels family (ncahip.models.dynca_extra.DyNCA), whose loop
 (ExtraChannels/utils/misc/video_utils.py:66-82) appends the grey frame to the state as its last channel before every call and
 drops it again after.
+
+Decoder-sized frames: reference_crop / resize_frames are the reference's host-side shrink (Pillow: centre crop, then an 8-bit
+Image.resize) on the device, bit for bit; stylize_clip(size=...) and stylize_clip_conditioned(size=...) apply it per chunk.
 """
 from typing import Iterable, Iterator, Optional
 
@@ -78,9 +81,55 @@ def _clip_route_xc(nca_model, h: torch.Tensor) -> bool:
     return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
 
 
+def reference_crop(kind: str, H: int, W: int):
+    """The crop box (x0, y0, w, h) the reference takes out of an H x W frame before it resizes.
+    'dynca' (preprocess_texture.py:17-25): a square frame is kept whole; otherwise cut = |W - H| // 2 comes off both ends of the
+    longer side -- an odd difference leaves that side one pixel longer than the other, as the reference does.
+    'conditioned' (EncoderConditioning/utils/utils.py:10-16): n = min(W, H), columns (W - n) // 2 .. (W + n) // 2, rows likewise."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"reference_crop: the frame must be at least 1 x 1, got {H} x {W}")
+    if kind == "dynca":
+        cut = abs(W - H) // 2
+        return (cut, 0, W - 2 * cut, H) if W > H else (0, cut, W, H - 2 * cut)
+    if kind == "conditioned":
+        n = min(W, H)
+        left, top = (W - n) // 2, (H - n) // 2
+        return (left, top, (W + n) // 2 - left, (H + n) // 2 - top)
+    raise ValueError(f"crop kind must be 'dynca' or 'conditioned', got {kind!r}")
+
+
+def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubic") -> torch.Tensor:
+    """frames [N,H,W,3] uint8 -> [N,out_h,out_w,3] uint8 on the frames' device: the reference's crop, then Pillow's 8-bit Image.resize,
+    bit for bit.  size = (out_h, out_w) -- rows first; the reference hands Pillow (x, y).  crop: 'dynca' or 'conditioned'
+    (reference_crop), None (the whole frame) or a box (x0, y0, w, h).  resample: 'bicubic' (Image.resize's default, what
+    preprocess_style_image gets) or 'lanczos' (load_image).  CUDA frames run ncahip_clip_resize_u8 (two launches for all N frames), CPU
+    frames its numpy mirror ops.clip_resize_host on the same tables."""
+    from . import ops
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"frames must be a uint8 tensor [N,H,W,3] (the reference resizes 8-bit images), got "
+                         f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)} {getattr(frames, 'dtype', '')}")
+    if isinstance(crop, str):
+        crop = reference_crop(crop, frames.shape[1], frames.shape[2])
+    return (ops.clip_resize if frames.is_cuda else ops.clip_resize_host)(frames, size, crop, resample)
+
+
+def _sized(frames: torch.Tensor, size):
+    """stylize_clip*(size=...): the model grid (H, W) after validating the frames the resize takes."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"with size set, frames must be [F,h,w,3] uint8 (the reference resizes 8-bit images), got {tuple(frames.shape)} {frames.dtype}")
+    try:
+        hh, ww = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    if hh < 1 or ww < 1:
+        raise ValueError(f"size must be positive, got {size!r}")
+    return hh, ww
+
+
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
-                 gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32):
+                 gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic"):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -98,7 +147,12 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     becomes the last state channel, forward_nsteps runs, the channel is dropped again.  `state` in and out is the reference's `h` with
     c_in - 1 channels (anything else: ValueError).  perception_scales [0] or the fused [0, 1] with an fp32 state run frames_per_call
     frames per C call (ncahip_clip_gray, then ncahip_dynca_clip_xc_f32 with the model's positional encoding); anything else runs that
-    loop in Python."""
+    loop in Python.
+
+    size=(H, W): decoder-sized frames.  frames must then be uint8 [F,h,w,3] (float frames: ValueError -- the reference resizes 8-bit
+    images); every chunk is uploaded at its native size, shrunk on the device by resize_frames(chunk, size, crop, resample) -- the
+    reference's preprocess_style_image (crop='dynca', bicubic), bit for bit -- and handed to the uint8 path above unchanged, on both
+    routes.  Seeding, the state and the images use (H, W).  size=None: crop and resample are not looked at."""
     from . import ops
     if gray not in ops.GRAY_WEIGHTS:
         raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
@@ -109,6 +163,14 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
     n_frames = frames.shape[0]
     hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
+    shrink = lambda chunk: chunk                                                   # noqa: E731
+    if size is not None:
+        hh, ww = _sized(frames, size)
+        box = reference_crop(crop, *frames.shape[1:3]) if isinstance(crop, str) else crop
+        ops._resize_filter(resample)                                               # bad resample / crop: before anything runs
+        if n_frames:
+            ops._resize_args(frames.shape, (hh, ww), box)
+        shrink = lambda chunk: resize_frames(chunk, (hh, ww), box, resample)       # noqa: E731
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
     extra = _extra_channels(nca_model)
@@ -128,7 +190,7 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
             bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
             do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
         for f0 in range(0, n_frames, per_call):
-            chunk = frames[f0:f0 + per_call].to(dev).unsqueeze(1)                 # [n,1,3,H,W] or [n,1,H,W,3]
+            chunk = shrink(frames[f0:f0 + per_call].to(dev)).unsqueeze(1)         # [n,1,3,H,W] or [n,1,H,W,3]
             n = chunk.shape[0]
             cond = ops.clip_gray(chunk, gray) if extra else ops.clip_cond(chunk, bank, gray, do_tanh)
             us = None
@@ -145,7 +207,7 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
             outs.append(imgs[:, 0])
     else:
         for f0 in range(0, n_frames, per_call):
-            chunk = frames[f0:f0 + per_call].to(dev)
+            chunk = shrink(frames[f0:f0 + per_call].to(dev))
             chunk = _widen(chunk) if u8_in else chunk
             for i in range(chunk.shape[0]):
                 cond = _gray(chunk[i:i + 1], gray)
@@ -177,7 +239,8 @@ def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
 
 @torch.no_grad()
 def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
-                             warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8):
+                             warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8, size=None, crop="conditioned",
+                             resample: str = "lanczos"):
     """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
     loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
     goal of its own steps:
@@ -193,7 +256,12 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     (ncahip_clip_encode for the goals of the chunk -- 34 MB at 8 x 256^2, E = 16 --, then ncahip_cond_clip_f32: the library's grow drivers and
     the image output, no Python per frame); the result does not depend on frames_per_call.  The fire masks are drawn exactly as
     ConditionedNCA._draw draws them per grow call, in order, and _mask_step advances as in the loop.  Anything else (a custom encoder, a bf16
-    state) runs the loop above in Python.  stylize_clip_conditioned.last_path records the route: 'clip' or 'loop'."""
+    state) runs the loop above in Python.  stylize_clip_conditioned.last_path records the route: 'clip' or 'loop'.
+
+    size=(H, W): decoder-sized frames, as in stylize_clip: uint8 [F,h,w,3] frames only (float frames: ValueError), each chunk uploaded at
+    its native size and shrunk on the device by resize_frames(chunk, size, crop, resample) -- the reference's load_image (crop='conditioned',
+    Lanczos), bit for bit -- on both routes; seeding, the state check and the images use (H, W).  size=None: crop and resample are not
+    looked at."""
     from . import ops
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
@@ -204,6 +272,14 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
         raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
     n_frames = frames.shape[0]
     hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
+    shrink = lambda chunk: chunk                                                   # noqa: E731
+    if size is not None:
+        hh, ww = _sized(frames, size)
+        box = reference_crop(crop, *frames.shape[1:3]) if isinstance(crop, str) else crop
+        ops._resize_filter(resample)                                               # bad resample / crop: before anything runs
+        if n_frames:
+            ops._resize_args(frames.shape, (hh, ww), box)
+        shrink = lambda chunk: resize_frames(chunk, (hh, ww), box, resample)       # noqa: E731
     if state is not None and (state.dim() != 4 or state.shape[1] != nca.num_channels or tuple(state.shape[2:]) != (hh, ww)):
         raise ValueError(f"state must be [B,{nca.num_channels},{hh},{ww}] (nca.num_channels channels, the frames' size), got {tuple(state.shape)}")
     if state is None and hh != ww:
@@ -226,7 +302,7 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
         draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(h, steps)      # noqa: E731
         args = (nca._alive_ch(), nca.alpha_living_threshold, nca.cell_fire_rate, -10.0, 10.0)
         for f0 in range(0, n_frames, per_call):
-            chunk = frames[f0:f0 + per_call].to(dev).unsqueeze(1)                 # [n,1,3,H,W] or [n,1,H,W,3]
+            chunk = shrink(frames[f0:f0 + per_call].to(dev)).unsqueeze(1)         # [n,1,3,H,W] or [n,1,H,W,3]
             n = chunk.shape[0]
             goal = ops.clip_encode(chunk, nca.encoder)
             if f0 == 0 and warm > 0:
@@ -240,7 +316,7 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
             outs.append(imgs[:, 0])
     else:
         for f0 in range(0, n_frames, per_call):
-            chunk = unit(frames[f0:f0 + per_call].to(dev))
+            chunk = unit(shrink(frames[f0:f0 + per_call].to(dev)))
             for i in range(chunk.shape[0]):
                 goal_img = chunk[i:i + 1]
                 if f0 == 0 and i == 0 and warm > 0:
