@@ -449,11 +449,14 @@ _COND_TRAINED = ("perception_net.weight", "update_net.out.0.weight", "update_net
 
 def cond_replay_vjp_step(x_in: torch.Tensor, pend_slot: torch.Tensor, pre_slot: torch.Tensor, goal_pad, u, prm,
                          g_next: torch.Tensor, alive_ch: int, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0,
-                         hi: float = 10.0):
+                         hi: float = 10.0, bf16_operands: bool = False):
     """One step of the replay VJP: for in_{k+1} = clamp((in_k + r * out(in_k)) * life, lo, hi) with the recorded masks --
     pre = pre slot k+1, post = alive(pend_slot = states slot k+1), neither carrying gradient -- and L = <g_next, in_{k+1}>,
     returns (dL/d in_k, dL/d goal_pad (None without goal), {param: dL/dparam} in the reference layouts).  The clamp passes
-    gradient on the closed interval [lo, hi] (torch.clamp, as the kernels).  Everything in x_in's dtype."""
+    gradient on the closed interval [lo, hi] (torch.clamp, as the kernels).  Everything in x_in's dtype.
+    bf16_operands: the three matrix products take their operands (perception, hidden activations, weights) rounded to bf16,
+    every rounding straight-through, the sums in x_in's dtype -- cond_grow_bf16_loss_grads' step, the function whose gradient
+    ncahip_cond_grow_bwd_bf16 evaluates on bf16 MFMA, restarted from a recorded input."""
     dt = x_in.dtype
     x = x_in.detach().clone().requires_grad_(True)
     g = None if goal_pad is None else goal_pad.detach().to(dt).clone().requires_grad_(True)
@@ -462,7 +465,13 @@ def cond_replay_vjp_step(x_in: torch.Tensor, pend_slot: torch.Tensor, pre_slot: 
     life = (_mask4(pre_slot, x, alive_ch) & _alive32(pend_slot.to(dt), alive_ch, thr)).to(dt)
     rmask = (u.reshape(pre.shape).float().clamp(0.0, 1.0) < _f32(fire_rate)).to(device=x.device, dtype=dt)
     z = x if g is None else x + g * pre
-    out = cond_update_net(cond_perceive(z, p["perception_net.weight"]), p)
+    if bf16_operands:
+        w1, w2, w3 = (_bf_ste(p[f"update_net.out.{i}.weight"]) for i in (0, 2, 4))
+        h1 = F.relu(_conv1x1(_bf_ste(cond_perceive(z, p["perception_net.weight"])), w1, p["update_net.out.0.bias"]))
+        h2 = F.relu(_conv1x1(_bf_ste(h1), w2, p["update_net.out.2.bias"]))
+        out = _conv1x1(_bf_ste(h2), w3, None)
+    else:
+        out = cond_update_net(cond_perceive(z, p["perception_net.weight"]), p)
     nxt = torch.clamp((x + rmask * out) * life, _f32(lo), _f32(hi))
     leaves = [x] + ([] if g is None else [g]) + [p[k] for k in _COND_TRAINED]
     grads = torch.autograd.grad(nxt, leaves, grad_outputs=g_next.to(dt))
@@ -473,17 +482,19 @@ def cond_replay_vjp_step(x_in: torch.Tensor, pend_slot: torch.Tensor, pre_slot: 
 
 def cond_replay_vjp(states: torch.Tensor, pre: torch.Tensor, goal_pad, us, prm, cot: torch.Tensor, alive_ch: int,
                     thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0,
-                    dtype: torch.dtype = torch.float64, on_step=None):
+                    dtype: torch.dtype = torch.float64, on_step=None, bf16_operands: bool = False):
     """The chained VJP of L = <cot, x_final> along a recorded history (x_final = in_T): pre masks from the pre slots, post masks
     alive(pending slot), masks without gradient, the clamp passing gradient on [lo, hi].  Returns (dL/dx0, dL/dgoal_pad or
     None, {param: grad} in the reference layouts), all in ``dtype``.  ``on_step(k, in_k, g_next, result)``, if given, sees every
-    step's one-step VJP (cond_replay_vjp_step) on the way down, g_next = dL/d in_{k+1}.  Inputs are rebuilt slot by slot."""
+    step's one-step VJP (cond_replay_vjp_step) on the way down, g_next = dL/d in_{k+1}.  Inputs are rebuilt slot by slot.
+    bf16_operands: see cond_replay_vjp_step."""
     Tn = states.shape[0] - 1
     gk = cot.to(dtype)
     gg_sum, gw_sum = None, None
     for k in range(Tn - 1, -1, -1):
         x_in = states[0].to(dtype) if k == 0 else cond_resolve(states[k].to(dtype), pre[k], alive_ch, thr, lo, hi)
-        r = cond_replay_vjp_step(x_in, states[k + 1], pre[k + 1], goal_pad, us[k], prm, gk, alive_ch, thr, fire_rate, lo, hi)
+        r = cond_replay_vjp_step(x_in, states[k + 1], pre[k + 1], goal_pad, us[k], prm, gk, alive_ch, thr, fire_rate, lo, hi,
+                                 bf16_operands)
         if on_step is not None:
             on_step(k, x_in, gk, r)
         gk, gg, gw = r
