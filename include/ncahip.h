@@ -11,7 +11,8 @@
  *   - work is enqueued asynchronously on `stream` (a hipStream_t; NULL = default stream), the
  *     call never synchronises (ncahip_selftest and ncahip_check_errors excepted) and is safe from several host
  *     threads on distinct streams and devices: launch state is cached per DEVICE (the device current at the call),
- *     the two process-wide switches (ncahip_cond_precision, ncahip_debug_force_generic) are test / tuning hooks;
+ *     the two process-wide switches (ncahip_cond_precision, ncahip_debug_force_generic) are test / tuning hooks, and
+ *     ncahip_dynca_precision is a process-wide mode read when a call enqueues;
  *   - return 0 on success, a negative NCAHIP_E* on an argument error (nothing was launched),
  *     or a positive hipError_t if the launch failed; ncahip_last_error() describes the last
  *     failure of the calling thread.
@@ -168,6 +169,25 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float *states, int ring, int T, const float *
                                    int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                    float update_rate, uint64_t seed, uint64_t step0, float *pc_scratch,
                                    ncahip_stream_t stream);
+
+/* ---- opt-in bf16 MFMA for the DyNCA forward step ----------------------------------------------------------------------
+ * Process-wide, host-only (needs no GPU), not a test hook: 0 = exact fp32 (default), 1 = both 1x1 products of the forward
+ * UpdateNet on v_mfma_f32_16x16x32_bf16.  Returns the PREVIOUS mode, or NCAHIP_EINVAL for any other value (the mode is then
+ * unchanged).  Arithmetic of mode 1 (the state stays fp32 in and out):
+ *   - perception -- and, two-scale, its blend with the up-sampled coarse perception -- in fp32, the code of mode 0;
+ *   - y = [perception | cond] rounded to bf16 (round to nearest even) as matrix operand; w1 and w2 rounded to bf16 (RNE) once
+ *     per launch, when the weight images are built; b1 and b2 stay fp32: they are the accumulators' initial values;
+ *   - layer 1 accumulates in fp32; ReLU; h rounded to bf16 (RNE); layer 2 accumulates in fp32;
+ *   - x_out = x + dx * mask in fp32, exactly as in mode 0; K is zero-padded to the instruction's 32;
+ *   - the order of k within a product is the implementation's (csrc/nca_dynca_bf16.h) and the same in every kernel of the mode:
+ *     per-step kernels (vector and any-shape form, single- and two-scale) and the two one-launch kernels agree bit for bit;
+ *   - fire masks (explicit u, packed bits, Philox), pad modes and conditioning are untouched; non-finite inputs are outside the
+ *     contract.  Per element the result differs from mode 0 by at most about 2^-8 * sum_j |w2_cj| (|h_j| + sum_k |w1_jk| |y_k|).
+ * The mode is read at enqueue time by ncahip_dynca_step_fwd_f32 / _ms_f32, ncahip_dynca_nsteps_fwd_f32 / _ms_f32,
+ * ncahip_dynca_nsteps_fwd_persist_f32 / _ms_f32 and ncahip_dynca_clip_f32 / _clip_xc_f32 (once per call of each) -- and by no
+ * backward entry point and no bf16-storage one: those always compute exactly, so a history for the backward must be recorded in
+ * mode 0.  Range: C <= 16 and fc <= 128.  For any other shape the mode is IGNORED: the result is bit-equal to mode 0.        */
+int ncahip_dynca_precision(int mode);
 
 /* Backward of ONE DyNCA step (autograd through dynca.py:117-138; dynca.py:123: no gradient into cond).
  *   In : x_t (the step's input state), the same cond / u (or seed, step) / weights, g_next = dL/dx_{t+1}.

@@ -164,6 +164,15 @@ int ncahip_cond_precision(int mode) {
     return 0;
 }
 
+// 0 = exact fp32 (default), 1 = both 1x1 products of the forward step on bf16 MFMA; read at enqueue time by the fp32 forward entry
+// points only (never by a backward one)
+static std::atomic<int> g_dynca_precision{0};
+int ncahip_dynca_precision(int mode) {
+    if (mode != 0 && mode != 1) return fail(NCAHIP_EINVAL, "dynca precision: 0 (exact fp32) or 1 (bf16 MFMA)");
+    return g_dynca_precision.exchange(mode, std::memory_order_relaxed);
+}
+static bool dynca_bf16_mfma(int C, int fc) { return g_dynca_precision.load(std::memory_order_relaxed) == 1 && nca_dynca_bf16_shape_ok(C, fc); }
+
 static int g_force_bits = 0;   // the last ncahip_debug_force_generic argument: the persistent grow runs only with none set
 int ncahip_debug_force_generic(int on) {
     g_force_bits = on;
@@ -222,7 +231,7 @@ int ncahip_dynca_step_fwd_f32(const float* x_in, float* x_out, const float* cond
     if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
     NcaDyncaArgs a{x_in, x_out, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step};
     a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream), "dynca_step_fwd");
+    return hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream, dynca_bf16_mfma(C, fc)), "dynca_step_fwd");
 }
 
 int ncahip_dynca_nsteps_fwd_f32(float* states, int ring, int T, const float* cond, const float* u, const float* w1,
@@ -234,12 +243,13 @@ int ncahip_dynca_nsteps_fwd_f32(float* states, int ring, int T, const float* con
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
     const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W;
+    const bool bf = dynca_bf16_mfma(C, fc);   // one read per call: every step of it runs the same arithmetic
     for (int t = 0; t < T; ++t) {
         NcaDyncaArgs a{states + (size_t)(t % ring) * slot, states + (size_t)((t + 1) % ring) * slot, cond,
                        u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
                        update_rate, seed, step0 + (uint64_t)t};
         a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream), "dynca_nsteps_fwd")) return rc;
+        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream, bf), "dynca_nsteps_fwd")) return rc;
     }
     return 0;
 }
@@ -275,7 +285,10 @@ static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, i
                           (int*)workspace, epoch, (unsigned long long*)((char*)workspace + 256),
                           nca_dynca_persist_xch_pairs(B, C, H, W, two_scale), nullptr, ubits ? 1 : 0};
     bool fits = false;
-    auto launch = two_scale ? nca_launch_dynca_persist_ms : nca_launch_dynca_persist;
+    const bool bf = dynca_bf16_mfma(C, fc);   // the variant's own instantiation: its own LDS size and co-residency test
+    auto launch = [&](const NcaDyncaPersistArgs& pa, hipStream_t ps, bool query_only, bool* f) {
+        return two_scale ? nca_launch_dynca_persist_ms(pa, ps, query_only, f, bf) : nca_launch_dynca_persist(pa, ps, query_only, f, bf);
+    };
     if (int rc = hip_result(launch(a, st, true, &fits), "dynca nsteps persist (occupancy)")) return rc;
     if (!fits) return fail(NCAHIP_ERANGE, "dynca nsteps persist: %d tiles cannot all be resident on this device; use ncahip_dynca_nsteps_fwd_f32",
                            nca_dynca_persist_tiles(B, H, W));
@@ -378,7 +391,7 @@ int ncahip_dynca_step_fwd_ms_f32(const float* x_in, float* x_out, const float* c
     NcaDyncaArgs a{x_in, x_out, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step};
     a.pc = pc_scratch;
     a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_fwd(a, st), "dynca_step_fwd_ms");
+    return hip_result(nca_launch_dynca_step_fwd(a, st, dynca_bf16_mfma(C, fc)), "dynca_step_fwd_ms");
 }
 
 int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* cond, const float* u, const float* w1,
@@ -392,6 +405,7 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* 
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
     const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W;
+    const bool bf = dynca_bf16_mfma(C, fc);
     for (int t = 0; t < T; ++t) {
         const float* const xi = states + (size_t)(t % ring) * slot;
         if (int rc = hip_result(nca_launch_dynca_coarse_perceive(xi, pc_scratch, B, C, H, W, pad_mode, st), "dynca coarse perceive")) return rc;
@@ -399,7 +413,7 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* 
                        W, fc, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t};
         a.pc = pc_scratch;
         a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, st), "dynca_nsteps_fwd_ms")) return rc;
+        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, st, bf), "dynca_nsteps_fwd_ms")) return rc;
     }
     return 0;
 }

@@ -89,6 +89,22 @@ __device__ __forceinline__ f32x4 nca_mfma(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// ---- bf16 MFMA (ncahip_dynca_precision mode 1): D(16x16) += A(16x32) * B(32x16), fp32 accumulation.  Lane l = 16*g + i holds
+//   a[j] = A[row i][k 8g + j], b[j] = B[k 8g + j][col i], j = 0..7 (two bf16 per 32-bit word, low half first), d[r] = D[row 4g + r][col i]
+// -- the accumulator layout of the f32 form, so a layer's tile is still the next layer's B operand: four registers of TWO
+// consecutive 16-row tiles are one lane's eight k values.
+typedef __bf16 nca_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned nca_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 nca_mfma_bf16(nca_u32x4 a, nca_u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nca_bf16x8, a), __builtin_bit_cast(nca_bf16x8, b), c, 0, 0, 0);
+}
+// two f32 -> two bf16 in one word (lo in bits 0..15), round-to-nearest-even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ unsigned nca_pk_bf16(float lo, float hi) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{lo, hi}, b2));
+}
+
 // XCD-aware persistent tile schedule: workgroups b and b+8 share an XCD (its L2), so each XCD
 // group walks one contiguous chunk of the tile list (spatially adjacent tiles share halos).
 struct NcaTileWalk {

@@ -1,0 +1,94 @@
+// nca_dynca_bf16.h -- the bf16-MFMA UpdateNet of the DyNCA forward step (ncahip_dynca_precision mode 1; contract: include/ncahip.h).
+// What fixes the bits of that mode exists ONCE, here, and is shared by the per-step kernel (nca_step_fwd.hip) and the two persistent
+// kernels (nca_dynca_persist.hip): the k order of both products (folded into the LDS weight images), the operand roundings and the
+// MFMA sequence per accumulator.  C <= 16 (one 16-row output tile), fc a multiple of 32 after padding.
+//
+// k order.  v_mfma_f32_16x16x32_bf16 takes eight k values per lane: lane (g, i) supplies k = 8g + j, j = 0..7.
+//   layer 1: lane (g, cell) holds y slots s = 0..K1S-1 (s = 4c'+f < CP: channel 4c'+g, filter f; s = CP: conditioning channel g) --
+//            the per-step kernel's perception registers.  Chunk q takes slots 8q..8q+7, zero beyond K1S: K1Q = ceil(K1S / 8) MFMAs per
+//            16 hidden units instead of K1S.
+//   layer 2: the accumulator registers r = 0..3 of hidden tile m are hidden units 16m + 4g + r of the lane's cell.  Pair p takes
+//            tiles 2p and 2p+1: j = 4 (m & 1) + r  <->  hidden 16 (2p + j / 4) + 4g + j % 4: FC / 32 MFMAs instead of FC / 4.
+// Image layout: 16-byte entries [tile][chunk | pair][lane], eight bf16 each; as 32-bit words idx = (entry * 64 + lane) * 4 + jj with
+// word jj = (j = 2jj in the low half, j = 2jj + 1 in the high half).
+#pragma once
+#include "nca_common.h"
+
+template <int CP, int FC, bool HAS_COND>
+struct NcaDyncaBf16 {
+    static constexpr int K1S = CP + (HAS_COND ? 1 : 0);
+    static constexpr int K1Q = (K1S + 7) / 8;       // layer-1 MFMAs per hidden tile
+    static constexpr int M1T = FC / 16, M1P = FC / 32;
+    static constexpr int W1_WORDS = M1T * K1Q * 256, W2_WORDS = M1P * 256;   // 32-bit words (= floats of LDS)
+    static_assert(CP % 4 == 0 && CP <= 16 && FC % 32 == 0, "bf16 UpdateNet: C <= 16, fc padded to a multiple of 32");
+
+    // source element in w1 [fc][K1 = 4C + CC] of half `hf` of image word idx, or -1 (zero padding)
+    static __device__ __forceinline__ long w1_src(int idx, int hf, int C, int CC, int fc) {
+        const int jj = idx & 3, l = (idx >> 2) & 63, q = (idx >> 8) % K1Q, m = (idx >> 8) / K1Q;
+        const int s = 8 * q + 2 * jj + hf, gg = l >> 4, o = 16 * m + (l & 15), K1 = 4 * C + CC;
+        if (o >= fc) return -1;
+        if (s < CP) {   // blocked [x|Sx|Sy|L], dynca.py:92-95
+            const int ch = (s & ~3) + gg;
+            return ch < C ? (long)o * K1 + (s & 3) * C + ch : -1;
+        }
+        return (HAS_COND && s == CP && gg < CC) ? (long)o * K1 + 4 * C + gg : -1;
+    }
+    // source element in w2 [C][fc]
+    static __device__ __forceinline__ long w2_src(int idx, int hf, int C, int fc) {
+        const int jj = idx & 3, l = (idx >> 2) & 63, p = idx >> 8;
+        const int j = 2 * jj + hf, gg = l >> 4, o = l & 15, k = 16 * (2 * p + (j >> 2)) + 4 * gg + (j & 3);
+        return (o < C && k < fc) ? (long)o * fc + k : -1;
+    }
+
+    // acc2 = b2 + W2 bf16(relu(b1 + W1 bf16(P))) for NT groups of 16 cells; fp32 accumulation, biases as initial values
+    template <int NT>
+    static __device__ __forceinline__ void mlp(const float* W1L, const float* W2L, const float* B1L, const float* B2L,
+                                               const float (&P)[NT][K1S], int lane, int g, f32x4 (&acc2)[NT]) {
+        const nca_u32x4* const W1B = reinterpret_cast<const nca_u32x4*>(W1L) + lane;
+        const nca_u32x4* const W2B = reinterpret_cast<const nca_u32x4*>(W2L) + lane;
+        {
+            const f32x4 bias = *reinterpret_cast<const f32x4*>(B2L + 4 * g);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc2[n] = bias;
+        }
+        nca_u32x4 PB[NT][K1Q];
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < K1Q; ++q)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int s = 8 * q + 2 * jj;
+                    PB[n][q][jj] = nca_pk_bf16(s < K1S ? P[n][s < K1S ? s : 0] : 0.0f, s + 1 < K1S ? P[n][s + 1 < K1S ? s + 1 : 0] : 0.0f);
+                }
+#pragma unroll
+        for (int p = 0; p < M1P; ++p) {
+            nca_u32x4 hb[NT];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int m = 2 * p + hf;
+                const f32x4 bias1 = *reinterpret_cast<const f32x4*>(B1L + 16 * m + 4 * g);
+                f32x4 acc1[NT];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc1[n] = bias1;
+#pragma unroll
+                for (int q = 0; q < K1Q; ++q) {
+                    const nca_u32x4 wa = W1B[(m * K1Q + q) * 64];
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) acc1[n] = nca_mfma_bf16(wa, PB[n][q], acc1[n]);
+                }
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    float h[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h[r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu
+                    hb[n][2 * hf] = nca_pk_bf16(h[0], h[1]);
+                    hb[n][2 * hf + 1] = nca_pk_bf16(h[2], h[3]);
+                }
+            }
+            const nca_u32x4 wb = W2B[p * 64];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc2[n] = nca_mfma_bf16(wb, hb[n], acc2[n]);
+        }
+    }
+};

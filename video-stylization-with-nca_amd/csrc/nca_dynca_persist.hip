@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "nca_dynca_bf16.h"
 #include "nca_kernels.h"
 
 static int g_drop_tiles = 0;
@@ -48,15 +49,18 @@ static_assert(PCS % 32 == 16 && PTW + 2 + 3 <= PRS, "tile carve");
 constexpr int kHalo = 2 * (PTW + 2) + 2 * PTH;             // 68 halo cells
 constexpr int kIW = PTW - 2;                               // interior width (14)
 
-template <int CP, int FC, bool HAS_COND>
+// BF: the bf16-MFMA UpdateNet (ncahip_dynca_precision mode 1, nca_dynca_bf16.h): other weight images, another MLP in the compute waves;
+// the sync wave, the exchange, the barrier schedule and the polls are the same code
+template <int CP, int FC, bool HAS_COND, bool BF = false>
 struct PersistCfg {
     static constexpr int CPAD = CP, FCPAD = FC;              // (for the shared helpers, which take the whole configuration)
-    static constexpr bool COND = HAS_COND;
+    static constexpr bool COND = HAS_COND, BF16 = BF;
+    using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
     static constexpr int K1S = CP + (HAS_COND ? 1 : 0);
     static constexpr int M1T = FC / 16, K2S = FC / 4;
     static constexpr int OFF_W1 = 0;
-    static constexpr int OFF_W2 = OFF_W1 + M1T * K1S * 64;
-    static constexpr int OFF_B1 = OFF_W2 + K2S * 64;
+    static constexpr int OFF_W2 = OFF_W1 + (BF ? BFK::W1_WORDS : M1T * K1S * 64);
+    static constexpr int OFF_B1 = OFF_W2 + (BF ? BFK::W2_WORDS : K2S * 64);
     static constexpr int OFF_B2 = OFF_B1 + FC;
     static constexpr int OFF_Z = OFF_B2 + 16;
     static constexpr int OFF_MK = OFF_Z + 2 * CP * PCS;               // fire masks of two steps, [2][256]
@@ -150,7 +154,35 @@ __device__ __forceinline__ void persist_prologue(const NcaDyncaPersistArgs& a, f
     const int tid = threadIdx.x, C = a.C, W = a.W, fc = a.fc, CC = a.c_cond, K1 = 4 * C + CC;
     // A-operand weight images (same layouts and k order as dynca_step_fwd_kernel).  Two-phase gather: every load of both images is
     // requested before the first LDS write (one cold round trip for the prologue, not one per element)
-    {
+    if constexpr (K::BF16) {   // bf16 images: one word = two consecutive k values of a lane in the bf16 k order, rounded to nearest even
+        using BFK = typename K::BFK;
+        constexpr int N1 = BFK::W1_WORDS, N2 = BFK::W2_WORDS, U1 = (N1 + kPT - 1) / kPT, U2 = (N2 + kPT - 1) / kPT;
+        float v1[U1][2], v2[U2][2];
+#pragma unroll
+        for (int u = 0; u < U1; ++u)
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int idx = tid + kPT * u;
+                const long src = idx < N1 ? BFK::w1_src(idx, hf, C, CC, fc) : -1;
+                const float w = a.w1[src >= 0 ? src : 0];
+                v1[u][hf] = src >= 0 ? w : 0.0f;
+            }
+#pragma unroll
+        for (int u = 0; u < U2; ++u)
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int idx = tid + kPT * u;
+                const long src = idx < N2 ? BFK::w2_src(idx, hf, C, fc) : -1;
+                const float w = a.w2[src >= 0 ? src : 0];
+                v2[u][hf] = src >= 0 ? w : 0.0f;
+            }
+#pragma unroll
+        for (int u = 0; u < U1; ++u)
+            if (tid + kPT * u < N1) smem[K::OFF_W1 + tid + kPT * u] = __uint_as_float(nca_pk_bf16(v1[u][0], v1[u][1]));
+#pragma unroll
+        for (int u = 0; u < U2; ++u)
+            if (tid + kPT * u < N2) smem[K::OFF_W2 + tid + kPT * u] = __uint_as_float(nca_pk_bf16(v2[u][0], v2[u][1]));
+    } else {
         float* const W1L = smem + K::OFF_W1;
         float* const W2L = smem + K::OFF_W2;
         constexpr int N1 = K::M1T * K::K1S * 64, N2 = K::K2S * 64, U1 = (N1 + kPT - 1) / kPT, U2 = (N2 + kPT - 1) / kPT;
@@ -213,6 +245,12 @@ __device__ __forceinline__ void persist_mlp(const float* smem, const float (&P)[
     const float* const W1L = smem + K::OFF_W1;
     const float* const W2L = smem + K::OFF_W2;
     const float* const B1L = smem + K::OFF_B1;
+    if constexpr (K::BF16) {   // mode 1: the per-step kernel's bf16 UpdateNet, the same function
+        if (!(dbg & 16)) {
+            K::BFK::template mlp<NTP>(W1L, W2L, B1L, smem + K::OFF_B2, P, lane, g, acc2);
+            return;
+        }
+    }
     {
         const f32x4 bias = *reinterpret_cast<const f32x4*>(smem + K::OFF_B2 + 4 * g);
 #pragma unroll
@@ -349,9 +387,9 @@ __device__ __forceinline__ void fine_halo_cell(int hc, int& r, int& q) {
 }
 
 // ---- the single-scale kernel ----------------------------------------------------------------------------------------------------------
-template <int CP, int FC, bool HAS_COND>
+template <int CP, int FC, bool HAS_COND, bool BF = false>
 __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPersistArgs a) {
-    using K = PersistCfg<CP, FC, HAS_COND>;
+    using K = PersistCfg<CP, FC, HAS_COND, BF>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const MK = smem + K::OFF_MK;
     float* const CN = smem + K::OFF_CN;
@@ -535,9 +573,9 @@ __device__ __forceinline__ void group_cell_ms(int j, int ci, int& r, int& q) {
     else { r = 4 + (idx - 160) / 4; q = 12 + (idx - 160) % 4; }
 }
 
-template <int CP, int FC, bool HAS_COND>
+template <int CP, int FC, bool HAS_COND, bool BF = false>
 struct PersistMsCfg {
-    using B = PersistCfg<CP, FC, HAS_COND>;
+    using B = PersistCfg<CP, FC, HAS_COND, BF>;
     static constexpr int OFF_XC = B::LDS_FLOATS;                 // [CP][12 x 12]
     static constexpr int OFF_PCL = OFF_XC + CP * XCS;            // [4 CP][10 x 10]
     static constexpr int NLC = (kCoarseHalo * CP + 63) / 64;     // coarse halo items per sync-wave lane
@@ -548,10 +586,10 @@ struct PersistMsCfg {
     static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 };
 
-template <int CP, int FC, bool HAS_COND>
+template <int CP, int FC, bool HAS_COND, bool BF = false>
 __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDyncaPersistArgs a) {
-    using K = PersistCfg<CP, FC, HAS_COND>;
-    using KM = PersistMsCfg<CP, FC, HAS_COND>;
+    using K = PersistCfg<CP, FC, HAS_COND, BF>;
+    using KM = PersistMsCfg<CP, FC, HAS_COND, BF>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const MK = smem + K::OFF_MK;
     float* const CN = smem + K::OFF_CN;
@@ -823,10 +861,10 @@ hipError_t launch_persist(int lds_floats, const NcaDyncaPersistArgs& a, hipStrea
     return hipGetLastError();
 }
 
-template <bool MS, int CP, int FC, bool HAS_COND>
+template <bool MS, int CP, int FC, bool HAS_COND, bool BF = false>
 hipError_t launch_cfg(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    if constexpr (MS) return launch_persist<dynca_persist_ms_kernel<CP, FC, HAS_COND>>(PersistMsCfg<CP, FC, HAS_COND>::LDS_FLOATS, a, st, query_only, fits);
-    else return launch_persist<dynca_persist_kernel<CP, FC, HAS_COND>>(PersistCfg<CP, FC, HAS_COND>::LDS_FLOATS, a, st, query_only, fits);
+    if constexpr (MS) return launch_persist<dynca_persist_ms_kernel<CP, FC, HAS_COND, BF>>(PersistMsCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS, a, st, query_only, fits);
+    else return launch_persist<dynca_persist_kernel<CP, FC, HAS_COND, BF>>(PersistCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS, a, st, query_only, fits);
 }
 
 int persist_dbg() {
@@ -835,11 +873,15 @@ int persist_dbg() {
 }
 
 template <bool MS>
-hipError_t dispatch_persist(const NcaDyncaPersistArgs& a_in, hipStream_t st, bool query_only, bool* fits) {
+hipError_t dispatch_persist(const NcaDyncaPersistArgs& a_in, hipStream_t st, bool query_only, bool* fits, bool bf16_mfma) {
     NcaDyncaPersistArgs a = a_in;
     a.err = nca_error_word_device();
     a.dbg = persist_dbg();
     const bool small = a.C <= 12 && a.fc <= 96;
+    if (bf16_mfma) {   // every shape the persistent kernels cover is in the mode's range (C <= 16, fc <= 128)
+        if (a.c_cond > 0) return small ? launch_cfg<MS, 12, 96, true, true>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, true, true>(a, st, query_only, fits);
+        return small ? launch_cfg<MS, 12, 96, false, true>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, false, true>(a, st, query_only, fits);
+    }
     if (a.c_cond > 0) return small ? launch_cfg<MS, 12, 96, true>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, true>(a, st, query_only, fits);
     return small ? launch_cfg<MS, 12, 96, false>(a, st, query_only, fits) : launch_cfg<MS, 16, 128, false>(a, st, query_only, fits);
 }
@@ -856,9 +898,9 @@ size_t nca_dynca_persist_xch_pairs(int B, int C, int H, int W, bool two_scale) {
     return (size_t)nca_dynca_persist_tiles(B, H, W) * C * (two_scale ? kXchMS : kRingCells);
 }
 
-hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    return dispatch_persist<false>(a, st, query_only, fits);
+hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits, bool bf16_mfma) {
+    return dispatch_persist<false>(a, st, query_only, fits, bf16_mfma);
 }
-hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    return dispatch_persist<true>(a, st, query_only, fits);
+hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits, bool bf16_mfma) {
+    return dispatch_persist<true>(a, st, query_only, fits, bf16_mfma);
 }

@@ -97,9 +97,10 @@ int nca_dynca_persist_tiles(int B, int H, int W);
 // (value, tag) pairs per parity of the ring exchange: tiles x C x 60 fine ring cells (+ 48 coarse means: two_scale)
 size_t nca_dynca_persist_xch_pairs(int B, int C, int H, int W, bool two_scale);
 // query_only: only decide whether every workgroup can be co-resident on the current device (*fits)
-hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
+// bf16_mfma: ncahip_dynca_precision mode 1 -- instantiations of their own (LDS size, occupancy cache and co-residency test per variant)
+hipError_t nca_launch_dynca_persist(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits, bool bf16_mfma = false);
 // two-scale perception (perception_scales = [0, 1]): exchanges 108 pairs per channel and tile (60 fine ring cells + 48 coarse means)
-hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
+hipError_t nca_launch_dynca_persist_ms(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits, bool bf16_mfma = false);
 
 // A whole ConditionedNCA grow in one launch (nca_cond_persist.hip): one workgroup per 16 x 16 tile for all T steps + finalize
 struct NcaCondPersistArgs {
@@ -248,7 +249,9 @@ int nca_resize_ksize(int in, int out, int filter);
 int nca_resize_build_tables(int in, int out, int filter, int32_t* k, int32_t* bounds, int ksize);
 
 // fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
-hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st);
+// bf16_mfma: ncahip_dynca_precision mode 1 (both 1x1 products on bf16 MFMA, nca_dynca_bf16.h) where nca_dynca_bf16_shape_ok
+hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma = false);
+inline bool nca_dynca_bf16_shape_ok(int C, int fc) { return C >= 1 && C <= 16 && fc >= 1 && fc <= 128; }
 hipError_t nca_launch_cond_step_fwd(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_dynca_step_bwd(const NcaDyncaArgs& a, hipStream_t st);
 hipError_t nca_launch_dynca_step_bwd_mlp(const NcaDyncaArgs& a, hipStream_t st, bool acc);      // MLP part only (hidden-layer slices)

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "nca_common.h"
+#include "nca_dynca_bf16.h"
 #include "nca_kernels.h"
 
 namespace {
@@ -78,6 +79,28 @@ __device__ __forceinline__ void fill_commit(const FillV<N>& r, float* __restrict
     for (int u = 0; u < (N + kThreads - 1) / kThreads; ++u) {
         const int idx = tid + kThreads * u;
         if (idx < N) dst[idx] = map(idx) >= 0 ? r.v[u] : 0.0f;
+    }
+}
+
+// bf16 weight images (nca_dynca_bf16.h): one 32-bit word = two consecutive k values of one lane, rounded to nearest even at commit
+template <int N>
+struct FillP { float lo[(N + kThreads - 1) / kThreads], hi[(N + kThreads - 1) / kThreads]; };
+template <int N, typename MapT>
+__device__ __forceinline__ void fill_issue_pk(FillP<N>& r, const float* __restrict__ src, int tid, MapT map) {
+#pragma unroll
+    for (int u = 0; u < (N + kThreads - 1) / kThreads; ++u) {
+        const int idx = tid + kThreads * u;
+        const long o0 = idx < N ? map(idx, 0) : -1, o1 = idx < N ? map(idx, 1) : -1;
+        r.lo[u] = src[o0 >= 0 ? o0 : 0];
+        r.hi[u] = src[o1 >= 0 ? o1 : 0];
+    }
+}
+template <int N, typename MapT>
+__device__ __forceinline__ void fill_commit_pk(const FillP<N>& r, float* __restrict__ dst, int tid, MapT map) {
+#pragma unroll
+    for (int u = 0; u < (N + kThreads - 1) / kThreads; ++u) {
+        const int idx = tid + kThreads * u;
+        if (idx < N) dst[idx] = __uint_as_float(nca_pk_bf16(map(idx, 0) >= 0 ? r.lo[u] : 0.0f, map(idx, 1) >= 0 ? r.hi[u] : 0.0f));
     }
 }
 
@@ -189,7 +212,8 @@ __device__ __forceinline__ void pos_store(const PosT& ps, float* __restrict__ Zc
 // =========================================================================================
 // DyNCA step (ConditioneDyNCA/models/dynca.py:117-138)
 // =========================================================================================
-template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT>
+// BF: the bf16-MFMA forward UpdateNet (ncahip_dynca_precision mode 1): only the two weight images differ (nca_dynca_bf16.h)
+template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT, bool BF = false>
 struct DyncaCfg {
     static constexpr int K1S = CP + (HAS_COND ? 1 : 0);  // k-steps of layer 1 (4 inputs each)
     static constexpr int M1T = FC / 16;                  // 16-row output tiles of layer 1
@@ -203,8 +227,10 @@ struct DyncaCfg {
     static constexpr int CPH = CP / 2;
     // LDS carve (floats)
     static constexpr int OFF_W1 = 0;
-    static constexpr int OFF_W2 = OFF_W1 + M1T * K1S * 64;
-    static constexpr int OFF_B1 = OFF_W2 + M2T * K2S * 64;
+    static constexpr int W1_FLOATS = BF ? M1T * ((K1S + 7) / 8) * 256 : M1T * K1S * 64;    // bf16 images: eight k values per 16-byte entry
+    static constexpr int W2_FLOATS = BF ? M2T * (FC / 32) * 256 : M2T * K2S * 64;
+    static constexpr int OFF_W2 = OFF_W1 + W1_FLOATS;
+    static constexpr int OFF_B1 = OFF_W2 + W2_FLOATS;
     static constexpr int OFF_B2 = OFF_B1 + FC;
     static constexpr int OFF_Z = OFF_B2 + M2T * 16;
     static constexpr int OFF_MK = OFF_Z + CP * CS;
@@ -234,12 +260,13 @@ struct DyncaCfg {
 // operand, as in the forward); writes relu(h), dh and dL/dy[:4C].  The two weight-gradient GEMMs
 // (dW2 = (G*mask) h^T, dW1 = dh y^T, K = all cells) are plain library GEMMs on those buffers.
 template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT, bool VEC, bool BWD = false, bool B16 = false, bool ACC = false, bool W2F = false,
-          bool MS = false>
+          bool MS = false, bool BF = false>
 __global__ __launch_bounds__(kThreads, (CP > 16 || MS) ? 1 : 2) void dynca_step_fwd_kernel(const NcaDyncaArgs a) {   // CP > 16: 140 KB of LDS -> one workgroup per CU anyway: 512 registers
     static_assert(!MS || (!B16 && !ACC && TH % 2 == 0 && TW % 2 == 0 && (!BWD || W2F)), "the two-scale step: fp32, one hidden slice");
     static_assert(!W2F || BWD, "fused dW2 is an option of the backward kernel");
     static_assert(!ACC || !B16, "accumulating passes (fc slices beyond the first) read fp32 partial results");
-    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT>;
+    static_assert(!BF || (!BWD && !B16 && !ACC && CP <= 16), "bf16 MFMA: the fp32-state forward step, one output tile, one hidden slice");
+    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
     using Pos = TilePos<TH, TW>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const W1L = smem + K::OFF_W1;
@@ -273,7 +300,23 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || MS) ? 1 : 2) void dynca_step_
     };
     auto map_b1 = [&](int idx) -> long { return idx < fc ? idx : -1; };
     auto map_b2 = [&](int idx) -> long { return (idx < C && !ACC) ? idx : -1; };
-    {
+    if constexpr (BF) {   // both weights rounded to bf16 (RNE) here, once; eight k values per lane and entry in the bf16 k order
+        using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
+        auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
+        auto bmap_w2 = [&](int idx, int hf) -> long { return BFK::w2_src(idx, hf, C, fc); };
+        FillP<BFK::W1_WORDS> f1;
+        FillP<BFK::W2_WORDS> f2;
+        FillV<FC> f3;
+        FillV<K::M2T * 16> f4;
+        fill_issue_pk(f1, a.w1, tid, bmap_w1);
+        fill_issue_pk(f2, a.w2, tid, bmap_w2);
+        fill_issue(f3, a.b1, tid, map_b1);
+        fill_issue(f4, a.b2, tid, map_b2);
+        fill_commit_pk(f1, W1L, tid, bmap_w1);
+        fill_commit_pk(f2, W2L, tid, bmap_w2);
+        fill_commit(f3, B1L, tid, map_b1);
+        fill_commit(f4, B2L, tid, map_b2);
+    } else {
         FillV<K::M1T * K::K1S * 64> f1;
         FillV<K::M2T * K::K2S * 64> f2;
         FillV<FC> f3;
@@ -658,6 +701,9 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || MS) ? 1 : 2) void dynca_step_
                             for (int r = 0; r < 4; ++r) xprev[n][m2][r] = ob[(size_t)min(16 * m2 + 4 * g + r, C - 1) * plane];
                     }
                 }
+                if constexpr (BF) {   // both products on bf16 MFMA, operands rounded to nearest even (nca_dynca_bf16.h)
+                    NcaDyncaBf16<CP, FC, HAS_COND>::template mlp<NT>(W1L, W2L, B1L, B2L, P, lane, g, acc2[0]);
+                } else {   // exact fp32: the lines up to the closing brace are as they were (not re-indented)
                 float wa1[K::K1S], wa2[4][K::M2T];
                 f32x4 bias1;
                 auto fetch = [&](int m) {
@@ -700,6 +746,7 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || MS) ? 1 : 2) void dynca_step_
                         for (int m2 = 0; m2 < K::M2T; ++m2)
     #pragma unroll
                             for (int n = 0; n < NT; ++n) acc2[m2][n] = nca_mfma(w2c[r][m2], h[n][r], acc2[m2][n]);
+                }
                 }
                 // ---- residual + stochastic mask (dynca.py:131-133) ---------------------------
     #pragma unroll
@@ -1136,11 +1183,11 @@ int grid_for(int ntiles, int wg_per_cu) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <int CP, int FC, bool HAS_COND, bool VEC, bool B16 = false, bool ACC = false>
+template <int CP, int FC, bool HAS_COND, bool VEC, bool B16 = false, bool ACC = false, bool BF = false>
 hipError_t launch_dynca_v(const NcaDyncaArgs& a, hipStream_t st) {
     constexpr int TH = 8, TW = 32, NT = 4;   // (C = 32 ran two rows per pass while it was compiled for 256 registers)
-    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT>;
-    auto kern = dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, VEC, false, B16, ACC>;
+    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
+    auto kern = dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, VEC, false, B16, ACC, false, false, BF>;
     const size_t lds = (size_t)K::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
@@ -1151,10 +1198,10 @@ hipError_t launch_dynca_v(const NcaDyncaArgs& a, hipStream_t st) {
 }
 
 // two-scale perception (a.pc = coarse-level perception of x_in, H and W even): one workgroup per CU (the coarse tile is in LDS)
-template <int CP, int FC, bool HAS_COND>
+template <int CP, int FC, bool HAS_COND, bool BF = false>
 hipError_t launch_dynca_ms(const NcaDyncaArgs& a, hipStream_t st) {
     constexpr int TH = 8, TW = 32, NT = 4;
-    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT>;
+    using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
     static_assert(K::LDS_FLOATS_MS * 4 <= 160 * 1024, "LDS budget (two-scale step)");
     const bool vec = (a.W % 4 == 0) && aligned16(a.x_in) && (((size_t)a.H * a.W) % 4 == 0);
     const size_t lds = (size_t)K::LDS_FLOATS_MS * sizeof(float);
@@ -1166,14 +1213,14 @@ hipError_t launch_dynca_ms(const NcaDyncaArgs& a, hipStream_t st) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, st, a);
         return hipGetLastError();
     };
-    return vec ? go(dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, true, false, false, false, false, true>)
-               : go(dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, false, false, false, false, false, true>);
+    return vec ? go(dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, true, false, false, false, false, true, BF>)
+               : go(dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, false, false, false, false, false, true, BF>);
 }
 
-template <int CP, int FC, bool HAS_COND, bool ACC = false>
+template <int CP, int FC, bool HAS_COND, bool ACC = false, bool BF = false>
 hipError_t launch_dynca(const NcaDyncaArgs& a, hipStream_t st) {
     const bool vec = (a.W % 4 == 0) && aligned16(a.x_in) && (((size_t)a.H * a.W) % 4 == 0);
-    return vec ? launch_dynca_v<CP, FC, HAS_COND, true, false, ACC>(a, st) : launch_dynca_v<CP, FC, HAS_COND, false, false, ACC>(a, st);
+    return vec ? launch_dynca_v<CP, FC, HAS_COND, true, false, ACC, BF>(a, st) : launch_dynca_v<CP, FC, HAS_COND, false, false, ACC, BF>(a, st);
 }
 
 template <int CP, int FC, bool HAS_COND, bool ACC>
@@ -1350,8 +1397,18 @@ void nca_set_cond_variant(int v) { g_cond_variant = v; }
 bool nca_cond_default_family() { return !g_force_generic && g_cond_variant == 0; }
 
 // ---- dispatch: smallest instantiation that covers (C, fc); padding lanes carry zero weights ---
-hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st) {
+hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma) {
     const bool hc = a.c_cond > 0;
+    if (bf16_mfma && nca_dynca_bf16_shape_ok(a.C, a.fc)) {   // ncahip_dynca_precision mode 1; shapes outside its range run exactly, below
+        const bool small = a.C <= 12 && a.fc <= 96;
+        if (a.pc) {
+            if ((a.H | a.W) & 1) return hipErrorInvalidValue;
+            if (small) return hc ? launch_dynca_ms<12, 96, true, true>(a, st) : launch_dynca_ms<12, 96, false, true>(a, st);
+            return hc ? launch_dynca_ms<16, 128, true, true>(a, st) : launch_dynca_ms<16, 128, false, true>(a, st);
+        }
+        if (small) return hc ? launch_dynca<12, 96, true, false, true>(a, st) : launch_dynca<12, 96, false, false, true>(a, st);
+        return hc ? launch_dynca<16, 128, true, false, true>(a, st) : launch_dynca<16, 128, false, false, true>(a, st);
+    }
     if (a.pc) {   // two-scale perception: the shipped video models (C = 12 / fc = 96 and C = 16 / fc = 128, pos_emb conditioning)
         if ((a.H | a.W) & 1) return hipErrorInvalidValue;
         if (a.C <= 12 && a.fc <= 96) return hc ? launch_dynca_ms<12, 96, true>(a, st) : launch_dynca_ms<12, 96, false>(a, st);

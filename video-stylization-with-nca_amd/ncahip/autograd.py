@@ -116,8 +116,9 @@ class _DyncaNSteps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cond, w1, b1, w2, b2, cfg):
         w = ops.DyncaWeights(w1, b1, w2, b2, x)
-        out, states = ops.dynca_nsteps(x, cfg["T"], cond, cfg["us"], w, cfg["pad"], cfg["rate"], cfg["seed"],
-                                       cfg["step0"], keep_history=True, two_scale=cfg.get("two_scale", False))
+        with ops.dynca_precision("f32"):      # the backward recomputes the hidden layer exactly: the history must be the exact one
+            out, states = ops.dynca_nsteps(x, cfg["T"], cond, cfg["us"], w, cfg["pad"], cfg["rate"], cfg["seed"],
+                                           cfg["step0"], keep_history=True, two_scale=cfg.get("two_scale", False))
         ctx.cfg, ctx.w = cfg, w
         ctx.save_for_backward(states, cond if cond is not None else x.new_empty(0))
         return out.clone(), states if cfg["want_states"] else None

@@ -1,7 +1,9 @@
 """Tensor-level wrappers over the C ABI: marshal torch CUDA tensors to raw pointers, enqueue on the
 current torch stream.  Every function here fails loudly for non-CUDA tensors -- the product path
 has no CPU fallback (the CPU restatement lives in oracle/ and is test infrastructure only)."""
+import contextlib
 import re
+import threading
 from typing import Optional, Sequence
 
 import numpy as np
@@ -94,6 +96,41 @@ def force_generic(on) -> None:
 def set_cond_precision(mode) -> None:
     """'exact' / 0 (default) or 'bf16x3' / 1: see ncahip_cond_precision in include/ncahip.h."""
     check(lib().ncahip_cond_precision({"exact": 0, "bf16x3": 1}.get(mode, mode)), "cond_precision")
+
+
+_DYNCA_PRECISIONS = ("f32", "bf16")         # ncahip_dynca_precision modes 0 / 1
+_dynca_precision_lock = threading.RLock()
+
+
+def set_dynca_precision(mode: str) -> str:
+    """'f32' (exact, the default) or 'bf16': both 1x1 products of the DyNCA FORWARD step on bf16 MFMA with fp32 accumulation, for
+    C <= 16 and fc <= 128 (dynca_bf16_ok; other shapes ignore the mode) -- ncahip_dynca_precision in include/ncahip.h.  Process-wide,
+    read when a call enqueues; needs no GPU.  Returns the previous mode.  Whatever keeps a history for autograd runs under 'f32'
+    regardless (the backward recomputes exactly)."""
+    if mode not in _DYNCA_PRECISIONS:
+        raise ValueError(f"dynca precision must be 'f32' or 'bf16', got {mode!r}")
+    with _dynca_precision_lock:
+        prev = lib().ncahip_dynca_precision(_DYNCA_PRECISIONS.index(mode))
+    if prev not in (0, 1):
+        check(prev, "dynca_precision")
+    return _DYNCA_PRECISIONS[prev]
+
+
+@contextlib.contextmanager
+def dynca_precision(mode: str):
+    """with ops.dynca_precision('bf16'): ...  -- set_dynca_precision(mode) for the block, the previous mode back on exit (exceptions
+    included).  The mode is process-wide: the block holds a re-entrant lock, so blocks of other threads wait for it."""
+    with _dynca_precision_lock:
+        prev = set_dynca_precision(mode)
+        try:
+            yield
+        finally:
+            set_dynca_precision(prev)
+
+
+def dynca_bf16_ok(C: int, fc: int) -> bool:
+    """Shapes the 'bf16' DyNCA precision covers: C <= 16 and fc <= 128 (one output tile, one hidden slice)."""
+    return 1 <= int(C) <= 16 and 1 <= int(fc) <= 128
 
 
 def check_errors(clear: bool = True) -> None:
@@ -266,7 +303,8 @@ def dynca_nsteps(x: torch.Tensor, T: int, cond: Optional[torch.Tensor], us: Opti
                  pad_mode: str = "replicate", update_rate: float = 0.5, seed: int = 0, step0: int = 0,
                  keep_history: bool = False, two_scale: bool = False):
     """T fused steps.  Returns (x_T, states) where states is the [ring,B,C,H,W] buffer (ring=T+1 when
-    keep_history, else 2).  two_scale: perception_scales = [0, 1] (ncahip_dynca_nsteps_fwd_ms_f32, fp32 states)."""
+    keep_history, else 2).  two_scale: perception_scales = [0, 1] (ncahip_dynca_nsteps_fwd_ms_f32, fp32 states).
+    fp32 states honour the ambient dynca_precision, keep_history included (autograd's forward sets 'f32' itself)."""
     dt, sfx = _state_dtype(x)           # bfloat16 state -> bf16-storage entry points (forward only)
     x = _dev(x, "x", dt)
     B, C, H, W = x.shape

@@ -11,6 +11,7 @@ drops it again after.
 Decoder-sized frames: reference_crop / resize_frames are the reference's host-side shrink (Pillow: centre crop, then an 8-bit
 Image.resize) on the device, bit for bit; stylize_clip(size=...) and stylize_clip_conditioned(size=...) apply it per chunk.
 """
+import contextlib
 from typing import Iterable, Iterator, Optional
 
 import torch
@@ -129,7 +130,8 @@ def _sized(frames: torch.Tensor, size):
 
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
-                 gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic"):
+                 gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic",
+                 precision: str = "f32"):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -152,8 +154,15 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     size=(H, W): decoder-sized frames.  frames must then be uint8 [F,h,w,3] (float frames: ValueError -- the reference resizes 8-bit
     images); every chunk is uploaded at its native size, shrunk on the device by resize_frames(chunk, size, crop, resample) -- the
     reference's preprocess_style_image (crop='dynca', bicubic), bit for bit -- and handed to the uint8 path above unchanged, on both
-    routes.  Seeding, the state and the images use (H, W).  size=None: crop and resample are not looked at."""
+    routes.  Seeding, the state and the images use (H, W).  size=None: crop and resample are not looked at.
+
+    precision: 'f32' (exact, the default) or 'bf16' -- the steps of this call run under ops.dynca_precision('bf16') (both 1x1 products
+    on bf16 MFMA, fp32 accumulation and state; include/ncahip.h, ncahip_dynca_precision), on both routes and for both model families;
+    the process-wide mode is afterwards what it was before.  'bf16' needs ops.dynca_bf16_ok(c_in, fc_dim), an fp32 state on the GPU and
+    a model whose steps run on the fused kernels: anything else raises ValueError rather than computing in the other arithmetic."""
     from . import ops
+    if precision not in ("f32", "bf16"):
+        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
     if gray not in ops.GRAY_WEIGHTS:
         raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
     if out_dtype not in (torch.float32, torch.uint8):
@@ -178,7 +187,22 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
     h = state if state is not None else nca_model.seed(1, size=(ww, hh))
     fused = (_clip_route_xc(nca_model, h) if extra else _clip_route(nca_model, h)) and torch.device(dev).type == "cuda"
+    if precision == "bf16":
+        fc = nca_model.w1.out_channels
+        if not ops.dynca_bf16_ok(nca_model.c_in, fc):
+            raise ValueError(f"precision='bf16' covers C <= 16 and fc <= 128 (ops.dynca_bf16_ok); the model has C = {nca_model.c_in}, fc = {fc}")
+        if not h.is_cuda or h.dtype != torch.float32:
+            raise ValueError(f"precision='bf16' needs a float32 state on the GPU (the state stays fp32), got {h.dtype} on {h.device}")
+        if nca_model._composed(h):
+            raise ValueError("precision='bf16' needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
     stylize_clip.last_path = "clip" if fused else "loop"
+    with ops.dynca_precision(precision) if precision == "bf16" else contextlib.nullcontext():
+        return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in)
+
+
+def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in):
+    """The two routes of stylize_clip (its arguments validated, the state seeded, the precision set)."""
+    from . import ops
     outs = []
     if fused:
         w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
