@@ -1,5 +1,5 @@
 """The ConditionedNCA step and its backward against float64 at the smallest shape of every class: the sibling of
-test_gpu_dynca_ref.py for the kernels bench.py's `value` runs on (csrc/nca_step_fwd.hip, nca_cond_pc.hip, nca_cond_bwd.hip,
+test_gpu_dynca_ref.py for the kernels bench.py's `value` runs on (csrc/nca_cond_generic.hip, nca_cond_pc.hip, nca_cond_bwd.hip,
 nca_cond_bwd_fm.hip, nca_cond_persist.hip).
 
 Method, that of test_gpu_cond_replay.py: the kernels record their own history (keep_history=True) and the float64 oracle is
@@ -48,7 +48,7 @@ ONE_WG = 1 << 8             # ncahip_debug_force_generic bits 8-15: one workgrou
 #   fwd   nca_launch_cond_step_fwd: W % 4 == 0 and C <= 20 -> nca_launch_cond_step_fwd_pc = launch_cond_pc<CP, EXACT, StF32, false, FC, CARRY>,
 #         EXACT iff C == CP and hidden == 64; default FC + CARRY at CP <= 16, FC without CARRY at CP = 20 and under force 64, dense under
 #         force 32; wave tile 4 x 16, super-tile 16 x 16, nwg = min(nst, CUs), nst = B ceil(W/16) ceil(H/16).  Force 2 (C <= 16): the wave
-#         kernel.  Force 1, W % 4 != 0 and every C > 20: launch_cond<12|16|20|24|32> (8 x 32 tiles), VEC iff W % 4 == 0.
+#         kernel.  Force 1, W % 4 != 0 and every C > 20: launch_cond<12|16|20|24|32> (csrc/nca_cond_generic.hip, 8 x 32 tiles), VEC iff W % 4 == 0.
 #   A     nca_launch_cond_step_bwd: C <= 16 -> launch_bwd<12|16, StF32>: front + matrix (launch_fm<CP, StF32, false>) iff 2 nst <= CUs, else
 #         one launch; C > 16 -> launch_fm<20|24|32> always.  The front kernel's last template flag is C == CP; msplit iff 2 nst <= CUs.
 #   B     cond_step_bwd_stencil_kernel<float, srows>, srows from stencil_srows: 4 on every small grid.

@@ -1,7 +1,7 @@
 """GPU tests of the opt-in bf16-MFMA DyNCA step (ops.dynca_precision('bf16'), ncahip_dynca_precision mode 1).
 
 Reference and caps: test_dynca_bf16_host.py (the float64 restatement of the contract, the first-order bound E, caps (a) and (b)).
-Kernels under test: the BF instantiations of dynca_step_fwd_kernel (vector and any-shape form, single- and two-scale) through
+Kernels under test: the DyncaFwdBf / DyncaFwdMsBf variants of dynca_step_fwd_kernel (csrc/nca_dynca_step.h; vector and any-shape form, single- and two-scale) through
 ops.dynca_nsteps(keep_history=True); dynca_persist_kernel / dynca_persist_ms_kernel through ops.dynca_nsteps with
 ops.persistent_steps; the clip drivers through ncahip.video.stylize_clip(precision='bf16').  Every test prints its figures (-s)."""
 import pytest

@@ -28,10 +28,12 @@ TN = 3
 MAX_CCOND = 4       # the largest c_cond check_dynca accepts (kMaxCond, csrc/nca_capi.hip)
 GRAD_KEYS = ("x0", "w1", "b1", "w2", "b2")
 
-# Tiles are TH x TW = 8 x 32 cells forward and backward (launch_dynca_v / launch_dynca_bwd, csrc/nca_step_fwd.hip), so H = 8 k + 2 and
-# W = 32 k + 2 (+ 4) leave remainder tiles.  What each row reaches, read off the four launchers:
-#   fwd   nca_launch_dynca_step_fwd: launch_dynca<CP, FC, HAS_COND[, ACC]>; VEC (16-byte loads) iff W % 4 == 0 and H W % 4 == 0
-#   mlp   nca_launch_dynca_step_bwd_mlp: launch_dynca_bwd<CP, FC, HAS_COND, ACC>, fused-dW2 form; VEC iff W % 4 == 0
+# Tiles are TH x TW = 8 x 32 cells forward and backward (launch_dynca, csrc/nca_dynca_step.h), so H = 8 k + 2 and
+# W = 32 k + 2 (+ 4) leave remainder tiles.  What each row reaches, read off the four launchers; the class <CP, FC> is the smallest of
+# <12,96>, <16,128>, <32,128> that covers (C, fc) (dispatch_dynca, csrc/nca_dynca_step.h), the rows write <CP, FC, HAS_COND[, ACC]>:
+#   fwd   nca_launch_dynca_step_fwd (csrc/nca_dynca_fwd.hip): variant DyncaFwd, ACC = DyncaFwdAcc (later slices, classes <16,128> and
+#         <32,128> only); VEC (16-byte loads) iff W % 4 == 0 and H W % 4 == 0
+#   mlp   nca_launch_dynca_step_bwd_mlp (csrc/nca_dynca_bwd.hip): variant DyncaBwdW2 (fused dW2), ACC = DyncaBwdW2Acc; VEC iff W % 4 == 0
 #   gram  nca_launch_gram_rows(ma = slice width, nb = 4 C + c_cond): launch_gram<RT, CT, ROWSPLIT>; ones column only at CT = 9
 #   adj   nca_launch_dynca_step_bwd_stencil: dynca_step_bwd_stencil_vec_kernel iff W % 4 == 0, W >= 12, H >= 5, else the generic kernel
 #        id              C   fc  c_cond      B  H   W

@@ -31,8 +31,8 @@ SCALES = (0, 1)
 TN = 3
 MAX_CCOND = 4       # the largest c_cond check_dynca accepts (kMaxCond, csrc/nca_capi.hip)
 
-# The two-scale launchers (launch_dynca_ms / launch_dynca_bwd_ms, csrc/nca_step_fwd.hip) use TH x TW = 8 x 32 cell tiles, forward
-# and backward, so H = 8 k + 2 / W = 32 k + 2 leave a remainder tile two cells tall / wide.
+# The two-scale variants (DyncaFwdMs / DyncaFwdMsBf / DyncaBwdW2Ms through launch_dynca, csrc/nca_dynca_step.h) use TH x TW = 8 x 32 cell
+# tiles, forward and backward, so H = 8 k + 2 / W = 32 k + 2 leave a remainder tile two cells tall / wide.
 #        id            C   fc  c_cond      B  H   W
 CASES = {"c1x1":      (12, 96, 2,          2, 2, 2),     # coarse grid 1 x 1: every up-sampling and coarse stencil tap lands on one cell
          "c2x2":      (12, 96, 0,          1, 4, 4),     # smallest shape reflect admits; no conditioning on the backward
@@ -439,3 +439,26 @@ def test_reflect_needs_a_2x2_coarse_grid(ops, H, W):
     assert not m._two_scale_fused(x0) and m._composed(x0)
     with pytest.raises((RuntimeError, _capi.NcaHipError)):
         m.forward_nsteps(x0, 1)
+
+
+# ================================================================================================ refused calls enqueue nothing
+def test_refused_single_step_enqueues_nothing(ops):
+    """ncahip_dynca_step_fwd_ms_f32 with bit-packed masks and update_rate = 1.0 is refused by the bit-mask check (NCAHIP_ERANGE:
+    floor(u + rate) must be 0 or 1).  Every host check runs before the first launch, so neither the coarse-perception scratch nor
+    x_out is touched: both still hold their canary after a synchronise."""
+    from ncahip import _capi
+    B, C, H, W, fc = 1, 4, 4, 4, 16
+    prm = rand_dynca_prm(C, fc, 0, seed=3)
+    x = torch.rand(B, C, H, W, device=DEV) - 0.5
+    w = _dyn_w(ops, prm, x)
+    bits = torch.full(((B * H * W + 31) // 32,), 0x5A5A, dtype=torch.int32, device=DEV)
+    canary = -1234.5
+    out = torch.full_like(x, canary)
+    pc = torch.full((B, 4 * C, H // 2, W // 2), canary, device=DEV)
+    rc = ops.lib().ncahip_dynca_step_fwd_ms_f32(ops._p(x), ops._p(out), None, ops._p(bits), ops._p(w.w1), ops._p(w.b1), ops._p(w.w2),
+                                                ops._p(w.b2), B, C, H, W, fc, 0, ops.PAD_MODES["replicate"], 1.0, _capi.SEED_U_IS_BITS, 0,
+                                                ops._p(pc), ops._stream())
+    torch.cuda.synchronize()
+    assert rc == _capi.ERANGE, (rc, _capi.lib().ncahip_last_error())
+    assert bool((pc == canary).all()), "the coarse pass ran before the call was refused"
+    assert bool((out == canary).all())

@@ -83,6 +83,14 @@ int check_cond(const void* x_in, const void* x_out, const void* pre_out, const v
     return 0;
 }
 
+int check_ms(int C, int H, int W, int fc, int pad_mode, const void* pc) {
+    if (!pc) return fail(NCAHIP_EINVAL, "dynca two-scale step: pc_scratch required");
+    if (int rc = check_ms_reflect(H, W, pad_mode)) return rc;
+    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)");
+    if (C > kMaxC || fc > kMaxFc) return fail(NCAHIP_ERANGE, "dynca two-scale step: C=%d fc=%d exceeds (%d,%d)", C, fc, kMaxC, kMaxFc);
+    return 0;
+}
+
 }  // namespace
 
 // ---- sticky device error word: one host-mapped word per device, written by kernels (system-scope atomic OR), read by the host
@@ -223,35 +231,84 @@ int ncahip_cond_perceive_f32(const float* z, const float* wp, float* y, int B, i
     return hip_result(nca_launch_cond_perceive(z, wp, y, B, C, H, W, (hipStream_t)stream), "cond_perceive");
 }
 
+// ---- the DyNCA forward: one body for single step / T steps x fp32 / two-scale fp32 / bf16 storage ------------------------------
+// fp32: C <= 32, fc in 128-wide slices.  Two-scale (perception_scales = [0, 1]): a coarse pass into pc_scratch, then the fused step
+// with on-the-fly bilinear up-sampling.  bf16: storage format only (same kernel, exact f32 compute, RNE on store).
+enum DyncaFwdKind { kDyncaFwdF32, kDyncaFwdMs, kDyncaFwdBf16 };
+// single: the one step x_in -> x_out.  Otherwise x_in is a ring of `ring` state slots and step t goes from slot t % ring to slot
+// (t + 1) % ring.  Nothing is enqueued before all checks have passed.
+static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, const void* x_in, void* x_out, int ring, int T, const float* cond, const float* u,
+                          const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
+                          int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, ncahip_stream_t stream) {
+    const bool ms = kind == kDyncaFwdMs, bf16 = kind == kDyncaFwdBf16;
+    char* const states = (char*)const_cast<void*>(x_in);
+    if (!single && (ring < 2 || T < 0)) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
+    if (int rc = check_dynca(x_in, single ? x_out : states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                             kind == kDyncaFwdF32 ? kMaxFcFwd : kMaxFc))
+        return rc;
+    if (ms) {
+        if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
+    }
+    const bool ubits = u_is_bits(u, seed);
+    if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t slot = (size_t)B * C * H * W * (bf16 ? sizeof(uint16_t) : sizeof(float)), uslot = (size_t)B * H * W;
+    const bool bf = !bf16 && dynca_bf16_mfma(C, fc);   // one read per call: every step of it runs the same arithmetic
+    for (int t = 0; t < T; ++t) {
+        const float* const xi = reinterpret_cast<const float*>(single ? x_in : states + (size_t)(t % ring) * slot);
+        float* const xo = reinterpret_cast<float*>(single ? x_out : states + (size_t)((t + 1) % ring) * slot);
+        if (ms) {
+            if (int rc = hip_result(nca_launch_dynca_coarse_perceive(xi, pc_scratch, B, C, H, W, pad_mode, st), "dynca coarse perceive")) return rc;
+        }
+        NcaDyncaArgs a{xi, xo, cond, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t};
+        a.pc = ms ? pc_scratch : nullptr;
+        a.u_bits = ubits;
+        if (int rc = hip_result(bf16 ? nca_launch_dynca_step_fwd_bf16(a, st) : nca_launch_dynca_step_fwd(a, st, bf), what)) return rc;
+    }
+    return 0;
+}
+
 int ncahip_dynca_step_fwd_f32(const float* x_in, float* x_out, const float* cond, const float* u, const float* w1,
                               const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
                               int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step,
                               ncahip_stream_t stream) {
-    if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, kMaxFcFwd)) return rc;
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
-    NcaDyncaArgs a{x_in, x_out, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step};
-    a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream, dynca_bf16_mfma(C, fc)), "dynca_step_fwd");
+    return dynca_fwd_impl(kDyncaFwdF32, "dynca_step_fwd", true, x_in, x_out, 0, 1, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate,
+                          seed, step, nullptr, stream);
 }
-
 int ncahip_dynca_nsteps_fwd_f32(float* states, int ring, int T, const float* cond, const float* u, const float* w1,
                                 const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
                                 int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step0,
                                 ncahip_stream_t stream) {
-    if (ring < 2 || T < 0) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
-    if (int rc = check_dynca(states, states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, kMaxFcFwd)) return rc;
-    const bool ubits = u_is_bits(u, seed);
-    if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
-    const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W;
-    const bool bf = dynca_bf16_mfma(C, fc);   // one read per call: every step of it runs the same arithmetic
-    for (int t = 0; t < T; ++t) {
-        NcaDyncaArgs a{states + (size_t)(t % ring) * slot, states + (size_t)((t + 1) % ring) * slot, cond,
-                       u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
-                       update_rate, seed, step0 + (uint64_t)t};
-        a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, (hipStream_t)stream, bf), "dynca_nsteps_fwd")) return rc;
-    }
-    return 0;
+    return dynca_fwd_impl(kDyncaFwdF32, "dynca_nsteps_fwd", false, states, nullptr, ring, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                          update_rate, seed, step0, nullptr, stream);
+}
+int ncahip_dynca_step_fwd_ms_f32(const float* x_in, float* x_out, const float* cond, const float* u, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
+                                 int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step, float* pc_scratch,
+                                 ncahip_stream_t stream) {
+    return dynca_fwd_impl(kDyncaFwdMs, "dynca_step_fwd_ms", true, x_in, x_out, 0, 1, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate,
+                          seed, step, pc_scratch, stream);
+}
+int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* cond, const float* u, const float* w1,
+                                   const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
+                                   int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch,
+                                   ncahip_stream_t stream) {
+    return dynca_fwd_impl(kDyncaFwdMs, "dynca_nsteps_fwd_ms", false, states, nullptr, ring, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                          update_rate, seed, step0, pc_scratch, stream);
+}
+int ncahip_dynca_step_fwd_bf16(const uint16_t* x_in, uint16_t* x_out, const float* cond, const float* u, const float* w1,
+                               const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
+                               int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step,
+                               ncahip_stream_t stream) {
+    return dynca_fwd_impl(kDyncaFwdBf16, "dynca_step_fwd_bf16", true, x_in, x_out, 0, 1, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate,
+                          seed, step, nullptr, stream);
+}
+int ncahip_dynca_nsteps_fwd_bf16(uint16_t* states, int ring, int T, const float* cond, const float* u, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
+                                 int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step0,
+                                 ncahip_stream_t stream) {
+    return dynca_fwd_impl(kDyncaFwdBf16, "dynca_nsteps_fwd_bf16", false, states, nullptr, ring, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond,
+                          pad_mode, update_rate, seed, step0, nullptr, stream);
 }
 
 // ---- T steps in ONE launch for small grids (B = 1 video inference), nca_dynca_persist.hip -------------------------------------
@@ -368,54 +425,6 @@ int ncahip_edge_extractor_f32(const float* img, const float* k3, float* out, int
     if (!img || !k3 || !out || img == out) return fail(NCAHIP_EINVAL, "edge_extractor: null or aliased pointer");
     if (!dims_ok(B, 1, H, W)) return fail(NCAHIP_EINVAL, "edge_extractor: bad size");
     return hip_result(nca_launch_edge_extractor(img, k3, out, B, H, W, apply_tanh != 0, (hipStream_t)stream), "edge_extractor");
-}
-
-// ---- two-scale perception (perception_scales = [0, 1]): coarse pass + fused step with on-the-fly bilinear up-sampling --------
-static int check_ms(int C, int H, int W, int fc, int pad_mode, const void* pc) {
-    if (!pc) return fail(NCAHIP_EINVAL, "dynca two-scale step: pc_scratch required");
-    if (int rc = check_ms_reflect(H, W, pad_mode)) return rc;
-    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)");
-    if (C > kMaxC || fc > kMaxFc) return fail(NCAHIP_ERANGE, "dynca two-scale step: C=%d fc=%d exceeds (%d,%d)", C, fc, kMaxC, kMaxFc);
-    return 0;
-}
-
-int ncahip_dynca_step_fwd_ms_f32(const float* x_in, float* x_out, const float* cond, const float* u, const float* w1,
-                                 const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
-                                 int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step, float* pc_scratch,
-                                 ncahip_stream_t stream) {
-    if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = hip_result(nca_launch_dynca_coarse_perceive(x_in, pc_scratch, B, C, H, W, pad_mode, st), "dynca coarse perceive")) return rc;
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
-    NcaDyncaArgs a{x_in, x_out, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step};
-    a.pc = pc_scratch;
-    a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_fwd(a, st, dynca_bf16_mfma(C, fc)), "dynca_step_fwd_ms");
-}
-
-int ncahip_dynca_nsteps_fwd_ms_f32(float* states, int ring, int T, const float* cond, const float* u, const float* w1,
-                                   const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
-                                   int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch,
-                                   ncahip_stream_t stream) {
-    if (ring < 2 || T < 0) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
-    if (int rc = check_dynca(states, states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const bool ubits = u_is_bits(u, seed);
-    if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
-    const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W;
-    const bool bf = dynca_bf16_mfma(C, fc);
-    for (int t = 0; t < T; ++t) {
-        const float* const xi = states + (size_t)(t % ring) * slot;
-        if (int rc = hip_result(nca_launch_dynca_coarse_perceive(xi, pc_scratch, B, C, H, W, pad_mode, st), "dynca coarse perceive")) return rc;
-        NcaDyncaArgs a{xi, states + (size_t)((t + 1) % ring) * slot, cond, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H,
-                       W, fc, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t};
-        a.pc = pc_scratch;
-        a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_dynca_step_fwd(a, st, bf), "dynca_nsteps_fwd_ms")) return rc;
-    }
-    return 0;
 }
 
 // ---- a whole clip per call (video_utils.py:50-83): conditioning of every frame, the existing step entry points, image output ----
@@ -603,31 +612,7 @@ int ncahip_dynca_clip_xc_f32(float* states, const float* gray, const float* cond
                            H, W, fc, pad_mode, two_scale, update_rate, seed, step0, pc_scratch, persist_ws, persist_bytes, epoch0, stream);
 }
 
-int ncahip_cond_step_fwd_f32(const float* x_in, const uint8_t* pre_in, float* x_out, uint8_t* pre_out,
-                             const float* goal, int goal_ch, const float* u, const float* wp, const float* w1,
-                             const float* b1, const float* w2, const float* b2, const float* w3, int B, int C, int H,
-                             int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
-                             float clamp_hi, uint64_t seed, uint64_t step, ncahip_stream_t stream) {
-    if (int rc = check_cond(x_in, x_out, pre_out, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwd))
-        return rc;
-    if (pre_in && pre_in == pre_out) return fail(NCAHIP_EINVAL, "cond step: pre_in and pre_out must not alias");
-    NcaCondArgs a{x_in, pre_in, x_out, pre_out, goal, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch,
-                  alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step};
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, fire_rate, false)) return rc;
-    a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_cond_step_fwd(a, (hipStream_t)stream), "cond_step_fwd");
-}
-
-int ncahip_cond_finalize_f32(const float* x_pend, const uint8_t* pre, float* x_out, int B, int C, int H, int W,
-                             int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
-    if (!x_pend || !x_out || (alive_ch >= 0 && !pre)) return fail(NCAHIP_EINVAL, "cond_finalize: null pointer");
-    if (!dims_ok(B, C, H, W) || alive_ch >= C) return fail(NCAHIP_EINVAL, "cond_finalize: bad size");
-    if (alive_ch >= 0 && x_pend == x_out) return fail(NCAHIP_EINVAL, "cond_finalize: in-place needs alive_ch < 0");
-    return hip_result(nca_launch_cond_finalize(x_pend, pre, x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi,
-                                               (hipStream_t)stream), "cond_finalize");
-}
-
-// ---- bf16 state storage (nca_cond_bf16.hip) ---------------------------------------------------------------
+// ---- the ConditionedNCA forward: shared bodies for fp32 and bf16 state storage (nca_cond_bf16.hip: bf16 state and goal, bf16 MFMA) ----
 static int check_bf16_shape(const void* x_in, const void* x_out, const void* goal, int H, int W) {
     if (W % 4 != 0 || (((uintptr_t)x_in | (uintptr_t)x_out | (uintptr_t)goal) & 7) != 0)
         return fail(NCAHIP_ERANGE, "bf16 cond step: needs W %% 4 == 0 and 8-byte aligned state / goal tensors");
@@ -635,46 +620,55 @@ static int check_bf16_shape(const void* x_in, const void* x_out, const void* goa
     return 0;
 }
 
-int ncahip_cond_step_fwd_bf16(const uint16_t* x_in, const uint8_t* pre_in, uint16_t* x_out, uint8_t* pre_out,
-                              const uint16_t* goal, int goal_ch, const float* u, const float* wp, const float* w1,
-                              const float* b1, const float* w2, const float* b2, const float* w3, int B, int C, int H,
-                              int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+static int cond_step_fwd_impl(bool bf16, const void* x_in, const uint8_t* pre_in, void* x_out, uint8_t* pre_out, const void* goal, int goal_ch,
+                              const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                              int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
                               float clamp_hi, uint64_t seed, uint64_t step, ncahip_stream_t stream) {
-    if (int rc = check_cond(x_in, x_out, pre_out, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwdBf16))
+    if (int rc = check_cond(x_in, x_out, pre_out, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch,
+                            bf16 ? kMaxCCondFwdBf16 : kMaxCCondFwd))
         return rc;
-    if (int rc = check_bf16_shape(x_in, x_out, goal, H, W)) return rc;
+    if (bf16) {
+        if (int rc = check_bf16_shape(x_in, x_out, goal, H, W)) return rc;
+    }
     if (pre_in && pre_in == pre_out) return fail(NCAHIP_EINVAL, "cond step: pre_in and pre_out must not alias");
     NcaCondArgs a{reinterpret_cast<const float*>(x_in), pre_in, reinterpret_cast<float*>(x_out), pre_out,
                   reinterpret_cast<const float*>(goal), u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch,
                   alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step};
     if (int rc = check_bits(u_is_bits(u, seed), B, H, W, fire_rate, false)) return rc;
     a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_cond_step_fwd_bf16(a, (hipStream_t)stream), "cond_step_fwd_bf16");
+    return bf16 ? hip_result(nca_launch_cond_step_fwd_bf16(a, (hipStream_t)stream), "cond_step_fwd_bf16")
+                : hip_result(nca_launch_cond_step_fwd(a, (hipStream_t)stream), "cond_step_fwd");
 }
 
-int ncahip_cond_finalize_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, int B, int C, int H, int W,
-                              int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
+static int cond_finalize_impl(bool bf16, const void* x_pend, const uint8_t* pre, void* x_out, int B, int C, int H, int W, int alive_ch,
+                              float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
     if (!x_pend || !x_out || (alive_ch >= 0 && !pre)) return fail(NCAHIP_EINVAL, "cond_finalize: null pointer");
     if (!dims_ok(B, C, H, W) || alive_ch >= C) return fail(NCAHIP_EINVAL, "cond_finalize: bad size");
     if (alive_ch >= 0 && x_pend == x_out) return fail(NCAHIP_EINVAL, "cond_finalize: in-place needs alive_ch < 0");
-    return hip_result(nca_launch_cond_finalize_bf16(x_pend, pre, x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo,
-                                                    clamp_hi, (hipStream_t)stream), "cond_finalize_bf16");
+    hipStream_t st = (hipStream_t)stream;
+    return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)x_pend, pre, (uint16_t*)x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo,
+                                                           clamp_hi, st), "cond_finalize_bf16")
+                : hip_result(nca_launch_cond_finalize((const float*)x_pend, pre, (float*)x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, st),
+                             "cond_finalize");
 }
 
-int ncahip_cond_grow_fwd_bf16(uint16_t* states, uint8_t* pre, int ring, int T, uint16_t* x_final, const uint16_t* goal,
-                              int goal_ch, const float* u, const float* wp, const float* w1, const float* b1,
-                              const float* w2, const float* b2, const float* w3, int B, int C, int H, int W, int hidden,
-                              int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
+static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring, int T, void* x_final, const void* goal, int goal_ch, const float* u,
+                              const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, int B, int C,
+                              int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
                               uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
+    char* const states = (char*)states_v;
     if (ring < 2 || T < 1 || !pre || !x_final) return fail(NCAHIP_EINVAL, "cond grow: ring >= 2, T >= 1, buffers required");
-    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwdBf16))
+    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch,
+                            bf16 ? kMaxCCondFwdBf16 : kMaxCCondFwd))
         return rc;
-    if (int rc = check_bf16_shape(states, states, goal, H, W)) return rc;
-    if (int rc = device_error_rc("cond grow (bf16)")) return rc;
+    if (bf16) {
+        if (int rc = check_bf16_shape(states, states, goal, H, W)) return rc;
+    }
+    if (int rc = device_error_rc(bf16 ? "cond grow (bf16)" : "cond grow")) return rc;
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
-    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W;
-    if ((slot * sizeof(uint16_t)) % 8 != 0) return fail(NCAHIP_ERANGE, "bf16 cond grow: state slots must stay 8-byte aligned");
+    const size_t slot = (size_t)B * C * H * W * (bf16 ? sizeof(uint16_t) : sizeof(float)), pslot = (size_t)B * H * W;   // slot: bytes
+    if (bf16 && slot % 8 != 0) return fail(NCAHIP_ERANGE, "bf16 cond grow: state slots must stay 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int sl = T % ring;
     if (x_final == states + (size_t)sl * slot && alive_ch >= 0)
@@ -686,10 +680,55 @@ int ncahip_cond_grow_fwd_bf16(uint16_t* states, uint8_t* pre, int ring, int T, u
                       reinterpret_cast<const float*>(goal), u_at(u, ubits, t, pslot), wp, w1, b1, w2, b2, w3, B, C, H,
                       W, hidden, goal_ch, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0 + (uint64_t)t};
         a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_cond_step_fwd_bf16(a, st), "cond_grow_fwd_bf16")) return rc;
+        if (int rc = bf16 ? hip_result(nca_launch_cond_step_fwd_bf16(a, st), "cond_grow_fwd_bf16") : hip_result(nca_launch_cond_step_fwd(a, st), "cond_grow_fwd"))
+            return rc;
     }
-    return hip_result(nca_launch_cond_finalize_bf16(states + (size_t)sl * slot, pre + (size_t)sl * pslot, x_final, B, C, H, W,
-                                                    alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)");
+    const uint8_t* const pre_last = pre + (size_t)sl * pslot;
+    return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, B, C, H, W, alive_ch,
+                                                           alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)")
+                : hip_result(nca_launch_cond_finalize((const float*)(states + (size_t)sl * slot), pre_last, (float*)x_final, B, C, H, W, alive_ch, alive_thr,
+                                                      clamp_lo, clamp_hi, st), "cond_grow finalize");
+}
+
+int ncahip_cond_step_fwd_f32(const float* x_in, const uint8_t* pre_in, float* x_out, uint8_t* pre_out,
+                             const float* goal, int goal_ch, const float* u, const float* wp, const float* w1,
+                             const float* b1, const float* w2, const float* b2, const float* w3, int B, int C, int H,
+                             int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                             float clamp_hi, uint64_t seed, uint64_t step, ncahip_stream_t stream) {
+    return cond_step_fwd_impl(false, x_in, pre_in, x_out, pre_out, goal, goal_ch, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr,
+                              fire_rate, clamp_lo, clamp_hi, seed, step, stream);
+}
+int ncahip_cond_step_fwd_bf16(const uint16_t* x_in, const uint8_t* pre_in, uint16_t* x_out, uint8_t* pre_out,
+                              const uint16_t* goal, int goal_ch, const float* u, const float* wp, const float* w1,
+                              const float* b1, const float* w2, const float* b2, const float* w3, int B, int C, int H,
+                              int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                              float clamp_hi, uint64_t seed, uint64_t step, ncahip_stream_t stream) {
+    return cond_step_fwd_impl(true, x_in, pre_in, x_out, pre_out, goal, goal_ch, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr,
+                              fire_rate, clamp_lo, clamp_hi, seed, step, stream);
+}
+int ncahip_cond_finalize_f32(const float* x_pend, const uint8_t* pre, float* x_out, int B, int C, int H, int W,
+                             int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
+    return cond_finalize_impl(false, x_pend, pre, x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, stream);
+}
+int ncahip_cond_finalize_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, int B, int C, int H, int W,
+                              int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
+    return cond_finalize_impl(true, x_pend, pre, x_out, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, stream);
+}
+int ncahip_cond_grow_fwd_f32(float* states, uint8_t* pre, int ring, int T, float* x_final, const float* goal,
+                             int goal_ch, const float* u, const float* wp, const float* w1, const float* b1,
+                             const float* w2, const float* b2, const float* w3, int B, int C, int H, int W, int hidden,
+                             int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
+                             uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
+    return cond_grow_fwd_impl(false, states, pre, ring, T, x_final, goal, goal_ch, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr,
+                              fire_rate, clamp_lo, clamp_hi, seed, step0, stream);
+}
+int ncahip_cond_grow_fwd_bf16(uint16_t* states, uint8_t* pre, int ring, int T, uint16_t* x_final, const uint16_t* goal,
+                              int goal_ch, const float* u, const float* wp, const float* w1, const float* b1,
+                              const float* w2, const float* b2, const float* w3, int B, int C, int H, int W, int hidden,
+                              int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
+                              uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
+    return cond_grow_fwd_impl(true, states, pre, ring, T, x_final, goal, goal_ch, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr,
+                              fire_rate, clamp_lo, clamp_hi, seed, step0, stream);
 }
 
 int ncahip_cond_alive_u8(const float* x, uint8_t* out, int B, int C, int H, int W, int alive_ch, float alive_thr,
@@ -697,35 +736,6 @@ int ncahip_cond_alive_u8(const float* x, uint8_t* out, int B, int C, int H, int 
     if (!x || !out) return fail(NCAHIP_EINVAL, "cond_alive: null pointer");
     if (!dims_ok(B, C, H, W) || alive_ch >= C) return fail(NCAHIP_EINVAL, "cond_alive: bad size");
     return hip_result(nca_launch_cond_alive(x, out, B, C, H, W, alive_ch, alive_thr, (hipStream_t)stream), "cond_alive");
-}
-
-int ncahip_cond_grow_fwd_f32(float* states, uint8_t* pre, int ring, int T, float* x_final, const float* goal,
-                             int goal_ch, const float* u, const float* wp, const float* w1, const float* b1,
-                             const float* w2, const float* b2, const float* w3, int B, int C, int H, int W, int hidden,
-                             int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
-                             uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
-    if (ring < 2 || T < 1 || !pre || !x_final) return fail(NCAHIP_EINVAL, "cond grow: ring >= 2, T >= 1, buffers required");
-    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwd))
-        return rc;
-    if (int rc = device_error_rc("cond grow")) return rc;
-    const bool ubits = u_is_bits(u, seed);
-    if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
-    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W;
-    hipStream_t st = (hipStream_t)stream;
-    const int sl = T % ring;
-    if (x_final == states + (size_t)sl * slot && alive_ch >= 0)
-        return fail(NCAHIP_EINVAL, "cond grow: x_final must not alias the last state slot");
-    for (int t = 0; t < T; ++t) {
-        const int si = t % ring, so = (t + 1) % ring;
-        NcaCondArgs a{states + (size_t)si * slot, t == 0 ? nullptr : pre + (size_t)si * pslot,
-                      states + (size_t)so * slot, pre + (size_t)so * pslot, goal,
-                      u_at(u, ubits, t, pslot), wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch,
-                      alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0 + (uint64_t)t};
-        a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_cond_step_fwd(a, st), "cond_grow_fwd")) return rc;
-    }
-    return hip_result(nca_launch_cond_finalize(states + (size_t)sl * slot, pre + (size_t)sl * pslot, x_final, B, C, H, W,
-                                               alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize");
 }
 
 // ---- a whole clip per call, ConditionedNCA (EncoderConditioning/visualisation.ipynb: the goal switched while the state runs) ----------
@@ -890,39 +900,6 @@ int ncahip_clip_resize_u8(const uint8_t* src, int N, int H, int W, int x0, int y
         return fail(NCAHIP_EINVAL, "clip_resize: frames, output and workspace must not overlap");
     return hip_result(nca_launch_clip_resize(src, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h, out_w,
                                              (unsigned char*)workspace, (hipStream_t)stream), "clip_resize");
-}
-
-// ---- bf16 state storage for the DyNCA step (same kernel, exact f32 compute, RNE on store) ----------------------
-int ncahip_dynca_step_fwd_bf16(const uint16_t* x_in, uint16_t* x_out, const float* cond, const float* u, const float* w1,
-                               const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
-                               int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step,
-                               ncahip_stream_t stream) {
-    if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    NcaDyncaArgs a{reinterpret_cast<const float*>(x_in), reinterpret_cast<float*>(x_out), cond, u, w1, b1, w2, b2, B, C, H, W,
-                   fc, c_cond, pad_mode, update_rate, seed, step};
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
-    a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_fwd_bf16(a, (hipStream_t)stream), "dynca_step_fwd_bf16");
-}
-
-int ncahip_dynca_nsteps_fwd_bf16(uint16_t* states, int ring, int T, const float* cond, const float* u, const float* w1,
-                                 const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc,
-                                 int c_cond, int pad_mode, float update_rate, uint64_t seed, uint64_t step0,
-                                 ncahip_stream_t stream) {
-    if (ring < 2 || T < 0) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
-    if (int rc = check_dynca(states, states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    const bool ubits = u_is_bits(u, seed);
-    if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
-    const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W;
-    for (int t = 0; t < T; ++t) {
-        NcaDyncaArgs a{reinterpret_cast<const float*>(states + (size_t)(t % ring) * slot),
-                       reinterpret_cast<float*>(states + (size_t)((t + 1) % ring) * slot), cond,
-                       u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
-                       update_rate, seed, step0 + (uint64_t)t};
-        a.u_bits = ubits;
-        if (int rc = hip_result(nca_launch_dynca_step_fwd_bf16(a, (hipStream_t)stream), "dynca_nsteps_fwd_bf16")) return rc;
-    }
-    return 0;
 }
 
 int ncahip_dynca_step_bwd_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,

@@ -490,7 +490,7 @@ void nca_set_cond_pc_dense(bool on) { g_pc_dense = on; }
 void nca_set_cond_pc_nocarry(bool on) { g_pc_nocarry = on; }
 void nca_set_cond_pc_wg_cap(int n) { g_pc_wg_cap = n > 0 ? n : 0; }
 
-// W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_step_fwd.hip dispatch) guarantees it.
+// W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_cond_generic.hip dispatch) guarantees it.
 extern "C" void nca_debug_set_stamp_buffer_pc(void* p);
 static unsigned long long* g_stamp_pc = nullptr;
 extern "C" void nca_debug_set_stamp_buffer_pc(void* p) { g_stamp_pc = (unsigned long long*)p; }

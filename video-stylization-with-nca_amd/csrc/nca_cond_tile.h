@@ -261,7 +261,7 @@ struct TileRegs {
 // EXACT: the launch guarantees a.C == CP (no channel-padding guards).
 // Addressing: raw buffer loads -- <buffer resource of the batch item (SGPRs)> + <32-bit VGPR byte offset shared by a
 // whole group of loads> + <uniform SGPR offset that steps through channels / rows>: no per-load vector arithmetic at all
-// on interior tiles.  Needs H*W < 2^24 and C*H*W*4 < 2^32 (checked by the dispatch in nca_step_fwd.hip; larger grids
+// on interior tiles.  Needs H*W < 2^24 and C*H*W*4 < 2^32 (checked by the dispatch in nca_cond_generic.hip; larger grids
 // take the generic kernel).  kAuxCoherent selects the cache policy of the state-type loads (x, pre mask): 0 = ordinary
 // cached loads (a step launch reads only what earlier launches wrote); 16 = sc1, agent-scope coherent -- what a fused
 // multi-step launch with grid barriers needs (tried and measured slower: DESIGN.md section 4).

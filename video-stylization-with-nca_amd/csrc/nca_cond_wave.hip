@@ -1,6 +1,6 @@
 // nca_cond_wave.hip -- ConditionedNCA fused step, wave-private tiles (gfx950, fp32 exact).
 //
-// Same math and MFMA mapping as nca_step_fwd.hip (see its header), different work decomposition:
+// Same math and MFMA mapping as the generic kernel (nca_cond_generic.hip; header of nca_dynca_step.h), different work decomposition:
 // every WAVE owns a 4 x 16 cell tile and a private LDS region (state tile +1 halo, resolved-state
 // copy for the residual, alpha/life/pre masks); the 8 waves of a workgroup share only the
 // A-operand weight image.  There is no workgroup barrier inside the tile loop -- LDS hand-offs are
@@ -10,7 +10,7 @@
 // halo lies inside the image (85 % at 256^2) skip every bounds check.
 //
 // Requires W % 4 == 0 and 16-byte aligned tensors (16-byte row loads); other shapes take the
-// generic kernel in nca_step_fwd.hip.
+// generic kernel in nca_cond_generic.hip.
 #include "nca_cond_tile.h"
 
 namespace {
@@ -134,7 +134,7 @@ static unsigned long long* g_stamp_buffer = nullptr;
 void nca_debug_set_stamp_buffer(unsigned long long* p) { g_stamp_buffer = p; }
 extern "C" void nca_debug_set_stamp_buffer_c(void* p) { g_stamp_buffer = (unsigned long long*)p; }
 
-// W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_step_fwd.hip dispatch) guarantees it.
+// W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_cond_generic.hip dispatch) guarantees it.
 hipError_t nca_launch_cond_step_fwd_wave(const NcaCondArgs& a_in, hipStream_t st) {
     NcaCondArgs a = a_in;
     a.dbg = g_stamp_buffer;

@@ -1,5 +1,5 @@
 // nca_dynca_bf16.h -- the bf16-MFMA UpdateNet of the DyNCA forward step (ncahip_dynca_precision mode 1; contract: include/ncahip.h).
-// What fixes the bits of that mode exists ONCE, here, and is shared by the per-step kernel (nca_step_fwd.hip) and the two persistent
+// What fixes the bits of that mode exists ONCE, here, and is shared by the per-step kernel (nca_dynca_step.h) and the two persistent
 // kernels (nca_dynca_persist.hip): the k order of both products (folded into the LDS weight images), the operand roundings and the
 // MFMA sequence per accumulator.  C <= 16 (one 16-row output tile), fc a multiple of 32 after padding.
 //

@@ -21,7 +21,7 @@
 //     an abort word in device memory; every workgroup leaves its step loop at its next step -- the launch always drains, the host
 //     sees NCAHIP_EDEVICE.
 // The host side launches this only when every workgroup can be co-resident (occupancy x CUs >= tiles), H % 16 == 0, W % 16 == 0,
-// C <= 16, fc <= 128; anything else runs the per-step kernels (nca_step_fwd.hip).  Same arithmetic per cell in the same order as the
+// C <= 16, fc <= 128; anything else runs the per-step kernels (nca_dynca_step.h).  Same arithmetic per cell in the same order as the
 // per-step kernel (perception from the LDS tile, exact-f32 MFMA chains with the same k order): bit-identical results.
 //
 // Two kernels live here: dynca_persist_kernel (single-scale) and dynca_persist_ms_kernel (two-scale).  What carries the bit-identity

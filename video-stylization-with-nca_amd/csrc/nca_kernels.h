@@ -248,7 +248,7 @@ hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W,
 int nca_resize_ksize(int in, int out, int filter);
 int nca_resize_build_tables(int in, int out, int filter, int32_t* k, int32_t* bounds, int ksize);
 
-// fused steps (nca_step_fwd.hip); hipErrorInvalidValue when no instantiation covers the shape
+// fused steps (nca_dynca_fwd.hip, nca_dynca_bwd.hip, nca_cond_generic.hip); hipErrorInvalidValue when no instantiation covers the shape
 // bf16_mfma: ncahip_dynca_precision mode 1 (both 1x1 products on bf16 MFMA, nca_dynca_bf16.h) where nca_dynca_bf16_shape_ok
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma = false);
 inline bool nca_dynca_bf16_shape_ok(int C, int fc) { return C >= 1 && C <= 16 && fc >= 1 && fc <= 128; }
