@@ -189,6 +189,29 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float *states, int ring, int T, const float *
  * mode 0.  Range: C <= 16 and fc <= 128.  For any other shape the mode is IGNORED: the result is bit-equal to mode 0.        */
 int ncahip_dynca_precision(int mode);
 
+/* ---- steered perception: a per-cell direction field for the DyNCA forward step ------------------------------------------
+ * What the WebGL runtime does with `rotationAngle` and `alignment` (docs/dynca.js:209-225, :417-426): every cell's Sobel pair is
+ * rotated by the cell's direction before the update rule sees it, which turns a trained motion model at run time.
+ *   dirs: float32 [Bd,2,H,W] on the device, Bd in {1, B}; plane 0 = s, plane 1 = c (dir.x, dir.y of dynca.js:420-421).
+ * For every cell and every state channel the perception [x | Sx | Sy | L] becomes
+ *   Sx' = c Sx - s Sy ,  Sy' = s Sx + c Sy          (x and L untouched)
+ * in fp32, on the FINAL perception (two-scale: after the blend with the up-sampled coarse level), before the conditioning channels
+ * are appended and before any bf16 rounding of the operand (ncahip_dynca_precision mode 1).  (s, c) is not normalised: a non-unit
+ * pair is a rotation-scale.  s = 0, c = 1 reproduces the unsteered step value for value.  The per-step kernels (all three shape
+ * classes, wide hidden layers in 128-wide slices, single- and two-scale, both precisions) and the two one-launch kernels evaluate
+ * the two lines with one helper and agree bit for bit.  The WebGL runtime rotates each scale at its own resolution; for a uniform
+ * field the two definitions agree exactly (the rotation is linear), for a varying field they differ on the coarse half.
+ * Process-wide, host-only (needs no GPU), like ncahip_dynca_precision.  dirs == NULL detaches.  Returns 0, or NCAHIP_EINVAL for a
+ * non-null pointer with Bd < 1, H < 1 or W < 1 (the attachment is then unchanged).  The library keeps the POINTER, not a copy:
+ * the memory must stay valid, and its contents unchanged, until every piece of work enqueued while it was attached has run.
+ * While a field is attached:
+ *   - ncahip_dynca_step_fwd_f32 / _ms_f32, ncahip_dynca_nsteps_fwd_f32 / _ms_f32, ncahip_dynca_nsteps_fwd_persist_f32 / _ms_f32
+ *     and ncahip_dynca_clip_f32 / _clip_xc_f32 read it once per call at enqueue time and steer every step of the call; a call with
+ *     another (H, W), or with B != Bd while Bd != 1, returns NCAHIP_EINVAL before anything is enqueued;
+ *   - every DyNCA backward entry point and every bf16-storage forward entry point returns NCAHIP_EINVAL: they do not steer, and a
+ *     silently unsteered result or gradient is what this excludes.  ncahip_dynca_perceive_f32 is untouched.                  */
+int ncahip_dynca_direction(const float *dirs, int Bd, int H, int W);
+
 /* Backward of ONE DyNCA step (autograd through dynca.py:117-138; dynca.py:123: no gradient into cond).
  *   In : x_t (the step's input state), the same cond / u (or seed, step) / weights, g_next = dL/dx_{t+1}.
  *   Out: g_x = dL/dx_t (data path through W2^T, relu', W1^T on MFMA, then the adjoint of "F.pad(mode) + fixed 3x3

@@ -22,6 +22,9 @@ HIP events on the launch stream).  `python tools/bench_paths.py [names...]`; wit
                   8 steps: (a) the hand loop over nca.grow + torch.clamp against stylize_clip_conditioned (b) float32 -> float32 and
                   (c) uint8 -> uint8, measured twice over (a b c a b c), with ops.persistent_cond off and on; then the encoder alone,
                   ImageEncoder.forward (front pass + MIOpen) against ops.clip_encode, for 8 frames at 256^2 and 1 frame at 64^2
+  steer           steered perception (ops.dynca_direction): in one process, unsteered and under a 'polar' field, B = 1 at 256^2 in one
+                  launch (single- and two-scale, fp32 and bf16 MFMA), the 8 x 16 x 256^2 step, and a 64-frame clip through
+                  stylize_clip(direction=("polar", 0)) against the same clip without
   trainer_default ConditionedNCATrainer at the reference's own defaults (C = 20, 64 x 64, batch 8, nca_steps [48, 96]): ms per iteration
   loss            the default objective (VGG16 features + batched OT + content + overflow) at 32 x 3 x 256^2, fp32 / bf16 features
   loss_ot         the objective and its OT term alone (precomputed features), ot_impl batched, fused and fused_all alternating in one
@@ -586,6 +589,64 @@ def video_clip_leg():
                  route=getattr(getattr(video, "stylize_clip", None), "last_path", None), **res, **ratios)
 
 
+def steer_leg():
+    """What a direction field costs: every row times the same call unsteered and under steer.direction_field('polar', 0), alternating in
+    one process (plain, steered per iteration).  B = 1 at 256^2: video_leg's shape (pos_emb conditioning, T = 32 in one launch)."""
+    from ncahip import steer, video
+    from ncahip.models.dynca import DyNCA
+    T = 32
+    for C, fc in ((12, 96), (16, 128)):
+        for two in (False, True):
+            for precision in ("f32", "bf16"):
+                gen = torch.Generator().manual_seed(0)
+                w = dyn_weights(C, fc, 2, gen)
+                x = (torch.rand(1, C, 256, 256, generator=gen) - 0.5).to(DEV)
+                cond = (torch.rand(1, 2, 256, 256, generator=gen) * 2 - 1).to(DEV)
+                dirs = steer.direction_field("polar", 0.0, 256, 256, DEV)
+                run = lambda: ops.dynca_nsteps(x, T, cond, None, w, "circular", 0.5, seed=1, two_scale=two)      # noqa: E731
+
+                def steered():
+                    with ops.dynca_direction(dirs):
+                        return run()
+
+                with ops.dynca_precision(precision):
+                    assert run()[1] is None and steered()[1] is None          # both took the one-launch kernel
+                    (a, b), (amin, bmin) = timed([run, steered], iters=20)
+                ops.check_errors()
+                emit(path="steer_video_B1", C=C, fc=fc, two_scale=two, precision=precision, HW=[256, 256], steps_per_call=T,
+                     us_per_step=a / T * 1e3, steered_us_per_step=b / T * 1e3, min_us_per_step=amin / T * 1e3,
+                     min_steered_us_per_step=bmin / T * 1e3, steered_over_plain=b / a)
+    for B, C, fc in ((8, 16, 128), (8, 12, 96)):
+        gen = torch.Generator().manual_seed(0)
+        w = dyn_weights(C, fc, 3, gen)
+        x = (torch.rand(B, C, 256, 256, generator=gen) - 0.5).to(DEV)
+        cond = (torch.rand(B, 3, 256, 256, generator=gen) * 2 - 1).to(DEV)
+        dirs = steer.direction_field("polar", 0.0, 256, 256, DEV)
+        run = lambda: ops.dynca_nsteps(x, T, cond, None, w, "circular", 0.5, seed=1)      # noqa: E731
+
+        def steered():
+            with ops.dynca_direction(dirs):
+                return run()
+
+        (a, b), (amin, bmin) = timed([run, steered])
+        emit(path="steer_dynca_fwd", B=B, C=C, fc=fc, HW=[256, 256], T=T, us_per_step=a / T * 1e3, steered_us_per_step=b / T * 1e3,
+             min_us_per_step=amin / T * 1e3, min_steered_us_per_step=bmin / T * 1e3, steered_over_plain=b / a)
+    n_frames, step_n, S = 64, 8, 256
+    for C, fc, two in ((12, 96, False), (16, 128, True)):
+        torch.manual_seed(0)
+        m = DyNCA(C, 3, fc_dim=fc, padding_mode="circular", conditioning="edges", edge_transform="tanh",
+                  perception_scales=[0, 1] if two else [0], device=torch.device(DEV))
+        m.mask_rng, m.mask_seed = "philox", 1
+        u8 = torch.randint(0, 256, (n_frames, S, S, 3), generator=torch.Generator().manual_seed(0), dtype=torch.uint8).to(DEV)
+        fns = [lambda: video.stylize_clip(m, u8, step_n=step_n, out_dtype=torch.uint8),
+               lambda: video.stylize_clip(m, u8, step_n=step_n, out_dtype=torch.uint8, direction=("polar", 0.0))]
+        (a, b), (amin, bmin) = timed_sync(fns)
+        ops.check_errors()
+        emit(path="steer_video_clip", C=C, fc=fc, two_scale=two, HW=[S, S], frames=n_frames, step_n=step_n, masks="philox", route=video.stylize_clip.last_path,
+             us_per_frame=a / n_frames * 1e3, steered_us_per_frame=b / n_frames * 1e3, min_us_per_frame=amin / n_frames * 1e3,
+             min_steered_us_per_frame=bmin / n_frames * 1e3, steered_over_plain=b / a)
+
+
 def video_clip_xc_leg():
     """video_clip_leg for the extra-channel family (ExtraChannels/utils/misc/video_utils.py:66-82; fit_video_motion.py's default model).
     (a) the reference's loop by hand: per frame h = cat(h, mean grey), forward_nsteps, h = state[:, :-1], one image; (b) stylize_clip
@@ -750,6 +811,8 @@ def main(names):
         video_clip_xc_leg()
     if allp or "video_clip_cond" in names:
         video_clip_cond_leg()
+    if allp or "steer" in names:
+        steer_leg()
     if allp or "trainer_default" in names:
         trainer_default_leg()
 

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <mutex>
 
 #include "nca_kernels.h"
 
@@ -181,6 +182,43 @@ int ncahip_dynca_precision(int mode) {
 }
 static bool dynca_bf16_mfma(int C, int fc) { return g_dynca_precision.load(std::memory_order_relaxed) == 1 && nca_dynca_bf16_shape_ok(C, fc); }
 
+// Steered perception: the per-cell direction field [Bd,2,H,W] (plane 0 = s, plane 1 = c) the DyNCA forward rotates every Sobel pair by.
+// Process-wide like the precision; the eight fp32 forward entry points that honour the precision take ONE snapshot per call at enqueue
+// time (the clip drivers hand theirs to the steps they enqueue).  Every other DyNCA step entry point refuses to run while a field is
+// attached: a silently unsteered result or gradient is the failure to exclude.
+namespace {
+struct DyncaDir {
+    const float* p;
+    int Bd, H, W;
+};
+std::mutex g_dynca_dir_mu;
+DyncaDir g_dynca_dir{nullptr, 0, 0, 0};
+DyncaDir dynca_dir_snapshot() {
+    std::lock_guard<std::mutex> lk(g_dynca_dir_mu);
+    return g_dynca_dir;
+}
+// an honouring entry point: the attached field must fit the call
+int dynca_dir_check(const DyncaDir& d, const char* who, int B, int H, int W) {
+    if (!d.p) return 0;
+    if (H != d.H || W != d.W)
+        return fail(NCAHIP_EINVAL, "%s: the attached direction field (ncahip_dynca_direction) is %d x %d, the call is %d x %d", who, d.H, d.W, H, W);
+    if (d.Bd != 1 && d.Bd != B)
+        return fail(NCAHIP_EINVAL, "%s: the attached direction field (ncahip_dynca_direction) has Bd = %d, the call B = %d (Bd must be 1 or B)", who, d.Bd, B);
+    return 0;
+}
+// an entry point that does not steer (backward, bf16 storage)
+int dynca_dir_refuse(const char* who) {
+    if (!dynca_dir_snapshot().p) return 0;
+    return fail(NCAHIP_EINVAL, "%s: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first", who);
+}
+}  // namespace
+int ncahip_dynca_direction(const float* dirs, int Bd, int H, int W) {
+    if (dirs && (Bd < 1 || H < 1 || W < 1)) return fail(NCAHIP_EINVAL, "dynca direction field: Bd=%d H=%d W=%d must all be positive", Bd, H, W);
+    std::lock_guard<std::mutex> lk(g_dynca_dir_mu);
+    g_dynca_dir = dirs ? DyncaDir{dirs, Bd, H, W} : DyncaDir{nullptr, 0, 0, 0};
+    return 0;
+}
+
 static int g_force_bits = 0;   // the last ncahip_debug_force_generic argument: the persistent grow runs only with none set
 int ncahip_debug_force_generic(int on) {
     g_force_bits = on;
@@ -239,8 +277,13 @@ enum DyncaFwdKind { kDyncaFwdF32, kDyncaFwdMs, kDyncaFwdBf16 };
 // (t + 1) % ring.  Nothing is enqueued before all checks have passed.
 static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, const void* x_in, void* x_out, int ring, int T, const float* cond, const float* u,
                           const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
-                          int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, ncahip_stream_t stream) {
+                          int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, ncahip_stream_t stream,
+                          const DyncaDir* dir_of_caller = nullptr) {
     const bool ms = kind == kDyncaFwdMs, bf16 = kind == kDyncaFwdBf16;
+    if (bf16) {
+        if (int rc = dynca_dir_refuse(what)) return rc;
+    }
+    const DyncaDir dir = bf16 ? DyncaDir{nullptr, 0, 0, 0} : dir_of_caller ? *dir_of_caller : dynca_dir_snapshot();   // one read per call
     char* const states = (char*)const_cast<void*>(x_in);
     if (!single && (ring < 2 || T < 0)) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
     if (int rc = check_dynca(x_in, single ? x_out : states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
@@ -249,6 +292,7 @@ static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, cons
     if (ms) {
         if (int rc = check_ms(C, H, W, fc, pad_mode, pc_scratch)) return rc;
     }
+    if (int rc = dynca_dir_check(dir, what, B, H, W)) return rc;
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -263,6 +307,8 @@ static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, cons
         NcaDyncaArgs a{xi, xo, cond, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t};
         a.pc = ms ? pc_scratch : nullptr;
         a.u_bits = ubits;
+        a.dirs = dir.p;
+        a.dirs_bstride = dir.Bd == 1 ? 0 : (size_t)2 * H * W;
         if (int rc = hip_result(bf16 ? nca_launch_dynca_step_fwd_bf16(a, st) : nca_launch_dynca_step_fwd(a, st, bf), what)) return rc;
     }
     return 0;
@@ -321,13 +367,15 @@ size_t ncahip_dynca_nsteps_persist_workspace(int B, int C, int H, int W, int fc,
 static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, int T, const float* cond, const float* u, const float* w1,
                                         const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
                                         int pad_mode, float update_rate, uint64_t seed, uint64_t step0, void* workspace,
-                                        size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream) {
+                                        size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream, const DyncaDir* dir_of_caller = nullptr) {
+    const DyncaDir dir = dir_of_caller ? *dir_of_caller : dynca_dir_snapshot();   // one read per call
     if (T < 1 || !workspace) return fail(NCAHIP_EINVAL, "dynca nsteps persist: T >= 1 and a workspace required");
     if (epoch < 1 || epoch >= (1u << 20)) return fail(NCAHIP_EINVAL, "dynca nsteps persist: epoch must be in [1, 2^20) (zero the workspace and restart at 1 when it runs out)");
     if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;   // (refuses x_in == x_out)
     if (two_scale) {
         if (int rc = check_ms_reflect(H, W, pad_mode)) return rc;
     }
+    if (int rc = dynca_dir_check(dir, "dynca nsteps persist", B, H, W)) return rc;
     const size_t need = ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, c_cond);
     if (need == 0 || T >= 4096)
         return fail(NCAHIP_ERANGE, "dynca nsteps persist: shape not covered (C <= 16, fc <= 128, H %% 16 == 0, W %% 16 == 0, T < 4096); use ncahip_dynca_nsteps_fwd_f32");
@@ -341,6 +389,8 @@ static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, i
     NcaDyncaPersistArgs a{x_in, x_out, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0,
                           (int*)workspace, epoch, (unsigned long long*)((char*)workspace + 256),
                           nca_dynca_persist_xch_pairs(B, C, H, W, two_scale), nullptr, ubits ? 1 : 0};
+    a.dirs = dir.p;
+    a.dirs_bstride = dir.Bd == 1 ? 0 : (size_t)2 * H * W;
     bool fits = false;
     const bool bf = dynca_bf16_mfma(C, fc);   // the variant's own instantiation: its own LDS size and co-residency test
     auto launch = [&](const NcaDyncaPersistArgs& pa, hipStream_t ps, bool query_only, bool* f) {
@@ -528,10 +578,16 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         return fail(NCAHIP_EINVAL, "%s: states, %scond and images must not overlap", who, gray ? "gray, " : "");
     if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
         return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
+    // the direction field of this call: read once, handed to every step the clip enqueues
+    const DyncaDir dir = dynca_dir_snapshot();
+    const DyncaFwdKind kind = two_scale ? kDyncaFwdMs : kDyncaFwdF32;
+    // the per-step entry point's body with this call's field: (x_in, x_out) a single step, x_out == NULL the ring `states` of 2 slots
+    auto steps = [&](const float* x_in, float* x_out, int T, const float* cf, const float* uf, uint64_t s0) {
+        return dynca_fwd_impl(kind, who, x_out != nullptr, x_in, x_out, 2, x_out ? 1 : T, cf, uf, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
+                              update_rate, seed, s0, pc_scratch, stream, &dir);
+    };
     // what the per-step entry point refuses for this shape, the clip refuses with its code (T = 0: every check, no launch)
-    if (int rc = two_scale ? ncahip_dynca_nsteps_fwd_ms_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, pc_scratch, stream)
-                           : ncahip_dynca_nsteps_fwd_f32(states, 2, 0, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, stream))
-        return rc;
+    if (int rc = steps(states, nullptr, 0, cond, u, step0)) return rc;
     if (persist_ws) {
         const size_t need = ncahip_dynca_nsteps_persist_workspace(B, C, H, W, fc, c_cond);
         if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "%s: persistent workspace too small", who);
@@ -551,9 +607,9 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         const uint64_t s0 = step0 + (uint64_t)t0;
         bool done = false;
         if (persist) {
-            auto fn = two_scale ? ncahip_dynca_nsteps_fwd_persist_ms_f32 : ncahip_dynca_nsteps_fwd_persist_f32;
-            const int rc = fn(states + (size_t)cur * slot, states + (size_t)(cur ^ 1) * slot, step_n, cf, u_at(u, ubits, t0, uslot), w1, b1, w2, b2, B, C,
-                              H, W, fc, c_cond, pad_mode, update_rate, seed, s0, persist_ws, persist_bytes, epoch0 + (unsigned)n, stream);
+            const int rc = dynca_persist_impl(two_scale != 0, states + (size_t)cur * slot, states + (size_t)(cur ^ 1) * slot, step_n, cf,
+                                              u_at(u, ubits, t0, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, s0,
+                                              persist_ws, persist_bytes, epoch0 + (unsigned)n, stream, &dir);
             if (rc == 0) {
                 cur ^= 1;
                 done = true;
@@ -566,18 +622,10 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         if (!done) {
             int T = step_n, t = t0;
             if (cur == 1) {   // the ring of the n-step entry point starts at slot 0: one single step brings the state there
-                if (int rc = two_scale ? ncahip_dynca_step_fwd_ms_f32(states + slot, states, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond,
-                                                                      pad_mode, update_rate, seed, step0 + (uint64_t)t, pc_scratch, stream)
-                                       : ncahip_dynca_step_fwd_f32(states + slot, states, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond,
-                                                                   pad_mode, update_rate, seed, step0 + (uint64_t)t, stream))
-                    return rc;
+                if (int rc = steps(states + slot, states, 1, cf, u_at(u, ubits, t, uslot), step0 + (uint64_t)t)) return rc;
                 --T, ++t;
             }
-            if (int rc = two_scale ? ncahip_dynca_nsteps_fwd_ms_f32(states, 2, T, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
-                                                                    update_rate, seed, step0 + (uint64_t)t, pc_scratch, stream)
-                                   : ncahip_dynca_nsteps_fwd_f32(states, 2, T, cf, u_at(u, ubits, t, uslot), w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
-                                                                 update_rate, seed, step0 + (uint64_t)t, stream))
-                return rc;
+            if (int rc = steps(states, nullptr, T, cf, u_at(u, ubits, t, uslot), step0 + (uint64_t)t)) return rc;
             cur = T & 1;
         }
         // image n and, in the same launch, the grey of the call that follows (the repeats j > 0 of a frame included: the channel has
@@ -906,6 +954,7 @@ int ncahip_dynca_step_bwd_f32(const float* x_t, const float* cond, const float* 
                               const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                               float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x, float* h_out,
                               float* dh_out, float* dy_scratch, ncahip_stream_t stream) {
+    if (int rc = dynca_dir_refuse("dynca step bwd")) return rc;
     if (!g_next || !g_x || !h_out || !dh_out || !dy_scratch) return fail(NCAHIP_EINVAL, "dynca step bwd: null pointer");
     if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
     if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd: g_next and g_x must not alias");
@@ -929,6 +978,7 @@ int ncahip_dynca_step_bwd_w2_f32(const float* x_t, const float* cond, const floa
                                  float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
                                  float* dh_out, float* dy_scratch, float* gw2_out, int accumulate, void* workspace,
                                  size_t workspace_bytes, ncahip_stream_t stream) {
+    if (int rc = dynca_dir_refuse("dynca step bwd_w2")) return rc;
     if (!g_next || !g_x || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_w2: null pointer");
     if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
     if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_w2: g_next and g_x must not alias");
@@ -998,6 +1048,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
                                 size_t workspace_bytes, ncahip_stream_t stream) {
     const char* const states = (const char*)states_v;
     const bool bf16 = sb == 2;
+    if (int rc = dynca_dir_refuse("dynca nsteps bwd")) return rc;
     if (T < 1 || !states || !g_final || !g_x0 || !g_w1 || !g_b1 || !g_w2 || !g_b2 || !workspace)
         return fail(NCAHIP_EINVAL, "dynca nsteps bwd: null pointer or T < 1");
     if (int rc = check_dynca(states, g_x0, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, kMaxFcFwd)) return rc;

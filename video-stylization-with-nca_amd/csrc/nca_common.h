@@ -44,6 +44,19 @@ __device__ __forceinline__ float nca_laplacian(const float (&a)[3][3]) {
            2.0f * ((a[0][1] + a[2][1]) + (a[1][0] + a[1][2])) - 12.0f * a[1][1];
 }
 
+// Steered perception (ncahip_dynca_direction; WebGL twin docs/dynca.js:417-426): a cell's Sobel pair rotated by its direction (s, c),
+//   Sx' = c Sx - s Sy,  Sy' = s Sx + c Sy,
+// in fp32, not normalised (a non-unit pair is a rotation-scale).  ONE definition with floating-point contraction off, used at every
+// site, for the reason given at nca_up2_blend: the per-step and the one-launch kernels must produce the same bits.  s = 0, c = 1 gives
+// back (Sx, Sy) value for value (1 * Sx - 0 * Sy is exact; only the sign of a zero may change).
+__device__ __forceinline__ void nca_steer(float& sx, float& sy, float s, float c) {
+#pragma clang fp contract(off)
+    const float rx = c * sx - s * sy;
+    const float ry = s * sx + c * sy;
+    sx = rx;
+    sy = ry;
+}
+
 // Two-scale perception (dynca.py:98, :105-110): bilinear x2 up-sampling (align_corners = False) of the coarse-level value from its
 // four taps, then the mean over the two scales.  ONE definition with floating-point contraction off: the per-step kernel and the
 // persistent kernel must produce the same bits, and left to the optimiser the same source expression was contracted into different

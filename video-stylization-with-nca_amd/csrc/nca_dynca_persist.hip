@@ -239,6 +239,28 @@ __device__ __forceinline__ void persist_prologue(const NcaDyncaPersistArgs& a, f
     }
 }
 
+// Steered perception (NcaDyncaPersistArgs::dirs; the STEER instantiations of both kernels -- a switch, not a branch on the pointer: with
+// the branch the unsteered two-scale kernel spilled 0.5 KB per lane): the tile's directions [2][256] (s | c), staged once per launch by
+// all 320 threads (the caller's barrier follows) behind the kernel's carve -- a workgroup keeps its tile for all T steps.
+constexpr int kDirFloats = 2 * PTH * PTW;
+__device__ __forceinline__ void persist_stage_dirs(const NcaDyncaPersistArgs& a, float* DR, const PersistTile& G) {
+    const float* const db = a.dirs + (size_t)G.b * a.dirs_bstride + (size_t)G.ty0 * a.W + G.tx0;
+    for (int i = threadIdx.x; i < kDirFloats; i += kPT) {
+        const int pl = i / (PTH * PTW), c = i % (PTH * PTW);
+        DR[i] = db[(size_t)pl * G.plane + (size_t)(c / PTW) * a.W + c % PTW];
+    }
+}
+// ... and applied to the finished perception of NTP groups: the per-step kernel's helper on the same operands (nca_steer)
+template <class K, int NTP>
+__device__ __forceinline__ void persist_steer(const float* DR, const int (&rr)[NTP], const int (&qq)[NTP], float (&P)[NTP][K::K1S]) {
+#pragma unroll
+    for (int n = 0; n < NTP; ++n) {
+        const float ds = DR[rr[n] * PTW + qq[n]], dc = DR[PTH * PTW + rr[n] * PTW + qq[n]];
+#pragma unroll
+        for (int cq4 = 0; cq4 < K::CPAD / 4; ++cq4) nca_steer(P[n][4 * cq4 + 1], P[n][4 * cq4 + 2], ds, dc);
+    }
+}
+
 // UpdateNet on NTP groups of 16 cells: acc2 = b2 + W2 relu(b1 + W1 P), both layers exact-f32 MFMA chains in the per-step kernel's k order
 template <class K, int NTP>
 __device__ __forceinline__ void persist_mlp(const float* smem, const float (&P)[NTP][K::K1S], int lane, int g, f32x4 (&acc2)[NTP], int dbg) {
@@ -387,13 +409,14 @@ __device__ __forceinline__ void fine_halo_cell(int hc, int& r, int& q) {
 }
 
 // ---- the single-scale kernel ----------------------------------------------------------------------------------------------------------
-template <int CP, int FC, bool HAS_COND, bool BF = false>
+template <int CP, int FC, bool HAS_COND, bool BF = false, bool STEER = false>
 __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPersistArgs a) {
     using K = PersistCfg<CP, FC, HAS_COND, BF>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const MK = smem + K::OFF_MK;
     float* const CN = smem + K::OFF_CN;
     int* const lflag = reinterpret_cast<int*>(smem + K::OFF_FLAG);
+    float* const DR = smem + K::LDS_FLOATS;      // the tile's directions; exists in the STEER instantiations only (launch_cfg)
 
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ci = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -402,6 +425,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
     const int ty0 = G.ty0, tx0 = G.tx0;
 
     persist_prologue<K>(a, smem, G);
+    if constexpr (STEER) persist_stage_dirs(a, DR, G);
     __syncthreads();
 
     if (wave == 4) {
@@ -521,6 +545,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_kernel(const NcaDyncaPer
                         P[n][4 * cq4 + 3] = nca_laplacian(nbv);
                     }
                 }
+                if constexpr (STEER) persist_steer<K, NTP>(DR, rr, qq, P);
                 if constexpr (HAS_COND) {
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) P[n][CP] = CN[g * PTH * PTW + rr[n] * PTW + qq[n]];
@@ -583,10 +608,10 @@ struct PersistMsCfg {
     static constexpr int LDS_FLOATS = OFF_TBL + 2 * (B::NLD + NLC) * 64;
     static constexpr int NPB = (kCoarseRing * CP + 63) / 64;     // own coarse ring cells to publish per sync-wave lane
     static constexpr int NPC = (PCR2 * PCR2 * CP + 255) / 256;   // coarse perception cells per compute thread
-    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
+    static_assert((LDS_FLOATS + 2 * PTH * PTW) * 4 <= 160 * 1024, "LDS budget (with the directions of a steered launch behind the carve)");
 };
 
-template <int CP, int FC, bool HAS_COND, bool BF = false>
+template <int CP, int FC, bool HAS_COND, bool BF = false, bool STEER = false>
 __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDyncaPersistArgs a) {
     using K = PersistCfg<CP, FC, HAS_COND, BF>;
     using KM = PersistMsCfg<CP, FC, HAS_COND, BF>;
@@ -596,6 +621,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
     float* const XC = smem + KM::OFF_XC;
     float* const PCL = smem + KM::OFF_PCL;
     int* const lflag = reinterpret_cast<int*>(smem + K::OFF_FLAG);
+    float* const DR = smem + KM::LDS_FLOATS;     // the tile's directions; exists in the STEER instantiations only (launch_cfg)
 
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ci = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -605,6 +631,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
     const int ty0 = G.ty0, tx0 = G.tx0, cy0 = ty0 >> 1, cx0 = tx0 >> 1;
 
     persist_prologue<K>(a, smem, G);
+    if constexpr (STEER) persist_stage_dirs(a, DR, G);
     __syncthreads();
     // 2 x 2 mean of tile-local coarse cell (i, j) of channel ch from an LDS state tile -- upsample_bilinear2d's own expression for the
     // exact x1/2 case, as dynca_coarse_perceive_kernel evaluates it
@@ -817,6 +844,7 @@ __global__ __launch_bounds__(kPT, 1) void dynca_persist_ms_kernel(const NcaDynca
                         }
                     }
                 }
+                if constexpr (STEER) persist_steer<K, NTP>(DR, rr, qq, P);       // the blended perception, as the per-step kernel
                 if constexpr (HAS_COND) {
 #pragma unroll
                     for (int n = 0; n < NTP; ++n) P[n][CP] = CN[g * PTH * PTW + rr[n] * PTW + qq[n]];
@@ -861,10 +889,17 @@ hipError_t launch_persist(int lds_floats, const NcaDyncaPersistArgs& a, hipStrea
     return hipGetLastError();
 }
 
+template <bool MS, int CP, int FC, bool HAS_COND, bool BF, bool STEER>
+hipError_t launch_steer(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
+    constexpr int DR = STEER ? kDirFloats : 0;   // steered: the tile's directions behind the carve
+    if constexpr (MS) return launch_persist<dynca_persist_ms_kernel<CP, FC, HAS_COND, BF, STEER>>(PersistMsCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS + DR, a, st, query_only, fits);
+    else return launch_persist<dynca_persist_kernel<CP, FC, HAS_COND, BF, STEER>>(PersistCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS + DR, a, st, query_only, fits);
+}
+// a launch with a direction field attached (ncahip_dynca_direction) runs the STEER instantiation: its own LDS size, occupancy cache and
+// co-residency test
 template <bool MS, int CP, int FC, bool HAS_COND, bool BF = false>
 hipError_t launch_cfg(const NcaDyncaPersistArgs& a, hipStream_t st, bool query_only, bool* fits) {
-    if constexpr (MS) return launch_persist<dynca_persist_ms_kernel<CP, FC, HAS_COND, BF>>(PersistMsCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS, a, st, query_only, fits);
-    else return launch_persist<dynca_persist_kernel<CP, FC, HAS_COND, BF>>(PersistCfg<CP, FC, HAS_COND, BF>::LDS_FLOATS, a, st, query_only, fits);
+    return a.dirs ? launch_steer<MS, CP, FC, HAS_COND, BF, true>(a, st, query_only, fits) : launch_steer<MS, CP, FC, HAS_COND, BF, false>(a, st, query_only, fits);
 }
 
 int persist_dbg() {

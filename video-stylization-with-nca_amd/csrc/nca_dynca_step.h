@@ -1,6 +1,6 @@
 // nca_dynca_step.h -- the fused DyNCA step kernel for MI355X (gfx950), fp32 exact: kernel template, its ten named variants, the
 // one launcher and the one dispatch ladder.  nca_dynca_fwd.hip instantiates the forward variants, nca_dynca_bwd.hip the backward
-// ones.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
+// ones, nca_dynca_steer.hip (a unit of its own) the steered forward variants DyncaSteered<V>.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
 //
 // One persistent launch per NCA step.  A workgroup (4 waves) owns TH x TW cell tiles:
 //   1. the state tile (+1 halo, pad mode resolved at load time; ConditionedNCA: the pending
@@ -21,6 +21,8 @@
 // leave registers.  Layer 1 is streamed m-tile by m-tile into layer 2's accumulators so only
 // one layer-1 tile is live (keeps 2 waves/SIMD).
 #pragma once
+#include <type_traits>
+
 #include "nca_step_tile.h"
 
 namespace {
@@ -56,6 +58,9 @@ struct DyncaCfg {
     static constexpr int PCR = TW / 2 + 4, PCS = (TH / 2 + 2) * PCR;
     static constexpr int OFF_PC = LDS_FLOATS;
     static constexpr int LDS_FLOATS_MS = OFF_PC + 4 * CP * PCS;
+    // steered variants: the tile's directions [2][TH * TW] (s | c) go BEHIND the variant's carve (forward: LDS_FLOATS, two-scale:
+    // LDS_FLOATS_MS); the unsteered variants ask for the LDS they always did
+    static constexpr int DR_FLOATS = 2 * TH * TW;
     // backward variant: the transposed operands (W2^T for dh, W1^T for dL/dy) are 16-byte reads of the FORWARD images (see the
     // kernel), so the backward needs no weight images of its own.  dL/dy is produced in tiles of 16 rows = 4 channels x 4
     // filters (row i <-> channel 4mj + (i & 3), filter i >> 2): MJ = CP / 4 tiles, no conditioning rows (dynca.py:123).
@@ -77,7 +82,12 @@ struct DyncaCfg {
 //   W2F  backward with the layer-2 weight gradient fused in (per-workgroup dW2 | db2 partials, h is not written)
 //   MS   two-scale perception: the coarse-level perception tile is staged in LDS and blended in
 //   BF   both 1x1 products of the forward on bf16 MFMA (ncahip_dynca_precision mode 1)
-struct DyncaVariant { static constexpr bool BWD = false, B16 = false, ACC = false, W2F = false, MS = false, BF = false; };
+//   STEER the perception's Sobel pair rotated by the cell's direction (NcaDyncaArgs::dirs, ncahip_dynca_direction): DyncaSteered<V> of a
+//        forward variant V with fp32 storage.  A switch and not a launch-uniform branch on the pointer: with the branch the unsteered
+//        kernels took up to 60 more registers, and the bf16-MFMA and one-launch kernels spilled ("Steered perception")
+struct DyncaVariant { static constexpr bool BWD = false, B16 = false, ACC = false, W2F = false, MS = false, BF = false, STEER = false; };
+template <class V>
+struct DyncaSteered : V { static constexpr bool STEER = true; };   // V steered: nca_dynca_steer.hip instantiates these
 struct DyncaFwd : DyncaVariant {};                                                                  // forward, exact fp32
 struct DyncaFwdBf : DyncaVariant { static constexpr bool BF = true; };                              // forward, bf16 MFMA
 struct DyncaFwdMs : DyncaVariant { static constexpr bool MS = true; };                              // forward, two-scale
@@ -95,7 +105,8 @@ struct DyncaBwdW2Acc : DyncaVariant { static constexpr bool BWD = true, W2F = tr
 // (dW2 = (G*mask) h^T, dW1 = dh y^T, K = all cells) are plain library GEMMs on those buffers.
 template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT, bool VEC, typename V>
 __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_step_fwd_kernel(const NcaDyncaArgs a) {   // CP > 16: 140 KB of LDS -> one workgroup per CU anyway: 512 registers
-    constexpr bool BWD = V::BWD, B16 = V::B16, ACC = V::ACC, W2F = V::W2F, MS = V::MS, BF = V::BF;
+    constexpr bool BWD = V::BWD, B16 = V::B16, ACC = V::ACC, W2F = V::W2F, MS = V::MS, BF = V::BF, STEER = V::STEER;
+    static_assert(!STEER || (!BWD && !B16), "steered: the forward variants with fp32 storage");
     static_assert(!MS || (TH % 2 == 0 && TW % 2 == 0), "the two-scale step: a tile covers whole coarse cells");
     static_assert(!BF || CP <= 16, "bf16 MFMA: one output tile");
     using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
     float* const Z = smem + K::OFF_Z;
     float* const MK = smem + K::OFF_MK;
     float* const CN = smem + K::OFF_CN;
+    float* const DR = smem + (MS ? K::LDS_FLOATS_MS : K::LDS_FLOATS);          // [2][TH * TW]; exists in the steered variants only (launch_dynca)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, ci = lane & 15;
     const int C = a.C, H = a.H, W = a.W, fc = a.fc, CC = a.c_cond;
@@ -217,6 +229,12 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
             for (int cc = 0; cc < 4; ++cc)
                 cnv[cc] = a.cond[((size_t)b * CC + min(cc, CC - 1)) * plane + (cell - (size_t)b * plane)];
         }
+        float dsv = 0.0f, dcv = 1.0f;   // this cell's direction (s, c); lanes outside the image read cell 0 of the plane and stage the identity
+        if constexpr (STEER) {
+            const float* const db = a.dirs + (size_t)b * a.dirs_bstride + (cell - (size_t)b * plane);
+            dsv = db[0];
+            dcv = db[plane];
+        }
         __syncthreads();  // previous tile fully consumed (also orders the weight image on iter 0)
         if (ps.active) {
 #pragma unroll
@@ -240,6 +258,10 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
         if (HAS_COND && !BWD) {
 #pragma unroll
             for (int cc = 0; cc < 4; ++cc) CN[cc * TH * TW + st] = (cin && cc < CC) ? cnv[cc] : 0.0f;
+        }
+        if constexpr (STEER) {
+            DR[st] = cin ? dsv : 0.0f;
+            DR[TH * TW + st] = cin ? dcv : 1.0f;
         }
         if constexpr (MS) {
             // coarse perception tile: rows ty0/2 - 1 .. ty0/2 + TH/2, columns tx0/2 - 1 .. tx0/2 + TW/2, indices clamped into the
@@ -296,6 +318,16 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
                             P[n][4 * cq4 + f] = nca_up2_blend(P[n][4 * cq4 + f], q[0], q[1], q[K::PCR], q[K::PCR + 1], h0, h1, w0, w1);
                         }
                     }
+                }
+            }
+            // steered perception: the final (blended) Sobel pair of every channel rotated by the cell's direction, in fp32, before the
+            // conditioning rows are appended and before any bf16 rounding of the operand
+            if constexpr (STEER) {
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    const float ds = DR[r0[n] * TW + q0[n]], dc = DR[TH * TW + r0[n] * TW + q0[n]];
+#pragma unroll
+                    for (int cq4 = 0; cq4 < CP / 4; ++cq4) nca_steer(P[n][4 * cq4 + 1], P[n][4 * cq4 + 2], ds, dc);
                 }
             }
             if (HAS_COND) {
@@ -659,7 +691,10 @@ hipError_t launch_dynca(const NcaDyncaArgs& a, hipStream_t st) {
     static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
     static_assert(!V::W2F || 4 * (16 * K::M2T * FC + 16 * K::M2T) <= K::LDS_FLOATS_BWD_W2, "the four waves' dW2 | db2 partials are summed through LDS");
     auto kern = dynca_step_fwd_kernel<CP, FC, HAS_COND, TH, TW, NT, VEC, V>;
-    const size_t lds = (size_t)LDS_FLOATS * sizeof(float);
+    constexpr size_t kDirBytes = V::STEER ? (size_t)K::DR_FLOATS * sizeof(float) : 0;   // steered: the tile's directions behind the carve
+    static_assert((size_t)LDS_FLOATS * 4 + kDirBytes <= 160 * 1024, "LDS budget of the steered variant");
+    if (V::STEER && !a.dirs) return hipErrorInvalidValue;
+    const size_t lds = (size_t)LDS_FLOATS * sizeof(float) + kDirBytes;
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
     int grid;
@@ -697,6 +732,40 @@ hipError_t dispatch_dynca(const NcaDyncaArgs& a, hipStream_t st) {
     if constexpr (FIRST <= kDynca32x128 && kDynca32x128 <= LAST)
         if (a.C <= 32 && a.fc <= 128) return launch_dynca_class<32, 128, V>(a, st);   // configs[4]
     return hipErrorInvalidValue;
+}
+
+// ---- the forward ladder (nca_dynca_fwd.hip: the variants as they are; nca_dynca_steer.hip: DyncaSteered<> of each) ------------------
+template <bool STEER, class V>
+using DyncaSel = std::conditional_t<STEER, DyncaSteered<V>, V>;
+
+template <bool STEER>
+hipError_t launch_dynca_fwd_ladder(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma) {
+    const bool bf = bf16_mfma && nca_dynca_bf16_shape_ok(a.C, a.fc);   // ncahip_dynca_precision mode 1; shapes outside its range run exactly
+    if (a.pc) {   // two-scale perception
+        if ((a.H | a.W) & 1) return hipErrorInvalidValue;
+        return bf ? dispatch_dynca<DyncaSel<STEER, DyncaFwdMsBf>, kDynca12x96, kDynca16x128>(a, st)
+                  : dispatch_dynca<DyncaSel<STEER, DyncaFwdMs>, kDynca12x96, kDynca16x128>(a, st);
+    }
+    if (bf) return dispatch_dynca<DyncaSel<STEER, DyncaFwdBf>, kDynca12x96, kDynca16x128>(a, st);
+    if (a.fc <= 128) return dispatch_dynca<DyncaSel<STEER, DyncaFwd>, kDynca12x96, kDynca32x128>(a, st);
+    if (a.C > 32) return hipErrorInvalidValue;
+    // fc > 128: the A-operand image of w1 no longer fits the LDS beside the tile.  w2 relu(w1 y + b1) is a sum over hidden
+    // units, so the step runs as one launch per 128-wide slice: the first writes x + mask*(slice + b2), the others add
+    // their slice to x_out (same mask: same explicit uniforms / Philox key).  Each launch recomputes the perception (steered: every
+    // slice steers it).
+    const int K1 = 4 * a.C + a.c_cond;
+    for (int h0 = 0; h0 < a.fc; h0 += 128) {
+        NcaDyncaArgs s = a;
+        s.w1 = a.w1 + (size_t)h0 * K1;
+        s.b1 = a.b1 + h0;
+        s.w2 = a.w2 + h0;
+        s.fc = a.fc - h0 < 128 ? a.fc - h0 : 128;
+        s.w2_ld = a.fc;
+        const hipError_t e = h0 == 0 ? dispatch_dynca<DyncaSel<STEER, DyncaFwd>, kDynca16x128, kDynca32x128>(s, st)
+                                     : dispatch_dynca<DyncaSel<STEER, DyncaFwdAcc>, kDynca16x128, kDynca32x128>(s, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace

@@ -68,6 +68,10 @@ struct NcaDyncaArgs {
     float* ybuf;              // backward MLP kernel: if set, the recomputed perception y (two-scale: the combined one) is written here,
                               // [B,4C,H,W] in perceive_torch's row order -- the B rows of the layer-1 weight-gradient product
     int u_bits;               // u points at bit-packed fire masks (uint32 words, cell i -> bit i & 31 of word i >> 5; B*H*W < 2^32)
+    // steered perception (ncahip_dynca_direction; forward variants with fp32 storage only): per-cell directions [Bd,2,H,W], plane 0 = s,
+    // plane 1 = c, or null; the Sobel pair of every channel becomes (c Sx - s Sy, s Sx + c Sy) before the first 1x1 product
+    const float* dirs;
+    size_t dirs_bstride;      // floats between the fields of two samples: 2*H*W, or 0 when one field serves the whole batch (Bd == 1)
 };
 
 // T DyNCA steps in one launch (nca_dynca_persist.hip): one workgroup per 16 x 16 tile for all steps, neighbour counters in `flags`
@@ -90,6 +94,8 @@ struct NcaDyncaPersistArgs {
     int dbg;             // diagnostic knobs (NCAHIP_PERSIST_DBG, timing experiments only -- results are then NOT valid): bit 0 no neighbour
                          // polls / halo loads, bit 1 no state stores, bit 2 no ring phase, bit 3 no mask refill, bit 4 no MFMA chains.
                          // The single-scale kernel honours all five; the two-scale kernel bits 0, 1 and 4 (1 and 4 sit in shared code)
+    const float* dirs;   // steered perception: per-cell directions [Bd,2,H,W] or null, as NcaDyncaArgs::dirs (staged once per launch)
+    size_t dirs_bstride; // 2*H*W, or 0 for Bd == 1
 };
 void nca_set_persist_drop_tiles(int n);   // test hook: the persistent launch leaves out its last n tiles (their neighbours' polls expire)
 bool nca_dynca_persist_shape_ok(int B, int C, int H, int W, int fc, int c_cond);
@@ -251,6 +257,8 @@ int nca_resize_build_tables(int in, int out, int filter, int32_t* k, int32_t* bo
 // fused steps (nca_dynca_fwd.hip, nca_dynca_bwd.hip, nca_cond_generic.hip); hipErrorInvalidValue when no instantiation covers the shape
 // bf16_mfma: ncahip_dynca_precision mode 1 (both 1x1 products on bf16 MFMA, nca_dynca_bf16.h) where nca_dynca_bf16_shape_ok
 hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma = false);
+// the same ladder over the steered variants (nca_dynca_steer.hip); a.dirs must be set.  nca_launch_dynca_step_fwd goes there itself
+hipError_t nca_launch_dynca_step_fwd_steered(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma);
 inline bool nca_dynca_bf16_shape_ok(int C, int fc) { return C >= 1 && C <= 16 && fc >= 1 && fc <= 128; }
 hipError_t nca_launch_cond_step_fwd(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_dynca_step_bwd(const NcaDyncaArgs& a, hipStream_t st);

@@ -7,13 +7,19 @@ reference, dynca.py:118-124) is hoisted: computed once per forward_nsteps call.
 
 Step (dynca.py:117-138):  y = [x | Sx*x | Sy*x | L*x | cond] ; dx = w2 relu(w1 y + b1) + b2 ;
                           x <- x + dx * floor(u + update_rate) ; rgb = 2 x[:, :c_out]
+
+forward() and forward_nsteps() take one keyword the reference does not have, last: direction=None -- a field tensor [Bd,2,H,W] or an
+(alignment, angle_deg) tuple (ncahip.steer): every cell's Sobel pair is rotated by its direction before w1 sees it, which turns a
+trained motion model at run time as the WebGL runtime does (docs/dynca.js:209-225, :417-426).  Inference only.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import ops, steer
 from ..autograd import dynca_nsteps_autograd, hip_perceive
 
 
@@ -153,11 +159,35 @@ class DyNCA(nn.Module):
         y = sum(self.perceive_torch(x, scale=s) for s in self.perception_scales) / len(self.perception_scales)
         return y if cond_mat is None else torch.cat([y, cond_mat], dim=1)
 
-    def _step_multiscale(self, x, cond, update_rate, u):
+    def _steer(self, x, direction, cond):
+        """direction=... of forward / forward_nsteps -> (field [Bd,2,H,W] on x's device or None, cond).  With an (alignment, angle) tuple a
+        pos_emb model's encoding is turned by the angle too (steer.rotate_pos_emb)."""
+        if direction is None:
+            return None, cond
+        if x.dtype != torch.float32:
+            raise ValueError(f"direction needs a float32 state (the bf16-storage steps do not steer), got {x.dtype}")
+        dirs, angle = steer.resolve(direction, x.shape[2], x.shape[3], x.device)
+        if dirs.shape[0] not in (1, x.shape[0]):
+            raise ValueError(f"direction field must have Bd = 1 or Bd = B = {x.shape[0]}, got {dirs.shape[0]}")
+        if angle is not None and cond is not None and self.conditioning == "pos_emb":
+            cond = steer.rotate_pos_emb(cond, angle)
+        return dirs, cond
+
+    def _refuse_steered_grad(self, x, direction):
+        """A steered step is inference only: the recompute backward does not know the field."""
+        if direction is not None and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise ValueError("direction=... is inference only (the backward does not know the field): call under torch.no_grad(), "
+                             "or with a state and parameters that do not require grad")
+
+    def _step_multiscale(self, x, cond, update_rate, u, dirs=None):
         """One step with perception_scales != [0] (dynca.py:117-138).  Not fused: HIP stencil per scale + device
         resampling + the two 1x1 convolutions as library GEMMs (the fused kernel covers the
-        single-scale models)."""
-        y = self.perceive_multiscale(x, cond)
+        single-scale models).  dirs: the fused kernels' steering (steer.rotate_perception) on the blended perception."""
+        if dirs is None:
+            y = self.perceive_multiscale(x, cond)
+        else:
+            y = steer.rotate_perception(self.perceive_multiscale(x), dirs, self.c_in)
+            y = y if cond is None else torch.cat([y, cond], dim=1)
         dx = self.w2(F.relu(self.w1(y)))
         mask = torch.floor(u + update_rate)
         return x + dx * mask
@@ -171,16 +201,19 @@ class DyNCA(nn.Module):
         self._mask_step += 1
         return u
 
-    def forward(self, x, update_rate=0.5, return_perception=False, cond_img=None):
-        cond = self._cond(x, cond_img)
+    def forward(self, x, update_rate=0.5, return_perception=False, cond_img=None, direction=None):
+        self._refuse_steered_grad(x, direction)
+        dirs, cond = self._steer(x, direction, self._cond(x, cond_img))
         if self._composed(x):
-            out = self._step_multiscale(x.float(), cond, update_rate, self._draw_one(x))
-        elif self._multiscale():
-            out, _ = dynca_nsteps_autograd(self, x, cond, 1, update_rate, two_scale=True)
+            out = self._step_multiscale(x.float(), cond, update_rate, self._draw_one(x), dirs)
         else:
-            out, _ = dynca_nsteps_autograd(self, x, cond, 1, update_rate)
+            with ops.dynca_direction(dirs) if dirs is not None else contextlib.nullcontext():
+                out, _ = dynca_nsteps_autograd(self, x, cond, 1, update_rate, two_scale=self._multiscale())
         if return_perception:
-            return out, self.to_rgb(out), self.perceive_multiscale(x, cond)
+            if dirs is None:
+                return out, self.to_rgb(out), self.perceive_multiscale(x, cond)
+            y = steer.rotate_perception(self.perceive_multiscale(x), dirs, self.c_in)
+            return out, self.to_rgb(out), (y if cond is None else torch.cat([y, cond], dim=1))
         return out, self.to_rgb(out)
 
     def to_rgb(self, x):
@@ -202,17 +235,19 @@ class DyNCA(nn.Module):
         sd = torch.rand(1, c, size_y, size_x) - 0.5
         return sd.repeat(n, 1, 1, 1).to(self.device)
 
-    def forward_nsteps(self, input_state, step_n, update_rate=0.5, return_middle_feature=False, cond_img=None):
-        cond = self._cond(input_state, cond_img)
+    def forward_nsteps(self, input_state, step_n, update_rate=0.5, return_middle_feature=False, cond_img=None, direction=None):
+        self._refuse_steered_grad(input_state, direction)
+        dirs, cond = self._steer(input_state, direction, self._cond(input_state, cond_img))
         if self._composed(input_state):
             x, mids = input_state.float(), []
             for _ in range(step_n):
-                x = self._step_multiscale(x, cond, update_rate, self._draw_one(x))
+                x = self._step_multiscale(x, cond, update_rate, self._draw_one(x), dirs)
                 if return_middle_feature:
                     mids.append(self.to_rgb(x))
             return (x, self.to_rgb(x), mids) if return_middle_feature else (x, self.to_rgb(x))
-        out, states = dynca_nsteps_autograd(self, input_state, cond, step_n, update_rate,
-                                            want_states=return_middle_feature, two_scale=self._multiscale())
+        with ops.dynca_direction(dirs) if dirs is not None else contextlib.nullcontext():
+            out, states = dynca_nsteps_autograd(self, input_state, cond, step_n, update_rate,
+                                                want_states=return_middle_feature, two_scale=self._multiscale())
         feature = self.to_rgb(out)
         if return_middle_feature:
             return out, feature, [self.to_rgb(states[t]) for t in range(1, step_n + 1)]

@@ -25,11 +25,11 @@ class DyNCA(_EdgeDyNCA):
     def _cond(self, x, cond_img=None):
         return None if self.pos_emb_2d is None else self.pos_emb_2d(x).float().contiguous()
 
-    def forward(self, x, update_rate=0.5, return_perception=False):
-        return super().forward(x, update_rate, return_perception, None)
+    def forward(self, x, update_rate=0.5, return_perception=False, direction=None):
+        return super().forward(x, update_rate, return_perception, None, direction)
 
-    def forward_nsteps(self, input_state, step_n, update_rate=0.5, return_middle_feature=False):
-        return super().forward_nsteps(input_state, step_n, update_rate, return_middle_feature, None)
+    def forward_nsteps(self, input_state, step_n, update_rate=0.5, return_middle_feature=False, direction=None):
+        return super().forward_nsteps(input_state, step_n, update_rate, return_middle_feature, None, direction)
 
     def seed(self, n, size=128):
         c, self.c_in = self.c_in, self.c_in - 1  # seed() makes c_in-1 channels (ExtraChannels dynca.py:139-150)

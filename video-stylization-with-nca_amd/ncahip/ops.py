@@ -128,6 +128,44 @@ def dynca_precision(mode: str):
             set_dynca_precision(prev)
 
 
+_dynca_direction_lock = threading.RLock()
+_dynca_direction_cur = None      # the attached field: the reference that keeps its memory alive while the library holds the pointer
+
+
+def _attach_direction(dirs: Optional[torch.Tensor]) -> None:
+    global _dynca_direction_cur
+    if dirs is None:
+        check(lib().ncahip_dynca_direction(None, 0, 0, 0), "dynca_direction")
+    else:
+        check(lib().ncahip_dynca_direction(dirs.data_ptr(), dirs.shape[0], dirs.shape[2], dirs.shape[3]), "dynca_direction")
+    _dynca_direction_cur = dirs
+
+
+@contextlib.contextmanager
+def dynca_direction(dirs: torch.Tensor):
+    """with ops.dynca_direction(dirs): ...  -- the fused DyNCA forward steps of the block rotate every cell's Sobel pair by its
+    direction: dirs [Bd,2,H,W] float32 CUDA contiguous, Bd in {1, B}, plane 0 = s, plane 1 = c; Sx' = c Sx - s Sy, Sy' = s Sx + c Sy
+    (ncahip_dynca_direction in include/ncahip.h; ncahip.steer builds fields).  dynca_step, dynca_nsteps (fp32 states), dynca_clip and
+    dynca_clip_xc honour it; the backward and the bf16-storage steps refuse to run while it is attached.  The block holds a reference
+    to the tensor (the library keeps the pointer, not a copy) and a re-entrant lock, as dynca_precision does; on exit -- exceptions
+    included -- the field attached before the block (normally none) is back.  Do not write to dirs while work enqueued in the block
+    may still run."""
+    if not isinstance(dirs, torch.Tensor) or not dirs.is_cuda:
+        raise _capi.NcaHipError("ncahip: the direction field must be a CUDA (ROCm) tensor -- the NCA hot path has no CPU fallback")
+    if dirs.dtype != torch.float32:
+        raise TypeError(f"ncahip: the direction field must be float32, got {dirs.dtype}")
+    if dirs.dim() != 4 or dirs.shape[1] != 2 or not dirs.is_contiguous():
+        raise ValueError(f"ncahip: the direction field must be a contiguous [Bd,2,H,W] tensor, got {tuple(dirs.shape)}"
+                         f"{'' if dirs.is_contiguous() else ' (not contiguous)'}")
+    with _dynca_direction_lock:
+        prev = _dynca_direction_cur
+        _attach_direction(dirs)
+        try:
+            yield dirs
+        finally:
+            _attach_direction(prev)
+
+
 def dynca_bf16_ok(C: int, fc: int) -> bool:
     """Shapes the 'bf16' DyNCA precision covers: C <= 16 and fc <= 128 (one output tile, one hidden slice)."""
     return 1 <= int(C) <= 16 and 1 <= int(fc) <= 128

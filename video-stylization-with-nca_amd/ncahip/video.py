@@ -131,7 +131,7 @@ def _sized(frames: torch.Tensor, size):
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                  gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic",
-                 precision: str = "f32"):
+                 precision: str = "f32", direction=None):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -159,8 +159,13 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     precision: 'f32' (exact, the default) or 'bf16' -- the steps of this call run under ops.dynca_precision('bf16') (both 1x1 products
     on bf16 MFMA, fp32 accumulation and state; include/ncahip.h, ncahip_dynca_precision), on both routes and for both model families;
     the process-wide mode is afterwards what it was before.  'bf16' needs ops.dynca_bf16_ok(c_in, fc_dim), an fp32 state on the GPU and
-    a model whose steps run on the fused kernels: anything else raises ValueError rather than computing in the other arithmetic."""
-    from . import ops
+    a model whose steps run on the fused kernels: anything else raises ValueError rather than computing in the other arithmetic.
+
+    direction: None, a field tensor [1,2,H,W] or an (alignment, angle_deg) tuple (ncahip.steer; forward_nsteps' keyword): every step of
+    the call rotates each cell's Sobel pair by its direction -- 'flow to the left', 'outwards from the centre', 'round two poles' for a
+    trained motion model.  ONE field serves the whole call (no field per frame), on both routes and for both model families; with a
+    tuple, an extra-channel model's positional encoding is turned by the angle as well.  Needs an fp32 state."""
+    from . import ops, steer
     if precision not in ("f32", "bf16"):
         raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
     if gray not in ops.GRAY_WEIGHTS:
@@ -196,19 +201,33 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         if nca_model._composed(h):
             raise ValueError("precision='bf16' needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
     stylize_clip.last_path = "clip" if fused else "loop"
+    dirs = angle = None
+    if direction is not None:
+        if h.dtype != torch.float32:
+            raise ValueError(f"direction needs a float32 state (the bf16-storage steps do not steer), got {h.dtype}")
+        dirs, angle = steer.resolve(direction, hh, ww, h.device)           # one field for the whole call
+        if dirs.shape[0] != 1:
+            raise ValueError(f"direction field must be [1,2,{hh},{ww}] (the clip runs one sample), got {tuple(dirs.shape)}")
     with ops.dynca_precision(precision) if precision == "bf16" else contextlib.nullcontext():
-        return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in)
+        # the clip route's steps run under the field; the loop route hands it to forward_nsteps, which attaches it per call
+        with ops.dynca_direction(dirs) if (fused and dirs is not None) else contextlib.nullcontext():
+            return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in,
+                                     direction, angle)
 
 
-def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in):
-    """The two routes of stylize_clip (its arguments validated, the state seeded, the precision set)."""
-    from . import ops
+def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in,
+                      direction=None, angle=None):
+    """The two routes of stylize_clip (its arguments validated, the state seeded, the precision set, the clip route's direction field
+    attached).  direction: what the loop route passes on to forward_nsteps; angle: a tuple's angle, for the positional encoding."""
+    from . import ops, steer
     outs = []
     if fused:
         w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
         rate, two = 0.5, list(nca_model.perception_scales) == [0, 1]
         if extra:
             pos = nca_model._cond(h.new_empty(1, nca_model.c_in, hh, ww))        # CPE (or None): a function of the shape alone
+            if pos is not None and angle is not None:
+                pos = steer.rotate_pos_emb(pos, angle)                           # as forward_nsteps turns it
         else:
             layer = nca_model.cond_layer
             bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
@@ -230,6 +249,7 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
             nca_model._mask_step += n * k * step_n
             outs.append(imgs[:, 0])
     else:
+        steer_kw = {} if direction is None else {"direction": direction}      # (a model without the keyword still runs unsteered clips)
         for f0 in range(0, n_frames, per_call):
             chunk = shrink(frames[f0:f0 + per_call].to(dev))
             chunk = _widen(chunk) if u8_in else chunk
@@ -237,10 +257,10 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
                 cond = _gray(chunk[i:i + 1], gray)
                 for _ in range(k):
                     if extra:       # the grey frame as the last state channel, dropped again after the call
-                        x, rgb = nca_model.forward_nsteps(torch.cat((h, cond.to(h.dtype)), 1), step_n)
+                        x, rgb = nca_model.forward_nsteps(torch.cat((h, cond.to(h.dtype)), 1), step_n, **steer_kw)
                         h = x[:, :-1]
                     else:
-                        h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond)
+                        h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond, **steer_kw)
                     img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
                     outs.append((img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img)
     if outs:
