@@ -85,7 +85,11 @@ int ncahip_cond_precision(int mode);
  * wave carries the cells of a partial group across the tiles it owns and runs UpdateNet on them once 16 have come together;
  * same bits for every cell; C > 16 always pads, so the bit changes nothing there);
  * bits 8-15 = a cap on the number of workgroups of a producer/consumer step launch, 0 = no cap (a small grid then gives every
- * workgroup many rounds: what the tests of bit 6's default need; never faster).
+ * workgroup many rounds: what the tests of bit 6's default need; never faster);
+ * bit 7 = ncahip_cond_grow_fwd_f32 never draws its fire masks before its steps (every step draws in the kernel; same bits);
+ * bits 16-23 = a cap on the steps per fire-word launch of that grow, 0 = no cap; a set cap also lets grows that are too short or
+ * too small to gain from it (see ncahip_cond_grow_fwd_f32) draw beforehand, so that the path and its chunking are reachable at
+ * test sizes.
  * Any bit set also keeps ncahip_cond_grow_fwd_persist_f32 from running (it returns NCAHIP_ERANGE). */
 int ncahip_debug_force_generic(int on);
 
@@ -380,6 +384,17 @@ int ncahip_cond_grow_fwd_bf16(uint16_t *states, uint8_t *pre, int ring, int T, u
                               float clamp_lo, float clamp_hi, uint64_t seed, uint64_t step0,
                               ncahip_stream_t stream);
 
+/* The fire masks of ConditionedNCA steps step0 .. step0 + Tc - 1 as the in-kernel Philox draw (u == NULL) produces them, one
+ * 64-bit word per 4 x 16 tile: words [Tc][B][H/4][W/16], bit 16 * row + col of a word <=> cell (4 ty + row, 16 tx + col) fires,
+ * i.e. clamp(u, 0, 1) < fire_rate for the cell's uniform (ncahip_philox_uniform_f32; nca.py:171-174).  What
+ * ncahip_cond_grow_fwd_f32 feeds its steps; exported so that the words can be tested on their own.  H % 4 == 0, W % 16 == 0,
+ * Tc <= 65535, 8-byte aligned words (NCAHIP_ERANGE otherwise).
+ * ncahip_debug_fire_word_launches: how many such launches the last completed ncahip_cond_grow_fwd_f32 of the process made
+ * (0: its steps drew their masks themselves); a test hook. */
+int ncahip_cond_fire_words(uint64_t *words, int Tc, int B, int H, int W, float fire_rate, uint64_t seed, uint64_t step0,
+                           ncahip_stream_t stream);
+int ncahip_debug_fire_word_launches(void);
+
 /* ConditionedNCA.alive(x)                   EncoderConditioning/nca.py:152-163 -> uint8 [B,H,W] */
 int ncahip_cond_alive_u8(const float *x, uint8_t *out, int B, int C, int H, int W,
                          int alive_ch, float alive_thr, ncahip_stream_t stream);
@@ -388,7 +403,15 @@ int ncahip_cond_alive_u8(const float *x, uint8_t *out, int B, int C, int H, int 
  *   T fused steps + one finalize.  states: `ring` slots of B*C*H*W floats, slot 0 = input (true
  *   state); slot k (k>=1) receives the PENDING output of step k-1; pre: `ring` slots of B*H*W
  *   bytes, slot k pairs with states slot k (slot 0 unused).  x_final receives grow()'s result.
- *   ring = 2 ping-pong, ring = T+1 keeps every pending state for the backward pass.          */
+ *   ring = 2 ping-pong, ring = T+1 keeps every pending state for the backward pass.
+ *   x_final may be used as scratch during the call: with in-kernel Philox (u == NULL) on the aligned fast path (C <= 20,
+ *   W % 16 == 0, H % 4 == 0) a grow draws its fire masks before its steps (ncahip_cond_fire_words, one launch per chunk of up to
+ *   32 C steps) into x_final, which is dead until the finalize writes it, and the steps read them instead of drawing: the same
+ *   masks, the same results bit for bit.  It does so only when x_final's bytes are disjoint from the ring, pre, goal and the
+ *   weight tensors; an x_final that is a ring slot (other than the last one, which is refused) is legal and simply keeps the
+ *   steps drawing in the kernel, as do explicit uniforms, bit-packed masks, ncahip_debug_force_generic bit 7, and grows for which
+ *   one more launch does not pay: with r = the 16 x 16 super-tiles per workgroup of a step launch (B * ceil(H/16) * ceil(W/16)
+ *   over min(that, the device's CUs), rounded up), r < 2 or T * r < 106.                                                     */
 int ncahip_cond_grow_fwd_f32(float *states, uint8_t *pre, int ring, int T, float *x_final,
                              const float *goal, int goal_ch, const float *u,
                              const float *wp, const float *w1, const float *b1,

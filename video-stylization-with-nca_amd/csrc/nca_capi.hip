@@ -700,6 +700,51 @@ static int cond_finalize_impl(bool bf16, const void* x_pend, const uint8_t* pre,
                              "cond_finalize");
 }
 
+// ---- fire words: a grow's fire masks drawn before its steps (nca_cond_fire.hip) ---------------------------------------------------
+int ncahip_cond_fire_words(uint64_t* words, int Tc, int B, int H, int W, float fire_rate, uint64_t seed, uint64_t step0,
+                           ncahip_stream_t stream) {
+    if (!words) return fail(NCAHIP_EINVAL, "cond_fire_words: null pointer");
+    if (Tc < 1 || !dims_ok(B, 1, H, W)) return fail(NCAHIP_EINVAL, "cond_fire_words: Tc=%d B=%d H=%d W=%d must all be positive", Tc, B, H, W);
+    if (W % 16 != 0 || H % 4 != 0) return fail(NCAHIP_ERANGE, "cond_fire_words: one word per 4 x 16 tile needs H %% 4 == 0 and W %% 16 == 0 (H=%d W=%d)", H, W);
+    if (Tc > 65535) return fail(NCAHIP_ERANGE, "cond_fire_words: at most 65535 steps per call (Tc=%d)", Tc);
+    if ((size_t)B * (H / 4) * (W / 16) > ((size_t)1 << 31)) return fail(NCAHIP_ERANGE, "cond_fire_words: more than 2^31 tiles per step");
+    if (((uintptr_t)words & 7) != 0) return fail(NCAHIP_ERANGE, "cond_fire_words: 8-byte aligned words required");
+    return hip_result(nca_launch_cond_fire_words(reinterpret_cast<unsigned long long*>(words), Tc, B, H, W, fire_rate, seed, step0, (hipStream_t)stream), "cond_fire_words");
+}
+
+// fire-word launches of the last ncahip_cond_grow_fwd_f32 that enqueued all its steps (0: its steps drew their masks themselves)
+static std::atomic<int> g_fire_word_launches{0};
+int ncahip_debug_fire_word_launches(void) { return g_fire_word_launches.load(std::memory_order_relaxed); }
+constexpr int kForceNoFireWords = 128;   // ncahip_debug_force_generic bit 7
+// Shortest grow that draws its masks beforehand.  One fire-word launch has to be bought back by the steps it serves, and what a step
+// saves grows with the tiles a wave pair stages in it: rounds = super-tiles per workgroup of the step launch.  Measured with the grow
+// timed both ways over a ladder of T (tools/fire_words_cost.py, profiles/r8a_fire_words_cost.jsonl: launch cost / saving per step,
+// the line through the ladder) at B x 16 x 256^2 on 256 CUs, where rounds = B:
+//   rounds 8: 3.34 us / 0.709 us -> break-even  4.7 steps = 38 step-rounds        rounds 2: 5.23 / 0.196 -> 26.7 steps = 53
+//   rounds 4: 4.55 us / 0.416 us -> break-even 10.9 steps = 44 step-rounds        rounds 1: 4.87 / 0.047 -> 104 steps: no gain to speak of
+// (rounds 8: the step kernel's 1.3 us, r8a_kernel_stats.txt against r8a_base_kernel_stats.txt, less the 0.32 us per step the fire-word
+// kernel runs for).  With one round per workgroup nothing is saved, and 8 x 20 x 64^2 and 1 x 20 x 256^2 lost 2 - 3 % over T = 64
+// (tools/bench_paths.py cond_small_persist on the first build, which drew beforehand from T = 10 on at every size: the scalar load
+// sits in the cold first tile).  So: at least two rounds, and T x rounds at least twice the largest break-even measured there, 2 x 53.
+// A chunk cap (ncahip_debug_force_generic bits 16-23) waives both: the tests reach the path on small grids and at small T that way.
+constexpr int kFireWordsMinRounds = 2, kFireWordsMinStepRounds = 106;
+static bool fire_words_pay(int T, int B, int H, int W) {
+    const long nst = (long)B * ((W + 15) / 16) * ((H + 15) / 16), cus = nca_cu_count();
+    const long nwg = nst < cus ? nst : cus, rounds = (nst + nwg - 1) / nwg;   // as launch_cond_pc walks them (nca_cond_pc.hip)
+    return rounds >= kFireWordsMinRounds && (long)T * rounds >= kFireWordsMinStepRounds;
+}
+// x_final can serve as the fire-word scratch: its bytes touch nothing a step reads or writes
+static bool fire_scratch_free(const void* x_final, size_t bytes, const void* states, size_t sbytes, const void* pre, size_t pbytes, const void* goal,
+                              size_t gbytes, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                              int C, int hidden) {
+    const size_t f = sizeof(float);
+    return !clip_overlap(x_final, bytes, states, sbytes) && !clip_overlap(x_final, bytes, pre, pbytes) &&
+           !(goal && clip_overlap(x_final, bytes, goal, gbytes)) && !clip_overlap(x_final, bytes, wp, (size_t)3 * C * 9 * f) &&
+           !clip_overlap(x_final, bytes, w1, (size_t)hidden * 3 * C * f) && !clip_overlap(x_final, bytes, b1, hidden * f) &&
+           !clip_overlap(x_final, bytes, w2, (size_t)hidden * hidden * f) && !clip_overlap(x_final, bytes, b2, hidden * f) &&
+           !clip_overlap(x_final, bytes, w3, (size_t)C * hidden * f);
+}
+
 static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring, int T, void* x_final, const void* goal, int goal_ch, const float* u,
                               const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, int B, int C,
                               int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
@@ -721,16 +766,53 @@ static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring,
     const int sl = T % ring;
     if (x_final == states + (size_t)sl * slot && alive_ch >= 0)
         return fail(NCAHIP_EINVAL, "cond grow: x_final must not alias the last state slot");
-    for (int t = 0; t < T; ++t) {
+    auto step_args = [&](int t) {
         const int si = t % ring, so = (t + 1) % ring;
         NcaCondArgs a{reinterpret_cast<const float*>(states + (size_t)si * slot), t == 0 ? nullptr : pre + (size_t)si * pslot,
                       reinterpret_cast<float*>(states + (size_t)so * slot), pre + (size_t)so * pslot,
                       reinterpret_cast<const float*>(goal), u_at(u, ubits, t, pslot), wp, w1, b1, w2, b2, w3, B, C, H,
                       W, hidden, goal_ch, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0 + (uint64_t)t};
         a.u_bits = ubits;
+        return a;
+    };
+    // Fire words (fp32, in-kernel Philox, the default producer/consumer kernels, whole 4 x 16 tiles): the masks of a chunk of steps
+    // are drawn by one launch of nca_cond_fire.hip into x_final, which is dead until the finalize below writes it, and each step
+    // reads its words instead of drawing.  Same stream, same predicate: the same bits as the steps would draw.
+    unsigned long long* const fw_scratch = reinterpret_cast<unsigned long long*>(x_final);
+    const size_t fw_step = pslot / 64;   // words per step
+    int fw_chunk = 0;                    // steps per fire-word launch; 0: the steps draw their masks themselves
+    const int fw_cap = (g_force_bits >> 16) & 255;   // test hook: steps per fire-word launch; set, it also waives fire_words_pay
+    if (!bf16 && !u && (g_force_bits & kForceNoFireWords) == 0 && (fw_cap > 0 || fire_words_pay(T, B, H, W))) {
+        NcaCondArgs a0 = step_args(0);
+        a0.fire_words = fw_scratch;
+        // every slot is aligned as slots 0 and 1 are (W % 16 == 0 makes the slot size a multiple of 64 bytes)
+        if (nca_cond_fire_words_ok(a0) &&
+            fire_scratch_free(x_final, slot, states, (size_t)ring * slot, pre, (size_t)ring * pslot, goal, (size_t)B * goal_ch * H * W * sizeof(float), wp,
+                              w1, b1, w2, b2, w3, C, hidden)) {
+            fw_chunk = 32 * C;   // slot bytes / (B*H*W / 8 bytes of words per step)
+            if (fw_cap > 0 && fw_chunk > fw_cap) fw_chunk = fw_cap;
+        }
+    }
+    int fw_launches = 0, fw_left = 0;
+    const unsigned long long* fw = nullptr;
+    for (int t = 0; t < T; ++t) {
+        NcaCondArgs a = step_args(t);
+        if (fw_chunk > 0) {
+            if (fw_left == 0) {
+                fw_left = T - t < fw_chunk ? T - t : fw_chunk;
+                if (int rc = hip_result(nca_launch_cond_fire_words(fw_scratch, fw_left, B, H, W, fire_rate, seed, step0 + (uint64_t)t, st), "cond_grow fire words"))
+                    return rc;
+                fw = fw_scratch;
+                ++fw_launches;
+            }
+            a.fire_words = fw;
+            fw += fw_step;
+            --fw_left;
+        }
         if (int rc = bf16 ? hip_result(nca_launch_cond_step_fwd_bf16(a, st), "cond_grow_fwd_bf16") : hip_result(nca_launch_cond_step_fwd(a, st), "cond_grow_fwd"))
             return rc;
     }
+    if (!bf16) g_fire_word_launches.store(fw_launches, std::memory_order_relaxed);
     const uint8_t* const pre_last = pre + (size_t)sl * pslot;
     return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, B, C, H, W, alive_ch,
                                                            alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)")

@@ -74,11 +74,14 @@ struct PCfg {
 // parked in the consumer's carry (FireCarry, on the dead W1 / W2 images); UpdateNet runs when 16 parked cells have come
 // together, whichever tiles of the pair they came from, and once more, padded, after the pair's last round.  Only the consumer
 // wave changes: hand-off, round counters, tile buffers and the producer are those of the kernel without the carry.
-template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false, bool CARRY = false>
+// FW (with FC): the producer takes each tile's fire mask from a.fire_words, drawn before the launch (issue_loads / stage_tile FW),
+// instead of drawing it; the lists it writes are the same, and nothing else changes.
+template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false>
 __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const NcaCondArgs a) {
     static_assert(!SPLIT || ST::BYTES == 4, "bf16x3 emulation is an option of the fp32-storage kernel");
     static_assert(!FC || (ST::BYTES == 4 && !SPLIT), "firing-cell lists: the exact-f32 fp32-storage consumer");
     static_assert(!CARRY || (FC && CP <= 16), "the carry: firing-cell lists on the narrow carve");
+    static_assert(!FW || FC, "fire words: the kernels with firing-cell lists");
     constexpr bool BF = ST::BYTES == 2;   // bf16 storage: UpdateNet on bf16 MFMA (operands rounded from the same LDS image)
     using K = WCfg<CP>;
     using PK = PCfg<CP>;
@@ -193,11 +196,11 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         TileRegs<CP, ST> R;
         const TileLds L = lds_of(which);
         if (t.inner) {
-            issue_loads<CP, true, true, 0, EXACT, ST>(a, t, lane, R);
-            stage_tile<CP, false, EXACT, ST, true, FC>(a, t, L, lane, R, tile_no);
+            issue_loads<CP, true, true, 0, EXACT, ST, FW>(a, t, lane, R);
+            stage_tile<CP, false, EXACT, ST, true, FC, FW>(a, t, L, lane, R, tile_no);
         } else {
-            issue_loads<CP, true, true, 1, EXACT, ST>(a, t, lane, R);
-            stage_tile<CP, true, EXACT, ST, true, FC>(a, t, L, lane, R, tile_no);
+            issue_loads<CP, true, true, 1, EXACT, ST, FW>(a, t, lane, R);
+            stage_tile<CP, true, EXACT, ST, true, FC, FW>(a, t, L, lane, R, tile_no);
         }
     };
     MlpRegs<CP> Wr;        // exact-f32 operands (f32 storage)
@@ -457,10 +460,10 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
 }
 
 int g_pc_wg_cap = 0;       // test hook (ncahip_debug_force_generic bits 8-15): at most this many workgroups per step launch (0: no cap)
-template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false>
+template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false>
 hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     using PK = PCfg<CP>;
-    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC, CARRY>;
+    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC, CARRY, FW>;
     const size_t lds = (size_t)PK::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
@@ -474,12 +477,18 @@ hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
 
 bool g_pc_dense = false;   // test hook (ncahip_debug_force_generic bit 5): the exact-f32 consumer runs every cell
 bool g_pc_nocarry = false; // test hook (bit 6): firing-cell lists with every tile's last group padded (no carry across tiles)
+// the default kernels of the exact-f32, fp32-storage step (no test hook set) have a twin that reads a.fire_words
+bool pc_fire_words_kernels() { return !g_pc_dense && !g_pc_nocarry; }
 // the exact-f32, fp32-storage step: firing-cell lists (narrow carve: with the carry) unless a test hook asks otherwise
 template <int CP, bool EXACT>
 hipError_t launch_cond_pc_f32(const NcaCondArgs& a, hipStream_t st) {
     if (g_pc_dense) return launch_cond_pc<CP, EXACT, StF32, false, false>(a, st);
+    const bool fw = a.fire_words != nullptr && nca_cond_pc_fire_words_ok(a);
     if constexpr (CP <= 16) {
+        if (fw) return launch_cond_pc<CP, EXACT, StF32, false, true, true, true>(a, st);
         if (!g_pc_nocarry) return launch_cond_pc<CP, EXACT, StF32, false, true, true>(a, st);
+    } else {
+        if (fw) return launch_cond_pc<CP, EXACT, StF32, false, true, false, true>(a, st);
     }
     return launch_cond_pc<CP, EXACT, StF32, false, true>(a, st);
 }
@@ -500,6 +509,11 @@ unsigned long long* nca_debug_stamp_ptr() { return g_stamp_pc; }
 static int g_cond_precision = 0;
 void nca_set_cond_precision(int mode) { g_cond_precision = mode; }
 int nca_get_cond_precision() { return g_cond_precision; }
+// the firing-cell-list kernels as they run by default; the words' grid needs whole, aligned tiles and 8-byte aligned words
+bool nca_cond_pc_fire_words_ok(const NcaCondArgs& a) {
+    return pc_fire_words_kernels() && g_cond_precision == 0 && a.u == nullptr && a.C <= 20 && a.W % 16 == 0 && a.H % 4 == 0 &&
+           ((uintptr_t)a.fire_words & 7) == 0;
+}
 hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) {
     NcaCondArgs a = a_in;
     a.dbg = g_stamp_pc;

@@ -248,6 +248,7 @@ struct TileRegs {
     typename ST::raw1 a3v[5];   // alpha' halo 3
     unsigned prv[4];            // previous pre mask bytes, halo 2 (raw: converting at load time would force a wait)
     float uu, up;               // fire-mask uniform of the lane's cell: loaded (explicit uniforms) / in-kernel Philox
+    unsigned long long fw;      // FW: the tile's fire word (wave-uniform), instead of uu / up
     typename ST::raw4 xf[CP / 2], gf[CP / 2];  // state / goal interior 4-cell groups
     typename ST::raw1 xh[CP / 4], gh[CP / 4];  // state / goal halo columns
 };
@@ -265,8 +266,12 @@ struct TileRegs {
 // take the generic kernel).  kAuxCoherent selects the cache policy of the state-type loads (x, pre mask): 0 = ordinary
 // cached loads (a step launch reads only what earlier launches wrote); 16 = sc1, agent-scope coherent -- what a fused
 // multi-step launch with grid barriers needs (tried and measured slower: DESIGN.md section 4).
+// FW: the tile's fire mask comes as one 64-bit word drawn before the launch (a.fire_words, nca_cond_fire.hip; the caller guarantees
+// W % 16 == 0 and H % 4 == 0, so every valid tile is whole and aligned to the words' grid): the word is requested here, through the
+// constant address space -- the address is wave-uniform, so it is one scalar load -- and neither the uniform load nor the Philox
+// block is compiled in.
 constexpr int kAuxCoherent = 0;
-template <int CP, bool STATE, bool GOAL, int CHK = -1, bool EXACT = false, typename ST = StF32>
+template <int CP, bool STATE, bool GOAL, int CHK = -1, bool EXACT = false, typename ST = StF32, bool FW = false>
 __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t, int lane_in, TileRegs<CP, ST>& R) {
     constexpr unsigned SB = ST::BYTES;   // "4" in the names below = one storage element
     const int C = EXACT ? CP : a.C, H = a.H, W = a.W;
@@ -315,7 +320,10 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
             }
         }
     }
-    if (STATE) {
+    if constexpr (STATE && FW) {
+        const size_t wi = ((size_t)t.b * (unsigned)(H >> 2) + (unsigned)(t.ty0 >> 2)) * (unsigned)(W >> 4) + (unsigned)(t.tx0 >> 4);
+        R.fw = *reinterpret_cast<const __attribute__((address_space(4))) unsigned long long*>((size_t)(a.fire_words + wi));
+    } else if (STATE) {
         const int cgy = t.ty0 + q4, cgx = t.tx0 + ci;
         const bool cin = !chk || (cgy < H && cgx < W);
         const unsigned pix = cin ? (unsigned)(__mul24(cgy, W) + cgx) : 0u;
@@ -378,7 +386,8 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
 // the residual.  CHECK=false: no bounds logic.  KEEPX=false: the resolved-state copy XR is not written (callers that only
 // want z, the masks and the fire mask: the backward's front kernel).
 // FCL: instead of the fire mask MK, write the firing-cell list (see kFirePad) into MK and its length into *NF.
-template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true, bool FCL = false>
+// FW (with FCL): the ballot of the tile's firing cells is R.fw (issue_loads FW) -- no uniform, no compare, no ballot here.
+template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true, bool FCL = false, bool FW = false>
 __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t, const TileLds& L, int lane_in,
                                            const TileRegs<CP, ST>& R, int tile_no) {
     float* const Z = L.Z;
@@ -454,19 +463,27 @@ __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t,
     {
         const int cgy = ty0 + q4, cgx = tx0 + ci;
         const bool cin = !CHECK || (cgy < H && cgx < W);
-        // the pick is a bit-mask the compiler cannot see through: a select would be sunk into the branches that
-        // produce the two values, share one register, and force a vmcnt(0) in front of the Philox rounds
-        unsigned um = a.u ? 0xFFFFFFFFu : 0u;
-        asm volatile("" : "+v"(um));
-        float uf = __uint_as_float(__float_as_uint(R.up) | (__float_as_uint(R.uu) & um));
-        if (a.u_bits) {   // the cell's bit of the loaded word: 1 -> fires (0 < rate), 0 -> never (clamp(2) = 1 < rate is false)
-            const unsigned cellg = (unsigned)((size_t)t.b * plane) + (cin ? (unsigned)(__mul24(cgy, W) + cgx) : 0u);
-            uf = ((__float_as_uint(R.uu) >> (cellg & 31u)) & 1u) ? 0.0f : 2.0f;
+        static_assert(!FW || FCL, "fire words feed the firing-cell list");
+        bool fires;
+        [[maybe_unused]] unsigned long long bal = 0ull;   // FCL: the ballot of the tile's firing cells
+        if constexpr (FW) {
+            bal = R.fw;   // every cell of the tile is inside the image (issue_loads FW)
+            fires = ((bal >> lane) & 1ull) != 0ull;
+        } else {
+            // the pick is a bit-mask the compiler cannot see through: a select would be sunk into the branches that
+            // produce the two values, share one register, and force a vmcnt(0) in front of the Philox rounds
+            unsigned um = a.u ? 0xFFFFFFFFu : 0u;
+            asm volatile("" : "+v"(um));
+            float uf = __uint_as_float(__float_as_uint(R.up) | (__float_as_uint(R.uu) & um));
+            if (a.u_bits) {   // the cell's bit of the loaded word: 1 -> fires (0 < rate), 0 -> never (clamp(2) = 1 < rate is false)
+                const unsigned cellg = (unsigned)((size_t)t.b * plane) + (cin ? (unsigned)(__mul24(cgy, W) + cgx) : 0u);
+                uf = ((__float_as_uint(R.uu) >> (cellg & 31u)) & 1u) ? 0.0f : 2.0f;
+            }
+            fires = cin && wclamp(uf, 0.0f, 1.0f) < a.fire_rate;  // nca.py:171-174
+            if constexpr (FCL) bal = __builtin_amdgcn_ballot_w64(fires);
         }
-        const bool fires = cin && wclamp(uf, 0.0f, 1.0f) < a.fire_rate;  // nca.py:171-174
         if constexpr (FCL) {
             // compaction: firing cell j of the tile (in cell order) -> entry j; invalid cells never fire
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(fires);
             const int pre = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
             const int cnt = __popcll(bal);
             int* const FL = reinterpret_cast<int*>(MK);

@@ -155,7 +155,17 @@ struct NcaCondArgs {
     unsigned long long* dbg;  // diagnostic builds (-DNCA_STAMPS) only: per-wave phase time stamps
     unsigned* err;            // sticky error word (nca_error_word_device()), or null
     int u_bits;               // u points at bit-packed fire masks (uint32 words, cell i -> bit i & 31 of word i >> 5; B*H*W < 2^32)
+    // this step's fire masks drawn beforehand (nca_cond_fire.hip): one word per 4 x 16 tile, [B][H/4][W/16], or null = the kernel
+    // draws them.  Needs u == null, W % 16 == 0, H % 4 == 0; read by the kernels nca_cond_fire_words_ok names, ignored by every
+    // other one (which then draws the same masks itself)
+    const unsigned long long* fire_words;
 };
+// the launch nca_launch_cond_step_fwd makes for `a` runs a kernel that reads a.fire_words (shape, alignment -- of a.fire_words too: 8 bytes --, test hooks)
+bool nca_cond_fire_words_ok(const NcaCondArgs& a);
+bool nca_cond_pc_fire_words_ok(const NcaCondArgs& a);   // the same question inside the producer/consumer family (nca_cond_pc.hip)
+// fire words of steps step0 .. step0 + Tc - 1, [Tc][B][H/4][W/16] (nca_cond_fire.hip)
+hipError_t nca_launch_cond_fire_words(unsigned long long* words, int Tc, int B, int H, int W, float fire_rate, uint64_t seed, uint64_t step0,
+                                      hipStream_t st);
 
 // One backward step of the ConditionedNCA grow loop (nca_cond_bwd.hip).  f describes forward step t exactly as
 // it was launched (x_in = states[t], pre_in = pre[t] or null for t == 0, goal, u / seed+step, weights).

@@ -89,7 +89,8 @@ def _w(t: torch.Tensor, name: str, like: torch.Tensor) -> torch.Tensor:
 def force_generic(on) -> None:
     """Test hook (see ncahip.h): True/1 = generic any-shape kernels, 2 = symmetric wave-private ConditionedNCA
     kernel, 32 = fp32 producer/consumer step without firing-cell lists, 64 = firing-cell lists without the carry across
-    tiles, n << 8 = at most n workgroups per producer/consumer step launch, False/0 = defaults."""
+    tiles, 128 = cond_grow's steps draw their fire masks in the kernel (no fire words), n << 8 = at most n workgroups per
+    producer/consumer step launch, n << 16 = at most n steps per fire-word launch (and no minimum grow length or grid size), False/0 = defaults."""
     lib().ncahip_debug_force_generic(int(on))
 
 
@@ -290,6 +291,19 @@ def philox_uniform(B: int, H: int, W: int, seed: int, step: int, device="cuda") 
     u = torch.empty(B, 1, H, W, device=device, dtype=torch.float32)
     check(lib().ncahip_philox_uniform_f32(_p(u), B, H, W, seed, step, _stream()), "philox_uniform")
     return u
+
+
+def cond_fire_words(Tc: int, B: int, H: int, W: int, fire_rate: float, seed: int, step0: int, device="cuda") -> torch.Tensor:
+    """The fire masks of ConditionedNCA steps step0 .. step0 + Tc - 1 (in-kernel Philox) as one 64-bit word per 4 x 16 tile,
+    [Tc, B, H/4, W/16] int64: bit 16 * row + col <=> the tile's cell (row, col) fires (ncahip_cond_fire_words)."""
+    words = torch.empty(Tc, B, H // 4, W // 16, device=device, dtype=torch.int64)
+    check(lib().ncahip_cond_fire_words(_p(words), Tc, B, H, W, fire_rate, seed, step0, _stream()), "cond_fire_words")
+    return words
+
+
+def fire_word_launches() -> int:
+    """Test hook: fire-word launches of the last cond_grow on the per-step fp32 kernels (0: its steps drew in the kernel)."""
+    return int(lib().ncahip_debug_fire_word_launches())
 
 
 # ------------------------------------------------------------------------------------ DyNCA
