@@ -189,8 +189,10 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float *states, int ring, int T, const float *
  *     contract.  Per element the result differs from mode 0 by at most about 2^-8 * sum_j |w2_cj| (|h_j| + sum_k |w1_jk| |y_k|).
  * The mode is read at enqueue time by ncahip_dynca_step_fwd_f32 / _ms_f32, ncahip_dynca_nsteps_fwd_f32 / _ms_f32,
  * ncahip_dynca_nsteps_fwd_persist_f32 / _ms_f32 and ncahip_dynca_clip_f32 / _clip_xc_f32 (once per call of each) -- and by no
- * backward entry point and no bf16-storage one: those always compute exactly, so a history for the backward must be recorded in
- * mode 0.  Range: C <= 16 and fc <= 128.  For any other shape the mode is IGNORED: the result is bit-equal to mode 0.        */
+ * backward entry point and no bf16-storage one.  The exact backward entry points (ncahip_dynca_step_bwd_*_f32 without "bfmma",
+ * ncahip_dynca_nsteps_bwd_f32 / _ms_f32 / _bf16) always compute exactly and need a history recorded in mode 0; the entry points of the
+ * bf16-MFMA training mode (ncahip_dynca_*_bfmma_f32, further down) need a history recorded in mode 1.
+ * Range: C <= 16 and fc <= 128.  For any other shape the mode is IGNORED: the result is bit-equal to mode 0.                  */
 int ncahip_dynca_precision(int mode);
 
 /* ---- steered perception: a per-cell direction field for the DyNCA forward step ------------------------------------------
@@ -289,6 +291,64 @@ int ncahip_dynca_nsteps_bwd_ms_f32(const float *states, int T, const float *cond
                                    const float *g_final, const float *g_states,
                                    float *g_x0, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
                                    void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+
+/* ---- opt-in "bf16-MFMA training" of DyNCA: mode-1 forward history + a backward on bf16 MFMA ---------------------------------
+ * C <= 16 and fc <= 128 (NCAHIP_ERANGE otherwise), single-scale and two-scale, fp32 state history.  No process-wide state: the
+ * caller records the T + 1 history slots with ncahip_dynca_precision mode 1 (ring = T + 1; the forward kernels are unchanged) and
+ * hands them to the entry points below.  The exact backward entry points above keep needing a mode-0 history.
+ * Backward of one step, given x_t from that history and g = dL/dx_{t+1}:
+ *   - y = the fp32 perception of the forward kernels (two-scale: blended) with cond appended; yb = bf16(y);
+ *     a1 = b1 + W1b yb with the rounded weights, the k order and the MFMA sequence of the forward (csrc/nca_dynca_bf16.h, one
+ *     shared routine): a1 has the forward's bits, gate = a1 > 0 is the forward's gate; hb = bf16(relu(a1));
+ *   - gm = g * mask in fp32 (mask as in the forward), gb = bf16(gm);
+ *   - dh = (W2b^T gb) * gate with fp32 accumulation (v_mfma_f32_16x16x16_bf16, K = the channels), dhb = bf16(dh);
+ *   - dL/dy[0:4C] = W1b^T dhb with fp32 accumulation (v_mfma_f32_16x16x32_bf16, K = the hidden units); no gradient into cond;
+ *   - dW2 += gb hb^T, db2 += sum gb, dW1 += dhb [yb | bf16(cond)]^T, db1 += sum dhb: sums over all cells, fp32 accumulation on
+ *     bf16 MFMA (products of two bf16 values are exact in fp32), per-workgroup partials added in a fixed order, no float
+ *     atomics.  The bias gradients sum the ROUNDED operands (db1 rides on the MFMA as a column of ones);
+ *   - dL/dx_t = g (+ g_states[t]) + stencil-adjoint(dL/dy) in fp32: the kernels of the exact backward, two-scale path included;
+ *   - every rounding is to nearest even and straight-through; the k order inside each product is the implementation's and fixed:
+ *     the vector and any-shape kernels agree bit for bit, and two runs give the same bits.
+ * ncahip_dynca_step_bwd_bfmma_f32 mirrors ncahip_dynca_step_bwd_w2_f32 (single-scale); it also writes the two operands of the
+ * layer-1 weight gradient AS BF16: y_out [B,4C,H,W] = yb[0:4C], dh_out [B,fc,H,W] = dhb (half the scratch traffic of the fp32
+ * backward), so that  dW1 | db1 = ncahip_gram_rows_bf16(dh_out, y_out, cond).  dy_scratch [B,4C,H,W] floats, gw2_out [C*fc + C].
+ * The *_workspace queries are host arithmetic and return 0 for a shape outside the range.                                  */
+size_t ncahip_dynca_step_bwd_bfmma_workspace(int B, int C, int H, int W, int fc);
+int ncahip_dynca_step_bwd_bfmma_f32(const float *x_t, const float *cond, const float *u,
+                                    const float *w1, const float *b1, const float *w2, const float *b2,
+                                    int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                    float update_rate, uint64_t seed, uint64_t step,
+                                    const float *g_next, float *g_x, uint16_t *y_out, uint16_t *dh_out,
+                                    float *dy_scratch, float *gw2_out, int accumulate, void *workspace,
+                                    size_t workspace_bytes, ncahip_stream_t stream);
+
+/* ncahip_gram_rows_f32 (below) over bf16 operands: a [B,ma,HW] and b1 [B,nb1,HW] hold bf16, b2 [B,nb2,HW] holds fp32 and is
+ * rounded to bf16 (RNE) as it is loaded (b2 may be NULL with nb2 = 0).  Same output layout [ma x nb | ma], same accumulate flag,
+ * same fixed-order reduction of per-workgroup partials.  The result differs from exact arithmetic on those bf16 values only by
+ * fp32 summation.  ma <= 128, nb = nb1 + nb2 <= 79 (NCAHIP_ERANGE otherwise).                                               */
+size_t ncahip_gram_rows_bf16_workspace(int ma, int nb, int B, int HW);
+int ncahip_gram_rows_bf16(const uint16_t *a, int ma, const uint16_t *b1, int nb1, const float *b2, int nb2, int B, int HW,
+                          float *out, int accumulate, void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+
+/* The T-step drivers of the mode: argument lists, outputs and refusals of ncahip_dynca_nsteps_bwd_f32 / _ms_f32; `states` is the
+ * MODE-1 history.  Per step: the bf16-MFMA MLP kernel (yb, dhb, dL/dy, dW2 | db2), ncahip_gram_rows_bf16, the exact stencil
+ * adjoint (two-scale: up-sampling adjoint, coarse stencil adjoint, 2x2-mean adjoint).  Deterministic.                        */
+size_t ncahip_dynca_nsteps_bwd_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond);
+int ncahip_dynca_nsteps_bwd_bfmma_f32(const float *states, int T, const float *cond, const float *u,
+                                      const float *w1, const float *b1, const float *w2, const float *b2,
+                                      int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                      float update_rate, uint64_t seed, uint64_t step0,
+                                      const float *g_final, const float *g_states,
+                                      float *g_x0, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                                      void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+size_t ncahip_dynca_nsteps_bwd_ms_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond);
+int ncahip_dynca_nsteps_bwd_ms_bfmma_f32(const float *states, int T, const float *cond, const float *u,
+                                         const float *w1, const float *b1, const float *w2, const float *b2,
+                                         int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                         float update_rate, uint64_t seed, uint64_t step0,
+                                         const float *g_final, const float *g_states,
+                                         float *g_x0, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                                         void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
 
 /* Weight-gradient products of the DyNCA backward with the cell axis as K (replaces the library GEMMs over transposed
  * copies that autograd through dynca.py:127-128 amounts to):

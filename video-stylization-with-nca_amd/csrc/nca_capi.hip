@@ -1084,21 +1084,22 @@ struct DyncaBwdPlan {
     size_t n, off_g[2], off_y, off_dy, off_dh, off_ws2, off_wsg, off_acc1, off_acc2, off_pc, off_dpc, off_dxc, off_x32, total;
     int grid2, gridg, K1;
 };
-DyncaBwdPlan dynca_bwd_plan(int B, int C, int H, int W, int fc, int c_cond, bool two_scale = false, bool bf16 = false) {
+// bfmma: the bf16-MFMA training mode -- y and dh are bf16 (half the floats), the gram partials are nca_gram_bf16_grid slabs
+DyncaBwdPlan dynca_bwd_plan(int B, int C, int H, int W, int fc, int c_cond, bool two_scale = false, bool bf16 = false, bool bfmma = false) {
     DyncaBwdPlan p{};
     p.nsl = (fc + 127) / 128;
     p.fs = fc < 128 ? fc : 128;
     p.K1 = 4 * C + c_cond;
     p.n = (size_t)B * C * H * W;
     p.grid2 = two_scale ? nca_dynca_bwd_ms_grid(B, H, W) : nca_dynca_bwd_grid_c(B, C, H, W);
-    p.gridg = nca_gram_grid(B, H * W);
+    p.gridg = bfmma ? nca_gram_bf16_grid(B, H * W) : nca_gram_grid(B, H * W);
     size_t o = 0;
     auto take = [&](size_t floats) { size_t at = o; o += (floats * sizeof(float) + 255) & ~(size_t)255; return at; };
     p.off_g[0] = take(p.n);
     p.off_g[1] = take(p.n);
-    p.off_y = take(4 * p.n);
+    p.off_y = take(bfmma ? 2 * p.n : 4 * p.n);
     p.off_dy = take(4 * p.n);
-    p.off_dh = take((size_t)B * p.fs * H * W);
+    p.off_dh = take(bfmma ? ((size_t)B * p.fs * H * W + 1) / 2 : (size_t)B * p.fs * H * W);
     p.off_ws2 = take((size_t)p.grid2 * ((size_t)C * p.fs + C));
     p.off_wsg = take((size_t)p.gridg * ((size_t)p.fs * p.K1 + p.fs));
     p.off_acc1 = take((size_t)p.nsl * ((size_t)p.fs * p.K1 + p.fs));
@@ -1127,7 +1128,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
                                 const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                 float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                 float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
-                                size_t workspace_bytes, ncahip_stream_t stream) {
+                                size_t workspace_bytes, ncahip_stream_t stream, bool bfmma = false) {
     const char* const states = (const char*)states_v;
     const bool bf16 = sb == 2;
     if (int rc = dynca_dir_refuse("dynca nsteps bwd")) return rc;
@@ -1138,12 +1139,14 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16): B*C*H*W %% 4 == 0 and 8-byte aligned states required");
     if ((size_t)(128 > 4 * C ? 128 : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
+    if (bfmma && !nca_dynca_bf16_shape_ok(C, fc))   // bf16-MFMA training mode: the history is a mode-1 one, the backward its own kernels
+        return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16 MFMA): C=%d fc=%d outside the mode's range (C <= 16, fc <= 128)", C, fc);
     if (two_scale) {
         if (int rc = check_ms(C, H, W, fc, pad_mode, workspace)) return rc;
     }
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
-    const DyncaBwdPlan p = dynca_bwd_plan(B, C, H, W, fc, c_cond, two_scale, bf16);
+    const DyncaBwdPlan p = dynca_bwd_plan(B, C, H, W, fc, c_cond, two_scale, bf16, bfmma);
     if (workspace_bytes < p.total) return fail(NCAHIP_EINVAL, "dynca nsteps bwd: workspace too small");
     if (((uintptr_t)workspace & 15) != 0) return fail(NCAHIP_ERANGE, "dynca nsteps bwd: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -1186,6 +1189,13 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
             a.gw2_ws = ws2;
             a.pc = pcb;
             a.ybuf = sl == 0 ? y : nullptr;
+            if (bfmma) {   // one slice (fc <= 128); y and dh are bf16 buffers in the same workspace regions
+                if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16(a, st), "dynca nsteps bwd step (bf16 MFMA)")) return rc;
+                if (int rc = hip_result(nca_launch_reduce_rows(ws2, acc2, p.grid2, C * fs + C, st, true), "dynca nsteps bwd reduce")) return rc;
+                if (int rc = hip_result(nca_launch_gram_rows_bf16(reinterpret_cast<const uint16_t*>(dh), fs, reinterpret_cast<const uint16_t*>(y), 4 * C,
+                                                                  cond, c_cond, B, H * W, acc1, wsg, st, true), "dynca nsteps bwd gram (bf16 MFMA)")) return rc;
+                continue;
+            }
             if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp(a, st, sl > 0), "dynca nsteps bwd step")) return rc;
             // slabs hold [C x fs | C] of THIS slice (compact); slices narrower than p.fs use the front of their accumulator
             if (int rc = hip_result(nca_launch_reduce_rows(ws2, acc2 + (size_t)sl * a2n, p.grid2, C * fs + C, st, true), "dynca nsteps bwd reduce")) return rc;
@@ -1269,6 +1279,82 @@ int ncahip_gram_rows_f32(const float* a, int ma, const float* b1, int nb1, const
     if (workspace_bytes < ncahip_gram_rows_workspace(ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "gram_rows: workspace too small");
     return hip_result(nca_launch_gram_rows(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream,
                                            accumulate != 0), "gram_rows");
+}
+
+// ---- the bf16-MFMA training mode of DyNCA: stage entry points (the drivers are ncahip_dynca_nsteps_bwd_bfmma_f32 / _ms_) ----------
+size_t ncahip_gram_rows_bf16_workspace(int ma, int nb, int B, int HW) {
+    if (ma <= 0 || ma > 128 || nb <= 0 || nb > 79 || B <= 0 || HW <= 0) return 0;
+    return (size_t)nca_gram_bf16_grid(B, HW) * ((size_t)ma * nb + ma) * sizeof(float);
+}
+
+int ncahip_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
+                          float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!a || !b1 || !out || !workspace || (nb2 > 0) != (b2 != nullptr)) return fail(NCAHIP_EINVAL, "gram_rows_bf16: null pointer");
+    if (ma <= 0 || nb1 <= 0 || nb2 < 0 || B <= 0 || HW <= 0) return fail(NCAHIP_EINVAL, "gram_rows_bf16: bad size");
+    const int nb = nb1 + nb2;
+    if (ma > 128 || nb > 79) return fail(NCAHIP_ERANGE, "gram_rows_bf16: ma=%d nb=%d outside (<=128 x <=79)", ma, nb);
+    if ((((uintptr_t)a | (uintptr_t)b1) & 1) != 0 || (((uintptr_t)b2 | (uintptr_t)out | (uintptr_t)workspace) & 3) != 0)
+        return fail(NCAHIP_ERANGE, "gram_rows_bf16: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)");
+    if (workspace_bytes < ncahip_gram_rows_bf16_workspace(ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "gram_rows_bf16: workspace too small");
+    return hip_result(nca_launch_gram_rows_bf16(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream, accumulate != 0),
+                      "gram_rows_bf16");
+}
+
+size_t ncahip_dynca_step_bwd_bfmma_workspace(int B, int C, int H, int W, int fc) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || !nca_dynca_bf16_shape_ok(C, fc)) return 0;
+    return (size_t)nca_dynca_bwd_grid_c(B, C, H, W) * ((size_t)C * fc + C) * sizeof(float);
+}
+
+int ncahip_dynca_step_bwd_bfmma_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
+                                    const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                    float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
+                                    uint16_t* y_out, uint16_t* dh_out, float* dy_scratch, float* gw2_out, int accumulate,
+                                    void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (int rc = dynca_dir_refuse("dynca step bwd_bfmma")) return rc;
+    if (!g_next || !g_x || !y_out || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: null pointer");
+    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
+    if (!nca_dynca_bf16_shape_ok(C, fc)) return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: C=%d fc=%d outside the bf16-MFMA range (C <= 16, fc <= 128)", C, fc);
+    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: g_next and g_x must not alias");
+    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
+        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
+    if (workspace_bytes < ncahip_dynca_step_bwd_bfmma_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: workspace too small");
+    if (((uintptr_t)workspace & 3) != 0 || (((uintptr_t)y_out | (uintptr_t)dh_out) & 1) != 0)
+        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: misaligned workspace (4 bytes) or bf16 output (2 bytes)");
+    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
+                   g_next, nullptr, reinterpret_cast<float*>(dh_out), dy_scratch, g_x};
+    a.gw2_ws = (float*)workspace;
+    a.ybuf = reinterpret_cast<float*>(y_out);
+    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
+    a.u_bits = u_is_bits(u, seed);
+    if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16(a, (hipStream_t)stream), "dynca_step_bwd_bfmma")) return rc;
+    if (int rc = hip_result(nca_launch_dynca_step_bwd_stencil(a, (hipStream_t)stream), "dynca_step_bwd_bfmma stencil")) return rc;
+    return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
+                                             (hipStream_t)stream, accumulate != 0), "dynca_step_bwd_bfmma reduce");
+}
+
+size_t ncahip_dynca_nsteps_bwd_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_shape_ok(C, fc) || 4 * C + c_cond > 79) return 0;
+    return dynca_bwd_plan(B, C, H, W, fc, c_cond, false, false, true).total;
+}
+size_t ncahip_dynca_nsteps_bwd_ms_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_shape_ok(C, fc) || 4 * C + c_cond > 79) return 0;
+    return dynca_bwd_plan(B, C, H, W, fc, c_cond, true, false, true).total;
+}
+int ncahip_dynca_nsteps_bwd_bfmma_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
+                                      const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                      float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
+                                      float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
+                                      size_t workspace_bytes, ncahip_stream_t stream) {
+    return dynca_nsteps_bwd_impl(false, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true);
+}
+int ncahip_dynca_nsteps_bwd_ms_bfmma_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
+                                         const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                         float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
+                                         float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
+                                         size_t workspace_bytes, ncahip_stream_t stream) {
+    return dynca_nsteps_bwd_impl(true, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true);
 }
 
 // ---- relaxed-EMD part of the OT appearance loss (nca_ot.hip) ---------------------------------------------------------

@@ -1,7 +1,10 @@
 // nca_dynca_bf16.h -- the bf16-MFMA UpdateNet of the DyNCA forward step (ncahip_dynca_precision mode 1; contract: include/ncahip.h).
-// What fixes the bits of that mode exists ONCE, here, and is shared by the per-step kernel (nca_dynca_step.h) and the two persistent
+// What fixes the bits of that mode lives here and is shared by the per-step kernel (nca_dynca_step.h) and the two persistent
 // kernels (nca_dynca_persist.hip): the k order of both products (folded into the LDS weight images), the operand roundings and the
-// MFMA sequence per accumulator.  C <= 16 (one 16-row output tile), fc a multiple of 32 after padding.
+// MFMA sequence per accumulator.  The weight images exist once.  The layer-1 operand packing and MFMA sequence exist TWICE: inside mlp
+// (every forward kernel) and as pack_y / layer1 (the bf16-MFMA backward), see the note at layer1; test_gpu_dynca_train_bf16.py compares
+// the two on the device at both shape classes, with and without conditioning.  C <= 16 (one 16-row output tile), fc a multiple of 32
+// after padding.
 //
 // k order.  v_mfma_f32_16x16x32_bf16 takes eight k values per lane: lane (g, i) supplies k = 8g + j, j = 0..7.
 //   layer 1: lane (g, cell) holds y slots s = 0..K1S-1 (s = 4c'+f < CP: channel 4c'+g, filter f; s = CP: conditioning channel g) --
@@ -38,6 +41,38 @@ struct NcaDyncaBf16 {
         const int jj = idx & 3, l = (idx >> 2) & 63, p = idx >> 8;
         const int j = 2 * jj + hf, gg = l >> 4, o = l & 15, k = 16 * (2 * p + (j >> 2)) + 4 * gg + (j & 3);
         return (o < C && k < fc) ? (long)o * fc + k : -1;
+    }
+
+    // the layer-1 B operands of NT groups: y slots 8q .. 8q+7 of chunk q rounded to bf16 (RNE), zero beyond K1S
+    template <int NT>
+    static __device__ __forceinline__ void pack_y(const float (&P)[NT][K1S], nca_u32x4 (&PB)[NT][K1Q]) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < K1Q; ++q)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int s = 8 * q + 2 * jj;
+                    PB[n][q][jj] = nca_pk_bf16(s < K1S ? P[n][s < K1S ? s : 0] : 0.0f, s + 1 < K1S ? P[n][s + 1 < K1S ? s + 1 : 0] : 0.0f);
+                }
+    }
+    // acc1 = b1 + W1 PB of hidden tile m (register r: hidden unit 16m + 4g + r of the lane's cell), chunks in ascending order.
+    // pack_y and layer1 are the operand packing and the per-accumulator MFMA sequence of mlp below, as functions, for the bf16-MFMA
+    // backward (nca_dynca_step.h): its pre-activation has the forward's bits, hence the forward's gate.  mlp keeps its own text: written
+    // through these two, the forward kernels were scheduled differently (their instruction streams are held fixed).  Change all three
+    // together; test_gpu_dynca_train_bf16.py (gate test) compares the two on the device.
+    template <int NT>
+    static __device__ __forceinline__ void layer1(const nca_u32x4* W1B, const float* B1L, int m, int g, const nca_u32x4 (&PB)[NT][K1Q],
+                                                  f32x4 (&acc1)[NT]) {
+        const f32x4 bias1 = *reinterpret_cast<const f32x4*>(B1L + 16 * m + 4 * g);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc1[n] = bias1;
+#pragma unroll
+        for (int q = 0; q < K1Q; ++q) {
+            const nca_u32x4 wa = W1B[(m * K1Q + q) * 64];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc1[n] = nca_mfma_bf16(wa, PB[n][q], acc1[n]);
+        }
     }
 
     // acc2 = b2 + W2 bf16(relu(b1 + W1 bf16(P))) for NT groups of 16 cells; fp32 accumulation, biases as initial values
@@ -90,5 +125,24 @@ struct NcaDyncaBf16 {
 #pragma unroll
             for (int n = 0; n < NT; ++n) acc2[n] = nca_mfma_bf16(wb, hb[n], acc2[n]);
         }
+    }
+
+    // ---- the bf16-MFMA backward (the "bf16-MFMA training" mode of include/ncahip.h): two transposed weight images -----------------
+    //   dh = W2b^T gb on v_mfma_f32_16x16x16_bf16 (K = the 16 channel slots, four k per lane: k = 4g + j).  Image [tile m][lane] of
+    //        8 bytes: lane (g, i), j  <->  W2[ch = 4g + j][hidden 16m + i]; as words idx = (m * 64 + lane) * 2 + jj.
+    //   dL/dy = W1b^T dhb on v_mfma_f32_16x16x32_bf16, K = the hidden units in the pair order of the forward's layer 2 (k = 8g + j  <->
+    //        hidden 16 (2p + j / 4) + 4g + j % 4: the operand is two consecutive dh accumulator tiles as they stand).  Output tile mj,
+    //        row i  <->  channel 4mj + (i & 3), filter i >> 2.  Image [pair p][tile mj][lane] of 16 bytes.
+    static constexpr int MJ = CP / 4;
+    static constexpr int W2T_WORDS = M1T * 128, W1T_WORDS = M1P * MJ * 256;
+    static __device__ __forceinline__ long w2t_src(int idx, int hf, int C, int fc) {
+        const int jj = idx & 1, l = (idx >> 1) & 63, m = idx >> 7;
+        const int ch = 4 * (l >> 4) + 2 * jj + hf, k = 16 * m + (l & 15);
+        return (ch < C && k < fc) ? (long)ch * fc + k : -1;
+    }
+    static __device__ __forceinline__ long w1t_src(int idx, int hf, int C, int CC, int fc) {
+        const int jj = idx & 3, l = (idx >> 2) & 63, e = idx >> 8, mj = e % MJ, p = e / MJ;
+        const int j = 2 * jj + hf, i = l & 15, k = 16 * (2 * p + (j >> 2)) + 4 * (l >> 4) + (j & 3), ch = 4 * mj + (i & 3);
+        return (k < fc && ch < C) ? (long)k * (4 * C + CC) + (i >> 2) * C + ch : -1;
     }
 };

@@ -1,6 +1,7 @@
-// nca_dynca_step.h -- the fused DyNCA step kernel for MI355X (gfx950), fp32 exact: kernel template, its ten named variants, the
+// nca_dynca_step.h -- the fused DyNCA step kernel for MI355X (gfx950), fp32 exact: kernel template, its twelve named variants, the
 // one launcher and the one dispatch ladder.  nca_dynca_fwd.hip instantiates the forward variants, nca_dynca_bwd.hip the backward
-// ones, nca_dynca_steer.hip (a unit of its own) the steered forward variants DyncaSteered<V>.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
+// ones, nca_dynca_steer.hip (a unit of its own) the steered forward variants DyncaSteered<V>, nca_dynca_bwd_bf16.hip (a unit of its
+// own) the two bf16-MFMA backward variants.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
 //
 // One persistent launch per NCA step.  A workgroup (4 waves) owns TH x TW cell tiles:
 //   1. the state tile (+1 halo, pad mode resolved at load time; ConditionedNCA: the pending
@@ -66,7 +67,9 @@ struct DyncaCfg {
     // filters (row i <-> channel 4mj + (i & 3), filter i >> 2): MJ = CP / 4 tiles, no conditioning rows (dynca.py:123).
     static constexpr int MJ = CP / 4;
     static constexpr int LDS_FLOATS_BWD = OFF_CN;                     // the backward reads the conditioning straight from memory (no CN tile)
-    static constexpr int TBS = M2T == 1 ? 20 : 36;                    // transposition tiles [16 cells][TBS] (16-byte rows)
+    // transposition tiles [16 cells][TBS] (16-byte rows).  bf16-MFMA backward: unpadded -- lane (g, ci) writes 16 bytes at 16 ci + 4g and
+    // reads word 64 s + 16 g + ci, both conflict-free, and the 2 KB saved are what lets <16, 128> with conditioning keep two workgroups per CU
+    static constexpr int TBS = BF ? 16 : (M2T == 1 ? 20 : 36);
     static constexpr int OFF_TB = LDS_FLOATS_BWD;                     // fused dW2: per wave NT tiles
     static constexpr int LDS_FLOATS_BWD_W2 = OFF_TB + 4 * NT * 16 * TBS;
     static_assert(FC % 16 == 0 && CP % 4 == 0 && TW % 16 == 0, "shape");
@@ -75,13 +78,14 @@ struct DyncaCfg {
     static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 };
 
-// ---- the ten variants of the step kernel: each names one combination of the six switches the kernel body reads ----------------
+// ---- the twelve variants of the step kernel: each names one combination of the six switches the kernel body reads -------------
 //   BWD  the backward data path of the step instead of the forward MLP (see the kernel)
 //   B16  bf16 state storage: x_in / x_out hold bf16, exact f32 compute, round-to-nearest-even on store
 //   ACC  a later 128-wide slice of a wide hidden layer: adds to what the earlier launches wrote
 //   W2F  backward with the layer-2 weight gradient fused in (per-workgroup dW2 | db2 partials, h is not written)
 //   MS   two-scale perception: the coarse-level perception tile is staged in LDS and blended in
-//   BF   both 1x1 products of the forward on bf16 MFMA (ncahip_dynca_precision mode 1)
+//   BF   both 1x1 products of the forward on bf16 MFMA (ncahip_dynca_precision mode 1); with BWD: every product of the backward on bf16
+//        MFMA, y and dh written as bf16 through ybuf / dhbuf (the "bf16-MFMA training" mode of include/ncahip.h)
 //   STEER the perception's Sobel pair rotated by the cell's direction (NcaDyncaArgs::dirs, ncahip_dynca_direction): DyncaSteered<V> of a
 //        forward variant V with fp32 storage.  A switch and not a launch-uniform branch on the pointer: with the branch the unsteered
 //        kernels took up to 60 more registers, and the bf16-MFMA and one-launch kernels spilled ("Steered perception")
@@ -98,6 +102,10 @@ struct DyncaBwd : DyncaVariant { static constexpr bool BWD = true; };           
 struct DyncaBwdW2 : DyncaVariant { static constexpr bool BWD = true, W2F = true; };                 // backward, fused dW2
 struct DyncaBwdW2Ms : DyncaVariant { static constexpr bool BWD = true, W2F = true, MS = true; };    // backward, fused dW2, two-scale
 struct DyncaBwdW2Acc : DyncaVariant { static constexpr bool BWD = true, W2F = true, ACC = true; };  // backward, fused dW2, accumulating slice
+// BWD and BF together: the "bf16-MFMA training" backward (include/ncahip.h): every product on bf16 MFMA, y and dh written as bf16.
+// nca_dynca_bwd_bf16.hip (a unit of its own) instantiates these two.
+struct DyncaBwdBf : DyncaVariant { static constexpr bool BWD = true, W2F = true, BF = true; };                  // backward, fused dW2, bf16 MFMA
+struct DyncaBwdBfMs : DyncaVariant { static constexpr bool BWD = true, W2F = true, MS = true, BF = true; };    // the same, two-scale
 
 // BWD = true: the backward data path of the same step (autograd through dynca.py:117-138).  Recomputes the
 // hidden layer, then dh = (W2^T (G*mask)) * 1[h>0] and dL/dy = W1^T dh on MFMA (accumulator tile == next B
@@ -144,7 +152,27 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
     };
     auto map_b1 = [&](int idx) -> long { return idx < fc ? idx : -1; };
     auto map_b2 = [&](int idx) -> long { return (idx < C && !ACC) ? idx : -1; };
-    if constexpr (BF) {   // both weights rounded to bf16 (RNE) here, once; eight k values per lane and entry in the bf16 k order
+    if constexpr (BF && BWD) {
+        // bf16-MFMA backward: the forward's layer-1 image (same bits: same pre-activation), W2^T where the forward keeps W2 (the
+        // backward never forms layer 2), W1^T behind the variant's carve; all rounded to bf16 (RNE) here, once.  b2 is not needed.
+        using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
+        auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
+        auto bmap_w2t = [&](int idx, int hf) -> long { return BFK::w2t_src(idx, hf, C, fc); };
+        auto bmap_w1t = [&](int idx, int hf) -> long { return BFK::w1t_src(idx, hf, C, CC, fc); };
+        static_assert(BFK::W2T_WORDS == BFK::W2_WORDS, "W2^T takes the place of the forward's W2 image");
+        FillP<BFK::W1_WORDS> f1;
+        FillP<BFK::W2T_WORDS> f2;
+        FillP<BFK::W1T_WORDS> f5;
+        FillV<FC> f3;
+        fill_issue_pk(f1, a.w1, tid, bmap_w1);
+        fill_issue_pk(f2, a.w2, tid, bmap_w2t);
+        fill_issue_pk(f5, a.w1, tid, bmap_w1t);
+        fill_issue(f3, a.b1, tid, map_b1);
+        fill_commit_pk(f1, W1L, tid, bmap_w1);
+        fill_commit_pk(f2, W2L, tid, bmap_w2t);
+        fill_commit_pk(f5, smem + K::LDS_FLOATS_BWD_W2 + (MS ? 4 * CP * K::PCS : 0), tid, bmap_w1t);
+        fill_commit(f3, B1L, tid, map_b1);
+    } else if constexpr (BF) {   // both weights rounded to bf16 (RNE) here, once; eight k values per lane and entry in the bf16 k order
         using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
         auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
         auto bmap_w2 = [&](int idx, int hf) -> long { return BFK::w2_src(idx, hf, C, fc); };
@@ -340,7 +368,147 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
                     } else P[n][CP] = CN[g * TH * TW + r0[n] * TW + q0[n]];
                 }
             }
-            if constexpr (BWD) {
+            if constexpr (BWD && BF) {
+                // ---- backward data path on bf16 MFMA ("bf16-MFMA training", include/ncahip.h) -------------------------------
+                // Lane (g, ci) of group n holds, in the accumulator layout throughout: a1 / dh of hidden 16m + 4g + r, gb of channel
+                // 4g + r, dL/dy of (filter g, channel 4mj + r), all of cell ci.  Every operand is rounded once (RNE) and every
+                // consumer reads those bits: yb feeds layer 1 and is written out, gb feeds dh, dW2 and db2, dhb feeds dL/dy and
+                // is written out, hb feeds dW2.
+                using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
+                static_assert(NT == 2 && K::M2T == 1, "dW2 takes the pass's 2 x 16 cells as ONE K = 32 product");
+                typedef short nca_s16x4 __attribute__((ext_vector_type(4)));
+                typedef unsigned nca_u32x2 __attribute__((ext_vector_type(2)));
+                const nca_u32x4* const W1B = reinterpret_cast<const nca_u32x4*>(W1L) + lane;
+                const nca_u32x2* const W2T = reinterpret_cast<const nca_u32x2*>(W2L) + lane;
+                const nca_u32x4* const W1T = reinterpret_cast<const nca_u32x4*>(smem + K::LDS_FLOATS_BWD_W2 + (MS ? 4 * CP * K::PCS : 0)) + lane;
+                auto lo16 = [](unsigned w) { return __uint_as_float(w << 16); };
+                auto hi16 = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
+                bool live[NT];
+                size_t cello[NT];
+                nca_u32x2 gbp[NT];      // gb = bf16(g * mask), channels 4g .. 4g + 3
+                unsigned doTp[4];       // the same, transposed: channel ci of cells (n, 4s + g), k = 4n + s
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    const int gy = ty0 + r0[n], gx = tx0 + q0[n];
+                    live[n] = gy < H && gx < W;
+                    cello[n] = live[n] ? (size_t)gy * W + gx : 0;
+                    const float mk = MK[r0[n] * TW + q0[n]];
+                    const float* const gp = a.g_next + (size_t)b * C * plane + cello[n];
+                    float gm[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = 4 * g + r;
+                        const float gv = gp[(size_t)min(ch, C - 1) * plane];
+                        gm[r] = (live[n] && ch < C) ? gv * mk : 0.0f;
+                    }
+                    gbp[n] = nca_u32x2{nca_pk_bf16(gm[0], gm[1]), nca_pk_bf16(gm[2], gm[3])};
+                    const f32x4 gr = f32x4{lo16(gbp[n][0]), hi16(gbp[n][0]), lo16(gbp[n][1]), hi16(gbp[n][1])};
+                    *reinterpret_cast<f32x4*>(TBW + n * 16 * K::TBS + ci * K::TBS + 4 * g) = gr;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) b2acc[0][r] += gr[r];   // db2 sums the rounded operand
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    float t4[4];
+#pragma unroll
+                    for (int s_ = 0; s_ < 4; ++s_) t4[s_] = TBW[n * 16 * K::TBS + (4 * s_ + g) * K::TBS + ci];
+                    doTp[2 * n] = nca_pk_bf16(t4[0], t4[1]);         // exact: the values are bf16 already
+                    doTp[2 * n + 1] = nca_pk_bf16(t4[2], t4[3]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                nca_u32x4 PB[NT][BFK::K1Q];
+                BFK::template pack_y<NT>(P, PB);
+                // yb out: slot s = 4c' + f of lane (g, cell) is row f*C + 4c' + g of perceive_torch's output (conditioning slot: not written)
+                {
+                    uint16_t* const yo = reinterpret_cast<uint16_t*>(a.ybuf) + (size_t)b * 4 * C * plane;
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+                        if (!live[n]) continue;
+#pragma unroll
+                        for (int s = 0; s < CP; ++s)
+                            if ((s & ~3) + g < C) {
+                                const unsigned w = PB[n][s >> 3][(s & 7) >> 1];
+                                yo[(size_t)((s & 3) * C + (s & ~3) + g) * plane + cello[n]] = (uint16_t)((s & 1) ? (w >> 16) : (w & 0xffffu));
+                            }
+                    }
+                }
+                uint16_t* const dho = reinterpret_cast<uint16_t*>(a.dhbuf) + (size_t)b * fc * plane;
+                f32x4 dY[K::MJ][NT];
+#pragma unroll
+                for (int mj = 0; mj < K::MJ; ++mj)
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) dY[mj][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int p = 0; p < BFK::M1P; ++p) {
+                    nca_u32x4 dhb[NT];
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int m = 2 * p + hf;
+                        f32x4 acc1[NT], dacc[NT];
+                        BFK::template layer1<NT>(W1B, B1L, m, g, PB, acc1);
+                        const nca_u32x2 wt2 = W2T[m * 64];
+#pragma unroll
+                        for (int n = 0; n < NT; ++n)
+                            dacc[n] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(nca_s16x4, wt2), __builtin_bit_cast(nca_s16x4, gbp[n]),
+                                                                                f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            float hv[4], dv[4];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                hv[r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu, as the forward takes it
+                                dv[r] = acc1[n][r] > 0.0f ? dacc[n][r] : 0.0f;                // relu' = 0 at exactly 0
+                            }
+                            const unsigned h01 = nca_pk_bf16(hv[0], hv[1]), h23 = nca_pk_bf16(hv[2], hv[3]);
+                            const unsigned d01 = nca_pk_bf16(dv[0], dv[1]), d23 = nca_pk_bf16(dv[2], dv[3]);
+                            dhb[n][2 * hf] = d01;
+                            dhb[n][2 * hf + 1] = d23;
+                            if (live[n]) {
+                                uint16_t* const o = dho + (size_t)(16 * m + 4 * g) * plane + cello[n];
+                                if (16 * m + 4 * g + 0 < fc) o[0] = (uint16_t)(d01 & 0xffffu);
+                                if (16 * m + 4 * g + 1 < fc) o[plane] = (uint16_t)(d01 >> 16);
+                                if (16 * m + 4 * g + 2 < fc) o[2 * plane] = (uint16_t)(d23 & 0xffffu);
+                                if (16 * m + 4 * g + 3 < fc) o[3 * plane] = (uint16_t)(d23 >> 16);
+                            }
+                            // hb of the group, for dW2 (cells outside the image and hidden units beyond fc meet gb = 0 / are never read)
+                            *reinterpret_cast<f32x4*>(TBW + n * 16 * K::TBS + ci * K::TBS + 4 * g) = f32x4{lo16(h01), hi16(h01), lo16(h23), hi16(h23)};
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        nca_u32x4 hTp;
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            float t4[4];
+#pragma unroll
+                            for (int s_ = 0; s_ < 4; ++s_) t4[s_] = TBW[n * 16 * K::TBS + (4 * s_ + g) * K::TBS + ci];
+                            hTp[2 * n] = nca_pk_bf16(t4[0], t4[1]);
+                            hTp[2 * n + 1] = nca_pk_bf16(t4[2], t4[3]);
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tiles are rewritten by the next hidden tile
+                        w2acc[m][0] = nca_mfma_bf16(nca_u32x4{doTp[0], doTp[1], doTp[2], doTp[3]}, hTp, w2acc[m][0]);
+                    }
+#pragma unroll
+                    for (int mj = 0; mj < K::MJ; ++mj) {
+                        const nca_u32x4 wt1 = W1T[(p * K::MJ + mj) * 64];
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) dY[mj][n] = nca_mfma_bf16(wt1, dhb[n], dY[mj][n]);
+                    }
+                }
+                // dL/dy out, fp32: tile mj, register r of lane (g, cell) = channel 4mj + r, filter g -> plane g*C + 4mj + r
+                const unsigned plane4 = (unsigned)plane * 4u;
+                const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(a.dybuf + (size_t)b * 4 * C * plane, 0, -1, 0x00020000);
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    if (!live[n]) continue;
+                    const unsigned voy = (unsigned)cello[n] * 4u + (unsigned)(g * C) * plane4;
+#pragma unroll
+                    for (int mj = 0; mj < K::MJ; ++mj)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (4 * mj + r < C)
+                                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dY[mj][n][r]), rdy, (int)voy, (int)((unsigned)(4 * mj + r) * plane4), 0);
+                }
+            } else if constexpr (BWD) {
                 // ---- backward data path -----------------------------------------------------------------
                 float dO[NT][K::M2T][4];   // dL/d(out) = G * mask, accumulator layout (channel 16 m2 + 4g + r, cell ci)
                 bool live[NT];
@@ -686,7 +854,9 @@ hipError_t launch_dynca(const NcaDyncaArgs& a, hipStream_t st) {
     constexpr int NT = V::BWD ? 2 : 4;           // backward: two 16-cell groups per pass: 2 workgroups per CU at C <= 16 (registers and LDS)
     using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, V::BF>;
     // two-scale: the coarse perception tile follows the variant's own carve (forward: K::OFF_PC; backward: after the dW2 tiles)
-    constexpr int LDS_FLOATS = V::BWD ? (V::W2F ? K::LDS_FLOATS_BWD_W2 : K::LDS_FLOATS_BWD) + (V::MS ? 4 * CP * K::PCS : 0)
+    // (the bf16-MFMA backward keeps its W1^T image, FC / 32 * CP / 4 entries of 1 KiB, behind all of that)
+    constexpr int LDS_FLOATS = V::BWD ? (V::W2F ? K::LDS_FLOATS_BWD_W2 : K::LDS_FLOATS_BWD) + (V::MS ? 4 * CP * K::PCS : 0) +
+                                            ((V::BWD && V::BF) ? (FC / 32) * (CP / 4) * 256 : 0)
                                       : (V::MS ? K::LDS_FLOATS_MS : K::LDS_FLOATS);
     static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
     static_assert(!V::W2F || 4 * (16 * K::M2T * FC + 16 * K::M2T) <= K::LDS_FLOATS_BWD_W2, "the four waves' dW2 | db2 partials are summed through LDS");

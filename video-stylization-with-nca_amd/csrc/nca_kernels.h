@@ -55,7 +55,7 @@ struct NcaDyncaArgs {
     // dL/dperception out, dL/dx_t out (stencil-adjoint kernel)
     const float* g_next;   // [B,C,H,W]
     float* hbuf;           // relu(w1 y + b1)                [B,fc,H,W]
-    float* dhbuf;          // dL/d(pre-activation)           [B,fc,H,W]
+    float* dhbuf;          // dL/d(pre-activation)           [B,fc,H,W]   (bf16-MFMA backward variants: points at bf16, as ybuf does)
     float* dybuf;          // dL/dy, first 4C rows           [B,4C,H,W]
     float* g_out;          // dL/dx_t                        [B,C,H,W]
     // fc > 128 runs as several launches over 128-wide slices of the hidden layer (nca_launch_dynca_step_fwd):
@@ -211,6 +211,12 @@ int nca_dynca_bwd_grid_c(int B, int C, int H, int W);   // the grid the backward
 int nca_gram_grid(int B, int HW);
 hipError_t nca_launch_gram_rows(const float* a, int ma, const float* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                 float* out, float* ws, hipStream_t st, bool accumulate = false);
+// nca_gram_bf16.hip: the same product over bf16 operands (a, b1: bf16; b2: fp32, rounded as loaded); ma <= 128, nb1 + nb2 <= 79
+int nca_gram_bf16_grid(int B, int HW);
+hipError_t nca_launch_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
+                                     float* out, float* ws, hipStream_t st, bool accumulate = false);
+// nca_dynca_bwd_bf16.hip: MLP part of one backward step in the bf16-MFMA training mode (ybuf / dhbuf point at bf16 buffers)
+hipError_t nca_launch_dynca_step_bwd_mlp_bf16(const NcaDyncaArgs& a, hipStream_t st);
 hipError_t nca_launch_reduce_wp(const float* part, float* dst, int B, int C, int H, int W, hipStream_t st);
 // nca_ot.hip: relaxed-EMD part of the OT appearance loss (gather / normalise, N x N cosine distances reduced in registers, adjoints)
 int nca_ot_bands(int N);   // column-minimum partials per column (one per 32-row band)

@@ -116,7 +116,9 @@ class _DyncaNSteps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cond, w1, b1, w2, b2, cfg):
         w = ops.DyncaWeights(w1, b1, w2, b2, x)
-        with ops.dynca_precision("f32"):      # the backward recomputes the hidden layer exactly: the history must be the exact one
+        # the backward recomputes the hidden layer: the history must be the one of ITS precision (cfg["precision"], the effective
+        # train_precision), whatever the ambient ops.dynca_precision is
+        with ops.dynca_precision(cfg.get("precision", "f32")):
             out, states = ops.dynca_nsteps(x, cfg["T"], cond, cfg["us"], w, cfg["pad"], cfg["rate"], cfg["seed"],
                                            cfg["step0"], keep_history=True, two_scale=cfg.get("two_scale", False))
         ctx.cfg, ctx.w = cfg, w
@@ -132,17 +134,35 @@ class _DyncaNSteps(torch.autograd.Function):
             gfin = gfin + g_states[cfg["T"]]
         g = ops.dynca_nsteps_backward(states, cond if cond.numel() else None, cfg["us"], ctx.w, gfin.float(),
                                       g_states, cfg["T"], cfg["pad"], cfg["rate"], cfg["seed"], cfg["step0"],
-                                      two_scale=cfg.get("two_scale", False))
+                                      two_scale=cfg.get("two_scale", False), precision=cfg.get("precision", "f32"))
         return g["x0"].to(states.dtype), None, g["w1"][:, :, None, None], g["b1"], g["w2"][:, :, None, None], g["b2"], None  # no grad to cond (dynca.py:123)
 
 
+def dynca_train_precision(model, x) -> str:
+    """The precision a differentiated forward_nsteps of `model` on state `x` runs in: the model's train_precision where the bf16-MFMA
+    training mode covers the shape (ops.dynca_bf16_ok), "f32" otherwise -- outside the range the setting is ignored, forward and
+    backward are then the exact ones.  Where the mode WOULD be selected, a bfloat16 pool raises: bf16 state storage is outside the mode
+    (outside the range the setting is ignored for a bfloat16 pool as for any other, and dynca_nsteps_autograd asks only when it
+    differentiates)."""
+    want = getattr(model, "train_precision", "f32")
+    if want != "bf16" or not ops.dynca_bf16_ok(x.shape[1], model.w1.weight.shape[0]):
+        return "f32"
+    if x.dtype == torch.bfloat16:
+        raise ValueError("ncahip: train_precision='bf16' (bf16-MFMA training) takes a float32 state; a bfloat16 pool is bf16 STORAGE, "
+                         "which that mode does not cover")
+    return "bf16"
+
+
 def dynca_nsteps_autograd(model, x, cond, T, update_rate, want_states=False, two_scale=False):
+    params = (model.w1.weight, model.w1.bias, model.w2.weight, model.w2.bias)
+    # the EFFECTIVE precision: recorded in cfg, so that a backward that runs much later, on an autograd thread, uses what the forward
+    # used.  Asked only where a history is recorded: a call without gradients is the ambient ops.dynca_precision's business.
+    precision = dynca_train_precision(model, x) if _needs_grad(x, *params) else "f32"
     bf16 = x.dtype == torch.bfloat16      # bf16 pool: bf16-storage entry points (storage format only), forward and backward
     x = x.contiguous() if bf16 else x.float().contiguous()
-    params = (model.w1.weight, model.w1.bias, model.w2.weight, model.w2.bias)
     us = model._draw(x, T, update_rate)
     cfg = dict(T=T, us=us, pad=model.padding_mode, rate=float(update_rate), seed=model.mask_seed, step0=model._mask_step,
-               want_states=want_states, two_scale=two_scale)
+               want_states=want_states, two_scale=two_scale, precision=precision)
     model._mask_step += T
     if _needs_grad(x, *params):
         return _DyncaNSteps.apply(x, cond, *params, cfg)

@@ -28,8 +28,11 @@ from . import dist as ncadist
 class DyNCATrainer:
     def __init__(self, model, loss_fn: Callable, pool_size: int = 256, size=(128, 128), batch_size: int = 4,
                  nca_steps: Sequence[int] = (32, 128), lr: float = 1e-3, lr_decay_step: Sequence[int] = (1000, 2000),
-                 inject_seed_step: int = 8, device: Optional[torch.device] = None, reseed_offset: int = 424):
+                 inject_seed_step: int = 8, device: Optional[torch.device] = None, reseed_offset: int = 424,
+                 train_precision: Optional[str] = None):
         self.model, self.loss_fn = model, loss_fn
+        if train_precision is not None:       # "f32" / "bf16" (bf16-MFMA training, models.dynca.DyNCA.train_precision); None: the model's own
+            model.train_precision = train_precision
         self.device = device if device is not None else next(model.parameters()).device
         self.size, self.batch_size = size, batch_size
         self.min_steps, self.max_steps = nca_steps

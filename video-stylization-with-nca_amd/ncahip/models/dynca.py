@@ -106,6 +106,22 @@ class DyNCA(nn.Module):
         self.identity_filter = torch.tensor([[0.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 0.0]], device=device)
         self.laplacian_filter = torch.tensor([[1.0, 2.0, 1.0], [2.0, -12.0, 2.0], [1.0, 2.0, 1.0]], device=device)
         self.mask_rng, self.mask_seed, self._mask_step = "torch", 0, 0
+        self._train_precision = "f32"
+
+    # Precision of a DIFFERENTIATED forward_nsteps / forward (autograd.dynca_nsteps_autograd): "f32" (default) = the exact kernels,
+    # "bf16" = the bf16-MFMA training mode of include/ncahip.h (mode-1 forward history, backward on bf16 MFMA) where C <= 16 and
+    # fc <= 128, ignored elsewhere.  Per model, no process-wide state; the ambient ops.dynca_precision does not reach autograd.
+    TRAIN_PRECISIONS = ("f32", "bf16")
+
+    @property
+    def train_precision(self):
+        return self._train_precision
+
+    @train_precision.setter
+    def train_precision(self, value):
+        if value not in DyNCA.TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be 'f32' or 'bf16', got {value!r}")
+        self._train_precision = value
 
     # ------------------------------------------------------------------ helpers
     def _draw(self, x, steps, update_rate=None):

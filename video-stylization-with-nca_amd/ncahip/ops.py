@@ -787,13 +787,18 @@ def _gram_fits(ma: int, nb: int) -> bool:
 
 def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us: Optional[torch.Tensor], w: DyncaWeights,
                           g_final: torch.Tensor, g_states: Optional[torch.Tensor], T: int, pad_mode: str = "replicate",
-                          update_rate: float = 0.5, seed: int = 0, step0: int = 0, two_scale: bool = False):
+                          update_rate: float = 0.5, seed: int = 0, step0: int = 0, two_scale: bool = False, precision: str = "f32"):
     """Backward of dynca_nsteps (states = the keep_history=True buffer [T+1,B,C,H,W]): ONE call into the C driver
     ncahip_dynca_nsteps_bwd_f32, which enqueues the whole T-step loop (perception, fused MLP-backward kernel per 128-wide
     slice of the hidden layer, weight-gradient products with the cell axis as K, stencil adjoint) on the current stream with
     one caller-owned workspace.  g_final must already include any cotangent of x_T itself; g_states (optional, [T+1,...])
     adds dL/dx_t cotangents of the intermediate states t < T (forward_nsteps' return_middle_feature).
+    precision="bf16": the bf16-MFMA training mode (ncahip_dynca_nsteps_bwd_bfmma_f32 / _ms_bfmma_f32, contract in include/ncahip.h):
+    `states` must be a float32 history recorded under dynca_precision("bf16"), C <= 16 and fc <= 128.  The ambient dynca_precision
+    plays no part here.
     Returns dict x0, w1 [fc,4C+cc], b1, w2 [C,fc], b2."""
+    if precision not in _DYNCA_PRECISIONS:
+        raise ValueError(f"dynca backward precision must be 'f32' or 'bf16', got {precision!r}")
     dt, dsfx = _state_dtype(states)      # bfloat16 history: ncahip_dynca_nsteps_bwd_bf16 (storage format only, fp32 gradients)
     states, g = _dev(states, "states", dt), _dev(g_final.float(), "g_final")
     _, B, C, H, W = states.shape
@@ -816,6 +821,12 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
     assert not (two_scale and dsfx == "bf16"), "the two-scale step is an fp32 kernel"
     fn = "ncahip_dynca_nsteps_bwd_bf16" if dsfx == "bf16" else f"ncahip_dynca_nsteps_bwd{sfx}_f32"
     wsfn = "ncahip_dynca_nsteps_bwd_bf16_workspace" if dsfx == "bf16" else f"ncahip_dynca_nsteps_bwd{sfx}_workspace"
+    if precision == "bf16":
+        if dsfx == "bf16":
+            raise _capi.NcaHipError("ncahip: the bf16-MFMA DyNCA backward takes a float32 history (bf16 state storage is out of its scope)")
+        if not dynca_bf16_ok(C, fc):
+            raise _capi.NcaHipError(f"ncahip: the bf16-MFMA DyNCA backward covers C <= 16 and fc <= 128, got C={C} fc={fc}")
+        fn, wsfn = f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_f32", f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_workspace"
     nbytes = getattr(lib(), wsfn)(B, C, H, W, fc, c_cond)
     ws = _workspace(nbytes, dev)
     check(getattr(lib(), fn)(_p(states), T, _p(cond), _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, H, W, fc,
