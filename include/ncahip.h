@@ -732,6 +732,53 @@ int ncahip_clip_resize_u8(const uint8_t *src, int N, int H, int W, int x0, int y
                           const int32_t *bx, int ksize_x, const int32_t *ky, const int32_t *by, int ksize_y, uint8_t *dst, int out_h,
                           int out_w, void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
 
+/* ---- a whole clip per call, planar YUV frames: I420 / NV12 in, RGB24 on the device -------------------------------------------------
+ * A decoder does not deliver RGB24: it delivers planar YUV 4:2:0, 1.5 bytes per pixel, and RGB exists only after a colour conversion.
+ * The reference never sees YUV (cv2 / moviepy hand it RGB), so there is no reference arithmetic to reproduce; this section fixes one.
+ * Matrix NCAHIP_YUV_BT601 (Kr = 0.299, Kb = 0.114) or NCAHIP_YUV_BT709 (Kr = 0.2126, Kb = 0.0722); Kg = 1 - Kr - Kb.
+ * Range NCAHIP_YUV_LIMITED: y' = Y - 16, sy = 255/219, sc = 255/224; NCAHIP_YUV_FULL: y' = Y, sy = sc = 1.  u' = U - 128, v' = V - 128.
+ * The real-valued definition:
+ *   R = sy y' + 2 (1 - Kr) sc v'
+ *   G = sy y' - (2 Kb (1 - Kb) / Kg) sc u' - (2 Kr (1 - Kr) / Kg) sc v'
+ *   B = sy y' + 2 (1 - Kb) sc u'
+ * The integer evaluation (the contract): every coefficient c is computed in C double and quantised to k = (int)(c * 2^16 + 0.5), or
+ *   (int)(c * 2^16 - 0.5) for c < 0;  channel = clamp((k_y y' + k_u u' + k_v v' + 2^15) >> 16, 0, 255), int32 accumulation, arithmetic
+ *   shift.  Over all 2^24 (Y, U, V) triples |accumulator| stays below 2^26, the result is never more than 1 away from the real-valued
+ *   definition rounded half up, and differs from it on at most 5.2e-4 of a channel's values (bt601 full, B).
+ *   (k_y, k_rv, k_gu, k_gv, k_bu):  bt601 limited 76309 104597 -25675 -53279 132201      bt601 full 65536  91881 -22553 -46802 116130
+ *                                   bt709 limited 76309 117489 -13975 -34925 138438      bt709 full 65536 103206 -12276 -30679 121609
+ * Chroma is nearest: pixel (x, y) uses chroma sample (x >> 1, y >> 1); no interpolation, no siting filter.
+ * Layouts, per frame of h x w pixels (h, w even), uint8 [3h/2, w]: NCAHIP_YUV_I420 = the Y plane (h x w bytes), then U (h/2 x w/2), then V;
+ *   NCAHIP_YUV_NV12 = the Y plane, then h/2 rows of w bytes with U and V interleaved (U first).
+ * ncahip_yuv_coeffs: k[0..4] = (k_y, k_rv, k_gu, k_gv, k_bu), k[5] = the luma offset (16 or 0), into CALLER (host) memory; plain host
+ *   code with floating-point contraction off, no GPU call.  An unknown matrix or range, or a null k: NCAHIP_EINVAL.  This is the only
+ *   implementation of the coefficient arithmetic.
+ * ncahip_clip_yuv420_to_rgb_u8: src [N, 3H/2, W] uint8 -> dst [N, crop_h, crop_w, 3] uint8, the RGB of the crop box (columns
+ *   x0 .. x0 + crop_w - 1, rows y0 .. y0 + crop_h - 1; any origin and size, odd ones included).  k: ncahip_yuv_coeffs' six words in HOST
+ *   memory (they travel as kernel arguments).  One launch for all N frames, nothing synchronises.  A lane writes one memory-aligned dword
+ *   of the output (bytes at a frame's two ends singly) and reads every source byte out of the aligned dword that holds it, inside the
+ *   tensor only: any alignment of src and dst and any W are served (plane starts such as byte H*W + H*W/4 are routinely misaligned).
+ *   NCAHIP_EINVAL: a null pointer, an unknown layout, a non-positive size, overlapping src / dst.  NCAHIP_ERANGE: H or W above 16384 or
+ *   odd, a crop outside the frame.  All checked before the launch.
+ * ncahip_clip_resize_yuv420_u8: ncahip_clip_resize_u8 with a planar source: the same tables, workspace, limits and return codes, plus
+ *   NCAHIP_EINVAL for a null k or an unknown layout and NCAHIP_ERANGE for odd H or W.  The horizontal pass stages, per row, the luma segment
+ *   and the chroma samples under it as memory-aligned dwords and writes the converted RGB bytes into the LDS rows its tap loop reads; no
+ *   full-size RGB image exists.  The vertical pass is the same kernel.  The result is bit for bit ncahip_clip_yuv420_to_rgb_u8 on the crop
+ *   followed by ncahip_clip_resize_u8 without a crop. */
+#define NCAHIP_YUV_I420 0
+#define NCAHIP_YUV_NV12 1
+#define NCAHIP_YUV_BT601 0
+#define NCAHIP_YUV_BT709 1
+#define NCAHIP_YUV_LIMITED 0
+#define NCAHIP_YUV_FULL 1
+int ncahip_yuv_coeffs(int matrix, int range, int32_t k[6]);
+int ncahip_clip_yuv420_to_rgb_u8(const uint8_t *src, int layout, int N, int H, int W, int x0, int y0, int crop_w, int crop_h,
+                                 const int32_t *k, uint8_t *dst, ncahip_stream_t stream);
+int ncahip_clip_resize_yuv420_u8(const uint8_t *src, int layout, const int32_t *k, int N, int H, int W, int x0, int y0, int crop_w,
+                                 int crop_h, const int32_t *kx, const int32_t *bx, int ksize_x, const int32_t *ky, const int32_t *by,
+                                 int ksize_y, uint8_t *dst, int out_h, int out_w, void *workspace, size_t workspace_bytes,
+                                 ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

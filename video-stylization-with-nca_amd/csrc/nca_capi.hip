@@ -1008,28 +1008,77 @@ size_t ncahip_clip_resize_workspace(int N, int crop_h, int out_w) {
     return (size_t)N * crop_h * out_w * 3;
 }
 
+// the checks of the two resize entry points; frame_bytes: H * W * 3 (RGB24) or H * W * 3 / 2 (planar 4:2:0)
+static int clip_resize_check(const char* who, const uint8_t* src, size_t frame_bytes, int N, int H, int W, int x0, int y0, int crop_w, int crop_h,
+                             const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst,
+                             int out_h, int out_w, void* workspace, size_t workspace_bytes) {
+    if (!src || !dst) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
+    if (N <= 0 || H <= 0 || W <= 0 || crop_w <= 0 || crop_h <= 0 || out_h <= 0 || out_w <= 0 || ksize_x <= 0 || ksize_y <= 0)
+        return fail(NCAHIP_EINVAL, "%s: bad size", who);
+    if (H > kResizeMaxDim || W > kResizeMaxDim || out_h > kResizeMaxDim || out_w > kResizeMaxDim)
+        return fail(NCAHIP_ERANGE, "%s: H=%d W=%d out_h=%d out_w=%d exceeds %d", who, H, W, out_h, out_w, kResizeMaxDim);
+    if (ksize_x > kResizeMaxKsize || ksize_y > kResizeMaxKsize)
+        return fail(NCAHIP_ERANGE, "%s: table width ksize_x=%d ksize_y=%d exceeds %d", who, ksize_x, ksize_y, kResizeMaxKsize);
+    if (x0 < 0 || y0 < 0 || crop_w > W - x0 || crop_h > H - y0)
+        return fail(NCAHIP_ERANGE, "%s: crop (x0=%d, y0=%d, w=%d, h=%d) lies outside the %d x %d frame", who, x0, y0, crop_w, crop_h, H, W);
+    if (!kx || !bx || !ky || !by || (((uintptr_t)kx | (uintptr_t)bx | (uintptr_t)ky | (uintptr_t)by) & 3) != 0)
+        return fail(NCAHIP_ERANGE, "%s: null or misaligned table (int32, 4-byte aligned)", who);
+    if (!workspace || ((uintptr_t)workspace & 3) != 0) return fail(NCAHIP_ERANGE, "%s: null or misaligned workspace (4-byte aligned)", who);
+    const size_t need = ncahip_clip_resize_workspace(N, crop_h, out_w);
+    if (workspace_bytes < need) return fail(NCAHIP_EINVAL, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    const size_t sbytes = (size_t)N * frame_bytes, dbytes = (size_t)N * out_h * out_w * 3;
+    if (clip_overlap(src, sbytes, dst, dbytes) || clip_overlap(src, sbytes, workspace, need) || clip_overlap(dst, dbytes, workspace, need))
+        return fail(NCAHIP_EINVAL, "%s: frames, output and workspace must not overlap", who);
+    return 0;
+}
+
 int ncahip_clip_resize_u8(const uint8_t* src, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t* kx, const int32_t* bx,
                           int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst, int out_h, int out_w, void* workspace,
                           size_t workspace_bytes, ncahip_stream_t stream) {
-    if (!src || !dst) return fail(NCAHIP_EINVAL, "clip_resize: null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || crop_w <= 0 || crop_h <= 0 || out_h <= 0 || out_w <= 0 || ksize_x <= 0 || ksize_y <= 0)
-        return fail(NCAHIP_EINVAL, "clip_resize: bad size");
-    if (H > kResizeMaxDim || W > kResizeMaxDim || out_h > kResizeMaxDim || out_w > kResizeMaxDim)
-        return fail(NCAHIP_ERANGE, "clip_resize: H=%d W=%d out_h=%d out_w=%d exceeds %d", H, W, out_h, out_w, kResizeMaxDim);
-    if (ksize_x > kResizeMaxKsize || ksize_y > kResizeMaxKsize)
-        return fail(NCAHIP_ERANGE, "clip_resize: table width ksize_x=%d ksize_y=%d exceeds %d", ksize_x, ksize_y, kResizeMaxKsize);
-    if (x0 < 0 || y0 < 0 || crop_w > W - x0 || crop_h > H - y0)
-        return fail(NCAHIP_ERANGE, "clip_resize: crop (x0=%d, y0=%d, w=%d, h=%d) lies outside the %d x %d frame", x0, y0, crop_w, crop_h, H, W);
-    if (!kx || !bx || !ky || !by || (((uintptr_t)kx | (uintptr_t)bx | (uintptr_t)ky | (uintptr_t)by) & 3) != 0)
-        return fail(NCAHIP_ERANGE, "clip_resize: null or misaligned table (int32, 4-byte aligned)");
-    if (!workspace || ((uintptr_t)workspace & 3) != 0) return fail(NCAHIP_ERANGE, "clip_resize: null or misaligned workspace (4-byte aligned)");
-    const size_t need = ncahip_clip_resize_workspace(N, crop_h, out_w);
-    if (workspace_bytes < need) return fail(NCAHIP_EINVAL, "clip_resize: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    const size_t sbytes = (size_t)N * H * W * 3, dbytes = (size_t)N * out_h * out_w * 3;
-    if (clip_overlap(src, sbytes, dst, dbytes) || clip_overlap(src, sbytes, workspace, need) || clip_overlap(dst, dbytes, workspace, need))
-        return fail(NCAHIP_EINVAL, "clip_resize: frames, output and workspace must not overlap");
+    if (int rc = clip_resize_check("clip_resize", src, (size_t)H * W * 3, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h,
+                                   out_w, workspace, workspace_bytes))
+        return rc;
     return hip_result(nca_launch_clip_resize(src, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h, out_w,
                                              (unsigned char*)workspace, (hipStream_t)stream), "clip_resize");
+}
+
+// ---- planar YUV 4:2:0 clip frames (nca_yuv.hip; the fused loader in nca_resize.hip) ------------------------------------------------
+static bool yuv_layout_ok(int layout) { return layout == NCAHIP_YUV_I420 || layout == NCAHIP_YUV_NV12; }
+
+int ncahip_yuv_coeffs(int matrix, int range, int32_t k[6]) {
+    if (!k) return fail(NCAHIP_EINVAL, "yuv_coeffs: null pointer");
+    if (matrix != NCAHIP_YUV_BT601 && matrix != NCAHIP_YUV_BT709) return fail(NCAHIP_EINVAL, "yuv_coeffs: unknown matrix %d", matrix);
+    if (range != NCAHIP_YUV_LIMITED && range != NCAHIP_YUV_FULL) return fail(NCAHIP_EINVAL, "yuv_coeffs: unknown range %d", range);
+    nca_yuv_build_coeffs(matrix, range, k);
+    return 0;
+}
+
+int ncahip_clip_yuv420_to_rgb_u8(const uint8_t* src, int layout, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t* k,
+                                 uint8_t* dst, ncahip_stream_t stream) {
+    if (!src || !dst || !k) return fail(NCAHIP_EINVAL, "clip_yuv420_to_rgb: null pointer");
+    if (!yuv_layout_ok(layout)) return fail(NCAHIP_EINVAL, "clip_yuv420_to_rgb: unknown layout %d", layout);
+    if (N <= 0 || H <= 0 || W <= 0 || crop_w <= 0 || crop_h <= 0) return fail(NCAHIP_EINVAL, "clip_yuv420_to_rgb: bad size");
+    if (H > kResizeMaxDim || W > kResizeMaxDim) return fail(NCAHIP_ERANGE, "clip_yuv420_to_rgb: H=%d W=%d exceeds %d", H, W, kResizeMaxDim);
+    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "clip_yuv420_to_rgb: 4:2:0 frames have even sides, got %d x %d", H, W);
+    if (x0 < 0 || y0 < 0 || crop_w > W - x0 || crop_h > H - y0)
+        return fail(NCAHIP_ERANGE, "clip_yuv420_to_rgb: crop (x0=%d, y0=%d, w=%d, h=%d) lies outside the %d x %d frame", x0, y0, crop_w, crop_h, H, W);
+    if (clip_overlap(src, (size_t)N * H * W / 2 * 3, dst, (size_t)N * crop_h * crop_w * 3))
+        return fail(NCAHIP_EINVAL, "clip_yuv420_to_rgb: frames and output must not overlap");
+    return hip_result(nca_launch_clip_yuv420_to_rgb(src, layout == NCAHIP_YUV_NV12, N, H, W, x0, y0, crop_w, crop_h, k, dst, (hipStream_t)stream),
+                      "clip_yuv420_to_rgb");
+}
+
+int ncahip_clip_resize_yuv420_u8(const uint8_t* src, int layout, const int32_t* k, int N, int H, int W, int x0, int y0, int crop_w, int crop_h,
+                                 const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst,
+                                 int out_h, int out_w, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!k) return fail(NCAHIP_EINVAL, "clip_resize_yuv420: null pointer");
+    if (!yuv_layout_ok(layout)) return fail(NCAHIP_EINVAL, "clip_resize_yuv420: unknown layout %d", layout);
+    if (int rc = clip_resize_check("clip_resize_yuv420", src, (size_t)H * W / 2 * 3, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y,
+                                   dst, out_h, out_w, workspace, workspace_bytes))
+        return rc;
+    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "clip_resize_yuv420: 4:2:0 frames have even sides, got %d x %d", H, W);
+    return hip_result(nca_launch_clip_resize_yuv420(src, layout == NCAHIP_YUV_NV12, k, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y,
+                                                    dst, out_h, out_w, (unsigned char*)workspace, (hipStream_t)stream), "clip_resize_yuv420");
 }
 
 int ncahip_dynca_step_bwd_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,

@@ -265,6 +265,16 @@ hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, 
 hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx, const int* bx,
                                   int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
                                   unsigned char* tmp, hipStream_t st);
+// the same with planar YUV 4:2:0 frames [N,3H/2,W] (I420, or NV12), H and W even: the horizontal pass's loader converts with the six
+// coefficient words k (HOST memory, nca_yuv_build_coeffs); the result is nca_launch_clip_yuv420_to_rgb on the crop, then the resize
+hipError_t nca_launch_clip_resize_yuv420(const unsigned char* src, bool nv12, const int* k, int N, int H, int W, int x0, int y0, int cw, int ch,
+                                         const int* kx, const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst,
+                                         int out_h, int out_w, unsigned char* tmp, hipStream_t st);
+// nca_yuv.hip: the crop (x0, y0, cw, ch) of N planar YUV 4:2:0 frames [N,3H/2,W] -> RGB [N,ch,cw,3] uint8, one launch; any alignment
+hipError_t nca_launch_clip_yuv420_to_rgb(const unsigned char* src, bool nv12, int N, int H, int W, int x0, int y0, int cw, int ch, const int* k,
+                                         unsigned char* dst, hipStream_t st);
+// host only: the coefficients (k_y, k_rv, k_gu, k_gv, k_bu, luma offset) of matrix 0 = BT.601 / 1 = BT.709, range 0 = limited / 1 = full
+void nca_yuv_build_coeffs(int matrix, int range, int32_t k[6]);
 // host only (no GPU call): table row width (-1: does not fit an int), and the tables of one axis; filter 0 = bicubic, 1 = Lanczos.  The
 // builder returns 0, or the 1-based row that breaks an integer bound of the passes
 int nca_resize_ksize(int in, int out, int filter);

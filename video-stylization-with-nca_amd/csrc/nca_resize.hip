@@ -16,6 +16,10 @@
 //                     loops over that column's runtime tap count.
 //   resize_v_kernel   one lane per 4 output bytes of a row (dword loads and stores when out_w * 3 and the buffers allow it), or per byte;
 //                     the row's coefficients are wave-uniform (scalar loads); n coalesced reads of intermediate rows.
+// Planar YUV 4:2:0 sources (ncahip_clip_resize_yuv420_u8): resize_h_kernel is a template over the source format.  Its I420 / NV12
+// instantiations stage the luma segment and the chroma samples under it the same way, behind the rows, and one lane per staged pixel
+// writes the converted RGB bytes (nca_yuv.h: include/ncahip.h's integer arithmetic, nearest chroma) into the rows the tap loop reads;
+// everything after that, the vertical pass included, is the RGB24 code, and no full-size RGB image exists.
 // |k| < 2^23 and pixels < 2^8: the multiply-adds are 24-bit (v_mad_i32_i24).  The tables come from device memory and are not trusted with
 // addresses: every row's (first tap, count) is cut to the staged segment / the crop before the tap loop, so a bad table gives wrong
 // pixels, never a read outside the frame.  Offsets per image are 64-bit.
@@ -23,6 +27,7 @@
 
 #include "nca_common.h"
 #include "nca_kernels.h"
+#include "nca_yuv.h"
 
 namespace {
 
@@ -33,14 +38,9 @@ constexpr int kRszLdsBudget = 60 * 1024;   // dynamic LDS per workgroup: coeffic
 
 __device__ __forceinline__ int rsz_clamp_u8(int acc) { return min(max(acc >> 22, 0), 255); }
 
-// Four accumulators -> four packed bytes.  For clamp(a0 >> 22) | clamp(a1 >> 22) << 8 the compiler selects v_ashr_pk_u8_i32 and ORs bytes 2
-// and 3 into its result as if the instruction had cleared bits 16..31 of its destination; on the MI355X those bits keep what the register
-// held before (observed: bytes 2 and 3 of every dword came out ORed with bits of the address that had lived there).  The empty asm
-// statement (no instruction, no memory access) makes the two low bytes opaque, so the fused form is not selected.
+// Four accumulators -> four packed bytes (nca_pack_u8x4: the form the compiler may not fuse, see nca_yuv.h)
 __device__ __forceinline__ unsigned rsz_pack_u8x4(int a0, int a1, int a2, int a3) {
-    unsigned b0 = (unsigned)rsz_clamp_u8(a0), b1 = (unsigned)rsz_clamp_u8(a1);
-    asm volatile("" : "+v"(b0), "+v"(b1));
-    return b0 | (b1 << 8) | ((unsigned)rsz_clamp_u8(a2) << 16) | ((unsigned)rsz_clamp_u8(a3) << 24);
+    return nca_pack_u8x4((unsigned)rsz_clamp_u8(a0), (unsigned)rsz_clamp_u8(a1), (unsigned)rsz_clamp_u8(a2), (unsigned)rsz_clamp_u8(a3));
 }
 
 // Pixels a block of `cols` output columns can touch: its first column's first tap to its last column's last tap.  With
@@ -52,13 +52,24 @@ int rsz_footprint(int cols, int in, int out, int ksize) {
     return (int)(fp < in ? fp : in);
 }
 int rsz_row_dwords(int fp) { return (3 * fp + 3 + 3) / 4 + 1; }   // aligned dwords that cover 3 * fp bytes at any phase
+int rsz_seg_dwords(int bytes) { return (bytes + 3 + 3) / 4 + 1; }  // the same for a segment of `bytes` bytes
+// Planar sources stage, per row, the luma segment (fp bytes) and the chroma samples under it (at most fp / 2 + 1: two planes' segments
+// for I420, one interleaved segment of twice the bytes for NV12; 2 * seg(c) >= seg(2 c) covers both)
+int rsz_yuv_luma_dwords(int fp) { return rsz_seg_dwords(fp); }
+int rsz_yuv_chroma_dwords(int fp) { return rsz_seg_dwords(fp / 2 + 1); }
+
+constexpr int kSrcRgb24 = 0, kSrcI420 = 1, kSrcNv12 = 2;
 
 // grid (column blocks * row bands, frames), block 256.  src [N,H,W,3] u8 (`total` bytes), crop (x0, y0, cw, ch); kx [out_w, ksize] and
 // bx [out_w, 2] = (xmin, n) per output column; tmp [N, ch, out_w, 3] u8.  Dynamic LDS: cols * ksize coefficients, then rows * row_dw dwords.
+// SRC = kSrcI420 / kSrcNv12: src is [N, 3H/2, W] u8 (H, W even).  The loader stages each row's luma segment and the chroma samples under it
+// (ydw + 2 * cdw more dwords per row, after the rows) and writes the converted RGB bytes (yk; nearest chroma) into the rows at phase 0;
+// the tap loop is the same.
+template <int SRC>
 __global__ __launch_bounds__(kRszThreads) void resize_h_kernel(const unsigned char* __restrict__ src, size_t total, int H, int W, int x0, int y0,
                                                                int cw, int ch, const int* __restrict__ kx, const int* __restrict__ bx, int ksize,
                                                                unsigned char* __restrict__ tmp, int out_w, int cols, int rows, int fp, int row_dw,
-                                                               int col_blocks) {
+                                                               int col_blocks, NcaYuvK yk, int ydw, int cdw) {
     extern __shared__ __attribute__((aligned(16))) int rsz_lds[];
     __shared__ int s_xmin[kRszMaxCols], s_n[kRszMaxCols];
     int* const s_k = rsz_lds;
@@ -81,21 +92,54 @@ __global__ __launch_bounds__(kRszThreads) void resize_h_kernel(const unsigned ch
 
     const uintptr_t mis = (uintptr_t)src & 3;
     const size_t plane = (size_t)H * W;
-    for (int i = tid; i < nrows * row_dw; i += kRszThreads) {
-        const int r = i / row_dw, d = i - r * row_dw;
-        const size_t first = (n * plane + (size_t)(y0 + r0 + r) * W + x0 + sx0) * 3;      // first byte of the row segment
-        const size_t last = first + (size_t)fpw * 3;                                      // one past its last byte
-        const ptrdiff_t a = (ptrdiff_t)((first + mis) & ~(size_t)3) - (ptrdiff_t)mis + 4 * (ptrdiff_t)d;   // aligned in memory; >= -3
-        if (a >= (ptrdiff_t)last) continue;
-        unsigned v;
-        if (a >= 0 && (size_t)a + 4 <= total) {
-            v = *reinterpret_cast<const unsigned*>(src + a);
-        } else {                               // the dword straddles an end of the tensor: only its bytes inside
-            v = 0u;
-            for (int k = 0; k < 4; ++k)
-                if (a + k >= 0 && (size_t)(a + k) < total) v |= (unsigned)src[a + k] << (8 * k);
+    if constexpr (SRC == kSrcRgb24) {
+        for (int i = tid; i < nrows * row_dw; i += kRszThreads) {
+            const int r = i / row_dw, d = i - r * row_dw;
+            const size_t first = (n * plane + (size_t)(y0 + r0 + r) * W + x0 + sx0) * 3;      // first byte of the row segment
+            unsigned v;
+            if (nca_stage_dword(src, total, mis, first, (size_t)fpw * 3, d, v)) raw[i] = v;
         }
-        raw[i] = v;
+    } else {
+        const int st_dw = ydw + 2 * cdw;
+        unsigned* const stage = raw + rows * row_dw;
+        const size_t frame = n * (plane + plane / 2), quarter = plane / 4;
+        const int px0 = x0 + sx0, cx0 = px0 >> 1;                    // first staged pixel of a row, first chroma sample under it
+        const int cn = ((px0 + fpw - 1) >> 1) - cx0 + 1;             // <= fp / 2 + 1
+        for (int i = tid; i < nrows * st_dw; i += kRszThreads) {
+            const int r = i / st_dw, d = i - r * st_dw, yy = y0 + r0 + r;
+            size_t first, len;
+            int dd;
+            if (d < ydw) {
+                first = frame + (size_t)yy * W + px0, len = (size_t)fpw, dd = d;
+            } else if (SRC == kSrcI420) {
+                const int pl = (d - ydw) / cdw;                      // 0 = U, 1 = V
+                first = frame + plane + pl * quarter + (size_t)(yy >> 1) * (W >> 1) + cx0, len = (size_t)cn, dd = d - ydw - pl * cdw;
+            } else {
+                first = frame + plane + (size_t)(yy >> 1) * W + 2 * cx0, len = 2 * (size_t)cn, dd = d - ydw;
+            }
+            unsigned v;
+            if (nca_stage_dword(src, total, mis, first, len, dd, v)) stage[i] = v;
+        }
+        __syncthreads();
+        for (int i = tid; i < nrows * fpw; i += kRszThreads) {       // one lane per staged pixel: three RGB bytes into its row
+            const int r = i / fpw, x = i - r * fpw, yy = y0 + r0 + r;
+            const unsigned char* const st = reinterpret_cast<const unsigned char*>(stage + r * st_dw);
+            const int c = ((px0 + x) >> 1) - cx0;
+            const int Y = st[(int)((frame + (size_t)yy * W + px0 + mis) & 3) + x];
+            int U, V;
+            if (SRC == kSrcI420) {
+                const size_t uf = frame + plane + (size_t)(yy >> 1) * (W >> 1) + cx0;
+                U = st[4 * ydw + (int)((uf + mis) & 3) + c];
+                V = st[4 * (ydw + cdw) + (int)((uf + quarter + mis) & 3) + c];
+            } else {
+                const unsigned char* const uv = st + 4 * ydw + (int)((frame + plane + (size_t)(yy >> 1) * W + 2 * cx0 + mis) & 3) + 2 * c;
+                U = uv[0], V = uv[1];
+            }
+            unsigned char* const o = reinterpret_cast<unsigned char*>(raw + r * row_dw) + 3 * x;
+            o[0] = (unsigned char)nca_yuv_channel(yk, Y, U, V, 0);
+            o[1] = (unsigned char)nca_yuv_channel(yk, Y, U, V, 1);
+            o[2] = (unsigned char)nca_yuv_channel(yk, Y, U, V, 2);
+        }
     }
     __syncthreads();
 
@@ -105,7 +149,8 @@ __global__ __launch_bounds__(kRszThreads) void resize_h_kernel(const unsigned ch
         const int r = i / rowb, b = i - r * rowb;
         const int col = b / 3, c = b - 3 * col;
         const size_t first = (n * plane + (size_t)(y0 + r0 + r) * W + x0 + sx0) * 3;
-        const unsigned char* px = rawb + (size_t)r * row_dw * 4 + (int)((first + mis) & 3) + 3 * s_xmin[col] + c;
+        const int phase = SRC == kSrcRgb24 ? (int)((first + mis) & 3) : 0;             // converted rows start at byte 0
+        const unsigned char* px = rawb + (size_t)r * row_dw * 4 + phase + 3 * s_xmin[col] + c;
         const int* const kr = s_k + col * ksize;
         const int taps = s_n[col];
         int acc = 1 << 21;
@@ -149,36 +194,46 @@ __global__ __launch_bounds__(kRszThreads) void resize_v_kernel(const unsigned ch
 
 }  // namespace
 
-hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx, const int* bx,
-                                  int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
-                                  unsigned char* tmp, hipStream_t st) {
+namespace {
+
+// src_fmt: kSrcRgb24 (src [N,H,W,3]) or kSrcI420 / kSrcNv12 (src [N,3H/2,W], converted by the horizontal pass's loader with yk)
+hipError_t rsz_launch(int src_fmt, const NcaYuvK& yk, const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx,
+                      const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
+                      unsigned char* tmp, hipStream_t st) {
+    const bool yuv = src_fmt != kSrcRgb24;
     // horizontal pass: the widest block of columns whose coefficient rows and one staged source row fit the LDS budget, then as many rows
-    int cols = out_w < kRszMaxCols ? out_w : kRszMaxCols, fp = 0, row_dw = 0;
+    int cols = out_w < kRszMaxCols ? out_w : kRszMaxCols, fp = 0, row_dw = 0, ydw = 0, cdw = 0;
+    size_t row_bytes = 0;                                 // LDS per row: the RGB row, and a planar source's staged segments
     for (;; cols = (cols + 1) / 2) {
         fp = rsz_footprint(cols, cw, out_w, ksize_x);
         row_dw = rsz_row_dwords(fp);
-        if (cols == 1 || (size_t)cols * ksize_x * 4 + (size_t)row_dw * 4 <= (size_t)kRszLdsBudget) break;
+        ydw = yuv ? rsz_yuv_luma_dwords(fp) : 0;
+        cdw = yuv ? rsz_yuv_chroma_dwords(fp) : 0;
+        row_bytes = ((size_t)row_dw + ydw + 2 * (size_t)cdw) * 4;
+        if (cols == 1 || (size_t)cols * ksize_x * 4 + row_bytes <= (size_t)kRszLdsBudget) break;
     }
     const size_t kbytes = (size_t)cols * ksize_x * 4;
-    if (kbytes + (size_t)row_dw * 4 > (size_t)kRszLdsBudget) return hipErrorInvalidValue;     // the caller's limits (16384, 2048) keep this away
-    int rows = (int)(((size_t)kRszLdsBudget - kbytes) / ((size_t)row_dw * 4));
+    if (kbytes + row_bytes > (size_t)kRszLdsBudget) return hipErrorInvalidValue;     // the caller's limits (16384, 2048) keep this away
+    int rows = (int)(((size_t)kRszLdsBudget - kbytes) / row_bytes);
     rows = rows < kRszMaxRows ? rows : kRszMaxRows;
     rows = rows < ch ? rows : ch;
     const int col_blocks = (out_w + cols - 1) / cols, bands = (ch + rows - 1) / rows;
-    const size_t lds = kbytes + (size_t)rows * row_dw * 4;
-    const size_t total = (size_t)N * H * W * 3;
+    const size_t lds = kbytes + (size_t)rows * row_bytes;
+    const size_t frame = yuv ? (size_t)H * W / 2 * 3 : (size_t)H * W * 3;
+    const size_t total = (size_t)N * frame;
     const int rowlen = out_w * 3;
     const bool vec = rowlen % 4 == 0 && ((uintptr_t)tmp & 3) == 0 && ((uintptr_t)dst & 3) == 0;
     const int per_block = kRszThreads * (vec ? 4 : 1);
+    const auto hk = src_fmt == kSrcI420 ? resize_h_kernel<kSrcI420> : src_fmt == kSrcNv12 ? resize_h_kernel<kSrcNv12> : resize_h_kernel<kSrcRgb24>;
     for (int n0 = 0; n0 < N; n0 += 65535) {              // grid y / z hold at most 65535 frames
         const int nn = N - n0 < 65535 ? N - n0 : 65535;
         // the frames of this chunk start at src + n0 frames, but the dword loader needs the whole tensor's extent: pass the chunk's
         // own base and the bytes from there to the tensor's end
-        const unsigned char* s = src + (size_t)n0 * H * W * 3;
+        const unsigned char* s = src + (size_t)n0 * frame;
         unsigned char* t = tmp + (size_t)n0 * ch * rowlen;
         unsigned char* d = dst + (size_t)n0 * out_h * rowlen;
-        hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)(col_blocks * bands), (unsigned)nn), dim3(kRszThreads), lds, st, s,
-                           total - (size_t)n0 * H * W * 3, H, W, x0, y0, cw, ch, kx, bx, ksize_x, t, out_w, cols, rows, fp, row_dw, col_blocks);
+        hipLaunchKernelGGL(hk, dim3((unsigned)(col_blocks * bands), (unsigned)nn), dim3(kRszThreads), lds, st, s, total - (size_t)n0 * frame, H, W, x0,
+                           y0, cw, ch, kx, bx, ksize_x, t, out_w, cols, rows, fp, row_dw, col_blocks, yk, ydw, cdw);
         if (hipError_t e = hipGetLastError()) return e;
         const dim3 grid((unsigned)((rowlen + per_block - 1) / per_block), (unsigned)out_h, (unsigned)nn);
         if (vec)
@@ -188,6 +243,21 @@ hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W,
         if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx, const int* bx,
+                                  int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
+                                  unsigned char* tmp, hipStream_t st) {
+    return rsz_launch(kSrcRgb24, NcaYuvK{}, src, N, H, W, x0, y0, cw, ch, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h, out_w, tmp, st);
+}
+
+hipError_t nca_launch_clip_resize_yuv420(const unsigned char* src, bool nv12, const int* k, int N, int H, int W, int x0, int y0, int cw, int ch,
+                                         const int* kx, const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst,
+                                         int out_h, int out_w, unsigned char* tmp, hipStream_t st) {
+    return rsz_launch(nv12 ? kSrcNv12 : kSrcI420, NcaYuvK{k[0], k[1], k[2], k[3], k[4], k[5]}, src, N, H, W, x0, y0, cw, ch, kx, bx, ksize_x, ky, by,
+                      ksize_y, dst, out_h, out_w, tmp, st);
 }
 
 // ---- the table builder: plain host C++, no GPU call.  ImagingResample's precompute_coeffs + normalize_coeffs_8bpc in C double, with

@@ -122,6 +122,9 @@ SIGNATURES = {
     "ncahip_resize_tables": [_I, _I, _I, _P, _P, _I],
     "ncahip_clip_resize_workspace": [_I, _I, _I],
     "ncahip_clip_resize_u8": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, ctypes.c_size_t, _P],
+    "ncahip_yuv_coeffs": [_I, _I, _P],
+    "ncahip_clip_yuv420_to_rgb_u8": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "ncahip_clip_resize_yuv420_u8": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, ctypes.c_size_t, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
@@ -145,6 +148,9 @@ EINVAL, ERANGE, EDEVICE = -1, -2, 100001     # include/ncahip.h return codes
 SEED_U_IS_BITS = 0x5354494255     # include/ncahip.h NCAHIP_SEED_U_IS_BITS: `u` holds bit-packed fire masks
 CLIP_F32_NCHW, CLIP_U8_NHWC = 0, 1     # include/ncahip.h NCAHIP_CLIP_*: frame / image formats of the clip entry points
 RESIZE_FILTERS = {"bicubic": 0, "lanczos": 1}     # include/ncahip.h NCAHIP_RESIZE_*
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}              # include/ncahip.h NCAHIP_YUV_*
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+YUV_RANGES = {"limited": 0, "full": 1}
 
 
 def lib():

@@ -1052,6 +1052,107 @@ def clip_resize_host(frames, size, crop=None, resample: str = "bicubic"):
     return torch.from_numpy(arr) if as_tensor else arr
 
 
+# ---------------------------------------------------------------- planar YUV 4:2:0 clip frames (csrc/nca_yuv.hip, the loader of nca_resize.hip)
+_YUV_COEFFS = {}             # (matrix, range) -> numpy int32 [6], read-only
+
+
+def yuv_coeffs(yuv_matrix: str = "bt709", yuv_range: str = "limited") -> np.ndarray:
+    """(k_y, k_rv, k_gu, k_gv, k_bu, luma offset) of include/ncahip.h's integer YUV -> RGB evaluation, from the library's host builder
+    ncahip_yuv_coeffs -- the only implementation of that arithmetic; no GPU involved.  numpy int32 [6], cached and read-only."""
+    if yuv_matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"yuv_matrix must be 'bt601' or 'bt709', got {yuv_matrix!r}")
+    if yuv_range not in _capi.YUV_RANGES:
+        raise ValueError(f"yuv_range must be 'limited' or 'full', got {yuv_range!r}")
+    k = _YUV_COEFFS.get((yuv_matrix, yuv_range))
+    if k is None:
+        k = np.empty(6, dtype=np.int32)
+        check(lib().ncahip_yuv_coeffs(_capi.YUV_MATRICES[yuv_matrix], _capi.YUV_RANGES[yuv_range], k.ctypes.data), "yuv_coeffs")
+        k.setflags(write=False)
+        _YUV_COEFFS[(yuv_matrix, yuv_range)] = k
+    return k
+
+
+def _yuv_layout(pixel_format) -> int:
+    if pixel_format not in _capi.YUV_LAYOUTS:
+        raise ValueError(f"pixel_format must be 'i420' or 'nv12' here, got {pixel_format!r}")
+    return _capi.YUV_LAYOUTS[pixel_format]
+
+
+def yuv420_frame_size(shape):
+    """(h, w) of planar 4:2:0 frames [N, 3h/2, w]; ValueError for any other shape and for odd h or w."""
+    if len(shape) != 3 or shape[1] % 3 != 0 or shape[1] < 3 or shape[2] < 2 or shape[2] % 2 != 0:      # rows % 3 == 0: h = 2 rows / 3 is even
+        raise ValueError(f"planar YUV 4:2:0 frames must be [N, 3h/2, w] uint8 with even h and w, got {tuple(shape)}")
+    return int(shape[1]) // 3 * 2, int(shape[2])
+
+
+def _yuv_box(shape, crop):
+    """(N, h, w, (x0, y0, cw, ch)) of a conversion call, validated with the resize's rules."""
+    h, w = yuv420_frame_size(shape)
+    N, _, _, _, _, box = _resize_args((shape[0], h, w, 3), (1, 1), crop)
+    return N, h, w, box
+
+
+def yuv420_to_rgb(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited", crop=None) -> torch.Tensor:
+    """Planar frames [N, 3h/2, w] uint8 on the device ('i420' or 'nv12') -> RGB [N, ch, cw, 3] uint8 of the crop box (x0, y0, w, h) (None:
+    the whole frame): ncahip_clip_yuv420_to_rgb_u8, one launch for all N frames, include/ncahip.h's integer arithmetic with nearest
+    chroma.  Any alignment of the tensor."""
+    layout, k = _yuv_layout(pixel_format), yuv_coeffs(yuv_matrix, yuv_range)
+    frames = _dev(frames, "frames", torch.uint8)
+    N, h, w, (x0, y0, cw, ch) = _yuv_box(frames.shape, crop)
+    with torch.cuda.device(frames.device):
+        out = torch.empty(N, ch, cw, 3, device=frames.device, dtype=torch.uint8)
+        check(lib().ncahip_clip_yuv420_to_rgb_u8(_p(frames), layout, N, h, w, x0, y0, cw, ch, k.ctypes.data, _p(out), _stream()), "clip_yuv420_to_rgb")
+    return out
+
+
+def yuv420_to_rgb_host(frames, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited", crop=None):
+    """yuv420_to_rgb evaluated with numpy on the library's coefficients (yuv_coeffs): the definition in code, bit for bit the kernels'
+    result, and the route for CPU tensors.  frames: a uint8 tensor or numpy array [N, 3h/2, w]; returns the same kind, on the host."""
+    layout, k = _yuv_layout(pixel_format), yuv_coeffs(yuv_matrix, yuv_range).astype(np.int32)
+    as_tensor = isinstance(frames, torch.Tensor)
+    arr = frames.detach().cpu().numpy() if as_tensor else np.asarray(frames)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"ncahip: `frames` must be uint8, got {arr.dtype}")
+    N, h, w, (x0, y0, cw, ch) = _yuv_box(arr.shape, crop)
+    arr = arr.reshape(N, -1)
+    Y = arr[:, :h * w].reshape(N, h, w)
+    if layout == _capi.YUV_LAYOUTS["i420"]:
+        U = arr[:, h * w:h * w + h * w // 4].reshape(N, h // 2, w // 2)
+        V = arr[:, h * w + h * w // 4:].reshape(N, h // 2, w // 2)
+    else:
+        UV = arr[:, h * w:].reshape(N, h // 2, w // 2, 2)
+        U, V = UV[..., 0], UV[..., 1]
+    ys, xs = np.arange(y0, y0 + ch), np.arange(x0, x0 + cw)
+    y = Y[:, ys][:, :, xs].astype(np.int32) - k[5]
+    u = U[:, ys >> 1][:, :, xs >> 1].astype(np.int32) - 128                      # nearest chroma: sample (x >> 1, y >> 1)
+    v = V[:, ys >> 1][:, :, xs >> 1].astype(np.int32) - 128
+    half = np.int32(1 << 15)
+    rgb = np.stack((k[0] * y + k[1] * v + half, k[0] * y + k[2] * u + k[3] * v + half, k[0] * y + k[4] * u + half), axis=-1)   # int32: < 2^26
+    out = np.ascontiguousarray(np.clip(rgb >> 16, 0, 255).astype(np.uint8))
+    return torch.from_numpy(out) if as_tensor else out
+
+
+def clip_resize_yuv420(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", pixel_format: str = "i420", yuv_matrix: str = "bt709",
+                       yuv_range: str = "limited") -> torch.Tensor:
+    """clip_resize of planar frames [N, 3h/2, w] uint8 on the device: ncahip_clip_resize_yuv420_u8, the same two launches, the
+    horizontal pass converting in its loader -- bit for bit clip_resize(yuv420_to_rgb(frames, ..., crop=crop), size, None, resample)
+    without the full-size RGB image."""
+    _resize_filter(resample)
+    layout, k = _yuv_layout(pixel_format), yuv_coeffs(yuv_matrix, yuv_range)
+    frames = _dev(frames, "frames", torch.uint8)
+    h, w = yuv420_frame_size(frames.shape)
+    N, _, _, out_h, out_w, box = _resize_args((frames.shape[0], h, w, 3), size, crop)
+    with torch.cuda.device(frames.device):
+        tx = _resize_tables_dev(box[2], out_w, resample, frames.device)
+        ty = _resize_tables_dev(box[3], out_h, resample, frames.device)
+        out = torch.empty(N, out_h, out_w, 3, device=frames.device, dtype=torch.uint8)
+        ws = _workspace(lib().ncahip_clip_resize_workspace(N, box[3], out_w), frames.device)
+        check(lib().ncahip_clip_resize_yuv420_u8(_p(frames), layout, k.ctypes.data, N, h, w, *box, _p(tx[0]), _p(tx[1]), tx[0].shape[1], _p(ty[0]),
+                                                 _p(ty[1]), ty[0].shape[1], _p(out), out_h, out_w, _p(ws), ws.numel() * ws.element_size(), _stream()),
+              "clip_resize_yuv420")
+    return out
+
+
 # ---------------------------------------------------------------- position sampler of the OT appearance loss (csrc/nca_ot_sample.hip)
 _U64_MASK = (1 << 64) - 1
 _OT_SAMPLE_DOMAIN = 0x4F5453     # 'OTS': the fourth counter word (include/ncahip.h)

@@ -10,6 +10,10 @@ drops it again after.
 
 Decoder-sized frames: reference_crop / resize_frames are the reference's host-side shrink (Pillow: centre crop, then an 8-bit
 Image.resize) on the device, bit for bit; stylize_clip(size=...) and stylize_clip_conditioned(size=...) apply it per chunk.
+
+Planar frames: a decoder writes YUV 4:2:0 (I420 or NV12), not RGB24.  pixel_format='i420' / 'nv12' hands such frames to the same entry
+points; the conversion (include/ncahip.h, "planar YUV frames") runs on the device, inside the resize's loader when size is set.  Pinned
+host frames are uploaded on a side stream, chunk k + 1 while chunk k computes (_chunks).
 """
 import contextlib
 from typing import Iterable, Iterator, Optional
@@ -100,13 +104,53 @@ def reference_crop(kind: str, H: int, W: int):
     raise ValueError(f"crop kind must be 'dynca' or 'conditioned', got {kind!r}")
 
 
-def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubic") -> torch.Tensor:
+PIXEL_FORMATS = ("rgb24", "i420", "nv12")
+
+
+def _planar(frames: torch.Tensor, pixel_format, yuv_matrix, yuv_range):
+    """None for pixel_format 'rgb24'; for 'i420' / 'nv12' the frames' (h, w), after validating the frames ([F, 3h/2, w] uint8, even h and w),
+    the matrix and the range.  ValueError for anything else, before anything runs."""
+    from . import ops
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format must be one of {PIXEL_FORMATS}, got {pixel_format!r}")
+    if pixel_format == "rgb24":
+        return None
+    ops.yuv_coeffs(yuv_matrix, yuv_range)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise ValueError(f"pixel_format={pixel_format!r} takes uint8 frames [F, 3h/2, w] (what the decoder wrote), got {getattr(frames, 'dtype', type(frames))}")
+    return ops.yuv420_frame_size(tuple(frames.shape))
+
+
+def yuv420_to_rgb(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited") -> torch.Tensor:
+    """Planar YUV 4:2:0 frames [N, 3h/2, w] uint8 ('i420': Y, U, V planes; 'nv12': Y plane, interleaved UV rows) -> RGB [N,h,w,3] uint8 on
+    the frames' device, by include/ncahip.h's integer arithmetic with nearest chroma.  yuv_matrix 'bt601' or 'bt709', yuv_range 'limited'
+    or 'full'.  CUDA frames run ncahip_clip_yuv420_to_rgb_u8 (one launch), CPU frames its numpy mirror ops.yuv420_to_rgb_host."""
+    from . import ops
+    if _planar(frames, pixel_format, yuv_matrix, yuv_range) is None:
+        raise ValueError(f"pixel_format must be 'i420' or 'nv12', got {pixel_format!r}")
+    return (ops.yuv420_to_rgb if frames.is_cuda else ops.yuv420_to_rgb_host)(frames, pixel_format, yuv_matrix, yuv_range)
+
+
+def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", pixel_format: str = "rgb24", yuv_matrix: str = "bt709",
+                  yuv_range: str = "limited") -> torch.Tensor:
     """frames [N,H,W,3] uint8 -> [N,out_h,out_w,3] uint8 on the frames' device: the reference's crop, then Pillow's 8-bit Image.resize,
     bit for bit.  size = (out_h, out_w) -- rows first; the reference hands Pillow (x, y).  crop: 'dynca' or 'conditioned'
     (reference_crop), None (the whole frame) or a box (x0, y0, w, h).  resample: 'bicubic' (Image.resize's default, what
     preprocess_style_image gets) or 'lanczos' (load_image).  CUDA frames run ncahip_clip_resize_u8 (two launches for all N frames), CPU
-    frames its numpy mirror ops.clip_resize_host on the same tables."""
+    frames its numpy mirror ops.clip_resize_host on the same tables.
+    pixel_format 'i420' / 'nv12': frames are planar YUV 4:2:0 [N, 3h/2, w] uint8 (yuv420_to_rgb); the result is resize_frames of their
+    RGB, bit for bit.  CUDA frames run ncahip_clip_resize_yuv420_u8 (the conversion inside the horizontal pass's loader, no full-size
+    RGB image), CPU frames the two mirrors."""
     from . import ops
+    planar = _planar(frames, pixel_format, yuv_matrix, yuv_range)
+    if planar is not None:
+        if isinstance(crop, str):
+            crop = reference_crop(crop, *planar)
+        if frames.is_cuda:
+            return ops.clip_resize_yuv420(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
+        ops._resize_filter(resample)
+        ops._resize_args((frames.shape[0],) + planar + (3,), size, crop)           # bad size / crop: before the conversion
+        return ops.clip_resize_host(ops.yuv420_to_rgb_host(frames, pixel_format, yuv_matrix, yuv_range, crop), size, None, resample)
     if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError(f"frames must be a uint8 tensor [N,H,W,3] (the reference resizes 8-bit images), got "
                          f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)} {getattr(frames, 'dtype', '')}")
@@ -115,9 +159,9 @@ def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubi
     return (ops.clip_resize if frames.is_cuda else ops.clip_resize_host)(frames, size, crop, resample)
 
 
-def _sized(frames: torch.Tensor, size):
-    """stylize_clip*(size=...): the model grid (H, W) after validating the frames the resize takes."""
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+def _sized(frames: torch.Tensor, size, planar=None):
+    """stylize_clip*(size=...): the model grid (H, W) after validating the frames the resize takes (planar frames: _planar did)."""
+    if planar is None and (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3):
         raise ValueError(f"with size set, frames must be [F,h,w,3] uint8 (the reference resizes 8-bit images), got {tuple(frames.shape)} {frames.dtype}")
     try:
         hh, ww = (int(v) for v in size)
@@ -128,10 +172,78 @@ def _sized(frames: torch.Tensor, size):
     return hh, ww
 
 
+def _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range):
+    """What the two clip entry points make of (frames, size, crop, resample, pixel_format, ...), validated before anything runs:
+    (u8_in, hh, ww, shrink) -- whether chunks reach the routes as uint8 [n,H,W,3], the model grid, and the device-side step from an
+    uploaded chunk to the routes' frames (nothing, the conversion, the resize or the resize that converts)."""
+    from . import ops
+    planar = _planar(frames, pixel_format, yuv_matrix, yuv_range)
+    u8_in = frames.dtype == torch.uint8
+    if planar is None and (frames.dim() != 4 or frames.shape[-1 if u8_in else 1] != 3 or not (u8_in or frames.dtype == torch.float32)):
+        raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
+    fh, fw = planar if planar is not None else (frames.shape[1:3] if u8_in else frames.shape[2:4])
+    kw = {} if planar is None else {"pixel_format": pixel_format, "yuv_matrix": yuv_matrix, "yuv_range": yuv_range}
+    if size is None:
+        shrink = (lambda chunk: chunk) if planar is None else (lambda chunk: yuv420_to_rgb(chunk, **kw))
+        return u8_in, fh, fw, shrink
+    hh, ww = _sized(frames, size, planar)
+    box = reference_crop(crop, fh, fw) if isinstance(crop, str) else crop
+    ops._resize_filter(resample)                                                   # bad resample / crop: before anything runs
+    if frames.shape[0]:
+        ops._resize_args((frames.shape[0], fh, fw, 3), (hh, ww), box)
+    return u8_in, hh, ww, lambda chunk: resize_frames(chunk, (hh, ww), box, resample, **kw)
+
+
+_UPLOAD_STREAMS = {}         # device index -> the module's one side stream for uploads
+
+
+def _chunks(fn, frames: torch.Tensor, per_call: int, dev):
+    """The chunks frames[f0 : f0 + per_call] on `dev`, in order; records the route in fn.last_upload.
+    'overlapped' (host frames in pinned memory, a GPU model): chunk k + 1 is copied with non_blocking=True on the module's side stream
+    of that device while the caller's stream computes on chunk k.  The copy waits for what the compute stream held when it was issued
+    (chunk k - 1's work), the compute stream waits for the copy's event before it touches the chunk, and record_stream keeps the
+    chunk's memory from reuse while that work runs.  The caller drops chunk k before asking for k + 1: at most two are resident.
+    Before the generator ends -- exhausted, or closed by an exception in the caller -- the host waits for the side stream: copies
+    complete in order, so every copy out of `frames` is done and the caller may overwrite its buffer as soon as the clip call returns,
+    as with the blocking copies.  (The last chunk's compute is enqueued by then: the wait hides nothing from the device.)
+    'sync' (anything else): frames[...].to(dev) per chunk, as before."""
+    dev = torch.device(dev)
+    n_frames = frames.shape[0]
+    overlapped = dev.type == "cuda" and not frames.is_cuda and frames.is_pinned()
+    fn.last_upload = "overlapped" if overlapped else "sync"
+    if not overlapped:
+        for f0 in range(0, n_frames, per_call):
+            yield frames[f0:f0 + per_call].to(dev)
+        return
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    side = _UPLOAD_STREAMS.get(index)
+    if side is None:
+        side = _UPLOAD_STREAMS[index] = torch.cuda.Stream(device=index)
+    compute = torch.cuda.current_stream(index)
+
+    def start(f0):
+        side.wait_stream(compute)
+        with torch.cuda.stream(side):
+            chunk = frames[f0:f0 + per_call].to(dev, non_blocking=True)
+            return chunk, side.record_event()
+
+    try:
+        ahead = start(0) if n_frames else None
+        for f0 in range(0, n_frames, per_call):
+            chunk, ready = ahead
+            ahead = start(f0 + per_call) if f0 + per_call < n_frames else None
+            compute.wait_event(ready)
+            chunk.record_stream(compute)
+            yield chunk
+            del chunk
+    finally:
+        side.synchronize()           # no copy out of the caller's buffer is in flight once the call returns
+
+
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                  gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic",
-                 precision: str = "f32", direction=None):
+                 precision: str = "f32", direction=None, pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited"):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -164,7 +276,17 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     direction: None, a field tensor [1,2,H,W] or an (alignment, angle_deg) tuple (ncahip.steer; forward_nsteps' keyword): every step of
     the call rotates each cell's Sobel pair by its direction -- 'flow to the left', 'outwards from the centre', 'round two poles' for a
     trained motion model.  ONE field serves the whole call (no field per frame), on both routes and for both model families; with a
-    tuple, an extra-channel model's positional encoding is turned by the angle as well.  Needs an fp32 state."""
+    tuple, an extra-channel model's positional encoding is turned by the angle as well.  Needs an fp32 state.
+
+    pixel_format: 'rgb24' (the default: frames as described above) or 'i420' / 'nv12' -- frames are planar YUV 4:2:0 [F, 3h/2, w] uint8 as
+    the decoder wrote them (yuv420_to_rgb; yuv_matrix 'bt601' / 'bt709', yuv_range 'limited' / 'full'; any other shape or dtype, odd h or
+    w: ValueError).  Every chunk is uploaded as it is (1.5 bytes per pixel) and becomes RGB on the device: with size set inside the
+    resize (resize_frames(chunk, ..., pixel_format=...)), without it by yuv420_to_rgb; the uint8 path above follows unchanged, on both
+    routes and for both model families.  The result is that of the same call on yuv420_to_rgb(frames, ...).
+
+    Uploads: host frames in pinned memory (frames.is_pinned()) with a model on the GPU are uploaded on a side stream, chunk k + 1 while
+    chunk k computes; anything else is uploaded as before.  stylize_clip.last_upload records which: 'overlapped' or 'sync'.  Either
+    way every copy out of `frames` is complete when the call returns: the caller may overwrite the buffer at once."""
     from . import ops, steer
     if precision not in ("f32", "bf16"):
         raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
@@ -172,19 +294,8 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-    u8_in = frames.dtype == torch.uint8
-    if frames.dim() != 4 or frames.shape[-1 if u8_in else 1] != 3 or not (u8_in or frames.dtype == torch.float32):
-        raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
+    u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
     n_frames = frames.shape[0]
-    hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
-    shrink = lambda chunk: chunk                                                   # noqa: E731
-    if size is not None:
-        hh, ww = _sized(frames, size)
-        box = reference_crop(crop, *frames.shape[1:3]) if isinstance(crop, str) else crop
-        ops._resize_filter(resample)                                               # bad resample / crop: before anything runs
-        if n_frames:
-            ops._resize_args(frames.shape, (hh, ww), box)
-        shrink = lambda chunk: resize_frames(chunk, (hh, ww), box, resample)       # noqa: E731
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
     extra = _extra_channels(nca_model)
@@ -232,10 +343,11 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
             layer = nca_model.cond_layer
             bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
             do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
-        for f0 in range(0, n_frames, per_call):
-            chunk = shrink(frames[f0:f0 + per_call].to(dev)).unsqueeze(1)         # [n,1,3,H,W] or [n,1,H,W,3]
+        for raw in _chunks(stylize_clip, frames, per_call, dev):
+            chunk = shrink(raw).unsqueeze(1)                                      # [n,1,3,H,W] or [n,1,H,W,3]
             n = chunk.shape[0]
             cond = ops.clip_gray(chunk, gray) if extra else ops.clip_cond(chunk, bank, gray, do_tanh)
+            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
             us = None
             if nca_model.mask_rng != "philox":     # the loop's own draws, call by call (DyNCA._draw): the generator ends where it would
                 us = torch.cat([ops.draw_fire_masks(1, hh, ww, step_n, rate, "dynca", h.device) for _ in range(n * k)])
@@ -250,8 +362,8 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
             outs.append(imgs[:, 0])
     else:
         steer_kw = {} if direction is None else {"direction": direction}      # (a model without the keyword still runs unsteered clips)
-        for f0 in range(0, n_frames, per_call):
-            chunk = shrink(frames[f0:f0 + per_call].to(dev))
+        for raw in _chunks(stylize_clip, frames, per_call, dev):
+            chunk = shrink(raw)
             chunk = _widen(chunk) if u8_in else chunk
             for i in range(chunk.shape[0]):
                 cond = _gray(chunk[i:i + 1], gray)
@@ -263,6 +375,7 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
                         h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond, **steer_kw)
                     img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
                     outs.append((img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img)
+            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
     if outs:
         images = torch.cat(outs)
     else:
@@ -273,6 +386,7 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
 
 
 stylize_clip.last_path = None
+stylize_clip.last_upload = None
 
 
 def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
@@ -284,7 +398,7 @@ def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
 @torch.no_grad()
 def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                              warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8, size=None, crop="conditioned",
-                             resample: str = "lanczos"):
+                             resample: str = "lanczos", pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited"):
     """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
     loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
     goal of its own steps:
@@ -305,25 +419,19 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     size=(H, W): decoder-sized frames, as in stylize_clip: uint8 [F,h,w,3] frames only (float frames: ValueError), each chunk uploaded at
     its native size and shrunk on the device by resize_frames(chunk, size, crop, resample) -- the reference's load_image (crop='conditioned',
     Lanczos), bit for bit -- on both routes; seeding, the state check and the images use (H, W).  size=None: crop and resample are not
-    looked at."""
+    looked at.
+
+    pixel_format, yuv_matrix, yuv_range: planar YUV 4:2:0 frames [F, 3h/2, w] uint8 ('i420' / 'nv12'), as in stylize_clip: converted on the
+    device, inside the resize when size is set; the result is that of the same call on yuv420_to_rgb(frames, ...).  Pinned host frames
+    are uploaded on a side stream while the previous chunk computes; stylize_clip_conditioned.last_upload records 'overlapped' or 'sync'.
+    Every copy out of `frames` is complete when the call returns."""
     from . import ops
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-    u8_in = frames.dtype == torch.uint8
-    if frames.dim() != 4 or frames.shape[-1 if u8_in else 1] != 3 or not (u8_in or frames.dtype == torch.float32):
-        raise ValueError(f"frames must be [F,3,H,W] float32 or [F,H,W,3] uint8, got {tuple(frames.shape)} {frames.dtype}")
+    u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
     if nca.num_target_channels != 3:
         raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
     n_frames = frames.shape[0]
-    hh, ww = (frames.shape[1:3] if u8_in else frames.shape[2:4])
-    shrink = lambda chunk: chunk                                                   # noqa: E731
-    if size is not None:
-        hh, ww = _sized(frames, size)
-        box = reference_crop(crop, *frames.shape[1:3]) if isinstance(crop, str) else crop
-        ops._resize_filter(resample)                                               # bad resample / crop: before anything runs
-        if n_frames:
-            ops._resize_args(frames.shape, (hh, ww), box)
-        shrink = lambda chunk: resize_frames(chunk, (hh, ww), box, resample)       # noqa: E731
     if state is not None and (state.dim() != 4 or state.shape[1] != nca.num_channels or tuple(state.shape[2:]) != (hh, ww)):
         raise ValueError(f"state must be [B,{nca.num_channels},{hh},{ww}] (nca.num_channels channels, the frames' size), got {tuple(state.shape)}")
     if state is None and hh != ww:
@@ -345,11 +453,12 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
         w = nca._weights(h)
         draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(h, steps)      # noqa: E731
         args = (nca._alive_ch(), nca.alpha_living_threshold, nca.cell_fire_rate, -10.0, 10.0)
-        for f0 in range(0, n_frames, per_call):
-            chunk = shrink(frames[f0:f0 + per_call].to(dev)).unsqueeze(1)         # [n,1,3,H,W] or [n,1,H,W,3]
+        for ci, raw in enumerate(_chunks(stylize_clip_conditioned, frames, per_call, dev)):
+            chunk = shrink(raw).unsqueeze(1)                                      # [n,1,3,H,W] or [n,1,H,W,3]
             n = chunk.shape[0]
             goal = ops.clip_encode(chunk, nca.encoder)
-            if f0 == 0 and warm > 0:
+            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
+            if ci == 0 and warm > 0:
                 h, _, _ = ops.cond_grow(h, warm, goal[0], draw(warm), w, *args, nca.mask_seed, nca._mask_step)
                 nca._mask_step += warm
             us = None
@@ -359,15 +468,17 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
             nca._mask_step += n * k * step_n
             outs.append(imgs[:, 0])
     else:
-        for f0 in range(0, n_frames, per_call):
-            chunk = unit(shrink(frames[f0:f0 + per_call].to(dev)))
+        for ci, raw in enumerate(_chunks(stylize_clip_conditioned, frames, per_call, dev)):
+            chunk = unit(shrink(raw))
             for i in range(chunk.shape[0]):
                 goal_img = chunk[i:i + 1]
-                if f0 == 0 and i == 0 and warm > 0:
+                if ci == 0 and i == 0 and warm > 0:
                     h = nca.grow(h, warm, goal_img)
                 for _ in range(k):
                     h = nca.grow(h, step_n, goal_img)
                     outs.append(_unit_image(h, out_dtype))
+            goal_img = None                                                       # (a view of the chunk)
+            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
     if outs:
         images = torch.cat(outs)
     else:
@@ -377,3 +488,4 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
 
 
 stylize_clip_conditioned.last_path = None
+stylize_clip_conditioned.last_upload = None
