@@ -10,9 +10,11 @@
  *   - the caller owns every buffer, nothing is allocated, freed or retained across calls;
  *   - work is enqueued asynchronously on `stream` (a hipStream_t; NULL = default stream), the
  *     call never synchronises (ncahip_selftest and ncahip_check_errors excepted) and is safe from several host
- *     threads on distinct streams and devices: launch state is cached per DEVICE (the device current at the call),
- *     the two process-wide switches (ncahip_cond_precision, ncahip_debug_force_generic) are test / tuning hooks, and
- *     ncahip_dynca_precision is a process-wide mode read when a call enqueues;
+ *     threads on distinct streams and devices: launch state is cached per DEVICE (the device current at the call).
+ *     Process-wide are only the modes kept in csrc/nca_modes.h, each an atomic that any thread may set while others
+ *     enqueue: the tuning / test hooks ncahip_cond_precision, ncahip_debug_force_generic and
+ *     ncahip_debug_persist_drop_tiles (with the environment variables that give their initial values), read per
+ *     launch, and the modes ncahip_dynca_precision and ncahip_dynca_direction, read once when a call enqueues;
  *   - return 0 on success, a negative NCAHIP_E* on an argument error (nothing was launched),
  *     or a positive hipError_t if the launch failed; ncahip_last_error() describes the last
  *     failure of the calling thread.
@@ -71,8 +73,8 @@ int ncahip_limits(int *max_c, int *max_fc, int *max_hidden);
  *      ~1e-5 per step (inside the 1e-4 bar, not exact), about twice the throughput.  The backward always recomputes exactly. */
 int ncahip_cond_precision(int mode);
 
-/* Test hook (process-wide) selecting which kernel family serves the fused steps, so every variant can be checked
- * against the oracle on the same inputs: bit 0 = generic any-shape kernels instead of the aligned fast paths;
+/* Test hook (process-wide; decoded in csrc/nca_modes.hip, the one place that knows the bit layout) selecting which kernel
+ * family serves the fused steps, so every variant can be checked against the oracle on the same inputs: bit 0 = generic any-shape kernels instead of the aligned fast paths;
  * bit 1 = symmetric wave-private ConditionedNCA kernel instead of the default producer/consumer one;
  * bit 2 = ncahip_cond_grow_bwd_bf16 evaluates its matrix products in exact fp32 instead of on bf16 MFMA;
  * bit 3 = the ConditionedNCA backward runs its main kernel in the other of its two forms (one launch <-> front kernel +

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import load, T
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +41,8 @@ def weights(ops, prm, like):
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    return _ops
+    with gpu_ops() as o:
+        yield o
 
 
 @pytest.mark.parametrize("C,shape,gch", [(16, (2, 32, 48), 12), (12, (2, 24, 32), 8), (16, (1, 8, 16), 12), (16, (1, 5, 20), 0),

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import REL_TOL, T, load, near_threshold, rel_err, sd
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +21,8 @@ SHAPES = [(1, 1, 1, 1), (2, 1, 5, 7), (1, 2, 16, 16), (1, 1, 17, 33), (2, 1, 3, 
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    keep = _ops.persistent_cond
-    yield _ops
-    _ops.persistent_cond = keep
+    with gpu_ops() as o:
+        yield o
 
 
 def _encoder(E, ch, seed, bias=None):

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_ops import gpu_ops
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 FILTERS = ("bicubic", "lanczos")
@@ -19,12 +21,9 @@ SHAPES = [((37, 53), (16, 16)), ((20, 24), (40, 48)), ((33, 21), (16, 32)), ((13
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
-    yield _ops
-    _ops.check_errors()                      # nothing recorded a device-side failure in this module
+    with gpu_ops(persistent_steps=True) as o:
+        yield o
+        o.check_errors()                      # nothing recorded a device-side failure in this module
 
 
 def _boxes(H, W):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -18,12 +19,8 @@ GRAY_TOL = 1e-6
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
-    yield _ops
-    _ops.persistent_steps = True
+    with gpu_ops(persistent_steps=True) as o:
+        yield o
 
 
 def _gray64(frames64, weights):

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_ops import gpu_ops
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 FORMATS = ("i420", "nv12")
@@ -15,12 +17,9 @@ FILTERS = ("bicubic", "lanczos")
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
-    yield _ops
-    _ops.check_errors()                      # nothing recorded a device-side failure in this module
+    with gpu_ops(persistent_steps=True) as o:
+        yield o
+        o.check_errors()                      # nothing recorded a device-side failure in this module
 
 
 def planar_frames(N, h, w, fmt, seed):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import REL_TOL, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -17,15 +18,9 @@ DEV = "cuda"
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    _ops.check_errors()
-    default = _ops.persistent_cond
-    _ops.persistent_cond = True
-    yield _ops
-    _ops.persistent_cond = default
+    with gpu_ops(persistent_cond=True) as o:
+        o.check_errors()
+        yield o
 
 
 def _prm(C, seed, hidden=64, out_scale=1.0):

@@ -30,6 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_gpu_configs import rand_cond_prm
 from test_gpu_cond_replay import Draws, _bf16_case, _cost, _grad_errs, _lever, _replay   # noqa: F401  (_cost: time per test)
 from test_gpu_fullsize_ref import COND_NAMES, GTOL, _cond_w, _f64, _rel, _rel2, _rmax, _say
@@ -219,17 +220,8 @@ def cu_count():
 # ================================================================================================ the kernels and their float64 reference
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    default = _ops.persistent_cond
-    _ops.persistent_cond = False
-    yield _ops
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    _ops.persistent_cond = default
+    with gpu_ops(persistent_cond=False) as o:
+        yield o
 
 
 def _forced(ops, force, fn, *a, **kw):

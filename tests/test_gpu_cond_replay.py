@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 import bench
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_gpu_configs import rand_cond_prm
 from test_gpu_cond_persist import _Spy
 from test_gpu_fullsize_ref import COND_NAMES, GTOL, _cond_hidden2, _cond_w, _f64, _lever_entry, _perturbed, _rel2, _rmax
@@ -37,17 +38,8 @@ PATHS = {"default": 0, "dense": 32, "wave": 2, "generic": 1}      # ncahip_debug
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    default = _ops.persistent_cond
-    _ops.persistent_cond = False
-    yield _ops
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    _ops.persistent_cond = default
+    with gpu_ops(persistent_cond=False) as o:
+        yield o
 
 
 @pytest.fixture(autouse=True)

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import GATE_K, REL_TOL, T, grads_match_outside, load, rel_err, sd
 
 pytestmark = pytest.mark.gpu
@@ -23,11 +24,8 @@ DEV = "cuda"
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(False)
-    return _ops
+    with gpu_ops() as o:
+        yield o
 
 
 def cond_w(ops, prm, like):

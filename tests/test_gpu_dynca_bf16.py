@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_dynca_bf16_host import bf16_inputs, check_caps, contract_step
 
 pytestmark = pytest.mark.gpu
@@ -17,15 +18,9 @@ PHILOX_SEED, PHILOX_STEP0 = 0x5EED0002, 9
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
-    assert _ops.set_dynca_precision("f32") == "f32"
-    yield _ops
-    _ops.persistent_steps = True
-    assert _ops.set_dynca_precision("f32") == "f32"          # every test left the mode as it found it
+    with gpu_ops(persistent_steps=True) as o:
+        yield o
+        assert o.set_dynca_precision("f32") == "f32"          # every test left the mode as it found it
 
 
 def _weights(ops, prm, x):

@@ -28,6 +28,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_dynca_bf16_host import FLIP_FRACTION, bf16_inputs, check_caps, contract_step
 from test_dynca_bf16_ref_host import (PERSIST_ROWS, ROW_PADS, ROWS, SINGLE, TWO, admits, bf16_class, bf16_form, geometry,
                                       make_inputs, scales_of)
@@ -57,16 +58,9 @@ PERSIST_ROW_PADS = [(two, row, pad) for two, row, pad in ROW_PADS if (two, row) 
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    was = _ops.persistent_steps
-    _ops.persistent_steps = False
-    assert _ops.set_dynca_precision("f32") == "f32"
-    yield _ops
-    _ops.persistent_steps = was
-    assert _ops.set_dynca_precision("f32") == "f32"
+    with gpu_ops(persistent_steps=False) as o:
+        yield o
+        assert o.set_dynca_precision("f32") == "f32"
 
 
 @pytest.fixture(autouse=True)

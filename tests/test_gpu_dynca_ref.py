@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_gpu_configs import rand_dynca_prm
 from test_gpu_fullsize_ref import (DEV, DYNCA_GATE_K, DYNCA_NAMES, GTOL, _dyn_w, _dynca_case, _f64, _lever_entry,
                                    _perturbed, _rel, _rmax, _say)
@@ -169,15 +170,8 @@ CASE_PADS = [(c, p) for c in CASES for p in O.PAD_MODES if admits(c, p)]
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    was = _ops.persistent_steps
-    _ops.persistent_steps = False
-    yield _ops
-    _ops.force_generic(0)
-    _ops.persistent_steps = was
+    with gpu_ops(persistent_steps=False) as o:
+        yield o
 
 
 def make_inputs(case, seed, device=DEV, B=None):

@@ -10,6 +10,7 @@ the float64 contract with scales = (0, 1) under a tolerance derived per case (ho
 import pytest
 import torch
 
+from gpu_ops import gpu_ops
 from test_dynca_train_bf16_host import (CLOSE_TO_F32, MS_ROWS, RATE, ROWS, _rb, check_gram, check_t1, from_bits, make_case, rel_l2,
                                         run_stage_checks)
 
@@ -21,16 +22,9 @@ PHILOX_SEED, PHILOX_STEP = 0x5EED0042, 5
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    was = _ops.persistent_steps
-    _ops.persistent_steps = False
-    assert _ops.set_dynca_precision("f32") == "f32"
-    yield _ops
-    _ops.persistent_steps = was
-    assert _ops.set_dynca_precision("f32") == "f32"
+    with gpu_ops(persistent_steps=False) as o:
+        yield o
+        assert o.set_dynca_precision("f32") == "f32"
 
 
 @pytest.fixture(autouse=True)

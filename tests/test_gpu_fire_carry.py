@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -20,16 +21,9 @@ NOCARRY, DENSE, WAVE = 64, 32, 2
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.set_cond_precision(0)
-    _ops.check_errors()
-    default = _ops.persistent_cond
-    _ops.persistent_cond = False          # the per-step kernels are under test
-    yield _ops
-    _ops.persistent_cond = default
-    _ops.force_generic(0)
+    with gpu_ops(persistent_cond=False) as o:          # the per-step kernels are under test
+        o.check_errors()
+        yield o
 
 
 def _prm(C, seed, hidden=64):

@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_gpu_configs import rand_cond_prm, rand_dynca_prm
 from util import GATE_K, REL_TOL, grads_match_outside
 
@@ -40,13 +41,8 @@ DYNCA_NAMES = {"w1": "w1.weight", "b1": "w1.bias", "w2": "w2.weight", "b2": "w2.
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    yield _ops
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
+    with gpu_ops() as o:
+        yield o
 
 
 @pytest.fixture(autouse=True)

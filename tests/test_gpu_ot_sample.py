@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_ops import gpu_ops
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 # (3, 1027, 1026) asks for more than the entry point's 1024 positions per row (the gather's limit): there the refusal is what is
@@ -18,9 +20,9 @@ KEY_BITS = (1, 4, 8, 9, 16, 17, 32)
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops
-    ops.check_errors()
-    return ops
+    with gpu_ops() as o:
+        o.check_errors()
+        yield o
 
 
 def mirror(ops, *a, **k):

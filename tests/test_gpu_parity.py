@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import REL_TOL, T, grad_close, grads_match_outside, load, rel_err, sd
 
 pytestmark = pytest.mark.gpu
@@ -19,13 +20,10 @@ DEV = "cuda"
 def ops(request):
     """Every parity test runs twice: aligned fast-path kernels where the shape allows, and with the
     generic any-shape kernels forced (ncahip_debug_force_generic)."""
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops._test_mode = {"fast": 0, "generic": 1, "wave": 2 | 8}[request.param]   # wave: + backward kernel A in the form that is not the mode's default
-    _ops.force_generic(_ops._test_mode)
-    yield _ops
-    _ops.force_generic(False)
+    mode = {"fast": 0, "generic": 1, "wave": 2 | 8}[request.param]   # wave: + backward kernel A in the form that is not the mode's default
+    with gpu_ops(force=mode) as o:
+        o._test_mode = mode
+        yield o
 
 
 def dyn_w(ops, prm, like):

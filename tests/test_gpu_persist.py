@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from util import REL_TOL, T, load, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -15,11 +16,8 @@ DEV = "cuda"
 
 @pytest.fixture(scope="module")
 def ops():
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    yield _ops
-    _ops.persistent_steps = True
+    with gpu_ops() as o:
+        yield o
 
 
 def _prm(C, fc, cc, seed, scale=1.0):

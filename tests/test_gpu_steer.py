@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_dynca_bf16_host import bf16_inputs, check_caps, contract_step
 from test_gpu_configs import rand_dynca_prm
 from util import REL_TOL, REPLAY_TOL, rel_err
@@ -42,16 +43,10 @@ T_FREE = 3
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    _ops.persistent_steps = True
-    assert _ops.set_dynca_precision("f32") == "f32"
-    yield _ops
-    _ops.persistent_steps = True
-    assert _ops.set_dynca_precision("f32") == "f32"
-    assert _ops.lib().ncahip_dynca_direction(None, 0, 0, 0) == 0
+    with gpu_ops(persistent_steps=True) as o:
+        yield o
+        assert o.set_dynca_precision("f32") == "f32"
+        assert o.lib().ncahip_dynca_direction(None, 0, 0, 0) == 0
 
 
 # ------------------------------------------------------------------ inputs and fields (built once per case, never written to)

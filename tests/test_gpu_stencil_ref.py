@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nca_oracle as O
+from gpu_ops import gpu_ops
 from test_stencil_ref_host import (DYNCA_FILTERS, EDGE, F64, PADS, ROWS8, SMALL, SOBEL_Y, THRESHOLD, _t, adjoint_abs, check_dynca, compare,
                                    cond_eval, cond_ref, dynca_eval, edge_ref, encoder_ref, gamma, pad_ok, rand, stencil)
 from util import rel_err
@@ -56,11 +57,8 @@ ADJOINT = [(2, 3, 5, 12), (1, 2, 9, 1)]
 
 @pytest.fixture(scope="module")
 def ops():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    from ncahip import ops as _ops
-    _ops.selftest()
-    _ops.force_generic(0)
-    return _ops
+    with gpu_ops() as o:
+        yield o
 
 
 def _say(case, **kv):

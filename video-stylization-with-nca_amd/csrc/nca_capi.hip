@@ -4,7 +4,6 @@
 
 #include <cstdarg>
 #include <cstdio>
-#include <mutex>
 
 #include "nca_kernels.h"
 
@@ -159,8 +158,8 @@ int ncahip_debug_inject_error(unsigned bits) {   // test hook: what a kernel doe
     return 0;
 }
 
-int ncahip_debug_persist_drop_tiles(int n) {   // test hook: see nca_set_persist_drop_tiles
-    nca_set_persist_drop_tiles(n < 0 ? 0 : n);
+int ncahip_debug_persist_drop_tiles(int n) {   // test hook: see NcaModes::persist_drop_tiles
+    nca_modes().persist_drop_tiles = n < 0 ? 0 : n;
     return 0;
 }
 
@@ -169,36 +168,22 @@ const char* ncahip_last_error(void) { return g_err; }
 
 int ncahip_cond_precision(int mode) {
     if (mode != 0 && mode != 1) return fail(NCAHIP_EINVAL, "cond precision: 0 (exact fp32) or 1 (bf16x3)");
-    nca_set_cond_precision(mode);
+    nca_modes().cond_precision = mode;
     return 0;
 }
 
-// 0 = exact fp32 (default), 1 = both 1x1 products of the forward step on bf16 MFMA; read at enqueue time by the fp32 forward entry
-// points only (never by a backward one)
-static std::atomic<int> g_dynca_precision{0};
 int ncahip_dynca_precision(int mode) {
     if (mode != 0 && mode != 1) return fail(NCAHIP_EINVAL, "dynca precision: 0 (exact fp32) or 1 (bf16 MFMA)");
-    return g_dynca_precision.exchange(mode, std::memory_order_relaxed);
+    return nca_dynca_precision_exchange(mode);
 }
-static bool dynca_bf16_mfma(int C, int fc) { return g_dynca_precision.load(std::memory_order_relaxed) == 1 && nca_dynca_bf16_shape_ok(C, fc); }
+static bool dynca_bf16_mfma(int C, int fc) { return nca_dynca_precision() == 1 && nca_dynca_bf16_shape_ok(C, fc); }
 
-// Steered perception: the per-cell direction field [Bd,2,H,W] (plane 0 = s, plane 1 = c) the DyNCA forward rotates every Sobel pair by.
-// Process-wide like the precision; the eight fp32 forward entry points that honour the precision take ONE snapshot per call at enqueue
-// time (the clip drivers hand theirs to the steps they enqueue).  Every other DyNCA step entry point refuses to run while a field is
-// attached: a silently unsteered result or gradient is the failure to exclude.
+// Steered perception: the direction field (nca_modes.h) is process-wide like the precision; the eight fp32 forward entry points that
+// honour the precision take ONE snapshot per call at enqueue time (the clip drivers hand theirs to the steps they enqueue).  Every
+// other DyNCA step entry point refuses to run while a field is attached: a silently unsteered result or gradient is the failure to exclude.
 namespace {
-struct DyncaDir {
-    const float* p;
-    int Bd, H, W;
-};
-std::mutex g_dynca_dir_mu;
-DyncaDir g_dynca_dir{nullptr, 0, 0, 0};
-DyncaDir dynca_dir_snapshot() {
-    std::lock_guard<std::mutex> lk(g_dynca_dir_mu);
-    return g_dynca_dir;
-}
 // an honouring entry point: the attached field must fit the call
-int dynca_dir_check(const DyncaDir& d, const char* who, int B, int H, int W) {
+int dynca_dir_check(const NcaDyncaDir& d, const char* who, int B, int H, int W) {
     if (!d.p) return 0;
     if (H != d.H || W != d.W)
         return fail(NCAHIP_EINVAL, "%s: the attached direction field (ncahip_dynca_direction) is %d x %d, the call is %d x %d", who, d.H, d.W, H, W);
@@ -208,28 +193,13 @@ int dynca_dir_check(const DyncaDir& d, const char* who, int B, int H, int W) {
 }
 // an entry point that does not steer (backward, bf16 storage)
 int dynca_dir_refuse(const char* who) {
-    if (!dynca_dir_snapshot().p) return 0;
+    if (!nca_dynca_dir_snapshot().p) return 0;
     return fail(NCAHIP_EINVAL, "%s: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first", who);
 }
 }  // namespace
 int ncahip_dynca_direction(const float* dirs, int Bd, int H, int W) {
     if (dirs && (Bd < 1 || H < 1 || W < 1)) return fail(NCAHIP_EINVAL, "dynca direction field: Bd=%d H=%d W=%d must all be positive", Bd, H, W);
-    std::lock_guard<std::mutex> lk(g_dynca_dir_mu);
-    g_dynca_dir = dirs ? DyncaDir{dirs, Bd, H, W} : DyncaDir{nullptr, 0, 0, 0};
-    return 0;
-}
-
-static int g_force_bits = 0;   // the last ncahip_debug_force_generic argument: the persistent grow runs only with none set
-int ncahip_debug_force_generic(int on) {
-    g_force_bits = on;
-    nca_set_force_generic((on & 1) != 0);    // bit 0: generic any-shape kernels
-    nca_set_cond_variant((on >> 1) & 1);     // bit 1: symmetric wave-private ConditionedNCA kernel instead of producer/consumer
-    nca_set_bwd_bf16_exact((on & 4) != 0);   // bit 2: bf16-history backward with exact-f32 products instead of bf16 MFMA
-    nca_set_bwd_variant((on & 8) ? 3 : 0);   // bit 3: ConditionedNCA backward kernel A in the form that is NOT the mode's default (one launch <-> front + matrix)
-    nca_set_bwd_fm_nosplit((on & 16) != 0);  // bit 4: the matrix kernel walks whole super-tiles on small grids too (its summation order then equals the one-launch form's)
-    nca_set_cond_pc_dense((on & 32) != 0);   // bit 5: the fp32 producer/consumer step runs every cell (no firing-cell lists)
-    nca_set_cond_pc_nocarry((on & 64) != 0); // bit 6: firing-cell lists pad every tile's last group (no carry across a pair's tiles)
-    nca_set_cond_pc_wg_cap((on >> 8) & 255); // bits 8-15: at most this many workgroups per producer/consumer step launch (0: no cap)
+    nca_dynca_dir_set(dirs ? NcaDyncaDir{dirs, Bd, H, W} : NcaDyncaDir{nullptr, 0, 0, 0});
     return 0;
 }
 
@@ -278,12 +248,12 @@ enum DyncaFwdKind { kDyncaFwdF32, kDyncaFwdMs, kDyncaFwdBf16 };
 static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, const void* x_in, void* x_out, int ring, int T, const float* cond, const float* u,
                           const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
                           int pad_mode, float update_rate, uint64_t seed, uint64_t step0, float* pc_scratch, ncahip_stream_t stream,
-                          const DyncaDir* dir_of_caller = nullptr) {
+                          const NcaDyncaDir* dir_of_caller = nullptr) {
     const bool ms = kind == kDyncaFwdMs, bf16 = kind == kDyncaFwdBf16;
     if (bf16) {
         if (int rc = dynca_dir_refuse(what)) return rc;
     }
-    const DyncaDir dir = bf16 ? DyncaDir{nullptr, 0, 0, 0} : dir_of_caller ? *dir_of_caller : dynca_dir_snapshot();   // one read per call
+    const NcaDyncaDir dir = bf16 ? NcaDyncaDir{nullptr, 0, 0, 0} : dir_of_caller ? *dir_of_caller : nca_dynca_dir_snapshot();   // one read per call
     char* const states = (char*)const_cast<void*>(x_in);
     if (!single && (ring < 2 || T < 0)) return fail(NCAHIP_EINVAL, "dynca nsteps: ring >= 2 and T >= 0 required");
     if (int rc = check_dynca(x_in, single ? x_out : states + 1, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode,
@@ -367,8 +337,8 @@ size_t ncahip_dynca_nsteps_persist_workspace(int B, int C, int H, int W, int fc,
 static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, int T, const float* cond, const float* u, const float* w1,
                                         const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
                                         int pad_mode, float update_rate, uint64_t seed, uint64_t step0, void* workspace,
-                                        size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream, const DyncaDir* dir_of_caller = nullptr) {
-    const DyncaDir dir = dir_of_caller ? *dir_of_caller : dynca_dir_snapshot();   // one read per call
+                                        size_t workspace_bytes, unsigned epoch, ncahip_stream_t stream, const NcaDyncaDir* dir_of_caller = nullptr) {
+    const NcaDyncaDir dir = dir_of_caller ? *dir_of_caller : nca_dynca_dir_snapshot();   // one read per call
     if (T < 1 || !workspace) return fail(NCAHIP_EINVAL, "dynca nsteps persist: T >= 1 and a workspace required");
     if (epoch < 1 || epoch >= (1u << 20)) return fail(NCAHIP_EINVAL, "dynca nsteps persist: epoch must be in [1, 2^20) (zero the workspace and restart at 1 when it runs out)");
     if (int rc = check_dynca(x_in, x_out, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;   // (refuses x_in == x_out)
@@ -447,7 +417,7 @@ int ncahip_cond_grow_fwd_persist_f32(float* states, uint8_t* pre, int ring, int 
     const bool ubits = u_is_bits(u, seed);
     if (u && !ubits) return fail(NCAHIP_ERANGE, "cond grow persist: explicit float uniforms not covered (bit-packed masks or Philox); use ncahip_cond_grow_fwd_f32");
     if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
-    if (nca_get_cond_precision() != 0 || g_force_bits != 0 || !nca_cond_default_family())
+    if (!nca_cond_fwd_default())
         return fail(NCAHIP_ERANGE, "cond grow persist: only the default exact-f32 producer/consumer family has a persistent twin; use ncahip_cond_grow_fwd_f32");
     if (int rc = device_error_rc("cond grow")) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -579,7 +549,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
     if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
         return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
     // the direction field of this call: read once, handed to every step the clip enqueues
-    const DyncaDir dir = dynca_dir_snapshot();
+    const NcaDyncaDir dir = nca_dynca_dir_snapshot();
     const DyncaFwdKind kind = two_scale ? kDyncaFwdMs : kDyncaFwdF32;
     // the per-step entry point's body with this call's field: (x_in, x_out) a single step, x_out == NULL the ring `states` of 2 slots
     auto steps = [&](const float* x_in, float* x_out, int T, const float* cf, const float* uf, uint64_t s0) {
@@ -715,7 +685,6 @@ int ncahip_cond_fire_words(uint64_t* words, int Tc, int B, int H, int W, float f
 // fire-word launches of the last ncahip_cond_grow_fwd_f32 that enqueued all its steps (0: its steps drew their masks themselves)
 static std::atomic<int> g_fire_word_launches{0};
 int ncahip_debug_fire_word_launches(void) { return g_fire_word_launches.load(std::memory_order_relaxed); }
-constexpr int kForceNoFireWords = 128;   // ncahip_debug_force_generic bit 7
 // Shortest grow that draws its masks beforehand.  One fire-word launch has to be bought back by the steps it serves, and what a step
 // saves grows with the tiles a wave pair stages in it: rounds = super-tiles per workgroup of the step launch.  Measured with the grow
 // timed both ways over a ladder of T (tools/fire_words_cost.py, profiles/r8a_fire_words_cost.jsonl: launch cost / saving per step,
@@ -781,8 +750,8 @@ static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring,
     unsigned long long* const fw_scratch = reinterpret_cast<unsigned long long*>(x_final);
     const size_t fw_step = pslot / 64;   // words per step
     int fw_chunk = 0;                    // steps per fire-word launch; 0: the steps draw their masks themselves
-    const int fw_cap = (g_force_bits >> 16) & 255;   // test hook: steps per fire-word launch; set, it also waives fire_words_pay
-    if (!bf16 && !u && (g_force_bits & kForceNoFireWords) == 0 && (fw_cap > 0 || fire_words_pay(T, B, H, W))) {
+    const int fw_cap = nca_modes().fire_words_cap;   // test hook: steps per fire-word launch; set, it also waives fire_words_pay
+    if (!bf16 && !u && !nca_modes().no_fire_words && (fw_cap > 0 || fire_words_pay(T, B, H, W))) {
         NcaCondArgs a0 = step_args(0);
         a0.fire_words = fw_scratch;
         // every slot is aligned as slots 0 and 1 are (W % 16 == 0 makes the slot size a multiple of 64 bytes)

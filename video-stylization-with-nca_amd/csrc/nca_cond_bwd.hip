@@ -987,8 +987,6 @@ __global__ __launch_bounds__(64) void reduce_wp_kernel(const float* __restrict__
     dst[c * 27 + i] = acc;
 }
 
-int g_bwd_variant = [] { const char* e = getenv("NCAHIP_BWD_VARIANT"); return e ? atoi(e) : 0; }();
-
 // rows per strip of kernel B: modelled cost = rounds of resident waves x (rows + 2 halo rows), smallest wins (ties: taller strips)
 int stencil_srows(int B, int C, int H, int W) {
     const long slots = (long)nca_cu_count() * 8;   // two waves per SIMD
@@ -1023,7 +1021,8 @@ hipError_t launch_stencil(const NcaCondBwdArgs& ba_in, hipStream_t st, bool bf16
 bool narrow_is_fm(const NcaCondBwdArgs& ba, bool bfm) {
     const int nst_ = ba.f.B * ((ba.f.W + 15) / 16) * ((ba.f.H + 15) / 16);
     const bool default_fm = bfm || 2 * nst_ <= ba.nslab;
-    return ba.pscr && ba.doscr && (g_bwd_variant == 2 || (g_bwd_variant == 0 && default_fm) || (g_bwd_variant == 3 && !default_fm));
+    const int v = nca_modes().bwd_variant;
+    return ba.pscr && ba.doscr && (v == 2 || (v == 0 && default_fm) || (v == 3 && !default_fm));
 }
 
 template <int CP, typename ST, bool BFM = false>
@@ -1068,14 +1067,11 @@ int nca_cond_bwd_slab_floats(int C, int hidden) { (void)hidden; return slab_floa
 int nca_cond_bwd_nslab() { return nca_cu_count(); }   // one persistent workgroup (and one slab) per CU
 int nca_cond_bwd_nblk(int B, int C, int H, int W) { return stencil_blocks(B, C, H, W, stencil_srows(B, C, H, W)); }
 
-static bool g_bwd_bf16_exact = getenv("NCAHIP_BWD_BF16_EXACT") != nullptr;
-void nca_set_bwd_bf16_exact(bool on) { g_bwd_bf16_exact = on; }
-void nca_set_bwd_variant(int v) { g_bwd_variant = v; }
-
 // W % 4 == 0 and 16-byte aligned tensors required (checked by the C ABI).
 hipError_t nca_launch_cond_step_bwd(const NcaCondBwdArgs& ba, hipStream_t st, bool bf16) {
     if (bf16) {   // history (f.x_in, x_next) and goal hold bf16; gradients and scratch stay f32
-        if (g_bwd_bf16_exact) {   // test hook: exact-f32 recomputation from the widened history
+        const bool exact = nca_modes().bwd_bf16_exact;
+        if (exact) {   // test hook: exact-f32 recomputation from the widened history
             if (ba.f.C <= 12) return launch_bwd<12, StBF16>(ba, st);
             if (ba.f.C <= 16) return launch_bwd<16, StBF16>(ba, st);
         }
@@ -1084,8 +1080,8 @@ hipError_t nca_launch_cond_step_bwd(const NcaCondBwdArgs& ba, hipStream_t st, bo
         if (ba.f.C <= 20) {   // the reference's default model over a bf16 history: front + matrix kernels at CP = 20 (bf16 MFMA, one wave per
                               // SIMD); with the exact hook: exact-f32 products of the widened history, as the fp32 form
             if (!ba.pscr || !ba.doscr) return hipErrorInvalidValue;
-            if (hipError_t e = nca_launch_cond_step_bwd_fm(ba, st, g_bwd_bf16_exact ? 1 : 2); e != hipSuccess) return e;
-            return ba.opmode == 1 ? hipSuccess : launch_stencil(ba, st, !g_bwd_bf16_exact);
+            if (hipError_t e = nca_launch_cond_step_bwd_fm(ba, st, exact ? 1 : 2); e != hipSuccess) return e;
+            return ba.opmode == 1 ? hipSuccess : launch_stencil(ba, st, !exact);
         }
         return hipErrorInvalidValue;
     }
@@ -1101,7 +1097,7 @@ hipError_t nca_launch_cond_step_bwd(const NcaCondBwdArgs& ba, hipStream_t st, bo
 
 bool nca_cond_bwd_is_fm(const NcaCondBwdArgs& ba, bool bf16) {
     if (ba.f.C > 16) return true;                                   // wide channel counts: front + matrix kernels only
-    return narrow_is_fm(ba, bf16 && !g_bwd_bf16_exact);
+    return narrow_is_fm(ba, bf16 && !nca_modes().bwd_bf16_exact);
 }
 
 hipError_t nca_launch_reduce_rows(const float* src, float* dst, int n, int m, hipStream_t st, bool accumulate) {
@@ -1111,7 +1107,7 @@ hipError_t nca_launch_reduce_rows(const float* src, float* dst, int n, int m, hi
 hipError_t nca_launch_cond_bwd_unpermute(const float* red, int C, int hidden, bool bf16_history, float* g_w1, float* g_w2, float* g_w3,
                                          float* g_b1, float* g_b2, hipStream_t st) {
     const int n = hidden * 3 * C + hidden * hidden + C * hidden + 2 * hidden;
-    const int slot_order = (bf16_history && !g_bwd_bf16_exact) ? 1 : 0;   // the bf16-MFMA products accumulate dW1 in operand-slot order
+    const int slot_order = (bf16_history && !nca_modes().bwd_bf16_exact) ? 1 : 0;   // the bf16-MFMA products accumulate dW1 in operand-slot order
     hipLaunchKernelGGL(cond_bwd_unpermute_kernel, dim3((n + 255) / 256), dim3(256), 0, st, red, C, bwd_cp(C), hidden, slot_order, g_w1, g_w2,
                        g_w3, g_b1, g_b2);
     return hipGetLastError();

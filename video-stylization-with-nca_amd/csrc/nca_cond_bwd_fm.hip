@@ -950,8 +950,6 @@ __global__ __launch_bounds__(64 * NW, 1) void cond_step_bwd_mlp_kernel(const Nca
 }
 
 
-bool g_fm_nosplit = false;   // test hook (ncahip_debug_force_generic bit 4): whole super-tiles per walk item on every grid
-
 template <int CP, typename ST, bool BFM, int NTW = 2>
 hipError_t launch_fm(const NcaCondBwdArgs& ba_in, hipStream_t st) {
     NcaCondBwdArgs ba = ba_in;
@@ -977,7 +975,7 @@ hipError_t launch_fm(const NcaCondBwdArgs& ba_in, hipStream_t st) {
     const size_t lds = (size_t)KM::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
-    ba.msplit = (!g_fm_nosplit && 2 * nst <= ba.nslab) ? 1 : 0;           // small grids: (super-tile, pass) items
+    ba.msplit = (!nca_modes().fm_nosplit && 2 * nst <= ba.nslab) ? 1 : 0;           // small grids: (super-tile, pass) items
     const int items = nst << ba.msplit;
     const int grid = ba.opmode == 1 ? 1 : (items < ba.nslab ? items : ba.nslab);   // one slab per workgroup (export launch: one workgroup)
 #if defined(NCA_STAMPS)
@@ -988,8 +986,6 @@ hipError_t launch_fm(const NcaCondBwdArgs& ba_in, hipStream_t st) {
 }
 
 }  // namespace
-
-void nca_set_bwd_fm_nosplit(bool on) { g_fm_nosplit = on; }
 
 // channel padding of the instantiation that serves C channels
 static int fm_cp(int C) { return C <= 12 ? 12 : (C <= 16 ? 16 : (C <= 20 ? 20 : (C <= 24 ? 24 : 32))); }

@@ -387,26 +387,21 @@ hipError_t launch_cond(const NcaCondArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// ---- test hooks, and the dispatch: smallest instantiation that covers C; padding lanes carry zero weights ---
-static bool g_force_generic = getenv("NCAHIP_FORCE_GENERIC") != nullptr;
-static int g_cond_variant = getenv("NCAHIP_COND_VARIANT") ? atoi(getenv("NCAHIP_COND_VARIANT")) : 0;
-void nca_set_force_generic(bool on) { g_force_generic = on; }
-void nca_set_cond_variant(int v) { g_cond_variant = v; }
-bool nca_cond_default_family() { return !g_force_generic && g_cond_variant == 0; }
+// ---- the dispatch (modes: nca_modes.h): smallest instantiation that covers C; padding lanes carry zero weights ---
 
 // the tile kernels address with 32-bit byte offsets from the batch item's base (issue_loads): H*W < 2^24, C*H*W*4 < 2^32
 static bool cond_tiled(const NcaCondArgs& a) {
     const bool small = (size_t)a.H * a.W < ((size_t)1 << 24) && (size_t)(a.C <= 16 ? 16 : 20) * a.H * a.W * 4 < ((size_t)1 << 32);
-    return !g_force_generic && small && (a.W % 4 == 0) && aligned16(a.x_in) && aligned16(a.x_out) && (a.goal == nullptr || aligned16(a.goal));
+    return !nca_modes().force_generic && small && (a.W % 4 == 0) && aligned16(a.x_in) && aligned16(a.x_out) && (a.goal == nullptr || aligned16(a.goal));
 }
 
 bool nca_cond_fire_words_ok(const NcaCondArgs& a) {
-    return cond_tiled(a) && a.C <= 20 && g_cond_variant != 1 && a.u == nullptr && a.W % 16 == 0 && a.H % 4 == 0 && nca_cond_pc_fire_words_ok(a);
+    return cond_tiled(a) && a.C <= 20 && nca_modes().cond_variant != 1 && a.u == nullptr && a.W % 16 == 0 && a.H % 4 == 0 && nca_cond_pc_fire_words_ok(a);
 }
 
 hipError_t nca_launch_cond_step_fwd(const NcaCondArgs& a, hipStream_t st) {
     const bool tiled = cond_tiled(a);
-    if (tiled && a.C <= 16) return g_cond_variant == 1 ? nca_launch_cond_step_fwd_wave(a, st) : nca_launch_cond_step_fwd_pc(a, st);
+    if (tiled && a.C <= 16) return nca_modes().cond_variant == 1 ? nca_launch_cond_step_fwd_wave(a, st) : nca_launch_cond_step_fwd_pc(a, st);
     if (tiled && a.C <= 20) return nca_launch_cond_step_fwd_pc(a, st);   // the reference's default C = 20: producer/consumer kernel, wide carve
     if (a.C <= 12) return launch_cond<12>(a, st);
     if (a.C <= 16) return launch_cond<16>(a, st);

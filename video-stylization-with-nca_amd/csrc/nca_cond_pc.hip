@@ -459,7 +459,6 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     }
 }
 
-int g_pc_wg_cap = 0;       // test hook (ncahip_debug_force_generic bits 8-15): at most this many workgroups per step launch (0: no cap)
 template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false>
 hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     using PK = PCfg<CP>;
@@ -470,23 +469,21 @@ hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     const int cus = nca_cu_count();
     const int nst = a.B * ((a.W + 15) / 16) * ((a.H + 15) / 16);
     int nwg = nst < cus ? nst : cus;
-    if (g_pc_wg_cap > 0 && nwg > g_pc_wg_cap) nwg = g_pc_wg_cap;
+    if (const int cap = nca_modes().pc_wg_cap; cap > 0 && nwg > cap) nwg = cap;   // test hook
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(kThreadsW), lds, st, a);
     return hipGetLastError();
 }
 
-bool g_pc_dense = false;   // test hook (ncahip_debug_force_generic bit 5): the exact-f32 consumer runs every cell
-bool g_pc_nocarry = false; // test hook (bit 6): firing-cell lists with every tile's last group padded (no carry across tiles)
-// the default kernels of the exact-f32, fp32-storage step (no test hook set) have a twin that reads a.fire_words
-bool pc_fire_words_kernels() { return !g_pc_dense && !g_pc_nocarry; }
+// the default kernels of the exact-f32, fp32-storage step (neither test hook set: pc_dense, pc_nocarry) have a twin that reads a.fire_words
+bool pc_fire_words_kernels() { return !nca_modes().pc_dense && !nca_modes().pc_nocarry; }
 // the exact-f32, fp32-storage step: firing-cell lists (narrow carve: with the carry) unless a test hook asks otherwise
 template <int CP, bool EXACT>
 hipError_t launch_cond_pc_f32(const NcaCondArgs& a, hipStream_t st) {
-    if (g_pc_dense) return launch_cond_pc<CP, EXACT, StF32, false, false>(a, st);
+    if (nca_modes().pc_dense) return launch_cond_pc<CP, EXACT, StF32, false, false>(a, st);
     const bool fw = a.fire_words != nullptr && nca_cond_pc_fire_words_ok(a);
     if constexpr (CP <= 16) {
         if (fw) return launch_cond_pc<CP, EXACT, StF32, false, true, true, true>(a, st);
-        if (!g_pc_nocarry) return launch_cond_pc<CP, EXACT, StF32, false, true, true>(a, st);
+        if (!nca_modes().pc_nocarry) return launch_cond_pc<CP, EXACT, StF32, false, true, true>(a, st);
     } else {
         if (fw) return launch_cond_pc<CP, EXACT, StF32, false, true, false, true>(a, st);
     }
@@ -495,10 +492,6 @@ hipError_t launch_cond_pc_f32(const NcaCondArgs& a, hipStream_t st) {
 
 }  // namespace
 
-void nca_set_cond_pc_dense(bool on) { g_pc_dense = on; }
-void nca_set_cond_pc_nocarry(bool on) { g_pc_nocarry = on; }
-void nca_set_cond_pc_wg_cap(int n) { g_pc_wg_cap = n > 0 ? n : 0; }
-
 // W % 4 == 0 and 16-byte aligned x_in / goal: caller (nca_cond_generic.hip dispatch) guarantees it.
 extern "C" void nca_debug_set_stamp_buffer_pc(void* p);
 static unsigned long long* g_stamp_pc = nullptr;
@@ -506,12 +499,9 @@ extern "C" void nca_debug_set_stamp_buffer_pc(void* p) { g_stamp_pc = (unsigned 
 #if defined(NCA_STAMPS)
 unsigned long long* nca_debug_stamp_ptr() { return g_stamp_pc; }
 #endif
-static int g_cond_precision = 0;
-void nca_set_cond_precision(int mode) { g_cond_precision = mode; }
-int nca_get_cond_precision() { return g_cond_precision; }
 // the firing-cell-list kernels as they run by default; the words' grid needs whole, aligned tiles and 8-byte aligned words
 bool nca_cond_pc_fire_words_ok(const NcaCondArgs& a) {
-    return pc_fire_words_kernels() && g_cond_precision == 0 && a.u == nullptr && a.C <= 20 && a.W % 16 == 0 && a.H % 4 == 0 &&
+    return pc_fire_words_kernels() && nca_modes().cond_precision == 0 && a.u == nullptr && a.C <= 20 && a.W % 16 == 0 && a.H % 4 == 0 &&
            ((uintptr_t)a.fire_words & 7) == 0;
 }
 hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) {
@@ -519,7 +509,7 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) 
     a.dbg = g_stamp_pc;
     a.err = nca_error_word_device();
     const bool h64 = a.hidden == 64;
-    if (g_cond_precision == 1 && h64) {   // opt-in bf16x3 emulation of the fp32 products (exact shapes only)
+    if (nca_modes().cond_precision == 1 && h64) {   // opt-in bf16x3 emulation of the fp32 products (exact shapes only)
         if (a.C == 12) return launch_cond_pc<12, true, StF32, true>(a, st);
         if (a.C == 16) return launch_cond_pc<16, true, StF32, true>(a, st);
     }

@@ -37,8 +37,6 @@
 #include "nca_dynca_bf16.h"
 #include "nca_kernels.h"
 
-static int g_drop_tiles = 0;
-void nca_set_persist_drop_tiles(int n) { g_drop_tiles = n; }
 
 namespace {
 
@@ -884,7 +882,8 @@ hipError_t launch_persist(int lds_floats, const NcaDyncaPersistArgs& a, hipStrea
     if (!*fits || query_only) return hipSuccess;
     // test hook (ncahip_debug_persist_drop_tiles): launch only the first tiles -- the others' neighbours never hear from them, their
     // bounded polls expire, the launch drains and the sticky error word carries bit 1: what a non-resident workgroup looks like
-    const int grid = g_drop_tiles > 0 && g_drop_tiles < ntiles ? ntiles - g_drop_tiles : ntiles;
+    const int drop = nca_modes().persist_drop_tiles;   // test hook
+    const int grid = drop > 0 && drop < ntiles ? ntiles - drop : ntiles;
     hipLaunchKernelGGL(KERN, dim3(grid), dim3(kPT), lds, st, a);
     return hipGetLastError();
 }

@@ -5,6 +5,8 @@
 
 #include <atomic>
 
+#include "nca_modes.h"
+
 // ---- per-DEVICE launch state (the C ABI is legal from any host thread on any device: caches are keyed by the device that is
 // current at the call, never by the calling thread) -----------------------------------------------------------------------
 constexpr int kNcaMaxDevices = 64;
@@ -97,7 +99,6 @@ struct NcaDyncaPersistArgs {
     const float* dirs;   // steered perception: per-cell directions [Bd,2,H,W] or null, as NcaDyncaArgs::dirs (staged once per launch)
     size_t dirs_bstride; // 2*H*W, or 0 for Bd == 1
 };
-void nca_set_persist_drop_tiles(int n);   // test hook: the persistent launch leaves out its last n tiles (their neighbours' polls expire)
 bool nca_dynca_persist_shape_ok(int B, int C, int H, int W, int fc, int c_cond);
 int nca_dynca_persist_tiles(int B, int H, int W);
 // (value, tag) pairs per parity of the ring exchange: tiles x C x 60 fine ring cells (+ 48 coarse means: two_scale)
@@ -135,11 +136,6 @@ int nca_cond_persist_tiles(int B, int H, int W);
 size_t nca_cond_persist_xch_pairs(int B, int C, int H, int W);
 // query_only: only decide whether every tile gets a CU of its own on the current device (*fits)
 hipError_t nca_launch_cond_persist(const NcaCondPersistArgs& a, hipStream_t st, bool query_only, bool* fits);
-int nca_get_cond_precision();
-void nca_set_cond_pc_dense(bool on);   // test hook: the fp32 producer/consumer step without firing-cell lists
-void nca_set_cond_pc_nocarry(bool on); // test hook: firing-cell lists without the carry of partial groups across tiles
-void nca_set_cond_pc_wg_cap(int n);    // test hook: cap on the workgroups of a producer/consumer step launch (0: none)
-bool nca_cond_default_family();   // no test hook / environment override routes the ConditionedNCA step away from its default kernels
 
 struct NcaCondArgs {
     const float* x_in;
@@ -195,7 +191,6 @@ hipError_t nca_launch_cond_bwd_unpermute(const float* red, int C, int hidden, bo
                                          float* g_b1, float* g_b2, hipStream_t st);
 int nca_cond_bwd_nslab();
 int nca_cond_bwd_nblk(int B, int C, int H, int W);
-void nca_set_bwd_fm_nosplit(bool on);
 bool nca_cond_bwd_is_fm(const NcaCondBwdArgs& ba, bool bf16);   // the form nca_launch_cond_step_bwd will run for these arguments
 constexpr size_t kNcaCondBwdOpimgBytes = 128 * 1024;            // upper bound of the matrix kernel's operand image (CP = 32: 100 KB)
 hipError_t nca_launch_cond_step_bwd(const NcaCondBwdArgs& a, hipStream_t st, bool bf16 = false);   // bf16: f.x_in / x_next / f.goal hold bf16
@@ -203,7 +198,6 @@ hipError_t nca_launch_cond_step_bwd(const NcaCondBwdArgs& a, hipStream_t st, boo
 hipError_t nca_launch_cond_step_bwd_fm(const NcaCondBwdArgs& a, hipStream_t st, int mode);
 size_t nca_cond_bwd_fm_pscr_bytes(int B, int C, int H, int W);
 size_t nca_cond_bwd_fm_doscr_bytes(int B, int C, int H, int W);
-void nca_set_bwd_variant(int v);   // kernel A: 0 = the faster form per mode (bf16 MFMA: front + matrix kernels; fp32 products: one launch), 1 = one launch always, 2 = front + matrix always, 3 = the slower form per mode (cross-check)
 hipError_t nca_launch_reduce_rows(const float* src, float* dst, int n, int m, hipStream_t st, bool accumulate = false);   // dst (+)= column sums
 // nca_gram.hip: out[ma*nb + ma] = [sum_n a[i][n] * b[j][n] | sum_n a[i][n]] over all B*HW cells; b rows from two tensors
 int nca_dynca_bwd_grid(int B, int H, int W);   // upper bound over C (workspace sizing)
@@ -299,15 +293,9 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_step_fwd_bf16(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_finalize_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, int B, int C, int H, int W,
                                          int alive_ch, float thr, float lo, float hi, hipStream_t st);
-void nca_set_cond_precision(int mode);   // 0 = exact-f32 MFMA (default), 1 = bf16x3 emulation in the producer/consumer kernel
-void nca_set_bwd_bf16_exact(bool on);  // test hook: the bf16-history backward recomputes in exact f32 instead of on bf16 MFMA
-void nca_set_cond_variant(int v);  // 0 = producer/consumer (default), 1 = symmetric wave-private
 
 // diagnostic build hook (-DNCA_STAMPS): buffer that receives s_memtime stamps, [wave][tile][8]
 void nca_debug_set_stamp_buffer(unsigned long long* p);
-
-// test hook: route every fused step through the generic (any-shape) kernels
-void nca_set_force_generic(bool on);
 
 // stencils and small kernels (nca_stencil.hip)
 hipError_t nca_launch_dynca_perceive(const float* x, float* y, int B, int C, int H, int W, int pad, hipStream_t st);

@@ -87,7 +87,7 @@ def _w(t: torch.Tensor, name: str, like: torch.Tensor) -> torch.Tensor:
 
 
 def force_generic(on) -> None:
-    """Test hook (see ncahip.h): True/1 = generic any-shape kernels, 2 = symmetric wave-private ConditionedNCA
+    """Test hook (see ncahip.h; the bits are decoded in csrc/nca_modes.hip): True/1 = generic any-shape kernels, 2 = symmetric wave-private ConditionedNCA
     kernel, 32 = fp32 producer/consumer step without firing-cell lists, 64 = firing-cell lists without the carry across
     tiles, 128 = cond_grow's steps draw their fire masks in the kernel (no fire words), n << 8 = at most n workgroups per
     producer/consumer step launch, n << 16 = at most n steps per fire-word launch (and no minimum grow length or grid size), False/0 = defaults."""
@@ -165,6 +165,21 @@ def dynca_direction(dirs: torch.Tensor):
             yield dirs
         finally:
             _attach_direction(prev)
+
+
+def reset_modes() -> None:
+    """Every process-wide mode back to what a fresh process without environment overrides has: force_generic(0), cond precision
+    'exact', DyNCA precision 'f32', no direction field attached, no dropped tiles, persistent_steps = True, persistent_cond = False.
+    Needs no GPU.  Takes the locks of dynca_precision and dynca_direction; it must not be called inside a block of either (the block
+    would put its previous mode back on exit)."""
+    global persistent_steps, persistent_cond
+    with _dynca_precision_lock, _dynca_direction_lock:
+        force_generic(0)
+        set_cond_precision("exact")
+        set_dynca_precision("f32")
+        _attach_direction(None)
+        lib().ncahip_debug_persist_drop_tiles(0)
+        persistent_steps, persistent_cond = True, False
 
 
 def dynca_bf16_ok(C: int, fc: int) -> bool:
