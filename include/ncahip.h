@@ -781,6 +781,58 @@ int ncahip_clip_resize_yuv420_u8(const uint8_t *src, int layout, const int32_t *
                                  int ksize_y, uint8_t *dst, int out_h, int out_w, void *workspace, size_t workspace_bytes,
                                  ncahip_stream_t stream);
 
+/* ---- a whole clip per call, planar YUV images: I420 / NV12 out, straight from the fp32 state ------------------------------------------
+ * A video encoder does not take RGB24 either: it takes planar YUV 4:2:0.  The image output of the clip entry points can write it, 1.5
+ * bytes per pixel instead of 3, with no RGB image in between.  The reference never produces YUV (moviepy / cv2 take RGB), so this
+ * section fixes the arithmetic, as the one above does for the way in.
+ * RGB is the uint8 image the emits write: (uint8_t)(img * 255.0f), truncating, img as ncahip_clip_emit defines it for the DyNCA families
+ * and as ncahip_clip_emit_unit defines it for ConditionedNCA.  Matrices, ranges, Kr / Kb / Kg and the luma offset yoff (16 or 0) as above;
+ * the scales run the other way: NCAHIP_YUV_LIMITED sy = 219/255, sc = 224/255; NCAHIP_YUV_FULL sy = sc = 1.
+ * The real-valued definition, with Y' = Kr R + Kg G + Kb B:
+ *   Y = yoff + sy Y'        U = 128 + sc (B - Y') / (2 (1 - Kb))        V = 128 + sc (R - Y') / (2 (1 - Kr))
+ * The integer evaluation (the contract): coefficients are quantised as the inverse's are, q(c) = (int)(c * 2^16 + 0.5), or
+ *   (int)(c * 2^16 - 0.5) for c < 0, in C double with contraction off: k_yr = q(sy Kr), k_yb = q(sy Kb), k_ur = q(-cu Kr),
+ *   k_ub = q(cu (1 - Kb)), k_vr = q(cv (1 - Kr)), k_vb = q(-cv Kb) with cu = sc / (2 (1 - Kb)), cv = sc / (2 (1 - Kr)).  In each row the
+ *   green coefficient is the remainder that makes the row sum exact: k_yg = q(sy) - k_yr - k_yb, k_ug = -k_ur - k_ub, k_vg = -k_vr - k_vb
+ *   (a grey pixel gives U = V = 128 exactly).
+ *   Luma, per pixel:         Y = clamp(yoff + ((k_yr R + k_yg G + k_yb B + 2^15) >> 16), 0, 255)
+ *   Chroma, per 2 x 2 block, from the block's channel sums (0 .. 1020), one rounding:
+ *                            U = clamp(128 + ((k_ur sum R + k_ug sum G + k_ub sum B + 2^17) >> 18), 0, 255), V likewise
+ *   int32 accumulation, arithmetic shift; |accumulator| stays below 2^27.  The chroma sample of block (x >> 1, y >> 1) is the block mean
+ *   (centre siting): the counterpart of the nearest chroma on the way in.
+ *   (R, G, B) rows of Y / U / V:  bt601 limited  16829 33039 6416 |  -9714 -19070 28784 | 28784 -24103 -4681
+ *                                 bt601 full     19595 38470 7471 | -11058 -21710 32768 | 32768 -27439 -5329
+ *                                 bt709 limited  11966 40254 4064 |  -6596 -22188 28784 | 28784 -26145 -2639
+ *                                 bt709 full     13933 46871 4732 |  -7509 -25259 32768 | 32768 -29763 -3005
+ *   Over all 2^24 flat colours (and 2^22 random channel sums for chroma) no result is more than 1 away from the real-valued definition
+ *   rounded half up, at most 7.7e-4 of a plane's values differ from it (bt709 limited, U), and limited range yields Y in [16, 235] and
+ *   chroma in [16, 240] before the clamp.
+ * Layouts as above, per image uint8 [3H/2, W] with H and W even: NCAHIP_YUV_I420, NCAHIP_YUV_NV12.
+ * NCAHIP_CLIP_YUV420(layout, matrix, range): eight more values (0x100 .. 0x107) of the IMAGE format img_fmt of ncahip_clip_emit,
+ *   ncahip_clip_emit_inject, ncahip_clip_emit_unit and of the drivers ncahip_dynca_clip_f32, ncahip_dynca_clip_xc_f32 and
+ *   ncahip_cond_clip_f32; image n then lies at images + n * B * 3HW/2 bytes, sample b of it at + b * 3HW/2.  c_out must be 3
+ *   (NCAHIP_EINVAL), H and W even (NCAHIP_ERANGE); overlap checks use this size; any byte alignment of the image pointer is served
+ *   (plane starts are routinely misaligned: with H = W = 6, V starts at byte 45 and the next image at byte 54).  The coefficients come
+ *   from the builder below.  A lane owns 2 rows x 4 columns: it reads each of the three state channels once, forms the truncated bytes in
+ *   registers and stores one dword of Y per row and the chroma under it (NV12: one dword of UVUV; I420: two bytes of U and two of V) --
+ *   whole dwords where the row segment is 4-byte aligned in memory, 16-bit halves where it is 2-byte aligned, single bytes where a plane
+ *   starts on an odd address; the last lane of a row whose W is no multiple of 4 stores half as much.  The extra-channel family's
+ *   emit + inject stays one launch.
+ *   The result is, bit for bit, the uint8 emit followed by ncahip_clip_rgb_to_yuv420_u8.  As a FRAME format (ncahip_clip_cond,
+ *   ncahip_clip_gray, ncahip_clip_encode) these values stay NCAHIP_EINVAL: planar frames come in through the section above.
+ * ncahip_rgb_yuv_coeffs: k[0..8] = the nine coefficients in the table's order, k[9] = the luma offset, into CALLER (host) memory; plain
+ *   host code with floating-point contraction off, no GPU call.  An unknown matrix or range, or a null k: NCAHIP_EINVAL.  This is the only
+ *   implementation of the coefficient arithmetic.
+ * ncahip_clip_rgb_to_yuv420_u8: src [N,H,W,3] uint8 -> dst [N,3H/2,W] uint8 in one launch for all N; nothing synchronises.  k:
+ *   ncahip_rgb_yuv_coeffs' ten words in HOST memory (they travel as kernel arguments).  Any alignment of src and dst, any even W: a lane
+ *   reads its source bytes out of the memory-aligned dwords that hold them, inside the tensor only, and stores as above.  NCAHIP_EINVAL: a
+ *   null pointer, an unknown layout, a non-positive size, overlapping src / dst.  NCAHIP_ERANGE: H or W odd or above 16384.  All checked
+ *   before the launch. */
+#define NCAHIP_CLIP_YUV420(layout, matrix, range) (0x100 | (layout) | (matrix) << 1 | (range) << 2)
+int ncahip_rgb_yuv_coeffs(int matrix, int range, int32_t k[10]);
+int ncahip_clip_rgb_to_yuv420_u8(const uint8_t *src, int layout, int N, int H, int W, const int32_t *k, uint8_t *dst,
+                                 ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

@@ -454,6 +454,32 @@ static bool clip_overlap(const void* a, size_t an, const void* b, size_t bn) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + bn && pb < pa + an;
 }
+// images (never frames) may also leave as planar YUV 4:2:0: NCAHIP_CLIP_YUV420(layout, matrix, range) = 0x100 .. 0x107
+static bool clip_fmt_planar(int fmt) { return (fmt & ~7) == 0x100; }
+static bool clip_img_fmt_ok(int fmt) { return clip_fmt_ok(fmt) || clip_fmt_planar(fmt); }
+// bytes of one image of B samples: [B,c,H,W] float32, [B,H,W,c] uint8 or [B,3H/2,W] uint8 (c == 3, H and W even: checked before)
+static size_t clip_img_bytes(int fmt, int B, int c, int H, int W) {
+    return clip_fmt_planar(fmt) ? (size_t)B * H * W / 2 * 3 : (size_t)B * c * H * W * clip_fmt_bytes(fmt);
+}
+// what a planar image format adds to an emit's checks: three channels (NCAHIP_EINVAL) and even sides (NCAHIP_ERANGE)
+static int check_clip_planar(const char* who, int img_fmt, int c_out, int H, int W) {
+    if (!clip_fmt_planar(img_fmt)) return 0;
+    if (c_out != 3) return fail(NCAHIP_EINVAL, "%s: a planar YUV image is made of 3 channels, got c_out=%d", who, c_out);
+    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "%s: 4:2:0 images have even sides, got %d x %d", who, H, W);
+    return 0;
+}
+// One image out of a state in format img_fmt: the float32 / uint8 launchers as before; a planar format builds its coefficients (the one
+// builder, host arithmetic) and writes the planes from the state.  unit: ConditionedNCA's image; gray: the inject of the same launch.
+static hipError_t clip_launch_emit(float* state, void* img, int img_fmt, bool unit, const float* gray, int B, int C, int c_out, int H, int W,
+                                   hipStream_t st) {
+    if (img && clip_fmt_planar(img_fmt)) {
+        int32_t k[10];
+        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
+        return nca_launch_clip_emit_yuv420(state, (unsigned char*)img, unit, (img_fmt & 1) == NCAHIP_YUV_NV12, k, gray, B, C, H, W, st);
+    }
+    const bool u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
+    return unit ? nca_launch_clip_emit_unit(state, img, u8, B, C, H, W, st) : nca_launch_clip_emit_inject(state, img, u8, gray, B, C, c_out, H, W, st);
+}
 
 size_t ncahip_clip_cond_workspace(int F, int B, int H, int W) {
     if (F <= 0 || !dims_ok(B, 3, H, W)) return 0;
@@ -475,20 +501,20 @@ int ncahip_clip_cond(const void* frames, int frame_fmt, const float* k3, float g
 
 static int check_clip_emit(const void* state, const void* img, int img_fmt, int B, int C, int c_out, int H, int W, bool need_img = true) {
     if (!state || (need_img && !img)) return fail(NCAHIP_EINVAL, "clip emit: null pointer");
-    if (!clip_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
+    if (!clip_img_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
     if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit: bad size");
     if (c_out < 1 || c_out > 4 || c_out > C) return fail(NCAHIP_EINVAL, "clip emit: c_out=%d must be in 1..4 and at most C=%d", c_out, C);
+    if (int rc = check_clip_planar("clip emit", img_fmt, c_out, H, W)) return rc;
     if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit: float32 images must be 4-byte aligned");
     return 0;
 }
 
 int ncahip_clip_emit(const float* state, void* img, int img_fmt, int B, int C, int c_out, int H, int W, ncahip_stream_t stream) {
     if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W)) return rc;
-    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt)))
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(img_fmt, B, c_out, H, W)))
         return fail(NCAHIP_EINVAL, "clip emit: the image overlaps the state");
     // without a grey plane the launcher only reads the state
-    return hip_result(nca_launch_clip_emit_inject(const_cast<float*>(state), img, img_fmt == NCAHIP_CLIP_U8_NHWC, nullptr, B, C, c_out, H, W,
-                                                  (hipStream_t)stream), "clip_emit");
+    return hip_result(clip_launch_emit(const_cast<float*>(state), img, img_fmt, false, nullptr, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit");
 }
 
 int ncahip_clip_gray(const void* frames, int frame_fmt, float gray_r, float gray_g, float gray_b, float* gray, int F, int B, int H, int W,
@@ -514,12 +540,11 @@ int ncahip_clip_emit_inject(float* state, void* img, int img_fmt, const float* g
     if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W, false)) return rc;
     if (int rc = check_extra_channel("clip emit_inject", C, c_out)) return rc;
     const size_t sbytes = (size_t)B * C * H * W * sizeof(float), gbytes = (size_t)B * H * W * sizeof(float);
-    const size_t ibytes = (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt);
+    const size_t ibytes = clip_img_bytes(img_fmt, B, c_out, H, W);
     if ((img && clip_overlap(state, sbytes, img, ibytes)) || (gray && clip_overlap(state, sbytes, gray, gbytes)) ||
         (img && gray && clip_overlap(img, ibytes, gray, gbytes)))
         return fail(NCAHIP_EINVAL, "clip emit_inject: state, image and grey plane must not overlap");
-    return hip_result(nca_launch_clip_emit_inject(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, gray, B, C, c_out, H, W, (hipStream_t)stream),
-                      "clip_emit_inject");
+    return hip_result(clip_launch_emit(state, img, img_fmt, false, gray, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit_inject");
 }
 
 // The body of the two clip drivers.  gray == NULL: ncahip_dynca_clip_f32 (cond [F] maps, one per frame).  gray != NULL:
@@ -538,7 +563,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
     const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
     if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
     const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W, cslot = (size_t)B * c_cond * H * W;
-    const size_t ibytes = (size_t)B * c_out * H * W * clip_fmt_bytes(img_fmt);
+    const size_t ibytes = clip_img_bytes(img_fmt, B, c_out, H, W);
     const size_t sbytes = 2 * slot * sizeof(float), cbytes = (cond_per_frame ? (size_t)F : 1) * cslot * sizeof(float);
     const size_t gbytes = (size_t)F * uslot * sizeof(float);
     if ((cond && clip_overlap(states, sbytes, cond, cbytes)) || clip_overlap(states, sbytes, images, (size_t)calls * ibytes) ||
@@ -564,7 +589,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
     }
     if (int rc = device_error_rc(who)) return rc;
 
-    const bool ubits = u_is_bits(u, seed), u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
+    const bool ubits = u_is_bits(u, seed);
     hipStream_t st = (hipStream_t)stream;
     bool persist = persist_ws != nullptr;
     int cur = 0;   // the slot that holds the state
@@ -601,7 +626,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         // image n and, in the same launch, the grey of the call that follows (the repeats j > 0 of a frame included: the channel has
         // evolved); after the last call the channel stays as the steps left it
         const float* const gnext = gray && n + 1 < (int)calls ? gray + (size_t)((n + 1) / steps_per_frame) * uslot : nullptr;
-        if (int rc = hip_result(nca_launch_clip_emit_inject(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, gnext, B, C, c_out, H, W, st),
+        if (int rc = hip_result(clip_launch_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, img_fmt, false, gnext, B, C, c_out, H, W, st),
                                 "dynca clip (emit)"))
             return rc;
     }
@@ -865,18 +890,19 @@ int ncahip_clip_encode(const void* frames, int frame_fmt, const float* k3, const
 
 static int check_clip_emit_unit(const void* state, const void* img, int img_fmt, int B, int C, int H, int W) {
     if (!state || !img) return fail(NCAHIP_EINVAL, "clip emit_unit: null pointer");
-    if (!clip_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit_unit: unknown image format %d", img_fmt);
+    if (!clip_img_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit_unit: unknown image format %d", img_fmt);
     if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit_unit: bad size");
     if (C < 3) return fail(NCAHIP_EINVAL, "clip emit_unit: the image is state[:, :3], C=%d has fewer than 3 channels", C);
+    if (int rc = check_clip_planar("clip emit_unit", img_fmt, 3, H, W)) return rc;
     if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: float32 images must be 4-byte aligned");
     return 0;
 }
 
 int ncahip_clip_emit_unit(const float* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
     if (int rc = check_clip_emit_unit(state, img, img_fmt, B, C, H, W)) return rc;
-    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, (size_t)B * 3 * H * W * clip_fmt_bytes(img_fmt)))
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(img_fmt, B, 3, H, W)))
         return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
-    return hip_result(nca_launch_clip_emit_unit(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, H, W, (hipStream_t)stream), "clip_emit_unit");
+    return hip_result(clip_launch_emit(const_cast<float*>(state), img, img_fmt, true, nullptr, B, C, 3, H, W, (hipStream_t)stream), "clip_emit_unit");
 }
 
 // The driver keeps the state in slot 0 or slot 2 of `states` (cur).  A persistent call reads slot cur and writes slot cur ^ 2.  A per-step call
@@ -896,10 +922,10 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
     if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
     // the checks of the grow drivers (ncahip_cond_grow_fwd_f32 takes no T = 0, so they are shared as functions): their codes
     if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwd)) return rc;
-    const bool ubits = u_is_bits(u, seed), u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
+    const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
     const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W, gslot = (size_t)B * goal_ch * H * W;
-    const size_t ibytes = (size_t)B * 3 * H * W * clip_fmt_bytes(img_fmt);
+    const size_t ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
     const size_t sbytes = 4 * slot * sizeof(float), pbytes = 2 * pslot, gbytes = (size_t)F * gslot * sizeof(float), abytes = (size_t)calls * ibytes;
     if (clip_overlap(states, sbytes, goal, gbytes) || clip_overlap(states, sbytes, images, abytes) || clip_overlap(states, sbytes, pre, pbytes) ||
         clip_overlap(goal, gbytes, images, abytes) || clip_overlap(goal, gbytes, pre, pbytes) || clip_overlap(images, abytes, pre, pbytes))
@@ -941,7 +967,8 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
                 return rc;
             cur = out;
         }
-        if (int rc = hip_result(nca_launch_clip_emit_unit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, u8, B, C, H, W, st), "cond clip (emit)"))
+        if (int rc = hip_result(clip_launch_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, img_fmt, true, nullptr, B, C, 3, H, W, st),
+                                "cond clip (emit)"))
             return rc;
     }
     if (cur != 0)   // the state returns in slot 0: the one copy of a call
@@ -1035,6 +1062,25 @@ int ncahip_clip_yuv420_to_rgb_u8(const uint8_t* src, int layout, int N, int H, i
         return fail(NCAHIP_EINVAL, "clip_yuv420_to_rgb: frames and output must not overlap");
     return hip_result(nca_launch_clip_yuv420_to_rgb(src, layout == NCAHIP_YUV_NV12, N, H, W, x0, y0, crop_w, crop_h, k, dst, (hipStream_t)stream),
                       "clip_yuv420_to_rgb");
+}
+
+int ncahip_rgb_yuv_coeffs(int matrix, int range, int32_t k[10]) {
+    if (!k) return fail(NCAHIP_EINVAL, "rgb_yuv_coeffs: null pointer");
+    if (matrix != NCAHIP_YUV_BT601 && matrix != NCAHIP_YUV_BT709) return fail(NCAHIP_EINVAL, "rgb_yuv_coeffs: unknown matrix %d", matrix);
+    if (range != NCAHIP_YUV_LIMITED && range != NCAHIP_YUV_FULL) return fail(NCAHIP_EINVAL, "rgb_yuv_coeffs: unknown range %d", range);
+    nca_rgb_yuv_build_coeffs(matrix, range, k);
+    return 0;
+}
+
+int ncahip_clip_rgb_to_yuv420_u8(const uint8_t* src, int layout, int N, int H, int W, const int32_t* k, uint8_t* dst, ncahip_stream_t stream) {
+    if (!src || !dst || !k) return fail(NCAHIP_EINVAL, "clip_rgb_to_yuv420: null pointer");
+    if (!yuv_layout_ok(layout)) return fail(NCAHIP_EINVAL, "clip_rgb_to_yuv420: unknown layout %d", layout);
+    if (N <= 0 || H <= 0 || W <= 0) return fail(NCAHIP_EINVAL, "clip_rgb_to_yuv420: bad size");
+    if (H > kResizeMaxDim || W > kResizeMaxDim) return fail(NCAHIP_ERANGE, "clip_rgb_to_yuv420: H=%d W=%d exceeds %d", H, W, kResizeMaxDim);
+    if ((H | W) & 1) return fail(NCAHIP_ERANGE, "clip_rgb_to_yuv420: 4:2:0 images have even sides, got %d x %d", H, W);
+    if (clip_overlap(src, (size_t)N * H * W * 3, dst, (size_t)N * H * W / 2 * 3))
+        return fail(NCAHIP_EINVAL, "clip_rgb_to_yuv420: images and output must not overlap");
+    return hip_result(nca_launch_clip_rgb_to_yuv420(src, layout == NCAHIP_YUV_NV12, N, H, W, k, dst, (hipStream_t)stream), "clip_rgb_to_yuv420");
 }
 
 int ncahip_clip_resize_yuv420_u8(const uint8_t* src, int layout, const int32_t* k, int N, int H, int W, int x0, int y0, int crop_w, int crop_h,

@@ -4,8 +4,11 @@
 // and, for the models that carry the grey frame as their last state channel (ExtraChannels/utils/misc/video_utils.py:66-82):
 //   clip_gray_kernel   frames of one call -> grey [F,B,H,W]
 //   the emit kernels with INJ: the image as above and, in the same launch, a grey plane written over state channel C - 1
+// and, for a video encoder behind the clip (include/ncahip.h, "planar YUV images"):
+//   clip_emit_yuv420_kernel   state -> one planar YUV 4:2:0 image (I420 / NV12), the uint8 image's bytes never leaving the registers
 #include "nca_kernels.h"
 #include "nca_clip_u8.h"
+#include "nca_yuv.h"
 
 namespace {
 
@@ -168,6 +171,42 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
     }
 }
 
+// Planar YUV 4:2:0 [B,3H/2,W] of the uint8 image above (CO = 3), without that image: a lane owns 2 rows x 4 columns of one sample, reads the
+// 4 consecutive floats of each row of the three channels once, truncates them to the bytes clip_emit_u8_kernel stores and hands them to
+// nca_yuv420_store_block (nca_yuv.h: a dword of Y per row and the chroma under it; halves or bytes where a plane's phase forces them).  The
+// result is bit for bit clip_emit_u8_kernel followed by rgb_to_yuv420_kernel (nca_yuv_out.hip).  INJ as above, for the lane's pixels.
+template <bool NV12, bool INJ, bool UNIT>
+__global__ __launch_bounds__(kYuvOutThreads) void clip_emit_yuv420_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
+                                                               const float* __restrict__ gray, int C, int H, int W, int bx, size_t lanes, NcaRgbYuvK k) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= lanes) return;
+    const int x0 = (int)(id % bx) * kYuvOutCols;
+    const size_t row = id / bx;                                   // row pair b * H/2 + y/2
+    const size_t b = row / (size_t)(H >> 1);
+    const int y = (int)(row % (size_t)(H >> 1)) * 2;
+    const int nv = min(kYuvOutCols, W - x0);
+    const size_t plane = (size_t)H * W;
+    int px[3][2][kYuvOutCols];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float* const xr = x + (b * C + c) * plane + (size_t)(y + j) * W;
+#pragma unroll
+            for (int i = 0; i < kYuvOutCols; ++i)      // columns past the row's end repeat its last pixel; nothing of them is stored
+                px[c][j][i] = (int)(unsigned char)__fmul_rn(clip_emit_value<UNIT>(xr[min(x0 + i, W - 1)]), 255.0f);
+        }
+    if (INJ) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            for (int i = 0; i < nv; ++i) {
+                const size_t p = (size_t)(y + j) * W + x0 + i;
+                xlast[b * C * plane + p] = gray[b * plane + p];
+            }
+    }
+    nca_yuv420_store_block<NV12>(img, k, b, H, W, y, x0, nv, px[0], px[1], px[2]);
+}
+
 // grey [N,H,W] of N = F*B frames, one 16 x 64 tile per workgroup and no halo.  U8: the tile's rows come in through clip_stage_u8_rows, the
 // loader of clip_cond_kernel; float32 planes are read in place (every pixel once, coalesced), so no LDS there.
 template <bool U8>
@@ -269,5 +308,33 @@ hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int
     const size_t groups = ((size_t)B * plane + 3) / 4;
     hipLaunchKernelGGL((clip_emit_u8_kernel<3, false, true>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, state, (unsigned char*)img,
                        (float*)nullptr, (const float*)nullptr, B, C, plane, ((uintptr_t)img & 3) == 0 ? 1 : 0);
+    return hipGetLastError();
+}
+
+// The planar image of state[:, :3] (unit: ConditionedNCA's clamp, else the DyNCA families') and, with gray, the inject of the same launch.
+// k: ncahip_rgb_yuv_coeffs' ten words in host memory.  H and W even (the caller checked).
+template <bool NV12, bool UNIT>
+static void clip_launch_emit_yuv420(bool inj, dim3 grid, hipStream_t st, const float* x, unsigned char* o, float* xlast, const float* gray, int C, int H,
+                                    int W, int bx, size_t lanes, const NcaRgbYuvK& k) {
+    if (inj) hipLaunchKernelGGL((clip_emit_yuv420_kernel<NV12, true, UNIT>), grid, dim3(kYuvOutThreads), 0, st, x, o, xlast, gray, C, H, W, bx, lanes, k);
+    else hipLaunchKernelGGL((clip_emit_yuv420_kernel<NV12, false, UNIT>), grid, dim3(kYuvOutThreads), 0, st, x, o, xlast, gray, C, H, W, bx, lanes, k);
+}
+
+hipError_t nca_launch_clip_emit_yuv420(float* state, unsigned char* img, bool unit, bool nv12, const int* k, const float* gray, int B, int C, int H, int W,
+                                       hipStream_t st) {
+    if (!img || C < 3 || ((H | W) & 1) || (gray && (unit || C < 4))) return hipErrorInvalidValue;
+    const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
+    const int bx = (W + kYuvOutCols - 1) / kYuvOutCols;
+    const size_t lanes = (size_t)B * (H / 2) * bx, blocks = (lanes + kYuvOutThreads - 1) / kYuvOutThreads;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks);
+    float* const xlast = state + (size_t)(C - 1) * H * W;
+    if (unit) {
+        if (nv12) clip_launch_emit_yuv420<true, true>(false, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+        else clip_launch_emit_yuv420<false, true>(false, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+    } else {
+        if (nv12) clip_launch_emit_yuv420<true, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+        else clip_launch_emit_yuv420<false, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+    }
     return hipGetLastError();
 }

@@ -269,6 +269,14 @@ hipError_t nca_launch_clip_yuv420_to_rgb(const unsigned char* src, bool nv12, in
                                          unsigned char* dst, hipStream_t st);
 // host only: the coefficients (k_y, k_rv, k_gu, k_gv, k_bu, luma offset) of matrix 0 = BT.601 / 1 = BT.709, range 0 = limited / 1 = full
 void nca_yuv_build_coeffs(int matrix, int range, int32_t k[6]);
+// nca_yuv_out.hip: N RGB24 images [N,H,W,3] -> planar YUV 4:2:0 [N,3H/2,W] (H, W even), one launch; any alignment.  k: the ten words of
+// nca_rgb_yuv_build_coeffs in HOST memory
+hipError_t nca_launch_clip_rgb_to_yuv420(const unsigned char* src, bool nv12, int N, int H, int W, const int* k, unsigned char* dst, hipStream_t st);
+void nca_rgb_yuv_build_coeffs(int matrix, int range, int32_t k[10]);
+// nca_clip.hip: the planar image [B,3H/2,W] of state[:, :3] straight from the fp32 state -- bit for bit the uint8 emit (unit: nca_launch_clip_emit_unit,
+// else nca_launch_clip_emit_inject with c_out = 3) followed by nca_launch_clip_rgb_to_yuv420; gray != NULL (not with unit): the inject of the same launch
+hipError_t nca_launch_clip_emit_yuv420(float* state, unsigned char* img, bool unit, bool nv12, const int* k, const float* gray, int B, int C, int H, int W,
+                                       hipStream_t st);
 // host only (no GPU call): table row width (-1: does not fit an int), and the tables of one axis; filter 0 = bicubic, 1 = Lanczos.  The
 // builder returns 0, or the 1-based row that breaks an integer bound of the passes
 int nca_resize_ksize(int in, int out, int filter);

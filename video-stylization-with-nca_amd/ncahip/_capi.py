@@ -125,6 +125,8 @@ SIGNATURES = {
     "ncahip_yuv_coeffs": [_I, _I, _P],
     "ncahip_clip_yuv420_to_rgb_u8": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "ncahip_clip_resize_yuv420_u8": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, ctypes.c_size_t, _P],
+    "ncahip_rgb_yuv_coeffs": [_I, _I, _P],
+    "ncahip_clip_rgb_to_yuv420_u8": [_P, _I, _I, _I, _I, _P, _P, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,
@@ -151,6 +153,11 @@ RESIZE_FILTERS = {"bicubic": 0, "lanczos": 1}     # include/ncahip.h NCAHIP_RESI
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}              # include/ncahip.h NCAHIP_YUV_*
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 YUV_RANGES = {"limited": 0, "full": 1}
+
+
+def clip_yuv420(layout: int, matrix: int, rng: int) -> int:
+    """include/ncahip.h NCAHIP_CLIP_YUV420: the image format of a planar YUV 4:2:0 output (0x100 .. 0x107)."""
+    return 0x100 | layout | matrix << 1 | rng << 2
 
 
 def lib():

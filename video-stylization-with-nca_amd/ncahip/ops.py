@@ -445,29 +445,70 @@ def clip_cond(frames: torch.Tensor, k3: torch.Tensor, gray="mean", apply_tanh: b
     return cond
 
 
-def _clip_images(n: int, B: int, c_out: int, H: int, W: int, out_dtype, device) -> torch.Tensor:
+OUT_FORMATS = ("rgb24", "i420", "nv12")
+
+
+def _clip_img_fmt(out_dtype, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited", c_out: int = 3, H: int = 2,
+                  W: int = 2) -> int:
+    """The image format word of the clip entry points: _clip_fmt(out_dtype) for 'rgb24' (as before), NCAHIP_CLIP_YUV420(...) for the planar
+    formats 'i420' / 'nv12', which need out_dtype=torch.uint8, c_out == 3 and even H, W (ValueError before anything runs)."""
+    if out_format not in OUT_FORMATS:
+        raise ValueError(f"out_format must be one of {OUT_FORMATS}, got {out_format!r}")
+    if out_format == "rgb24":
+        return _clip_fmt(out_dtype)
+    rgb_yuv_coeffs(yuv_matrix, yuv_range)
+    if out_dtype != torch.uint8:
+        raise ValueError(f"out_format={out_format!r} needs out_dtype=torch.uint8 (planar YUV images are bytes), got {out_dtype}")
+    if c_out != 3:
+        raise ValueError(f"out_format={out_format!r} needs an RGB image (c_out == 3), got c_out = {c_out}")
+    if H % 2 or W % 2:
+        raise ValueError(f"out_format={out_format!r} needs even H and W (4:2:0), got {H} x {W}")
+    return _capi.clip_yuv420(_capi.YUV_LAYOUTS[out_format], _capi.YUV_MATRICES[yuv_matrix], _capi.YUV_RANGES[yuv_range])
+
+
+def _clip_images(n: int, B: int, c_out: int, H: int, W: int, out_dtype, device, fmt: Optional[int] = None) -> torch.Tensor:
+    if fmt is not None and fmt >= 0x100:
+        return torch.empty(n, B, 3 * H // 2, W, device=device, dtype=torch.uint8)
     if _clip_fmt(out_dtype) == _capi.CLIP_U8_NHWC:
         return torch.empty(n, B, H, W, c_out, device=device, dtype=torch.uint8)
     return torch.empty(n, B, c_out, H, W, device=device, dtype=torch.float32)
 
 
-def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32) -> torch.Tensor:
-    """State [B,C,H,W] -> (clamp(2 x[:, :c_out], -1, 1) + 1) / 2 as float32 [B,c_out,H,W], or truncated to uint8 [B,H,W,c_out]."""
+def _clip_images_into(images: Optional[torch.Tensor], n: int, B: int, c_out: int, H: int, W: int, out_dtype, device, fmt: int) -> torch.Tensor:
+    """The images tensor of a clip driver: a new one, or the caller's after checking that it is what a new one would be."""
+    if images is None:
+        return _clip_images(n, B, c_out, H, W, out_dtype, device, fmt)
+    want = _clip_images(0, B, c_out, H, W, out_dtype, device, fmt)
+    if not images.is_cuda or images.dtype != want.dtype or tuple(images.shape) != (n,) + tuple(want.shape[1:]) or not images.is_contiguous():
+        raise ValueError(f"images must be a contiguous {want.dtype} device tensor {(n,) + tuple(want.shape[1:])}, got {tuple(images.shape)} {images.dtype}")
+    return images
+
+
+def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709",
+              yuv_range: str = "limited") -> torch.Tensor:
+    """State [B,C,H,W] -> (clamp(2 x[:, :c_out], -1, 1) + 1) / 2 as float32 [B,c_out,H,W], or truncated to uint8 [B,H,W,c_out].
+    out_format 'i420' / 'nv12' (uint8, c_out == 3, even H and W): that uint8 image as planar YUV 4:2:0 [B,3H/2,W], written straight from
+    the state -- bit for bit rgb_to_yuv420 of the uint8 image."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
-    img = _clip_images(1, B, c_out, H, W, out_dtype, x.device)[0]
-    check(lib().ncahip_clip_emit(_p(x), _p(img), _clip_fmt(out_dtype), B, C, c_out, H, W, _stream()), "clip_emit")
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    img = _clip_images(1, B, c_out, H, W, out_dtype, x.device, fmt)[0]
+    check(lib().ncahip_clip_emit(_p(x), _p(img), fmt, B, C, c_out, H, W, _stream()), "clip_emit")
     return img
 
 
 def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], w: DyncaWeights, steps_per_frame: int, step_n: int,
                c_out: int = 3, pad_mode: str = "replicate", update_rate: float = 0.5, seed: int = 0, step0: int = 0,
-               two_scale: bool = False, out_dtype=torch.float32):
+               two_scale: bool = False, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
+               images: Optional[torch.Tensor] = None):
     """The video loop over the F frames of cond [F,B,3,H,W] in one C call (ncahip_dynca_clip_f32): per frame steps_per_frame times
     {step_n DyNCA steps, one image}.  us: None (Philox: seed, step0), or the masks / uniforms of all F * steps_per_frame * step_n steps.
-    Returns (images [F * steps_per_frame, B, c_out, H, W] float32 or [.., B, H, W, c_out] uint8, final state [B,C,H,W])."""
+    Returns (images [F * steps_per_frame, B, c_out, H, W] float32 or [.., B, H, W, c_out] uint8, final state [B,C,H,W]).
+    out_format 'i420' / 'nv12': images [.., B, 3H/2, W] uint8, planar YUV 4:2:0 (clip_emit).  images: a device tensor of the images'
+    shape and dtype to write into instead of a new one (what a caller that stages downloads hands in)."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
     cond = _dev(cond, "cond")
     F_ = cond.shape[0]
     assert cond.shape == (F_, B, 3, H, W), (tuple(cond.shape), tuple(x.shape))
@@ -476,14 +517,14 @@ def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], 
     assert w.c == C and w.k1 == 4 * C + 3, (w.c, w.k1, C)
     states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
     states[0].copy_(x)
-    images = _clip_images(calls, B, c_out, H, W, out_dtype, x.device)
+    images = _clip_images_into(images, calls, B, c_out, H, W, out_dtype, x.device, fmt)
     pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
     ws, nbytes, epoch = None, 0, 0
     if persistent_steps:
         nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, 3)
         if nbytes and calls < (1 << 20) - 2:
             ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_dynca_clip_f32(_p(states), _p(cond), _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n, _p(us), _p(w.w1),
+    check(lib().ncahip_dynca_clip_f32(_p(states), _p(cond), _p(images), fmt, F_, steps_per_frame, step_n, _p(us), _p(w.w1),
                                       _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode], int(two_scale), update_rate,
                                       seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "dynca_clip")
     return images, states[0]
@@ -506,30 +547,34 @@ def clip_gray(frames: torch.Tensor, gray="mean") -> torch.Tensor:
 
 
 def clip_emit_inject(state: torch.Tensor, c_out: int = 3, gray_plane: Optional[torch.Tensor] = None, out_dtype=torch.float32,
-                     emit: bool = True) -> Optional[torch.Tensor]:
-    """One launch (ncahip_clip_emit_inject): the image of state[:, :c_out] as clip_emit (emit=True; returned) and gray_plane [B,H,W]
-    written over state[:, C-1] IN PLACE (gray_plane given).  c_out <= C-1.  emit=False: inject only, returns None."""
+                     emit: bool = True, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited") -> Optional[torch.Tensor]:
+    """One launch (ncahip_clip_emit_inject): the image of state[:, :c_out] as clip_emit (emit=True; returned; out_format as there) and
+    gray_plane [B,H,W] written over state[:, C-1] IN PLACE (gray_plane given).  c_out <= C-1.  emit=False: inject only, returns None."""
     if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float32 or not state.is_contiguous():
         raise _capi.NcaHipError("ncahip: `state` must be a contiguous float32 CUDA (ROCm) tensor -- it is written in place")
     B, C, H, W = state.shape
     if gray_plane is not None:
         gray_plane = _dev(gray_plane, "gray_plane")
         assert gray_plane.numel() == B * H * W, (tuple(gray_plane.shape), tuple(state.shape))
-    img = _clip_images(1, B, c_out, H, W, out_dtype, state.device)[0] if emit else None
-    check(lib().ncahip_clip_emit_inject(_p(state), _p(img), _clip_fmt(out_dtype), _p(gray_plane), B, C, c_out, H, W, _stream()), "clip_emit_inject")
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    img = _clip_images(1, B, c_out, H, W, out_dtype, state.device, fmt)[0] if emit else None
+    check(lib().ncahip_clip_emit_inject(_p(state), _p(img), fmt, _p(gray_plane), B, C, c_out, H, W, _stream()), "clip_emit_inject")
     return img
 
 
 def dynca_clip_xc(x: torch.Tensor, gray: torch.Tensor, cond: Optional[torch.Tensor], us: Optional[torch.Tensor], w: DyncaWeights,
                   steps_per_frame: int, step_n: int, c_out: int = 3, pad_mode: str = "replicate", update_rate: float = 0.5, seed: int = 0,
-                  step0: int = 0, two_scale: bool = False, out_dtype=torch.float32):
+                  step0: int = 0, two_scale: bool = False, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709",
+                  yuv_range: str = "limited", images: Optional[torch.Tensor] = None):
     """dynca_clip for the models whose last state channel is the grey frame (ncahip_dynca_clip_xc_f32): over the F frames of gray
     [F,B,H,W], per frame steps_per_frame times {state[:, -1] = gray[f], step_n DyNCA steps with cond, one image}.  x: the state with all
     C = w.c channels, or with C - 1 (the reference's `h`: the last channel is written before the first call anyway).  cond: ONE map
-    [B,2,H,W] (CPE) for all frames, or None.  us as dynca_clip.  Returns (images, final state [B,C,H,W] with the evolved last channel)."""
+    [B,2,H,W] (CPE) for all frames, or None.  us, out_format and images as dynca_clip.  Returns (images, final state [B,C,H,W] with the
+    evolved last channel)."""
     x = _dev(x, "x")
     B, cx, H, W = x.shape
     C = w.c
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
     gray = _dev(gray, "gray")
     F_ = gray.shape[0]
     assert gray.shape == (F_, B, H, W) and cx in (C - 1, C), (tuple(gray.shape), tuple(x.shape), C)
@@ -542,14 +587,14 @@ def dynca_clip_xc(x: torch.Tensor, gray: torch.Tensor, cond: Optional[torch.Tens
     assert w.k1 == 4 * C + c_cond, (w.c, w.k1, c_cond)
     states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
     states[0, :, :cx].copy_(x)
-    images = _clip_images(calls, B, c_out, H, W, out_dtype, x.device)
+    images = _clip_images_into(images, calls, B, c_out, H, W, out_dtype, x.device, fmt)
     pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
     ws, nbytes, epoch = None, 0, 0
     if persistent_steps:
         nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, c_cond)
         if nbytes and calls < (1 << 20) - 2:
             ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_dynca_clip_xc_f32(_p(states), _p(gray), _p(cond), c_cond, _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n,
+    check(lib().ncahip_dynca_clip_xc_f32(_p(states), _p(gray), _p(cond), c_cond, _p(images), fmt, F_, steps_per_frame, step_n,
                                          _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode],
                                          int(two_scale), update_rate, seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch,
                                          _stream()), "dynca_clip_xc")
@@ -706,24 +751,30 @@ def clip_encode(frames: torch.Tensor, encoder_module) -> torch.Tensor:
     return goal
 
 
-def clip_emit_unit(state: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
-    """State [B,C,H,W] -> clamp(state[:, :3], 0, 1) as float32 [B,3,H,W], or truncated to uint8 [B,H,W,3] (ncahip_clip_emit_unit)."""
+def clip_emit_unit(state: torch.Tensor, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709",
+                   yuv_range: str = "limited") -> torch.Tensor:
+    """State [B,C,H,W] -> clamp(state[:, :3], 0, 1) as float32 [B,3,H,W], or truncated to uint8 [B,H,W,3] (ncahip_clip_emit_unit).
+    out_format 'i420' / 'nv12' as clip_emit: the uint8 image as planar YUV 4:2:0 [B,3H/2,W]."""
     x = _dev(state, "state")
     B, C, H, W = x.shape
-    img = _clip_images(1, B, 3, H, W, out_dtype, x.device)[0]
-    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), _clip_fmt(out_dtype), B, C, H, W, _stream()), "clip_emit_unit")
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
+    img = _clip_images(1, B, 3, H, W, out_dtype, x.device, fmt)[0]
+    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), fmt, B, C, H, W, _stream()), "clip_emit_unit")
     return img
 
 
 def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w: CondWeights, steps_per_frame: int, step_n: int,
               alive_ch: int = 3, thr: float = 0.1, fire_rate: float = 0.5, lo: float = -10.0, hi: float = 10.0, seed: int = 0, step0: int = 0,
-              out_dtype=torch.float32):
+              out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
+              images: Optional[torch.Tensor] = None):
     """The ConditionedNCA clip loop over the F frames of goal [F,B,E,H,W] in one C call (ncahip_cond_clip_f32): per frame steps_per_frame times
     {grow(state, step_n) with goal[f], one image clamp(state[:, :3], 0, 1)}.  us: None (Philox: seed, step0), or the masks / uniforms of all
     F * steps_per_frame * step_n steps.  With persistent_cond the calls go to the one-launch grow where it applies.
-    Returns (images [F * steps_per_frame, B, 3, H, W] float32 or [.., B, H, W, 3] uint8, final state [B,C,H,W])."""
+    Returns (images [F * steps_per_frame, B, 3, H, W] float32 or [.., B, H, W, 3] uint8, final state [B,C,H,W]).  out_format and images as
+    dynca_clip."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
+    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
     goal = _dev(goal, "goal")
     F_, gch = goal.shape[0], goal.shape[2]
     assert goal.shape == (F_, B, gch, H, W) and 0 < gch <= C, (tuple(goal.shape), tuple(x.shape))
@@ -733,13 +784,13 @@ def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w
     states = torch.empty(4, B, C, H, W, device=x.device, dtype=torch.float32)
     states[0].copy_(x)
     pre = torch.empty(2, B, H, W, device=x.device, dtype=torch.uint8)
-    images = _clip_images(calls, B, 3, H, W, out_dtype, x.device)
+    images = _clip_images_into(images, calls, B, 3, H, W, out_dtype, x.device, fmt)
     ws, nbytes, epoch = None, 0, 0
     if persistent_cond and not torch.cuda.is_current_stream_capturing():
         nbytes = lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch)
         if nbytes and calls < (1 << 20) - 2:
             ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), _clip_fmt(out_dtype), F_, steps_per_frame, step_n, _p(us),
+    check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), fmt, F_, steps_per_frame, step_n, _p(us),
                                      _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
                                      lo, hi, seed, step0, _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "cond_clip")
     return images, states[0]
@@ -1166,6 +1217,72 @@ def clip_resize_yuv420(frames: torch.Tensor, size, crop=None, resample: str = "b
                                                  _p(ty[1]), ty[0].shape[1], _p(out), out_h, out_w, _p(ws), ws.numel() * ws.element_size(), _stream()),
               "clip_resize_yuv420")
     return out
+
+
+# ---------------------------------------------------------------- planar YUV 4:2:0 images out (csrc/nca_yuv_out.hip, the planar emit of nca_clip.hip)
+_RGB_YUV_COEFFS = {}         # (matrix, range) -> numpy int32 [10], read-only
+
+
+def rgb_yuv_coeffs(yuv_matrix: str = "bt709", yuv_range: str = "limited") -> np.ndarray:
+    """The (R, G, B) rows of Y, U and V and the luma offset of include/ncahip.h's integer RGB -> YUV evaluation, from the library's host
+    builder ncahip_rgb_yuv_coeffs -- the only implementation of that arithmetic; no GPU involved.  numpy int32 [10], cached and read-only."""
+    if yuv_matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"yuv_matrix must be 'bt601' or 'bt709', got {yuv_matrix!r}")
+    if yuv_range not in _capi.YUV_RANGES:
+        raise ValueError(f"yuv_range must be 'limited' or 'full', got {yuv_range!r}")
+    k = _RGB_YUV_COEFFS.get((yuv_matrix, yuv_range))
+    if k is None:
+        k = np.empty(10, dtype=np.int32)
+        check(lib().ncahip_rgb_yuv_coeffs(_capi.YUV_MATRICES[yuv_matrix], _capi.YUV_RANGES[yuv_range], k.ctypes.data), "rgb_yuv_coeffs")
+        k.setflags(write=False)
+        _RGB_YUV_COEFFS[(yuv_matrix, yuv_range)] = k
+    return k
+
+
+def _rgb_images_shape(shape):
+    """(N, h, w) of RGB24 images [N,h,w,3] with even h and w; ValueError for anything else."""
+    if len(shape) != 4 or shape[3] != 3 or shape[1] < 2 or shape[2] < 2 or shape[1] % 2 or shape[2] % 2:
+        raise ValueError(f"RGB images for planar YUV 4:2:0 must be [N,h,w,3] uint8 with even h and w, got {tuple(shape)}")
+    return int(shape[0]), int(shape[1]), int(shape[2])
+
+
+def rgb_to_yuv420(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited") -> torch.Tensor:
+    """RGB24 images [N,h,w,3] uint8 on the device -> planar YUV 4:2:0 [N, 3h/2, w] uint8 ('i420' or 'nv12'): ncahip_clip_rgb_to_yuv420_u8,
+    one launch for all N images, include/ncahip.h's integer arithmetic with the chroma of a 2 x 2 block its mean.  Any alignment."""
+    layout, k = _yuv_layout(pixel_format), rgb_yuv_coeffs(yuv_matrix, yuv_range)
+    frames = _dev(frames, "frames", torch.uint8)
+    N, h, w = _rgb_images_shape(frames.shape)
+    with torch.cuda.device(frames.device):
+        out = torch.empty(N, 3 * h // 2, w, device=frames.device, dtype=torch.uint8)
+        if N:
+            check(lib().ncahip_clip_rgb_to_yuv420_u8(_p(frames), layout, N, h, w, k.ctypes.data, _p(out), _stream()), "clip_rgb_to_yuv420")
+    return out
+
+
+def rgb_to_yuv420_host(frames, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited"):
+    """rgb_to_yuv420 evaluated with numpy on the library's coefficients (rgb_yuv_coeffs): the definition in code, bit for bit the kernels'
+    result, and the route for CPU tensors.  frames: a uint8 tensor or numpy array [N,h,w,3]; returns the same kind, on the host."""
+    layout, k = _yuv_layout(pixel_format), rgb_yuv_coeffs(yuv_matrix, yuv_range).astype(np.int32)
+    as_tensor = isinstance(frames, torch.Tensor)
+    arr = frames.detach().cpu().numpy() if as_tensor else np.asarray(frames)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"ncahip: `frames` must be uint8, got {arr.dtype}")
+    N, h, w = _rgb_images_shape(arr.shape)
+    rgb = arr.astype(np.int32)
+    Y, U, V = rgb_yuv_planes_host(rgb, rgb[:, 0::2, 0::2] + rgb[:, 0::2, 1::2] + rgb[:, 1::2, 0::2] + rgb[:, 1::2, 1::2], k)
+    chroma = np.concatenate((U.reshape(N, -1), V.reshape(N, -1)), axis=1) if layout == _capi.YUV_LAYOUTS["i420"] else np.stack((U, V), axis=-1).reshape(N, -1)
+    out = np.ascontiguousarray(np.concatenate((Y.reshape(N, -1), chroma), axis=1).reshape(N, 3 * h // 2, w))
+    return torch.from_numpy(out) if as_tensor else out
+
+
+def rgb_yuv_planes_host(rgb: np.ndarray, sums: np.ndarray, k: np.ndarray):
+    """The integer contract itself: pixels rgb [..., 3] (0 .. 255) -> Y, and 2 x 2 channel sums [..., 3] (0 .. 1020) -> (U, V); int32 in,
+    uint8 out.  k: rgb_yuv_coeffs' ten words."""
+    rgb, sums, k = rgb.astype(np.int32), sums.astype(np.int32), k.astype(np.int32)
+    Y = k[9] + ((k[0] * rgb[..., 0] + k[1] * rgb[..., 1] + k[2] * rgb[..., 2] + np.int32(1 << 15)) >> 16)
+    U = 128 + ((k[3] * sums[..., 0] + k[4] * sums[..., 1] + k[5] * sums[..., 2] + np.int32(1 << 17)) >> 18)          # int32: < 2^27
+    V = 128 + ((k[6] * sums[..., 0] + k[7] * sums[..., 1] + k[8] * sums[..., 2] + np.int32(1 << 17)) >> 18)
+    return tuple(np.clip(p, 0, 255).astype(np.uint8) for p in (Y, U, V))
 
 
 # ---------------------------------------------------------------- position sampler of the OT appearance loss (csrc/nca_ot_sample.hip)

@@ -14,6 +14,10 @@ Image.resize) on the device, bit for bit; stylize_clip(size=...) and stylize_cli
 Planar frames: a decoder writes YUV 4:2:0 (I420 or NV12), not RGB24.  pixel_format='i420' / 'nv12' hands such frames to the same entry
 points; the conversion (include/ncahip.h, "planar YUV frames") runs on the device, inside the resize's loader when size is set.  Pinned
 host frames are uploaded on a side stream, chunk k + 1 while chunk k computes (_chunks).
+
+Planar images: a video encoder takes YUV 4:2:0 as well.  out_format='i420' / 'nv12' makes the clip entry points write it straight from
+the state (include/ncahip.h, "planar YUV images"), and out=<pinned host tensor> delivers the images into the caller's buffer on a second
+side stream, chunk k while chunk k + 1 computes (_Downloads).
 """
 import contextlib
 from typing import Iterable, Iterator, Optional
@@ -131,6 +135,20 @@ def yuv420_to_rgb(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt
     return (ops.yuv420_to_rgb if frames.is_cuda else ops.yuv420_to_rgb_host)(frames, pixel_format, yuv_matrix, yuv_range)
 
 
+def rgb_to_yuv420(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt709", yuv_range: str = "limited") -> torch.Tensor:
+    """RGB24 images [N,h,w,3] uint8 (even h and w) -> planar YUV 4:2:0 [N, 3h/2, w] uint8 ('i420' or 'nv12') on the images' device, by
+    include/ncahip.h's integer arithmetic; the chroma sample of a 2 x 2 block is its mean.  CUDA images run ncahip_clip_rgb_to_yuv420_u8
+    (one launch), CPU images its numpy mirror ops.rgb_to_yuv420_host.  What out_format= of the clip calls writes without the RGB image."""
+    from . import ops
+    if pixel_format not in ("i420", "nv12"):
+        raise ValueError(f"pixel_format must be 'i420' or 'nv12', got {pixel_format!r}")
+    ops.rgb_yuv_coeffs(yuv_matrix, yuv_range)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise ValueError(f"rgb_to_yuv420 takes uint8 images [N,h,w,3], got {getattr(frames, 'dtype', type(frames))}")
+    ops._rgb_images_shape(tuple(frames.shape))
+    return (ops.rgb_to_yuv420 if frames.is_cuda else ops.rgb_to_yuv420_host)(frames, pixel_format, yuv_matrix, yuv_range)
+
+
 def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", pixel_format: str = "rgb24", yuv_matrix: str = "bt709",
                   yuv_range: str = "limited") -> torch.Tensor:
     """frames [N,H,W,3] uint8 -> [N,out_h,out_w,3] uint8 on the frames' device: the reference's crop, then Pillow's 8-bit Image.resize,
@@ -240,10 +258,108 @@ def _chunks(fn, frames: torch.Tensor, per_call: int, dev):
         side.synchronize()           # no copy out of the caller's buffer is in flight once the call returns
 
 
+def _images_spec(out_dtype, out_format, yuv_matrix, yuv_range, c_out: int, hh: int, ww: int):
+    """(shape of one image, the drivers' keywords for it), validated before anything runs: planar output needs out_dtype=torch.uint8,
+    c_out == 3 and even H, W (ValueError)."""
+    from . import ops
+    ops._clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, hh, ww)
+    if out_format != "rgb24":
+        return (3 * hh // 2, ww), {"out_format": out_format, "yuv_matrix": yuv_matrix, "yuv_range": yuv_range}
+    return ((hh, ww, c_out) if out_dtype == torch.uint8 else (c_out, hh, ww)), {}
+
+
+def _check_out(out, n_images: int, shape, out_dtype):
+    """out= of the clip calls: None, or a contiguous tensor of exactly the images' shape and dtype (ValueError otherwise)."""
+    if out is None:
+        return
+    want = (n_images,) + tuple(shape)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != out_dtype or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {out_dtype} tensor {want} (the images of this call), got "
+                         f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out)} {getattr(out, 'dtype', '')}")
+
+
+_DOWNLOAD_STREAMS = {}       # device index -> the module's one side stream for downloads
+
+
+class _Downloads:
+    """The way out of a clip call with out=: the mirror image of _chunks.  Records the route in fn.last_download.
+    'overlapped' (out in pinned host memory, a GPU model): the images of chunk k are written to one of two device staging buffers
+    (staging), then copied with non_blocking=True into out[...] on the module's download stream of that device while the caller's stream
+    computes chunk k + 1 (put).  The copy waits for an event recorded after the chunk's emit; the compute stream waits for a staging
+    buffer's last copy before it writes the buffer again.  finish() makes the host wait for the side stream -- the clip calls run it in a
+    finally, so also when an exception unwinds --: every byte of `out` is valid when the call returns.
+    'sync' (pageable or device `out`, a CPU model): out[...].copy_(images) per chunk."""
+
+    def __init__(self, fn, out, shape, per_chunk: int, dev):
+        dev = torch.device(dev)
+        self.out, self.pos, self.shape, self.per_chunk = out, 0, tuple(shape), per_chunk
+        self.overlapped = dev.type == "cuda" and not out.is_cuda and out.is_pinned()
+        fn.last_download = "overlapped" if self.overlapped else "sync"
+        if self.overlapped:
+            self.index = dev.index if dev.index is not None else torch.cuda.current_device()
+            self.side = _DOWNLOAD_STREAMS.get(self.index)
+            if self.side is None:
+                self.side = _DOWNLOAD_STREAMS[self.index] = torch.cuda.Stream(device=self.index)
+            self.compute = torch.cuda.current_stream(self.index)
+            self.bufs, self.done, self.turn = [None, None], [None, None], 0
+
+    def staging(self, n: int):
+        """The device tensor [n, 1, *shape] the next chunk's images go to, or None (sync: the producer allocates as it always did)."""
+        if not self.overlapped:
+            return None
+        i = self.turn
+        if self.bufs[i] is None:
+            with torch.cuda.device(self.index):
+                self.bufs[i] = torch.empty((self.per_chunk, 1) + self.shape, dtype=self.out.dtype, device=f"cuda:{self.index}")
+        if self.done[i] is not None:
+            self.compute.wait_event(self.done[i])          # the buffer's last copy has left it
+        return self.bufs[i][:n]
+
+    def put(self, imgs: torch.Tensor):
+        """imgs [n, *shape]: the chunk just produced (staging's buffer when overlapped) -> out[pos : pos + n]."""
+        n = imgs.shape[0]
+        dst = self.out[self.pos:self.pos + n]
+        self.pos += n
+        if not self.overlapped:
+            dst.copy_(imgs)
+            return
+        self.side.wait_event(self.compute.record_event())   # the chunk's emit
+        with torch.cuda.stream(self.side):
+            dst.copy_(imgs, non_blocking=True)
+            self.done[self.turn] = self.side.record_event()
+        self.turn ^= 1
+
+    def finish(self):
+        if self.overlapped:
+            self.side.synchronize()
+
+
+def _deliver(sink, outs, imgs: torch.Tensor):
+    """One chunk's images [n, *shape] on their way out: kept for the final cat (out=None, as before) or handed to the sink."""
+    if sink is None:
+        outs.append(imgs)
+    else:
+        sink.put(imgs)
+
+
+def _deliver_loop(sink, outs, chunk_imgs):
+    """The loop routes' images of one chunk (a list of [1, *shape])."""
+    if sink is None:
+        outs.extend(chunk_imgs)
+    elif chunk_imgs:
+        imgs = torch.cat(chunk_imgs)
+        buf = sink.staging(imgs.shape[0])
+        if buf is not None:
+            buf[:, 0].copy_(imgs)
+            imgs = buf[:, 0]
+        sink.put(imgs)
+
+
 @torch.no_grad()
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                  gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic",
-                 precision: str = "f32", direction=None, pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited"):
+                 precision: str = "f32", direction=None, pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
+                 out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited", out: Optional[torch.Tensor] = None):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -286,7 +402,18 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
 
     Uploads: host frames in pinned memory (frames.is_pinned()) with a model on the GPU are uploaded on a side stream, chunk k + 1 while
     chunk k computes; anything else is uploaded as before.  stylize_clip.last_upload records which: 'overlapped' or 'sync'.  Either
-    way every copy out of `frames` is complete when the call returns: the caller may overwrite the buffer at once."""
+    way every copy out of `frames` is complete when the call returns: the caller may overwrite the buffer at once.
+
+    out_format: 'rgb24' (the default: images as described above) or 'i420' / 'nv12' -- images are planar YUV 4:2:0
+    [F*steps_per_frame, 3H/2, W] uint8, what a video encoder takes (rgb_to_yuv420; out_yuv_matrix 'bt601' / 'bt709', out_yuv_range
+    'limited' / 'full').  Needs out_dtype=torch.uint8, c_out == 3 and even H, W (ValueError otherwise, before any work).  The clip route's
+    image output writes the planes straight from the state; the loop route converts its uint8 image.  Either way the result is
+    rgb_to_yuv420 of the uint8 images of the same call, bit for bit.
+
+    out: None, or a tensor of exactly the images' shape and dtype (anything else: ValueError before any work) that receives the images
+    and is returned as `images`.  A pinned host tensor with a model on the GPU is filled on a side stream, chunk k while chunk k + 1
+    computes; the host waits for the last copy before the call returns (also when it raises), so every byte is valid then.  A pageable or
+    device tensor is filled by a plain copy per chunk.  stylize_clip.last_download records 'overlapped', 'sync' or None (out=None)."""
     from . import ops, steer
     if precision not in ("f32", "bf16"):
         raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
@@ -298,6 +425,8 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     n_frames = frames.shape[0]
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
+    shape, okw = _images_spec(out_dtype, out_format, out_yuv_matrix, out_yuv_range, getattr(nca_model, "c_out", 3), hh, ww)
+    _check_out(out, n_frames * k, shape, out_dtype)
     extra = _extra_channels(nca_model)
     if extra and state is not None and (state.dim() != 4 or state.shape[1] != nca_model.c_in - 1):
         raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
@@ -312,6 +441,8 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         if nca_model._composed(h):
             raise ValueError("precision='bf16' needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
     stylize_clip.last_path = "clip" if fused else "loop"
+    stylize_clip.last_download = None
+    sink = None if out is None else _Downloads(stylize_clip, out, shape, per_call * k, dev)
     dirs = angle = None
     if direction is not None:
         if h.dtype != torch.float32:
@@ -322,16 +453,21 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     with ops.dynca_precision(precision) if precision == "bf16" else contextlib.nullcontext():
         # the clip route's steps run under the field; the loop route hands it to forward_nsteps, which attaches it per call
         with ops.dynca_direction(dirs) if (fused and dirs is not None) else contextlib.nullcontext():
-            return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in,
-                                     direction, angle)
+            try:
+                return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev,
+                                         u8_in, direction, angle, shape, okw, sink)
+            finally:
+                if sink is not None:
+                    sink.finish()        # no copy into the caller's buffer is in flight once the call returns
 
 
 def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in,
-                      direction=None, angle=None):
+                      direction=None, angle=None, shape=None, okw=None, sink=None):
     """The two routes of stylize_clip (its arguments validated, the state seeded, the precision set, the clip route's direction field
-    attached).  direction: what the loop route passes on to forward_nsteps; angle: a tuple's angle, for the positional encoding."""
+    attached).  direction: what the loop route passes on to forward_nsteps; angle: a tuple's angle, for the positional encoding.
+    shape, okw: _images_spec's image shape and driver keywords; sink: the _Downloads of out= (None: the images are concatenated)."""
     from . import ops, steer
-    outs = []
+    outs, okw = [], okw or {}
     if fused:
         w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
         rate, two = 0.5, list(nca_model.perception_scales) == [0, 1]
@@ -351,20 +487,22 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
             us = None
             if nca_model.mask_rng != "philox":     # the loop's own draws, call by call (DyNCA._draw): the generator ends where it would
                 us = torch.cat([ops.draw_fire_masks(1, hh, ww, step_n, rate, "dynca", h.device) for _ in range(n * k)])
+            buf = None if sink is None else sink.staging(n * k)
             if extra:                              # h keeps c_in - 1 channels: the driver's last channel is the grey frame
                 imgs, x = ops.dynca_clip_xc(h, cond, pos, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
-                                            nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
+                                            nca_model._mask_step, two_scale=two, out_dtype=out_dtype, images=buf, **okw)
                 h = x[:, :-1]
             else:
                 imgs, h = ops.dynca_clip(h, cond, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
-                                         nca_model._mask_step, two_scale=two, out_dtype=out_dtype)
+                                         nca_model._mask_step, two_scale=two, out_dtype=out_dtype, images=buf, **okw)
             nca_model._mask_step += n * k * step_n
-            outs.append(imgs[:, 0])
+            _deliver(sink, outs, imgs[:, 0])
     else:
         steer_kw = {} if direction is None else {"direction": direction}      # (a model without the keyword still runs unsteered clips)
         for raw in _chunks(stylize_clip, frames, per_call, dev):
             chunk = shrink(raw)
             chunk = _widen(chunk) if u8_in else chunk
+            chunk_imgs = []
             for i in range(chunk.shape[0]):
                 cond = _gray(chunk[i:i + 1], gray)
                 for _ in range(k):
@@ -374,10 +512,16 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
                     else:
                         h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond, **steer_kw)
                     img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
-                    outs.append((img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img)
+                    img = (img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img
+                    chunk_imgs.append(rgb_to_yuv420(img.contiguous(), okw["out_format"], okw["yuv_matrix"], okw["yuv_range"]) if okw else img)
+            _deliver_loop(sink, outs, chunk_imgs)
             del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-    if outs:
+    if sink is not None:
+        images = sink.out
+    elif outs:
         images = torch.cat(outs)
+    elif okw:
+        images = torch.empty((0,) + tuple(shape), dtype=out_dtype, device=dev)
     else:
         c = getattr(nca_model, "c_out", 3)
         images = torch.empty((0, hh, ww, c) if out_dtype == torch.uint8 else (0, c, hh, ww), dtype=out_dtype, device=dev)
@@ -387,6 +531,7 @@ def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, sh
 
 stylize_clip.last_path = None
 stylize_clip.last_upload = None
+stylize_clip.last_download = None
 
 
 def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
@@ -398,7 +543,9 @@ def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
 @torch.no_grad()
 def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                              warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8, size=None, crop="conditioned",
-                             resample: str = "lanczos", pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited"):
+                             resample: str = "lanczos", pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
+                             out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited",
+                             out: Optional[torch.Tensor] = None):
     """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
     loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
     goal of its own steps:
@@ -424,11 +571,16 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     pixel_format, yuv_matrix, yuv_range: planar YUV 4:2:0 frames [F, 3h/2, w] uint8 ('i420' / 'nv12'), as in stylize_clip: converted on the
     device, inside the resize when size is set; the result is that of the same call on yuv420_to_rgb(frames, ...).  Pinned host frames
     are uploaded on a side stream while the previous chunk computes; stylize_clip_conditioned.last_upload records 'overlapped' or 'sync'.
-    Every copy out of `frames` is complete when the call returns."""
+    Every copy out of `frames` is complete when the call returns.
+
+    out_format, out_yuv_matrix, out_yuv_range, out: planar YUV 4:2:0 images [F*steps_per_frame, 3H/2, W] uint8 and delivery into a
+    caller's tensor (a pinned one on a side stream while the next chunk computes), as in stylize_clip;
+    stylize_clip_conditioned.last_download records 'overlapped', 'sync' or None."""
     from . import ops
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
+    shape, okw = _images_spec(out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
     if nca.num_target_channels != 3:
         raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
     n_frames = frames.shape[0]
@@ -439,10 +591,23 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     k, step_n, warm, per_call = int(steps_per_frame), int(step_n), int(warmup_steps), max(1, int(frames_per_call))
     if k < 1 or step_n < 1 or warm < 0:
         raise ValueError("steps_per_frame and step_n must be positive and warmup_steps non-negative")
+    _check_out(out, n_frames * k, shape, out_dtype)
     dev = next(nca.parameters()).device
     h = (nca.generate_seed(1, size=hh) if state is None else state).to(dev)
     fused = h.is_cuda and h.dtype == torch.float32 and h.shape[0] == 1 and ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3
     stylize_clip_conditioned.last_path = "clip" if fused else "loop"
+    stylize_clip_conditioned.last_download = None
+    sink = None if out is None else _Downloads(stylize_clip_conditioned, out, shape, per_call * k, dev)
+    try:
+        return _stylize_clip_conditioned_run(nca, frames, h, fused, per_call, shrink, k, step_n, warm, out_dtype, hh, ww, dev, u8_in, shape, okw, sink)
+    finally:
+        if sink is not None:
+            sink.finish()                # no copy into the caller's buffer is in flight once the call returns
+
+
+def _stylize_clip_conditioned_run(nca, frames, h, fused, per_call, shrink, k, step_n, warm, out_dtype, hh, ww, dev, u8_in, shape, okw, sink):
+    """The two routes of stylize_clip_conditioned (its arguments validated, the state seeded).  shape, okw, sink as in _stylize_clip_run."""
+    from . import ops
 
     def unit(chunk):      # frames of a chunk as the module takes them: [n,3,H,W] float32 in [0, 1]
         return (chunk.float() / 255.0).permute(0, 3, 1, 2).contiguous() if u8_in else chunk
@@ -464,23 +629,31 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
             us = None
             if nca.mask_rng != "philox":           # the loop's own draws, grow call by grow call: the generator ends where it would
                 us = torch.cat([draw(step_n) for _ in range(n * k)])
-            imgs, h = ops.cond_clip(h, goal, us, w, k, step_n, *args, nca.mask_seed, nca._mask_step, out_dtype=out_dtype)
+            buf = None if sink is None else sink.staging(n * k)
+            imgs, h = ops.cond_clip(h, goal, us, w, k, step_n, *args, nca.mask_seed, nca._mask_step, out_dtype=out_dtype, images=buf, **okw)
             nca._mask_step += n * k * step_n
-            outs.append(imgs[:, 0])
+            _deliver(sink, outs, imgs[:, 0])
     else:
         for ci, raw in enumerate(_chunks(stylize_clip_conditioned, frames, per_call, dev)):
             chunk = unit(shrink(raw))
+            chunk_imgs = []
             for i in range(chunk.shape[0]):
                 goal_img = chunk[i:i + 1]
                 if ci == 0 and i == 0 and warm > 0:
                     h = nca.grow(h, warm, goal_img)
                 for _ in range(k):
                     h = nca.grow(h, step_n, goal_img)
-                    outs.append(_unit_image(h, out_dtype))
+                    img = _unit_image(h, out_dtype)
+                    chunk_imgs.append(rgb_to_yuv420(img.contiguous(), okw["out_format"], okw["yuv_matrix"], okw["yuv_range"]) if okw else img)
+            _deliver_loop(sink, outs, chunk_imgs)
             goal_img = None                                                       # (a view of the chunk)
             del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-    if outs:
+    if sink is not None:
+        images = sink.out
+    elif outs:
         images = torch.cat(outs)
+    elif okw:
+        images = torch.empty((0,) + tuple(shape), dtype=out_dtype, device=dev)
     else:
         images = torch.empty((0, hh, ww, 3) if out_dtype == torch.uint8 else (0, 3, hh, ww), dtype=out_dtype, device=dev)
     stylize_clip_conditioned.last_state = h
@@ -489,3 +662,4 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
 
 stylize_clip_conditioned.last_path = None
 stylize_clip_conditioned.last_upload = None
+stylize_clip_conditioned.last_download = None
