@@ -194,8 +194,26 @@ int ncahip_dynca_nsteps_fwd_ms_f32(float *states, int ring, int T, const float *
  * backward entry point and no bf16-storage one.  The exact backward entry points (ncahip_dynca_step_bwd_*_f32 without "bfmma",
  * ncahip_dynca_nsteps_bwd_f32 / _ms_f32 / _bf16) always compute exactly and need a history recorded in mode 0; the entry points of the
  * bf16-MFMA training mode (ncahip_dynca_*_bfmma_f32, further down) need a history recorded in mode 1.
- * Range: C <= 16 and fc <= 128.  For any other shape the mode is IGNORED: the result is bit-equal to mode 0.                  */
+ * Range: C <= 16 and fc <= 128 (the NARROW range; ncahip_dynca_bf16_range below adds a second one).  For any other shape the
+ * mode is IGNORED: the result is bit-equal to mode 0.                                                                        */
 int ncahip_dynca_precision(int mode);
+
+/* ---- the range of mode 1 ---------------------------------------------------------------------------------------------------
+ * Process-wide, host-only, like the precision: 0 = narrow (default; the range stated above), 1 = wide.  Returns the PREVIOUS
+ * value, or NCAHIP_EINVAL for any other argument (the setting is then unchanged).  It matters only while the precision is 1 and
+ * is read together with it, once per call.  Under (precision 1, range 1):
+ *   - a shape inside the narrow range runs exactly what (1, narrow) runs -- per-step, two-scale, both one-launch kernels, steered;
+ *   - a shape outside it with 1 <= C <= 32 and 1 <= fc <= 256 runs the arithmetic of mode 1, as stated above, in the SINGLE-SCALE,
+ *     UNSTEERED per-step kernels: ncahip_dynca_step_fwd_f32, ncahip_dynca_nsteps_fwd_f32 (with or without history),
+ *     ncahip_dynca_clip_f32 and ncahip_dynca_clip_xc_f32 -- one launch per step for the whole hidden layer (mode 0 runs fc > 128
+ *     as one launch per 128-wide slice).  With C > 16 there are two 16-row output tiles: channel c is row c % 16 of tile c / 16, both
+ *     tiles are formed from the same bf16 hidden operand, and each accumulator starts at its b2 and sums the hidden units in the k
+ *     order of the narrow range (csrc/nca_dynca_bf16.h, "two output tiles"); layer 1 takes up to five 8-slot chunks in ascending
+ *     order, the conditioning slot last.  Vector and any-shape form agree bit for bit;
+ *   - everything else is the exact fp32 call, bit for bit: shapes outside both ranges, two-scale calls at C > 16 or fc > 128 and
+ *     calls with a direction field attached at such shapes.
+ * No backward entry point and no bf16-storage entry point reads the setting.                                                */
+int ncahip_dynca_bf16_range(int range);
 
 /* ---- steered perception: a per-cell direction field for the DyNCA forward step ------------------------------------------
  * What the WebGL runtime does with `rotationAngle` and `alignment` (docs/dynca.js:209-225, :417-426): every cell's Sobel pair is

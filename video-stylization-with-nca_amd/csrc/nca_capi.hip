@@ -177,6 +177,10 @@ int ncahip_dynca_precision(int mode) {
     return nca_dynca_precision_exchange(mode);
 }
 static bool dynca_bf16_mfma(int C, int fc) { return nca_dynca_precision() == 1 && nca_dynca_bf16_shape_ok(C, fc); }
+int ncahip_dynca_bf16_range(int range) {
+    if (range != 0 && range != 1) return fail(NCAHIP_EINVAL, "dynca bf16 range: 0 (narrow: C <= 16, fc <= 128) or 1 (wide: C <= 32, fc <= 256)");
+    return nca_dynca_bf16_range_exchange(range);
+}
 
 // Steered perception: the direction field (nca_modes.h) is process-wide like the precision; the eight fp32 forward entry points that
 // honour the precision take ONE snapshot per call at enqueue time (the clip drivers hand theirs to the steps they enqueue).  Every
@@ -267,7 +271,11 @@ static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, cons
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t slot = (size_t)B * C * H * W * (bf16 ? sizeof(uint16_t) : sizeof(float)), uslot = (size_t)B * H * W;
-    const bool bf = !bf16 && dynca_bf16_mfma(C, fc);   // one read per call: every step of it runs the same arithmetic
+    // one read per call: every step of it runs the same arithmetic.  Mode 1 covers the narrow range in every form; in the wide range
+    // (ncahip_dynca_bf16_range 1) also the single-scale unsteered step up to C = 32 / fc = 256.  Everything else runs exactly.
+    const NcaDyncaPrec prec = bf16 ? NcaDyncaPrec{0, 0} : nca_dynca_prec_snapshot();
+    const bool bfw = prec.precision == 1 && prec.range == 1 && !ms && !dir.p && !nca_dynca_bf16_shape_ok(C, fc) && nca_dynca_bf16_wide_shape_ok(C, fc);
+    const bool bf = prec.precision == 1 && (nca_dynca_bf16_shape_ok(C, fc) || bfw);
     for (int t = 0; t < T; ++t) {
         const float* const xi = reinterpret_cast<const float*>(single ? x_in : states + (size_t)(t % ring) * slot);
         float* const xo = reinterpret_cast<float*>(single ? x_out : states + (size_t)((t + 1) % ring) * slot);
@@ -279,7 +287,7 @@ static int dynca_fwd_impl(DyncaFwdKind kind, const char* what, bool single, cons
         a.u_bits = ubits;
         a.dirs = dir.p;
         a.dirs_bstride = dir.Bd == 1 ? 0 : (size_t)2 * H * W;
-        if (int rc = hip_result(bf16 ? nca_launch_dynca_step_fwd_bf16(a, st) : nca_launch_dynca_step_fwd(a, st, bf), what)) return rc;
+        if (int rc = hip_result(bf16 ? nca_launch_dynca_step_fwd_bf16(a, st) : nca_launch_dynca_step_fwd(a, st, bf, bfw), what)) return rc;
     }
     return 0;
 }

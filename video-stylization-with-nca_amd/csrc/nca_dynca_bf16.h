@@ -2,9 +2,10 @@
 // What fixes the bits of that mode lives here and is shared by the per-step kernel (nca_dynca_step.h) and the two persistent
 // kernels (nca_dynca_persist.hip): the k order of both products (folded into the LDS weight images), the operand roundings and the
 // MFMA sequence per accumulator.  The weight images exist once.  The layer-1 operand packing and MFMA sequence exist TWICE: inside mlp
-// (every forward kernel) and as pack_y / layer1 (the bf16-MFMA backward), see the note at layer1; test_gpu_dynca_train_bf16.py compares
-// the two on the device at both shape classes, with and without conditioning.  C <= 16 (one 16-row output tile), fc a multiple of 32
-// after padding.
+// (every forward kernel of the narrow range) and as pack_y / layer1 (the bf16-MFMA backward, and mlp_wide), see the note at layer1; test_gpu_dynca_train_bf16.py compares
+// the two on the device at both shape classes, with and without conditioning.  The narrow range is C <= 16 (one 16-row output tile)
+// and fc <= 128; the wide range (ncahip_dynca_bf16_range 1, forward per-step kernels only: mlp_wide, nca_dynca_bf16_wide.hip) is C <= 32
+// (two output tiles) and fc <= 256.  fc is a multiple of 32 after padding.
 //
 // k order.  v_mfma_f32_16x16x32_bf16 takes eight k values per lane: lane (g, i) supplies k = 8g + j, j = 0..7.
 //   layer 1: lane (g, cell) holds y slots s = 0..K1S-1 (s = 4c'+f < CP: channel 4c'+g, filter f; s = CP: conditioning channel g) --
@@ -12,6 +13,11 @@
 //            16 hidden units instead of K1S.
 //   layer 2: the accumulator registers r = 0..3 of hidden tile m are hidden units 16m + 4g + r of the lane's cell.  Pair p takes
 //            tiles 2p and 2p+1: j = 4 (m & 1) + r  <->  hidden 16 (2p + j / 4) + 4g + j % 4: FC / 32 MFMAs instead of FC / 4.
+//   two output tiles (the wide range, CP = 32): output tile t holds channels 16t + 4g + r in register r.  Layer 1 is the same product
+//            with K1S up to 33 slots (K1Q up to 5 chunks, ascending; the conditioning slot alone in the last chunk).  Layer 2 forms
+//            both tiles from the SAME operand: per pair p = 0..FC/32-1 in ascending order, one MFMA per tile t (t = 0, then t = 1) with
+//            the W2 entry [t][p], whose k order is the one above.  Each accumulator therefore sums b2, then pairs 0, 1, .. in that
+//            order, whatever the other tile does.  W2 image of the wide range: [out tile t][pair p][lane] (w2w_src).
 // Image layout: 16-byte entries [tile][chunk | pair][lane], eight bf16 each; as 32-bit words idx = (entry * 64 + lane) * 4 + jj with
 // word jj = (j = 2jj in the low half, j = 2jj + 1 in the high half).
 #pragma once
@@ -23,7 +29,7 @@ struct NcaDyncaBf16 {
     static constexpr int K1Q = (K1S + 7) / 8;       // layer-1 MFMAs per hidden tile
     static constexpr int M1T = FC / 16, M1P = FC / 32;
     static constexpr int W1_WORDS = M1T * K1Q * 256, W2_WORDS = M1P * 256;   // 32-bit words (= floats of LDS)
-    static_assert(CP % 4 == 0 && CP <= 16 && FC % 32 == 0, "bf16 UpdateNet: C <= 16, fc padded to a multiple of 32");
+    static_assert(CP % 4 == 0 && CP <= 32 && FC % 32 == 0 && FC <= 256, "bf16 UpdateNet: C <= 32, fc <= 256 padded to a multiple of 32");
 
     // source element in w1 [fc][K1 = 4C + CC] of half `hf` of image word idx, or -1 (zero padding)
     static __device__ __forceinline__ long w1_src(int idx, int hf, int C, int CC, int fc) {
@@ -124,6 +130,58 @@ struct NcaDyncaBf16 {
             const nca_u32x4 wb = W2B[p * 64];
 #pragma unroll
             for (int n = 0; n < NT; ++n) acc2[n] = nca_mfma_bf16(wb, hb[n], acc2[n]);
+        }
+    }
+
+    // ---- the wide range (ncahip_dynca_bf16_range 1): C <= 32, fc <= 256 in ONE launch -------------------------------------------------
+    // M2T = ceil(CP / 16) output tiles.  The W1 image is the one above (up to 16 tiles x 5 chunks); the W2 image gains the output tile
+    // as its slowest index: entry [t][p][lane], lane (g, i), j  <->  W2[ch = 16t + i][hidden 16 (2p + j / 4) + 4g + j % 4].
+    static constexpr int M2T = (CP + 15) / 16;
+    static constexpr int W2W_WORDS = M2T * M1P * 256;
+    static __device__ __forceinline__ long w2w_src(int idx, int hf, int C, int fc) {
+        const int jj = idx & 3, l = (idx >> 2) & 63, e = idx >> 8, p = e % M1P, t = e / M1P;
+        const int j = 2 * jj + hf, gg = l >> 4, o = 16 * t + (l & 15), k = 16 * (2 * p + (j >> 2)) + 4 * gg + (j & 3);
+        return (o < C && k < fc) ? (long)o * fc + k : -1;
+    }
+    // acc2[t] = b2[16t ..] + W2[16t ..] bf16(relu(b1 + W1 bf16(P))) for NT groups of 16 cells and both output tiles; fp32 accumulation,
+    // biases as initial values.  Layer 1 is streamed pair by pair (pack_y / layer1: the sequence of mlp) into the layer-2 accumulators:
+    // the hidden activations of a pair live in NT registers of four words and nowhere else.  A function of its own: mlp's instruction
+    // streams are held fixed (see the note at layer1).
+    template <int NT>
+    static __device__ __forceinline__ void mlp_wide(const float* W1L, const float* W2L, const float* B1L, const float* B2L,
+                                                    const float (&P)[NT][K1S], int lane, int g, f32x4 (&acc2)[M2T][NT]) {
+        const nca_u32x4* const W1B = reinterpret_cast<const nca_u32x4*>(W1L) + lane;
+        const nca_u32x4* const W2B = reinterpret_cast<const nca_u32x4*>(W2L) + lane;
+#pragma unroll
+        for (int t = 0; t < M2T; ++t) {
+            const f32x4 bias = *reinterpret_cast<const f32x4*>(B2L + 16 * t + 4 * g);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc2[t][n] = bias;
+        }
+        nca_u32x4 PB[NT][K1Q];
+        pack_y<NT>(P, PB);
+#pragma unroll
+        for (int p = 0; p < M1P; ++p) {
+            nca_u32x4 hb[NT];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                f32x4 acc1[NT];
+                layer1<NT>(W1B, B1L, 2 * p + hf, g, PB, acc1);
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    float h[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h[r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu
+                    hb[n][2 * hf] = nca_pk_bf16(h[0], h[1]);
+                    hb[n][2 * hf + 1] = nca_pk_bf16(h[2], h[3]);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < M2T; ++t) {
+                const nca_u32x4 wb = W2B[(t * M1P + p) * 64];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc2[t][n] = nca_mfma_bf16(wb, hb[n], acc2[t][n]);
+            }
         }
     }
 

@@ -1,7 +1,8 @@
 // nca_dynca_step.h -- the fused DyNCA step kernel for MI355X (gfx950), fp32 exact: kernel template, its twelve named variants, the
 // one launcher and the one dispatch ladder.  nca_dynca_fwd.hip instantiates the forward variants, nca_dynca_bwd.hip the backward
 // ones, nca_dynca_steer.hip (a unit of its own) the steered forward variants DyncaSteered<V>, nca_dynca_bwd_bf16.hip (a unit of its
-// own) the two bf16-MFMA backward variants.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
+// own) the two bf16-MFMA backward variants, nca_dynca_bf16_wide.hip (a unit of its own) DyncaFwdBf at the three wide shape classes
+// <32, 128>, <16, 256> and <32, 256> (its own small ladder).  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
 //
 // One persistent launch per NCA step.  A workgroup (4 waves) owns TH x TW cell tiles:
 //   1. the state tile (+1 halo, pad mode resolved at load time; ConditionedNCA: the pending
@@ -112,11 +113,13 @@ struct DyncaBwdBfMs : DyncaVariant { static constexpr bool BWD = true, W2F = tru
 // operand, as in the forward); writes relu(h), dh and dL/dy[:4C].  The two weight-gradient GEMMs
 // (dW2 = (G*mask) h^T, dW1 = dh y^T, K = all cells) are plain library GEMMs on those buffers.
 template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT, bool VEC, typename V>
-__global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_step_fwd_kernel(const NcaDyncaArgs a) {   // CP > 16: 140 KB of LDS -> one workgroup per CU anyway: 512 registers
+__global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128)) ? 1 : 2) void dynca_step_fwd_kernel(const NcaDyncaArgs a) {   // CP > 16: 140 KB of LDS -> one workgroup per CU anyway: 512 registers (bf16 MFMA at FC = 256: 85 KB, the same)
     constexpr bool BWD = V::BWD, B16 = V::B16, ACC = V::ACC, W2F = V::W2F, MS = V::MS, BF = V::BF, STEER = V::STEER;
+    // the wide range of the bf16-MFMA forward (ncahip_dynca_bf16_range 1; nca_dynca_bf16_wide.hip): two output tiles and / or FC = 256
+    constexpr bool BFW = BF && (CP > 16 || FC > 128);
     static_assert(!STEER || (!BWD && !B16), "steered: the forward variants with fp32 storage");
     static_assert(!MS || (TH % 2 == 0 && TW % 2 == 0), "the two-scale step: a tile covers whole coarse cells");
-    static_assert(!BF || CP <= 16, "bf16 MFMA: one output tile");
+    static_assert(!BFW || (!BWD && !MS && !STEER && !ACC && !B16), "bf16 MFMA, wide range: the plain forward only");
     using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
     using Pos = TilePos<TH, TW>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -172,6 +175,23 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
         fill_commit_pk(f2, W2L, tid, bmap_w2t);
         fill_commit_pk(f5, smem + K::LDS_FLOATS_BWD_W2 + (MS ? 4 * CP * K::PCS : 0), tid, bmap_w1t);
         fill_commit(f3, B1L, tid, map_b1);
+    } else if constexpr (BFW) {   // the wide range: the same W1 image (up to 16 tiles x 5 chunks), the W2 image [out tile][pair][lane]
+        using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
+        static_assert(BFK::W1_WORDS == K::W1_FLOATS && BFK::W2W_WORDS == K::W2_FLOATS && BFK::M2T == K::M2T, "the carve holds both images");
+        auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
+        auto bmap_w2 = [&](int idx, int hf) -> long { return BFK::w2w_src(idx, hf, C, fc); };
+        FillP<BFK::W1_WORDS> f1;
+        FillP<BFK::W2W_WORDS> f2;
+        FillV<FC> f3;
+        FillV<K::M2T * 16> f4;
+        fill_issue_pk(f1, a.w1, tid, bmap_w1);
+        fill_issue_pk(f2, a.w2, tid, bmap_w2);
+        fill_issue(f3, a.b1, tid, map_b1);
+        fill_issue(f4, a.b2, tid, map_b2);
+        fill_commit_pk(f1, W1L, tid, bmap_w1);
+        fill_commit_pk(f2, W2L, tid, bmap_w2);
+        fill_commit(f3, B1L, tid, map_b1);
+        fill_commit(f4, B2L, tid, map_b2);
     } else if constexpr (BF) {   // both weights rounded to bf16 (RNE) here, once; eight k values per lane and entry in the bf16 k order
         using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
         auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
@@ -734,7 +754,9 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS) ? 1 : 2) void dynca_st
                             for (int r = 0; r < 4; ++r) xprev[n][m2][r] = ob[(size_t)min(16 * m2 + 4 * g + r, C - 1) * plane];
                     }
                 }
-                if constexpr (BF) {   // both products on bf16 MFMA, operands rounded to nearest even (nca_dynca_bf16.h)
+                if constexpr (BFW) {   // the same on two output tiles and / or sixteen hidden tiles, still one pass over the perception
+                    NcaDyncaBf16<CP, FC, HAS_COND>::template mlp_wide<NT>(W1L, W2L, B1L, B2L, P, lane, g, acc2);
+                } else if constexpr (BF) {   // both products on bf16 MFMA, operands rounded to nearest even (nca_dynca_bf16.h)
                     NcaDyncaBf16<CP, FC, HAS_COND>::template mlp<NT>(W1L, W2L, B1L, B2L, P, lane, g, acc2[0]);
                 } else {   // exact fp32: the lines up to the closing brace are as they were (not re-indented)
                 float wa1[K::K1S], wa2[4][K::M2T];

@@ -284,7 +284,13 @@ int nca_resize_build_tables(int in, int out, int filter, int32_t* k, int32_t* bo
 
 // fused steps (nca_dynca_fwd.hip, nca_dynca_bwd.hip, nca_cond_generic.hip); hipErrorInvalidValue when no instantiation covers the shape
 // bf16_mfma: ncahip_dynca_precision mode 1 (both 1x1 products on bf16 MFMA, nca_dynca_bf16.h) where nca_dynca_bf16_shape_ok
-hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma = false);
+// bf16_wide: with bf16_mfma, ncahip_dynca_bf16_range 1 -- a single-scale unsteered step outside the narrow range and inside
+// nca_dynca_bf16_wide_shape_ok runs nca_launch_dynca_step_fwd_bf16_wide; every other call is what it is without the flag
+hipError_t nca_launch_dynca_step_fwd(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma = false, bool bf16_wide = false);
+// the bf16-MFMA forward at the wide shape classes <32, 128>, <16, 256>, <32, 256> (nca_dynca_bf16_wide.hip): the whole hidden layer in one
+// launch; single-scale, unsteered, a shape inside the wide and outside the narrow range (anything else: hipErrorInvalidValue)
+hipError_t nca_launch_dynca_step_fwd_bf16_wide(const NcaDyncaArgs& a, hipStream_t st);
+inline bool nca_dynca_bf16_wide_shape_ok(int C, int fc) { return C >= 1 && C <= 32 && fc >= 1 && fc <= 256; }
 // the same ladder over the steered variants (nca_dynca_steer.hip); a.dirs must be set.  nca_launch_dynca_step_fwd goes there itself
 hipError_t nca_launch_dynca_step_fwd_steered(const NcaDyncaArgs& a, hipStream_t st, bool bf16_mfma);
 inline bool nca_dynca_bf16_shape_ok(int C, int fc) { return C >= 1 && C <= 16 && fc >= 1 && fc <= 128; }

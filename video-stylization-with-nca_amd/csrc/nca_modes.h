@@ -53,6 +53,14 @@ inline bool nca_cond_fwd_default() {
 // enqueue time by the fp32 forward entry points only (never by a backward one)
 int nca_dynca_precision();
 int nca_dynca_precision_exchange(int mode);   // returns the previous mode
+// The range of mode 1 (ncahip_dynca_bf16_range): 0 = narrow (C <= 16, fc <= 128; default), 1 = wide (C <= 32, fc <= 256: single-scale
+// unsteered per-step kernels beyond the narrow range).  It lives in ONE word with the precision, so the snapshot a call takes is a
+// pair some setter left behind, never half of one change and half of another.
+struct NcaDyncaPrec {
+    int precision, range;
+};
+NcaDyncaPrec nca_dynca_prec_snapshot();
+int nca_dynca_bf16_range_exchange(int range);   // returns the previous range
 
 // Steered perception (ncahip_dynca_direction): the per-cell direction field [Bd,2,H,W] (plane 0 = s, plane 1 = c) the DyNCA forward
 // rotates every Sobel pair by; p == nullptr: none attached

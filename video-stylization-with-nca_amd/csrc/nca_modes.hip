@@ -19,7 +19,7 @@ struct ModesFromEnv : NcaModes {
     }
 } g_modes;
 
-std::atomic<int> g_dynca_precision{0};
+std::atomic<int> g_dynca_prec{0};   // precision | range << 8: one word, so that a call's snapshot is one consistent pair
 std::mutex g_dynca_dir_mu;
 NcaDyncaDir g_dynca_dir{nullptr, 0, 0, 0};
 
@@ -27,8 +27,21 @@ NcaDyncaDir g_dynca_dir{nullptr, 0, 0, 0};
 
 NcaModes& nca_modes() { return g_modes; }
 
-int nca_dynca_precision() { return g_dynca_precision.load(std::memory_order_relaxed); }
-int nca_dynca_precision_exchange(int mode) { return g_dynca_precision.exchange(mode, std::memory_order_relaxed); }
+int nca_dynca_precision() { return g_dynca_prec.load(std::memory_order_relaxed) & 255; }
+int nca_dynca_precision_exchange(int mode) {
+    int cur = g_dynca_prec.load(std::memory_order_relaxed);
+    while (!g_dynca_prec.compare_exchange_weak(cur, (cur & ~255) | mode, std::memory_order_relaxed)) {}
+    return cur & 255;
+}
+NcaDyncaPrec nca_dynca_prec_snapshot() {
+    const int v = g_dynca_prec.load(std::memory_order_relaxed);
+    return NcaDyncaPrec{v & 255, (v >> 8) & 255};
+}
+int nca_dynca_bf16_range_exchange(int range) {
+    int cur = g_dynca_prec.load(std::memory_order_relaxed);
+    while (!g_dynca_prec.compare_exchange_weak(cur, (cur & 255) | (range << 8), std::memory_order_relaxed)) {}
+    return (cur >> 8) & 255;
+}
 
 NcaDyncaDir nca_dynca_dir_snapshot() {
     std::lock_guard<std::mutex> lk(g_dynca_dir_mu);

@@ -38,6 +38,7 @@ SIGNATURES = {
                                  _F, _F, _F, _U64, _U64, _P],
     "ncahip_cond_precision": [_I],
     "ncahip_dynca_precision": [_I],
+    "ncahip_dynca_bf16_range": [_I],
     "ncahip_dynca_direction": [_P, _I, _I, _I],
     "ncahip_dynca_step_fwd_bf16": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P],
     "ncahip_dynca_nsteps_fwd_bf16": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P],

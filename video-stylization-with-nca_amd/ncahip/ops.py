@@ -99,27 +99,41 @@ def set_cond_precision(mode) -> None:
     check(lib().ncahip_cond_precision({"exact": 0, "bf16x3": 1}.get(mode, mode)), "cond_precision")
 
 
-_DYNCA_PRECISIONS = ("f32", "bf16")         # ncahip_dynca_precision modes 0 / 1
+_DYNCA_PRECISIONS = ("f32", "bf16")         # ncahip_dynca_precision modes 0 / 1 (what the backward's `precision` takes)
+# the forward's names: (ncahip_dynca_precision mode, ncahip_dynca_bf16_range) pairs
+_DYNCA_FWD_PRECISIONS = {"f32": (0, 0), "bf16": (1, 0), "bf16_wide": (1, 1)}
 _dynca_precision_lock = threading.RLock()
 
 
 def set_dynca_precision(mode: str) -> str:
-    """'f32' (exact, the default) or 'bf16': both 1x1 products of the DyNCA FORWARD step on bf16 MFMA with fp32 accumulation, for
-    C <= 16 and fc <= 128 (dynca_bf16_ok; other shapes ignore the mode) -- ncahip_dynca_precision in include/ncahip.h.  Process-wide,
-    read when a call enqueues; needs no GPU.  Returns the previous mode.  Whatever keeps a history for autograd runs under 'f32'
-    regardless (the backward recomputes exactly)."""
-    if mode not in _DYNCA_PRECISIONS:
-        raise ValueError(f"dynca precision must be 'f32' or 'bf16', got {mode!r}")
+    """'f32' (exact, the default), 'bf16' or 'bf16_wide': both 1x1 products of the DyNCA FORWARD step on bf16 MFMA with fp32
+    accumulation -- ncahip_dynca_precision and ncahip_dynca_bf16_range in include/ncahip.h.  'bf16' covers C <= 16 and fc <= 128
+    (dynca_bf16_ok); 'bf16_wide' covers those shapes exactly as 'bf16' does and, for single-scale unsteered per-step calls, also
+    C <= 32 and fc <= 256 (dynca_bf16_wide_ok).  Other shapes ignore the mode.  Process-wide, read when a call enqueues; needs no GPU.
+    Returns the previous name (one of the three).  Whatever keeps a history for autograd runs under 'f32' regardless (the backward
+    recomputes exactly)."""
+    if mode not in _DYNCA_FWD_PRECISIONS:
+        raise ValueError(f"dynca precision must be 'f32', 'bf16' or 'bf16_wide', got {mode!r}")
+    prec, rng = _DYNCA_FWD_PRECISIONS[mode]
     with _dynca_precision_lock:
-        prev = lib().ncahip_dynca_precision(_DYNCA_PRECISIONS.index(mode))
-    if prev not in (0, 1):
-        check(prev, "dynca_precision")
-    return _DYNCA_PRECISIONS[prev]
+        # two settings, one name: a call enqueued on another thread between the two lines never sees (1, a range nobody asked for) --
+        # switching mode 1 on, the range goes first; switching it off, last
+        if prec == 1:
+            prev_rng = lib().ncahip_dynca_bf16_range(rng)
+        prev = lib().ncahip_dynca_precision(prec)
+        if prec != 1:
+            prev_rng = lib().ncahip_dynca_bf16_range(rng)
+        if prev not in (0, 1):
+            check(prev, "dynca_precision")
+        if prev_rng not in (0, 1):
+            check(prev_rng, "dynca_bf16_range")
+    # the range matters only while the precision is 1: (0, wide) is not a state this module leaves behind, and reads as 'f32'
+    return "f32" if prev == 0 else ("bf16_wide" if prev_rng == 1 else "bf16")
 
 
 @contextlib.contextmanager
 def dynca_precision(mode: str):
-    """with ops.dynca_precision('bf16'): ...  -- set_dynca_precision(mode) for the block, the previous mode back on exit (exceptions
+    """with ops.dynca_precision('bf16'): ... (or 'bf16_wide', 'f32')  -- set_dynca_precision(mode) for the block, the previous mode back on exit (exceptions
     included).  The mode is process-wide: the block holds a re-entrant lock, so blocks of other threads wait for it."""
     with _dynca_precision_lock:
         prev = set_dynca_precision(mode)
@@ -169,7 +183,7 @@ def dynca_direction(dirs: torch.Tensor):
 
 def reset_modes() -> None:
     """Every process-wide mode back to what a fresh process without environment overrides has: force_generic(0), cond precision
-    'exact', DyNCA precision 'f32', no direction field attached, no dropped tiles, persistent_steps = True, persistent_cond = False.
+    'exact', DyNCA precision 'f32' (its bf16 range narrow), no direction field attached, no dropped tiles, persistent_steps = True, persistent_cond = False.
     Needs no GPU.  Takes the locks of dynca_precision and dynca_direction; it must not be called inside a block of either (the block
     would put its previous mode back on exit)."""
     global persistent_steps, persistent_cond
@@ -185,6 +199,12 @@ def reset_modes() -> None:
 def dynca_bf16_ok(C: int, fc: int) -> bool:
     """Shapes the 'bf16' DyNCA precision covers: C <= 16 and fc <= 128 (one output tile, one hidden slice)."""
     return 1 <= int(C) <= 16 and 1 <= int(fc) <= 128
+
+
+def dynca_bf16_wide_ok(C: int, fc: int) -> bool:
+    """Shapes the 'bf16_wide' DyNCA precision covers: C <= 32 and fc <= 256 (two output tiles, the whole hidden layer in one launch).
+    Beyond dynca_bf16_ok that is the single-scale, unsteered per-step forward only."""
+    return 1 <= int(C) <= 32 and 1 <= int(fc) <= 256
 
 
 def check_errors(clear: bool = True) -> None:

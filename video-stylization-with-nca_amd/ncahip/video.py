@@ -384,10 +384,12 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     reference's preprocess_style_image (crop='dynca', bicubic), bit for bit -- and handed to the uint8 path above unchanged, on both
     routes.  Seeding, the state and the images use (H, W).  size=None: crop and resample are not looked at.
 
-    precision: 'f32' (exact, the default) or 'bf16' -- the steps of this call run under ops.dynca_precision('bf16') (both 1x1 products
-    on bf16 MFMA, fp32 accumulation and state; include/ncahip.h, ncahip_dynca_precision), on both routes and for both model families;
-    the process-wide mode is afterwards what it was before.  'bf16' needs ops.dynca_bf16_ok(c_in, fc_dim), an fp32 state on the GPU and
-    a model whose steps run on the fused kernels: anything else raises ValueError rather than computing in the other arithmetic.
+    precision: 'f32' (exact, the default), 'bf16' or 'bf16_wide' -- the steps of this call run under ops.dynca_precision(precision)
+    (both 1x1 products on bf16 MFMA, fp32 accumulation and state; include/ncahip.h, ncahip_dynca_precision and
+    ncahip_dynca_bf16_range), on both routes and for both model families; the process-wide mode is afterwards what it was before.
+    'bf16' needs ops.dynca_bf16_ok(c_in, fc_dim), 'bf16_wide' ops.dynca_bf16_wide_ok(c_in, fc_dim) (C <= 32, fc <= 256); both need an
+    fp32 state on the GPU and a model whose steps run on the fused kernels, and a `direction` needs a model inside dynca_bf16_ok:
+    anything else raises ValueError rather than computing in the other arithmetic.
 
     direction: None, a field tensor [1,2,H,W] or an (alignment, angle_deg) tuple (ncahip.steer; forward_nsteps' keyword): every step of
     the call rotates each cell's Sobel pair by its direction -- 'flow to the left', 'outwards from the centre', 'round two poles' for a
@@ -415,8 +417,8 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     computes; the host waits for the last copy before the call returns (also when it raises), so every byte is valid then.  A pageable or
     device tensor is filled by a plain copy per chunk.  stylize_clip.last_download records 'overlapped', 'sync' or None (out=None)."""
     from . import ops, steer
-    if precision not in ("f32", "bf16"):
-        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
+    if precision not in ("f32", "bf16", "bf16_wide"):
+        raise ValueError(f"precision must be 'f32', 'bf16' or 'bf16_wide', got {precision!r}")
     if gray not in ops.GRAY_WEIGHTS:
         raise ValueError(f"gray must be 'mean' or 'luma', got {gray!r}")
     if out_dtype not in (torch.float32, torch.uint8):
@@ -432,14 +434,24 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
     h = state if state is not None else nca_model.seed(1, size=(ww, hh))
     fused = (_clip_route_xc(nca_model, h) if extra else _clip_route(nca_model, h)) and torch.device(dev).type == "cuda"
-    if precision == "bf16":
+    if precision != "f32":
         fc = nca_model.w1.out_channels
-        if not ops.dynca_bf16_ok(nca_model.c_in, fc):
+        if precision == "bf16" and not ops.dynca_bf16_ok(nca_model.c_in, fc):
             raise ValueError(f"precision='bf16' covers C <= 16 and fc <= 128 (ops.dynca_bf16_ok); the model has C = {nca_model.c_in}, fc = {fc}")
+        if precision == "bf16_wide" and not ops.dynca_bf16_wide_ok(nca_model.c_in, fc):
+            raise ValueError(f"precision='bf16_wide' covers C <= 32 and fc <= 256 (ops.dynca_bf16_wide_ok); the model has C = {nca_model.c_in}, fc = {fc}")
+        if not ops.dynca_bf16_ok(nca_model.c_in, fc):
+            # 'bf16_wide' beyond the narrow range: the single-scale unsteered step only, whatever the state is
+            if nca_model._multiscale():
+                raise ValueError(f"precision='bf16_wide' needs the fused step kernels; multi-scale perception at C = {nca_model.c_in}, fc = {fc} "
+                                 "runs the composed multi-scale step")
+            if direction is not None:
+                raise ValueError(f"precision='bf16_wide' does not steer beyond C <= 16 and fc <= 128 (ops.dynca_bf16_ok): a direction on a model "
+                                 f"with C = {nca_model.c_in}, fc = {fc} would run in fp32")
         if not h.is_cuda or h.dtype != torch.float32:
-            raise ValueError(f"precision='bf16' needs a float32 state on the GPU (the state stays fp32), got {h.dtype} on {h.device}")
+            raise ValueError(f"precision={precision!r} needs a float32 state on the GPU (the state stays fp32), got {h.dtype} on {h.device}")
         if nca_model._composed(h):
-            raise ValueError("precision='bf16' needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
+            raise ValueError(f"precision={precision!r} needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
     stylize_clip.last_path = "clip" if fused else "loop"
     stylize_clip.last_download = None
     sink = None if out is None else _Downloads(stylize_clip, out, shape, per_call * k, dev)
@@ -450,7 +462,7 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         dirs, angle = steer.resolve(direction, hh, ww, h.device)           # one field for the whole call
         if dirs.shape[0] != 1:
             raise ValueError(f"direction field must be [1,2,{hh},{ww}] (the clip runs one sample), got {tuple(dirs.shape)}")
-    with ops.dynca_precision(precision) if precision == "bf16" else contextlib.nullcontext():
+    with ops.dynca_precision(precision) if precision != "f32" else contextlib.nullcontext():
         # the clip route's steps run under the field; the loop route hands it to forward_nsteps, which attaches it per call
         with ops.dynca_direction(dirs) if (fused and dirs is not None) else contextlib.nullcontext():
             try:
