@@ -91,7 +91,9 @@ int ncahip_cond_precision(int mode);
  * bit 7 = ncahip_cond_grow_fwd_f32 never draws its fire masks before its steps (every step draws in the kernel; same bits);
  * bits 16-23 = a cap on the steps per fire-word launch of that grow, 0 = no cap; a set cap also lets grows that are too short or
  * too small to gain from it (see ncahip_cond_grow_fwd_f32) draw beforehand, so that the path and its chunking are reachable at
- * test sizes.
+ * test sizes;
+ * bit 24 = ncahip_cond_grow_fwd_f32 never sends several steps out as one launch (see there: one launch per step, same bits);
+ * bits 25-27 = a cap on the steps per such fused-steps launch, 0 = no cap (a chunk's steps in one launch).
  * Any bit set also keeps ncahip_cond_grow_fwd_persist_f32 from running (it returns NCAHIP_ERANGE). */
 int ncahip_debug_force_generic(int on);
 
@@ -491,7 +493,24 @@ int ncahip_cond_alive_u8(const float *x, uint8_t *out, int B, int C, int H, int 
  *   weight tensors; an x_final that is a ring slot (other than the last one, which is refused) is legal and simply keeps the
  *   steps drawing in the kernel, as do explicit uniforms, bit-packed masks, ncahip_debug_force_generic bit 7, and grows for which
  *   one more launch does not pay: with r = the 16 x 16 super-tiles per workgroup of a step launch (B * ceil(H/16) * ceil(W/16)
- *   over min(that, the device's CUs), rounded up), r < 2 or T * r < 106.                                                     */
+ *   over min(that, the device's CUs), rounded up), r < 2 or T * r < 106.
+ *   Fused steps: where a grow draws its masks beforehand AND C <= 16 (the narrow-carve producer/consumer kernels) AND 2 <= r <= 12
+ *   (beyond that the saved launch cost no longer pays for the path's cost per round), the steps of a chunk go out as ONE launch
+ *   instead of one launch each.  A tile of step t + 1 then waits only for its 3 x 3
+ *   neighbourhood of 4 x 16 tiles of step t, through one 32-bit counter per tile; the counters live in x_final behind the chunk's
+ *   words (the chunk is at most 32 C - 1 steps then).  Same masks, same arithmetic, same results bit for bit.  The launch needs
+ *   every one of its workgroups resident at once (one per CU, at most the device's CUs): on a device whose CUs another process
+ *   holds, a tile's wait expires (bounded, about 0.2 s), the call or the next one returns NCAHIP_EDEVICE (error word bit 2), and
+ *   the ring has been overwritten by then.  ncahip_debug_force_generic bit 24 switches the path off (one launch per step, the
+ *   results are the same), bits 25-27 cap the steps per launch; ncahip_debug_fused_step_launches tells how many such launches the
+ *   last completed ncahip_cond_grow_fwd_f32 of the process made (0: one launch per step).                                     */
+int ncahip_debug_fused_step_launches(void);
+/* Where that path keeps its counters in x_final (host only, no GPU call): *chunk = the steps per fire-word chunk, at most 32 C, at
+ * most chunk_cap (0: no cap) and as many as leave room for the counters; *done_offset = the byte offset of the counters in x_final
+ * (= *chunk * B*H*W/8, behind the words); *done_bytes = their size (B * H/4 * W/16 counters and the abort word, padded to 64 bytes).
+ * *done_offset + *done_bytes <= B*C*H*W*4 always.  NCAHIP_EINVAL: null pointer, a size that is not positive, a negative cap;
+ * NCAHIP_ERANGE: H % 4 != 0 or W % 16 != 0. */
+int ncahip_cond_fused_steps_layout(int B, int C, int H, int W, int chunk_cap, int *chunk, uint64_t *done_offset, uint64_t *done_bytes);
 int ncahip_cond_grow_fwd_f32(float *states, uint8_t *pre, int ring, int T, float *x_final,
                              const float *goal, int goal_ch, const float *u,
                              const float *wp, const float *w1, const float *b1,

@@ -136,7 +136,8 @@ static int device_error_rc(const char* where) {
     const unsigned v = nca_error_word_read(false);
     if (!v) return 0;
     return fail(NCAHIP_EDEVICE, "%s: a device-side failure was recorded earlier on this device (error word 0x%x: bit 0 = "
-                "producer/consumer hand-off poll expired, bit 1 = neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired); results since "
+                "producer/consumer hand-off poll expired, bit 1 = neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired, bit 2 = tile "
+                "gate of a fused-steps ConditionedNCA launch expired); results since "
                 "the last ncahip_check_errors are not valid", where, v);
 }
 
@@ -148,7 +149,8 @@ int ncahip_check_errors(ncahip_stream_t stream, int clear) {
     const unsigned v = nca_error_word_read(clear != 0);
     if (!v) return 0;
     return fail(NCAHIP_EDEVICE, "device error word 0x%x (bit 0: a producer/consumer hand-off poll expired -- the affected launch "
-                "produced stale tiles; bit 1: a neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired -- that launch stopped early)", v);
+                "produced stale tiles; bit 1: a neighbour poll of a persistent DyNCA / ConditionedNCA kernel expired -- that launch stopped early; "
+                "bit 2: a tile gate of a fused-steps ConditionedNCA launch expired -- its later steps read tiles that were not ready)", v);
 }
 
 int ncahip_debug_inject_error(unsigned bits) {   // test hook: what a kernel does when a poll expires
@@ -718,6 +720,9 @@ int ncahip_cond_fire_words(uint64_t* words, int Tc, int B, int H, int W, float f
 // fire-word launches of the last ncahip_cond_grow_fwd_f32 that enqueued all its steps (0: its steps drew their masks themselves)
 static std::atomic<int> g_fire_word_launches{0};
 int ncahip_debug_fire_word_launches(void) { return g_fire_word_launches.load(std::memory_order_relaxed); }
+// fused-steps launches (several steps per launch, nca_cond_pc.hip MS) of the last ncahip_cond_grow_fwd_f32 that enqueued all its steps
+static std::atomic<int> g_fused_step_launches{0};
+int ncahip_debug_fused_step_launches(void) { return g_fused_step_launches.load(std::memory_order_relaxed); }
 // Shortest grow that draws its masks beforehand.  One fire-word launch has to be bought back by the steps it serves, and what a step
 // saves grows with the tiles a wave pair stages in it: rounds = super-tiles per workgroup of the step launch.  Measured with the grow
 // timed both ways over a ladder of T (tools/fire_words_cost.py, profiles/r8a_fire_words_cost.jsonl: launch cost / saving per step,
@@ -745,6 +750,26 @@ static bool fire_scratch_free(const void* x_final, size_t bytes, const void* sta
            !clip_overlap(x_final, bytes, w1, (size_t)hidden * 3 * C * f) && !clip_overlap(x_final, bytes, b1, hidden * f) &&
            !clip_overlap(x_final, bytes, w2, (size_t)hidden * hidden * f) && !clip_overlap(x_final, bytes, b2, hidden * f) &&
            !clip_overlap(x_final, bytes, w3, (size_t)C * hidden * f);
+}
+
+// Where the fused-steps path keeps its per-tile step counters: x_final holds the fire words of a chunk of steps, [chunk][B*H*W/64] 64-bit
+// words, and behind them B * H/4 * W/16 counters + the abort word (nca_cond_ms_done_bytes).  chunk = as many steps as fit beside the
+// counters, at most 32 C (what the words alone allow) and at most chunk_cap (0: no cap).  Host only.
+int ncahip_cond_fused_steps_layout(int B, int C, int H, int W, int chunk_cap, int* chunk, uint64_t* done_offset, uint64_t* done_bytes) {
+    if (!chunk || !done_offset || !done_bytes) return fail(NCAHIP_EINVAL, "cond_fused_steps_layout: null pointer");
+    if (!dims_ok(B, C, H, W) || chunk_cap < 0)
+        return fail(NCAHIP_EINVAL, "cond_fused_steps_layout: B=%d C=%d H=%d W=%d must all be positive, chunk_cap=%d not negative", B, C, H, W, chunk_cap);
+    if (W % 16 != 0 || H % 4 != 0) return fail(NCAHIP_ERANGE, "cond_fused_steps_layout: one counter per 4 x 16 tile needs H %% 4 == 0 and W %% 16 == 0 (H=%d W=%d)", H, W);
+    if ((size_t)B * (H / 4) * (W / 16) > ((size_t)1 << 31)) return fail(NCAHIP_ERANGE, "cond_fused_steps_layout: more than 2^31 tiles per step");
+    const size_t pslot = (size_t)B * H * W, slot = pslot * C * sizeof(float), words_bytes = pslot / 8, db = nca_cond_ms_done_bytes(B, H, W);
+    if (slot < db + words_bytes) return fail(NCAHIP_ERANGE, "cond_fused_steps_layout: x_final has no room for one step's words and the counters");
+    size_t n = (slot - db) / words_bytes;
+    if (n > (size_t)32 * C) n = (size_t)32 * C;
+    if (chunk_cap > 0 && n > (size_t)chunk_cap) n = (size_t)chunk_cap;
+    *chunk = (int)n;
+    *done_offset = n * words_bytes;
+    *done_bytes = db;
+    return 0;
 }
 
 static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring, int T, void* x_final, const void* goal, int goal_ch, const float* u,
@@ -795,26 +820,62 @@ static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring,
             if (fw_cap > 0 && fw_chunk > fw_cap) fw_chunk = fw_cap;
         }
     }
-    int fw_launches = 0, fw_left = 0;
+    // Fused steps (nca_cond_pc.hip, the MS kernels): where the steps read fire words AND the narrow-carve producer/consumer kernel walks at
+    // least two rounds per workgroup, a chunk's steps go out as ONE launch; tiles of step t + 1 wait for their 3 x 3 tile neighbourhood of
+    // step t through one counter per 4 x 16 tile.  The counters (and the abort word) live in x_final behind the chunk's words, so the
+    // chunk shrinks until both fit the slot; the grow's first fire-word launch zeroes them, later chunks count on.  Everything that keeps
+    // a grow off the fire words keeps it off this path; hook bit 24 switches it off, bits 25-27 cap the steps per launch.
+    unsigned* ms_done = nullptr;
+    if (fw_chunk > 0) {
+        NcaCondArgs a0 = step_args(0);
+        a0.fire_words = fw_scratch;
+        int chunk = 0;
+        uint64_t done_off = 0, done_bytes = 0;
+        if (nca_cond_pc_fused_steps_ok(a0) && ncahip_cond_fused_steps_layout(B, C, H, W, fw_chunk, &chunk, &done_off, &done_bytes) == 0) {
+            fw_chunk = chunk;
+            ms_done = reinterpret_cast<unsigned*>(static_cast<char*>(x_final) + done_off);
+        }
+    }
+    const int ms_cap = nca_modes().fused_steps_cap;   // test hook: steps per fused launch
+    int fw_launches = 0, fw_left = 0, ms_launches = 0;
     const unsigned long long* fw = nullptr;
     for (int t = 0; t < T; ++t) {
         NcaCondArgs a = step_args(t);
         if (fw_chunk > 0) {
             if (fw_left == 0) {
                 fw_left = T - t < fw_chunk ? T - t : fw_chunk;
-                if (int rc = hip_result(nca_launch_cond_fire_words(fw_scratch, fw_left, B, H, W, fire_rate, seed, step0 + (uint64_t)t, st), "cond_grow fire words"))
+                if (int rc = hip_result(nca_launch_cond_fire_words(fw_scratch, fw_left, B, H, W, fire_rate, seed, step0 + (uint64_t)t, st,
+                                                                   t == 0 ? ms_done : nullptr), "cond_grow fire words"))
                     return rc;
                 fw = fw_scratch;
                 ++fw_launches;
             }
             a.fire_words = fw;
+            if (ms_done) {
+                const int n = ms_cap > 0 && fw_left > ms_cap ? ms_cap : fw_left;
+                a.ms_steps = n;
+                a.ms_t0 = t;
+                a.ms_ring = ring;
+                a.ms_states = states;
+                a.ms_pre = pre;
+                a.ms_done = ms_done;
+                if (int rc = hip_result(nca_launch_cond_steps_fwd_pc(a, st), "cond_grow_fwd (fused steps)")) return rc;
+                fw += (size_t)n * fw_step;
+                fw_left -= n;
+                t += n - 1;
+                ++ms_launches;
+                continue;
+            }
             fw += fw_step;
             --fw_left;
         }
         if (int rc = bf16 ? hip_result(nca_launch_cond_step_fwd_bf16(a, st), "cond_grow_fwd_bf16") : hip_result(nca_launch_cond_step_fwd(a, st), "cond_grow_fwd"))
             return rc;
     }
-    if (!bf16) g_fire_word_launches.store(fw_launches, std::memory_order_relaxed);
+    if (!bf16) {
+        g_fire_word_launches.store(fw_launches, std::memory_order_relaxed);
+        g_fused_step_launches.store(ms_launches, std::memory_order_relaxed);
+    }
     const uint8_t* const pre_last = pre + (size_t)sl * pslot;
     return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, B, C, H, W, alive_ch,
                                                            alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)")

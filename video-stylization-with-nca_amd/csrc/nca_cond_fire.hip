@@ -16,11 +16,17 @@ namespace {
 
 // grid (ceil(B * H/4 * W/16 / 256), Tc), block 256
 __global__ __launch_bounds__(256) void cond_fire_words_kernel(unsigned long long* __restrict__ words, int B, int H, int W, float fire_rate,
-                                                              uint64_t seed, uint64_t step0) {
+                                                              uint64_t seed, uint64_t step0, unsigned* __restrict__ done_zero) {
     const int tw = W >> 4, th = H >> 2;
     const size_t per_step = (size_t)B * th * tw;
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= per_step) return;
+    // a grow's first chunk on the fused-steps path (nca_cond_pc.hip, MS): the tile's step counter starts at zero, and so does the abort
+    // word behind the counters
+    if (done_zero && blockIdx.y == 0) {
+        done_zero[id] = 0u;
+        if (id == 0) done_zero[per_step] = 0u;
+    }
     const int tx = (int)(id % tw), ty = (int)((id / tw) % th), b = (int)(id / ((size_t)tw * th));
     const uint64_t step = step0 + blockIdx.y;
     const size_t cell0 = (size_t)b * H * W + (size_t)(4 * ty) * W + 16 * tx;
@@ -45,10 +51,11 @@ __global__ __launch_bounds__(256) void cond_fire_words_kernel(unsigned long long
 }  // namespace
 
 // W % 16 == 0, H % 4 == 0, 1 <= Tc <= 65535, 8-byte aligned words: the callers check (nca_capi.hip)
+// done_zero: null, or the per-tile step counters of the fused-steps path ([B * H/4 * W/16] + the abort word), zeroed by the same launch
 hipError_t nca_launch_cond_fire_words(unsigned long long* words, int Tc, int B, int H, int W, float fire_rate, uint64_t seed, uint64_t step0,
-                                      hipStream_t st) {
+                                      hipStream_t st, unsigned* done_zero) {
     const size_t per_step = (size_t)B * (H >> 2) * (W >> 4);
     hipLaunchKernelGGL(cond_fire_words_kernel, dim3((unsigned)((per_step + 255) / 256), (unsigned)Tc), dim3(256), 0, st, words, B, H, W,
-                       fire_rate, seed, step0);
+                       fire_rate, seed, step0, done_zero);
     return hipGetLastError();
 }

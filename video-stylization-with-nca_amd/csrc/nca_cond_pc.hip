@@ -76,12 +76,34 @@ struct PCfg {
 // wave changes: hand-off, round counters, tile buffers and the producer are those of the kernel without the carry.
 // FW (with FC): the producer takes each tile's fire mask from a.fire_words, drawn before the launch (issue_loads / stage_tile FW),
 // instead of drawing it; the lists it writes are the same, and nothing else changes.
-template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false>
-__global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const NcaCondArgs a) {
+// MS (with FC, CARRY and FW): the launch runs a.ms_steps steps of a grow (NcaCondArgs, nca_kernels.h).  Every step walks the same
+// tiles, so a workgroup owns the same super-tiles and a pair the same tiles throughout; roles, hand-off counters, tile buffers,
+// lists and carry are those of the one-step kernel, and the round numbers keep counting across the steps, so a pair's pipeline runs
+// from the last tile of step t straight into the first tile of step t + 1.  What a tile of step t + 1 reads -- alpha' at halo 3,
+// the pre mask at halo 2, the state at halo 1 -- lies in its 3 x 3 neighbourhood of 4 x 16 tiles, so instead of a grid-wide wait
+// there is one counter per tile, a.ms_done = steps of the grow completed for it:
+//   * the consumer publishes a tile (counter = t + 1, one lane, agent scope) once every store to it has completed: its store_tile,
+//     the store_carry of each of its cells that was parked, and the producer's pre mask bytes (complete before the hand-off);
+//   * the producer waits, before it issues a tile's loads for step t, until the nine counters of its neighbourhood (inside the
+//     image) have reached t (gate below).  With the static walk the neighbours finished about a step's rounds earlier: the gate
+//     is almost never closed, and a slow pair delays only its neighbours, and only when they catch up with it.
+// All state stores are write-through (kNtStore; stage_tile's pre mask bytes: AUX) and all state loads agent-coherent (AUX = sc1).
+// The carry is flushed at the end of every step: no parked cell crosses a step.  Every workgroup must be resident (grid <= CUs,
+// one workgroup per CU by its LDS): a workgroup that never runs lets its neighbours' polls expire -- bounded, recorded in the error
+// word (bit 2) and in the abort word behind the counters, which every later gate reads first and then passes without polling.
+template <int CP, bool EXACT, typename ST, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false, bool MS = false>
+__global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const NcaCondArgs a_launch) {
     static_assert(!SPLIT || ST::BYTES == 4, "bf16x3 emulation is an option of the fp32-storage kernel");
     static_assert(!FC || (ST::BYTES == 4 && !SPLIT), "firing-cell lists: the exact-f32 fp32-storage consumer");
     static_assert(!CARRY || (FC && CP <= 16), "the carry: firing-cell lists on the narrow carve");
     static_assert(!FW || FC, "fire words: the kernels with firing-cell lists");
+    static_assert(!MS || (CARRY && FW && kNtStore), "several steps per launch: the narrow-carve fire-word kernels, write-through stores");
+    constexpr int AUX = MS ? 16 : kAuxCoherent;   // cache policy of the state-type accesses (issue_loads)
+    // MS: `a` is the view of the step a wave is working on -- the producer refills its part from the wave's words in LDS before every
+    // tile (view_in below), the consumer's part, x_out, changes at a step boundary (next_step); otherwise the launch's arguments themselves
+    [[maybe_unused]] NcaCondArgs a_step;
+    if constexpr (MS) a_step = a_launch;
+    const NcaCondArgs& a = MS ? a_step : a_launch;
     constexpr bool BF = ST::BYTES == 2;   // bf16 storage: UpdateNet on bf16 MFMA (operands rounded from the same LDS image)
     using K = WCfg<CP>;
     using PK = PCfg<CP>;
@@ -189,6 +211,79 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         return w;
     };
     int tile_no = 0;
+    // ---- MS: the step a wave is at, the gate and the publication ---------------------------------------------------------------
+    // What a wave needs only at a step boundary (the walk's first position, the ring's bases, the step counts) and the producer's
+    // view of its step wait in LDS, on the dead W1 / W2 images above the four carries (valid once the consumers hold the weights in
+    // registers: the second barrier).  The consumer's tile loop reads none of it: an LDS round trip there is exposed time, so what
+    // it needs per tile (x_out, the counter value, its unpublished tiles) stays in registers.
+    constexpr int kCarrySize = [] { if constexpr (CARRY) return FireCarry<CP>::SIZE; else return 0; }();
+    [[maybe_unused]] int step = 0, gbase = 0;   // MS: step of the launch, and its first round's number (rounds count on across steps)
+    typedef __attribute__((address_space(1))) unsigned gu32;   // a counter is a global agent-scope access, never a flat or plain one
+    constexpr int kMsList = 64, kMsWave = 24, kMsPair = 2 * kMsWave;   // unpublished tiles a consumer can hold (its lanes); words per wave, per pair
+    static_assert(!MS || 4 * (kCarrySize + kMsPair) <= K::OFF_W3, "carries and the MS state fit on the W1 / W2 images");
+    [[maybe_unused]] int* const WS_ = reinterpret_cast<int*>(smem) + 4 * kCarrySize + pair * kMsPair + (producer ? kMsWave : 0);   // this wave's words
+    enum { MS_R = 0, MS_T, MS_SX, MS_SY, MS_B, MS_NSTEPS, MS_T0, MS_RING, MS_RIN, MS_STATES, MS_PRE = MS_STATES + 2, MS_XIN = MS_PRE + 2,
+           MS_PIN = MS_XIN + 2, MS_XOUT = MS_PIN + 2, MS_POUT = MS_XOUT + 2, MS_FW = MS_POUT + 2, MS_END = MS_FW + 2 };
+    static_assert(MS_END <= kMsWave, "a wave's words");
+    [[maybe_unused]] auto ms_get = [&](int i) -> int { return __builtin_amdgcn_readfirstlane(WS_[i]); };
+    [[maybe_unused]] auto ms_get64 = [&](int i) -> size_t { return (size_t)(unsigned)ms_get(i) | ((size_t)(unsigned)ms_get(i + 1) << 32); };
+    [[maybe_unused]] gu32* const done = reinterpret_cast<gu32*>((uintptr_t)a_launch.ms_done);
+    [[maybe_unused]] const int tgh = H >> 2, tgw = W >> 4;     // the counters' grid (whole 4 x 16 tiles: FW)
+    [[maybe_unused]] auto ms_put64 = [&](int i, size_t v) { WS_[i] = (int)(unsigned)v, WS_[i + 1] = (int)(unsigned)(v >> 32); };   // one lane
+    // the step's view: what the producer reads and writes / where the consumer stores
+    [[maybe_unused]] auto view_in = [&]() {
+        a_step.x_in = reinterpret_cast<const float*>(ms_get64(MS_XIN));
+        a_step.pre_in = reinterpret_cast<const uint8_t*>(ms_get64(MS_PIN));
+        a_step.pre_out = reinterpret_cast<uint8_t*>(ms_get64(MS_POUT));
+        a_step.fire_words = reinterpret_cast<const unsigned long long*>(ms_get64(MS_FW));
+    };
+    // the next step of the launch: ring slots as cond_grow_fwd_impl's step_args chooses them (never the grow's step 0: a pre mask comes in)
+    [[maybe_unused]] auto next_step = [&]() {
+        const size_t slot = (size_t)a_launch.B * C * H * W * 4u, pslot = (size_t)a_launch.B * H * W;
+        const int ring = ms_get(MS_RING);
+        int ring_in = ms_get(MS_RIN) + 1;
+        if (ring_in == ring) ring_in = 0;
+        const size_t ring_out = ring_in + 1 == ring ? 0 : ring_in + 1;
+        const size_t x_in = ms_get64(MS_XOUT), pre_in = ms_get64(MS_POUT), fw = ms_get64(MS_FW) + (pslot >> 6) * sizeof(unsigned long long);
+        const size_t x_out = ms_get64(MS_STATES) + ring_out * slot, pre_out = ms_get64(MS_PRE) + ring_out * pslot;
+        if (lane == 0) {
+            WS_[MS_RIN] = ring_in;
+            ms_put64(MS_XIN, x_in), ms_put64(MS_PIN, pre_in), ms_put64(MS_XOUT, x_out), ms_put64(MS_POUT, pre_out), ms_put64(MS_FW, fw);
+        }
+        wave_sync();
+        a_step.x_out = reinterpret_cast<float*>(x_out);   // the consumer's only use of the view: kept in registers (the producer refills its view per tile)
+    };
+    // Producer gate of tile t for a step with `need` earlier steps in the grow: lanes 0..8 read the counters of the 3 x 3 tile
+    // neighbourhood (same batch item; the tile itself included), lane 9 (and a lane whose neighbour lies outside the image) the abort
+    // word.  The wait that makes this step's reads correct also makes its writes safe: the tile's output overwrites the ring slot its
+    // neighbours READ one step earlier (ring == 2; a longer ring only moves that slot further away), and they have published that
+    // step -- every load of it long retired -- before the tile is even staged.
+    constexpr int kGateSpins = 1 << 17;   // x (one L2 round trip + s_sleep 16): some 0.2 s, against waits of at most a few steps
+    [[maybe_unused]] auto gate = [&](const WTile& t, int step_no) {
+        const unsigned need = (unsigned)(ms_get(MS_T0) + step_no);
+        const int dy = (lane >= 3) + (lane >= 6) - 1, dx = lane - 3 * (dy + 1) - 1;
+        const int ny = (t.ty0 >> 2) + dy, nx = (t.tx0 >> 4) + dx;
+        const bool nb = lane < 9 && ny >= 0 && ny < tgh && nx >= 0 && nx < tgw;
+        const unsigned ntile = (unsigned)(a_launch.B * tgh * tgw);
+        gu32* const p = done + (nb ? (unsigned)((t.b * tgh + ny) * tgw + nx) : ntile);
+        for (int spins = 0;;) {
+            unsigned v = need;
+            if (lane < 10) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_ballot_w64(lane < 10 && !nb && v != 0u) != 0ull) break;   // some gate gave up: drain, no polling
+            if (__builtin_amdgcn_ballot_w64(nb && v < need) == 0ull) break;
+            if (++spins >= kGateSpins) {
+                // a neighbour never got there (a workgroup that is not resident): recorded like an expired hand-off (await), and
+                // told to every later gate of the launch through the abort word
+                if (lane == 0) {
+                    if (a_launch.err) __hip_atomic_fetch_or(a_launch.err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(done + ntile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                break;
+            }
+            __builtin_amdgcn_s_sleep(16);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // no instruction: keeps the tile's loads behind the poll
+    };
     // (A register-carried prefetch of the NEXT tile's loads was tried here and measured slower, 97 -> 102 us f32 and
     // 60 -> 64 us bf16: border tiles force waits inside the issue sequence, and the producer is off the critical path.)
     auto produce = [&](const WTile& t, int which) {
@@ -196,20 +291,36 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         TileRegs<CP, ST> R;
         const TileLds L = lds_of(which);
         if (t.inner) {
-            issue_loads<CP, true, true, 0, EXACT, ST, FW>(a, t, lane, R);
-            stage_tile<CP, false, EXACT, ST, true, FC, FW>(a, t, L, lane, R, tile_no);
+            issue_loads<CP, true, true, 0, EXACT, ST, FW, AUX>(a, t, lane, R);
+            stage_tile<CP, false, EXACT, ST, true, FC, FW, AUX>(a, t, L, lane, R, tile_no);
         } else {
-            issue_loads<CP, true, true, 1, EXACT, ST, FW>(a, t, lane, R);
-            stage_tile<CP, true, EXACT, ST, true, FC, FW>(a, t, L, lane, R, tile_no);
+            issue_loads<CP, true, true, 1, EXACT, ST, FW, AUX>(a, t, lane, R);
+            stage_tile<CP, true, EXACT, ST, true, FC, FW, AUX>(a, t, L, lane, R, tile_no);
         }
+        // MS: the tile's pre mask bytes are in memory before the hand-off, so that the consumer's publication covers them
+        if constexpr (MS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     MlpRegs<CP> Wr;        // exact-f32 operands (f32 storage)
     MlpRegsBf<CP> Wb;      // bf16 operands (bf16 storage)
     MlpRegsSplit<CP> Ws;   // bf16 hi/lo operand pairs (fp32 storage, ncahip_cond_precision(1))
     // CARRY: number of parked cells (wave-uniform) and the consumer's carry, on the W1 / W2 images (nothing without CARRY)
-    constexpr int kCarrySize = [] { if constexpr (CARRY) return FireCarry<CP>::SIZE; else return 0; }();
     [[maybe_unused]] int carry_n = 0;
     [[maybe_unused]] float* const CR = smem + pair * kCarrySize;
+    // MS, consumer: the counters of the pair's unpublished tiles of the current step wait in ONE register, a ring over the lanes:
+    // entry i (oldest first) in lane (head + i) mod 64, npend entries, of which the first `ready` are publishable -- every cell of
+    // theirs is stored or on its way.  They are published one tile late, behind that tile's full groups (publish in consume): the
+    // wave issues no loads, so the vmcnt(0) in front of the counter stores waits there for stores issued a tile's chain ago, i.e.
+    // for nothing.
+    [[maybe_unused]] int pend = 0, head = 0, npend = 0, ready = 0;
+    [[maybe_unused]] unsigned pub_val = 0u;   // the counter value of the current step: steps of the grow completed with it
+    [[maybe_unused]] auto publish = [&]() {
+        if (ready == 0) return;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every store of this wave so far has completed (write-through)
+        if (((lane - head) & 63) < ready) __hip_atomic_store(done + (unsigned)pend, pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        head = (head + ready) & 63;
+        npend -= ready;
+        ready = 0;
+    };
     // FC: ng full groups of 16 listed cells of tile L, two per pass and one for an odd last one.  Without the carry ng counts the
     // partial last group too: its padding entries (kFirePad) compute on a real cell and write XR's padding column.
     auto fire_groups = [&]([[maybe_unused]] const TileLds& L, [[maybe_unused]] int ng) {
@@ -250,6 +361,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                 q = nf >> 4;
                 rem = nf & 15;
                 fire_groups(L, q);   // the full groups, as without the carry
+                if constexpr (MS) publish();
             }
             // the lane's own places in the carry: derived here, from an opaque lane id, so that nothing of it is kept in
             // registers through the full groups above
@@ -322,6 +434,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                 store_carry<CP, EXACT, kNtStore>(a, CX, lane, old, *CPIX, *CBAT);
                 if (old && has) park_x();
                 carry_n = flush ? 0 : carry_n + rem - 16;
+                if constexpr (MS) ready = npend;   // what is parked now came from this tile: every listed tile (all older, or with the flush all) is complete
             }
             if (flush) return;
         } else if constexpr (FC) {
@@ -371,6 +484,19 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     int which = 0;
     Pos pos = pos_first();
     WTile cur = tile_of(pos);
+    // MS: a wave's boundary words (valid from the second barrier on), and the walk's first position back from them
+    [[maybe_unused]] auto ms_save = [&]() {
+        if (lane == 0) {
+            WS_[MS_R] = pos.r, WS_[MS_T] = pos.t, WS_[MS_SX] = pos.sx, WS_[MS_SY] = pos.sy, WS_[MS_B] = pos.b;
+            WS_[MS_NSTEPS] = a_launch.ms_steps, WS_[MS_T0] = a_launch.ms_t0, WS_[MS_RING] = a_launch.ms_ring;
+            WS_[MS_RIN] = a_launch.ms_t0 % a_launch.ms_ring;
+            ms_put64(MS_STATES, (uintptr_t)a_launch.ms_states), ms_put64(MS_PRE, (uintptr_t)a_launch.ms_pre);
+            ms_put64(MS_XIN, (uintptr_t)a_launch.x_in), ms_put64(MS_PIN, (uintptr_t)a_launch.pre_in), ms_put64(MS_XOUT, (uintptr_t)a_launch.x_out);
+            ms_put64(MS_POUT, (uintptr_t)a_launch.pre_out), ms_put64(MS_FW, (uintptr_t)a_launch.fire_words);
+        }
+        wave_sync();
+    };
+    [[maybe_unused]] auto ms_pos0 = [&]() -> Pos { return Pos{0, ms_get(MS_R), ms_get(MS_T), ms_get(MS_SX), ms_get(MS_SY), ms_get(MS_B)}; };
     // Hand-off between the two waves of a pair: two monotonic round counters in LDS instead of a workgroup barrier per
     // tile.  A workgroup barrier keeps the four pairs of a CU in lock-step, so their perception phases (LDS-bandwidth-bound)
     // and their stores all collide; with pair-local hand-offs the pairs drift apart.  LDS operations of one wave execute in
@@ -405,17 +531,35 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
         __syncthreads();              // weight image complete, counters initialised
         if constexpr (PK::WIDE || CARRY) __syncthreads();   // ... and moved into the consumers' registers: the second buffers (wide carve) / the carries may overwrite it
         NCA_KSTAMP(2);
-        while (pos.k + 1 < n_rounds) {
-            const Pos pn = advance(pos);
+        if constexpr (MS) ms_save();   // the first position is still in `pos`: the first tile was staged before the barriers
+        for (;;) {
+            Pos pn;
+            if (pos.k + 1 < n_rounds) {
+                pn = advance(pos);
+            } else {
+                if constexpr (!MS) {
+                    break;
+                } else {   // the first tile of the next step follows the last of this one
+                    if (step + 1 >= ms_get(MS_NSTEPS)) break;
+                    ++step;
+                    gbase += n_rounds;
+                    next_step();
+                    pn = ms_pos0();
+                }
+            }
             const WTile nxt = tile_of(pn);
             __builtin_amdgcn_s_setprio(0);
-            await(1, pn.k - 2);       // the consumer is done with the round that used this buffer
+            await(1, gbase + pn.k - 2);       // the consumer is done with the round that used this buffer
+            if constexpr (MS) {
+                if (step > 0 && nxt.valid) gate(nxt, step);   // the launch's first step reads what earlier launches wrote
+            }
             __builtin_amdgcn_s_setprio(3);
 #ifdef NCA_STAMPS
             if (a.seed != 0xD1A6ull && (a.seed < 0xD1AAull || a.seed > 0xD1ADull))  // diagnostic knob (stamps build only): idle producers
 #endif
+            if constexpr (MS) view_in();
             produce(nxt, which ^ 1);
-            post(0, pn.k);
+            post(0, gbase + pn.k);
             cur = nxt;
             pos = pn;
             which ^= 1;
@@ -434,35 +578,68 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
             __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the image reads have landed
             __syncthreads();
         }
-        while (pos.k < n_rounds) {
-            const Pos pn = advance(pos);
-            const WTile nxt = tile_of(pn);
-            await(0, pos.k);          // this round's tile has been staged
-            if (tile_no == 2) NCA_KSTAMP(4);            // light stamps around one steady-state tile
-#ifdef NCA_STAMPS
-            if (a.seed != 0xD1A7ull)  // diagnostic knob: idle consumers
-#endif
-            consume(cur, which, false);
-            if (tile_no == 2) NCA_KSTAMP(5);
-            post(1, pos.k);
-            if (tile_no == 2) NCA_KSTAMP(6);
-            if (tile_no == 3) NCA_KSTAMP(7);
-            cur = nxt;
-            pos = pn;
-            which ^= 1;
-            ++tile_no;
+        if constexpr (MS) {
+            ms_save();
+            pub_val = (unsigned)a_launch.ms_t0 + 1u;
         }
-        if constexpr (CARRY) {
-            if (carry_n > 0) consume(cur, which, true);
+        for (;;) {
+            while (pos.k < n_rounds) {
+                const Pos pn = advance(pos);
+                const WTile nxt = tile_of(pn);
+                await(0, gbase + pos.k);  // this round's tile has been staged
+                if (tile_no == 2) NCA_KSTAMP(4);            // light stamps around one steady-state tile
+#ifdef NCA_STAMPS
+                if (a.seed != 0xD1A7ull)  // diagnostic knob: idle consumers
+#endif
+                consume(cur, which, false);
+                if (tile_no == 2) NCA_KSTAMP(5);
+                post(1, gbase + pos.k);
+                if constexpr (MS) {
+                    if (cur.valid) {
+                        if (lane == ((head + npend) & 63)) pend = (cur.b * tgh + (cur.ty0 >> 2)) * tgw + (cur.tx0 >> 4);
+                        ++npend;
+                        if (carry_n == 0) ready = npend;   // nothing parked: every tile so far is complete
+                        // every lane holds a tile and cells are still parked (no carry group for 64 tiles: hardly any cell fires): run the padded
+                        // group now, as at the end of a step -- the same bits for every cell -- and publish
+                        if (npend == kMsList && ready < npend) {
+                            consume(cur, which, true);
+                            publish();
+                        }
+                    }
+                }
+                if (tile_no == 2) NCA_KSTAMP(6);
+                if (tile_no == 3) NCA_KSTAMP(7);
+                cur = nxt;
+                pos = pn;
+                which ^= 1;
+                ++tile_no;
+            }
+            if constexpr (CARRY) {
+                if (carry_n > 0) consume(cur, which, true);
+            }
+            if constexpr (!MS) {
+                break;
+            } else {
+                // the step is complete for this pair: publish what is left NOW (the gates of the next step's first tiles, this pair's
+                // own producer's among them, may be waiting for exactly these), then walk the same tiles again
+                ready = npend;
+                publish();
+                if (++step >= ms_get(MS_NSTEPS)) break;
+                gbase += n_rounds;
+                ++pub_val;
+                next_step();
+                pos = ms_pos0();
+                cur = tile_of(pos);
+            }
         }
         NCA_KSTAMP(3);
     }
 }
 
-template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false>
+template <int CP, bool EXACT, typename ST = StF32, bool SPLIT = false, bool FC = false, bool CARRY = false, bool FW = false, bool MS = false>
 hipError_t launch_cond_pc(const NcaCondArgs& a, hipStream_t st) {
     using PK = PCfg<CP>;
-    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC, CARRY, FW>;
+    auto kern = cond_step_fwd_pc_kernel<CP, EXACT, ST, SPLIT, FC, CARRY, FW, MS>;
     const size_t lds = (size_t)PK::LDS_FLOATS * sizeof(float);
     static NcaLdsAttr attr;   // per instantiation; keyed by device inside
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
@@ -521,6 +698,35 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) 
     if (a.C == 20 && h64) return launch_cond_pc_f32<20, true>(a, st);
     if (a.C <= 20) return launch_cond_pc_f32<20, false>(a, st);
     return hipErrorInvalidValue;
+}
+
+// Several steps of a grow in one launch (a.ms_steps >= 1 and the ms_* fields set, a.fire_words the words of the launch's first step):
+// the MS twins of the narrow-carve kernels that read fire words.  The caller asks nca_cond_pc_fused_steps_ok first.
+bool nca_cond_pc_fused_steps_ok(const NcaCondArgs& a) {
+    if (nca_modes().pc_no_fused_steps || a.C > 16 || a.fire_words == nullptr || !nca_cond_pc_fire_words_ok(a)) return false;
+    // At least two rounds per workgroup, as launch_cond_pc sizes the grid: with one, a pair's next tile is its own last one and
+    // nothing overlaps the gate.  And at most kFusedMaxRounds: the fused launch saves about half of a step's fixed cost and pays
+    // 8 - 10 % more per round (profiles/r9a_fixed_cost_fit.txt, B x 16 x 256^2 on 256 CUs: F 17.4 -> 9.2 us, v 7.18 -> 7.76 us per
+    // round), which is -7 % per step at 4 rounds, -5 % at 8, even at 16 and +4.5 % at 32; the line through those crosses at 15.
+    // A set fire-word chunk cap (test hook) waives the upper bound, as it waives the minimum grow length.
+    constexpr long kFusedMaxRounds = 12;
+    const long nst = (long)a.B * ((a.W + 15) / 16) * ((a.H + 15) / 16);
+    long nwg = nst < nca_cu_count() ? nst : nca_cu_count();
+    if (const int cap = nca_modes().pc_wg_cap; cap > 0 && nwg > cap) nwg = cap;
+    const long rounds = (nst + nwg - 1) / nwg;
+    return rounds >= 2 && (rounds <= kFusedMaxRounds || nca_modes().fire_words_cap > 0);
+}
+hipError_t nca_launch_cond_steps_fwd_pc(const NcaCondArgs& a_in, hipStream_t st) {
+    if (a_in.ms_steps < 1 || a_in.ms_ring < 2 || !a_in.ms_states || !a_in.ms_pre || !a_in.ms_done || !nca_cond_pc_fused_steps_ok(a_in))
+        return hipErrorInvalidValue;
+    NcaCondArgs a = a_in;
+    a.dbg = g_stamp_pc;
+    a.err = nca_error_word_device();
+    const bool h64 = a.hidden == 64;
+    if (a.C == 12 && h64) return launch_cond_pc<12, true, StF32, false, true, true, true, true>(a, st);
+    if (a.C == 16 && h64) return launch_cond_pc<16, true, StF32, false, true, true, true, true>(a, st);
+    if (a.C <= 12) return launch_cond_pc<12, false, StF32, false, true, true, true, true>(a, st);
+    return launch_cond_pc<16, false, StF32, false, true, true, true, true>(a, st);
 }
 
 // bf16 state / goal behind the float-typed pointers of NcaCondArgs.  Caller (nca_capi.hip) guarantees W % 4 == 0, 8-byte

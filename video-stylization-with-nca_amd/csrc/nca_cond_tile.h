@@ -263,15 +263,17 @@ struct TileRegs {
 // Addressing: raw buffer loads -- <buffer resource of the batch item (SGPRs)> + <32-bit VGPR byte offset shared by a
 // whole group of loads> + <uniform SGPR offset that steps through channels / rows>: no per-load vector arithmetic at all
 // on interior tiles.  Needs H*W < 2^24 and C*H*W*4 < 2^32 (checked by the dispatch in nca_cond_generic.hip; larger grids
-// take the generic kernel).  kAuxCoherent selects the cache policy of the state-type loads (x, pre mask): 0 = ordinary
-// cached loads (a step launch reads only what earlier launches wrote); 16 = sc1, agent-scope coherent -- what a fused
-// multi-step launch with grid barriers needs (tried and measured slower: DESIGN.md section 4).
+// take the generic kernel).  AUX selects the cache policy of the state-type loads (x, alpha', pre mask) and of stage_tile's
+// pre mask store: kAuxCoherent = 0 = ordinary cached accesses (a step launch reads only what earlier launches wrote);
+// 16 = sc1, agent-scope coherent -- what the multi-step launch (nca_cond_pc.hip, MS) passes: there a tile of step t + 1
+// reads what other workgroups stored during the same launch.  Goal, weights and fire words are written by nobody during a
+// launch and stay ordinary loads.
 // FW: the tile's fire mask comes as one 64-bit word drawn before the launch (a.fire_words, nca_cond_fire.hip; the caller guarantees
 // W % 16 == 0 and H % 4 == 0, so every valid tile is whole and aligned to the words' grid): the word is requested here, through the
 // constant address space -- the address is wave-uniform, so it is one scalar load -- and neither the uniform load nor the Philox
 // block is compiled in.
 constexpr int kAuxCoherent = 0;
-template <int CP, bool STATE, bool GOAL, int CHK = -1, bool EXACT = false, typename ST = StF32, bool FW = false>
+template <int CP, bool STATE, bool GOAL, int CHK = -1, bool EXACT = false, typename ST = StF32, bool FW = false, int AUX = kAuxCoherent>
 __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t, int lane_in, TileRegs<CP, ST>& R) {
     constexpr unsigned SB = ST::BYTES;   // "4" in the names below = one storage element
     const int C = EXACT ? CP : a.C, H = a.H, W = a.W;
@@ -294,13 +296,13 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
         if (!chk) {   // interior: one lane offset (columns >= 22 re-read column 21), rows step through the SGPR offset
             const unsigned vo = (unsigned)(__mul24(t.ty0 - 3 + hl, W) + t.tx0 - 3 + min(l5, 21)) * SB;
 #pragma unroll
-            for (int k = 0; k < 5; ++k) R.a3v[k] = ST::template ld1<kAuxCoherent>(ra, vo, 2u * k * W4);
+            for (int k = 0; k < 5; ++k) R.a3v[k] = ST::template ld1<AUX>(ra, vo, 2u * k * W4);
         } else {
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
                 const int gy = t.ty0 - 3 + 2 * k + hl, gx = t.tx0 - 3 + l5;
                 const bool ok = l5 < 22 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                R.a3v[k] = ST::template ld1<kAuxCoherent>(ra, ok ? (unsigned)(__mul24(gy, W) + gx) * SB : 0u, 0u);
+                R.a3v[k] = ST::template ld1<AUX>(ra, ok ? (unsigned)(__mul24(gy, W) + gx) * SB : 0u, 0u);
             }
         }
     }
@@ -310,13 +312,13 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
         if (!chk) {
             const unsigned vo = (unsigned)(__mul24(t.ty0 - 2 + hl, W) + t.tx0 - 2 + min(l5, 19));
 #pragma unroll
-            for (int k = 0; k < 4; ++k) R.prv[k] = __builtin_amdgcn_raw_buffer_load_b8(rp, (int)vo, (int)(2u * k * (unsigned)W), kAuxCoherent);
+            for (int k = 0; k < 4; ++k) R.prv[k] = __builtin_amdgcn_raw_buffer_load_b8(rp, (int)vo, (int)(2u * k * (unsigned)W), AUX);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int gy = t.ty0 - 2 + 2 * k + hl, gx = t.tx0 - 2 + l5;
                 const bool ok = l5 < 20 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                R.prv[k] = __builtin_amdgcn_raw_buffer_load_b8(rp, ok ? __mul24(gy, W) + gx : 0, 0, kAuxCoherent);
+                R.prv[k] = __builtin_amdgcn_raw_buffer_load_b8(rp, ok ? __mul24(gy, W) + gx : 0, 0, AUX);
             }
         }
     }
@@ -343,8 +345,8 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
         if (STATE) {
 #pragma unroll
             for (int k = 0; k < CP / 2; ++k) {
-                if (EXACT) R.xf[k] = ST::template ld4<kAuxCoherent>(rx, vox, 2u * k * plane4);
-                else R.xf[k] = ST::template ld4<kAuxCoherent>(rx, pix4 + nca_mul_u32((unsigned)min(2 * k + hl, C - 1), plane4), 0u);
+                if (EXACT) R.xf[k] = ST::template ld4<AUX>(rx, vox, 2u * k * plane4);
+                else R.xf[k] = ST::template ld4<AUX>(rx, pix4 + nca_mul_u32((unsigned)min(2 * k + hl, C - 1), plane4), 0u);
             }
         }
         if (GOAL && has_goal) {
@@ -366,8 +368,8 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
         if (STATE) {
 #pragma unroll
             for (int k = 0; k < CP / 4; ++k) {
-                if (EXACT) R.xh[k] = ST::template ld1<kAuxCoherent>(rx, voh, 4u * k * plane4);
-                else R.xh[k] = ST::template ld1<kAuxCoherent>(rx, pix4 + nca_mul_u32((unsigned)min(4 * k + q4, C - 1), plane4), 0u);
+                if (EXACT) R.xh[k] = ST::template ld1<AUX>(rx, voh, 4u * k * plane4);
+                else R.xh[k] = ST::template ld1<AUX>(rx, pix4 + nca_mul_u32((unsigned)min(4 * k + q4, C - 1), plane4), 0u);
             }
         }
         if (GOAL && has_goal) {
@@ -387,7 +389,7 @@ __device__ __forceinline__ void issue_loads(const NcaCondArgs& a, const WTile& t
 // want z, the masks and the fire mask: the backward's front kernel).
 // FCL: instead of the fire mask MK, write the firing-cell list (see kFirePad) into MK and its length into *NF.
 // FW (with FCL): the ballot of the tile's firing cells is R.fw (issue_loads FW) -- no uniform, no compare, no ballot here.
-template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true, bool FCL = false, bool FW = false>
+template <int CP, bool CHECK, bool EXACT = false, typename ST = StF32, bool KEEPX = true, bool FCL = false, bool FW = false, int AUX = kAuxCoherent>
 __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t, const TileLds& L, int lane_in,
                                            const TileRegs<CP, ST>& R, int tile_no) {
     float* const Z = L.Z;
@@ -496,7 +498,7 @@ __device__ __forceinline__ void stage_tile(const NcaCondArgs& a, const WTile& t,
         wave_sync();
         if (cin && a.pre_out)
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)PN[(q4 + 1) * RS + ci + 4], nca_rsrc(a.pre_out + (size_t)t.b * plane),
-                                                 __mul24(cgy, W) + cgx, 0, kAuxCoherent);
+                                                 __mul24(cgy, W) + cgx, 0, AUX);
     }
     NCA_STAMP(11);
     // ---- S4: z = x + goal * pre (nca.py:177) on halo 1; resolved state kept for the residual -----

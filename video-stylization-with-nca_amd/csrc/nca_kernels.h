@@ -155,13 +155,30 @@ struct NcaCondArgs {
     // draws them.  Needs u == null, W % 16 == 0, H % 4 == 0; read by the kernels nca_cond_fire_words_ok names, ignored by every
     // other one (which then draws the same masks itself)
     const unsigned long long* fire_words;
+    // Several steps of a grow in one launch (nca_cond_pc.hip, the MS kernels; ms_steps == 0: an ordinary one-step launch, nothing
+    // below is read).  The launch runs steps ms_t0 .. ms_t0 + ms_steps - 1 of the grow (ms_t0 = steps the grow made before it); step t
+    // reads ring slot t % ms_ring and writes slot (t + 1) % ms_ring of ms_states / ms_pre, takes no pre mask at t == 0, and reads
+    // fire_words + (t - ms_t0) * (B*H*W / 64).  x_in / pre_in / x_out / pre_out describe the launch's first step as for a one-step launch.
+    // ms_done: one counter per 4 x 16 tile, [B][H/4][W/16] = steps of this grow completed for the tile (zero before the grow's first
+    // step), and behind them, at ms_done[B * H/4 * W/16], the abort word (zero likewise): set by a gate whose poll expired
+    int ms_steps, ms_t0, ms_ring;
+    char* ms_states;
+    uint8_t* ms_pre;
+    unsigned* ms_done;
 };
+// the fused-steps launch (several steps of a grow per launch) exists for `a`: narrow carve, the kernels that read fire words, at least
+// two rounds per workgroup, not switched off (nca_modes.h pc_no_fused_steps)
+bool nca_cond_pc_fused_steps_ok(const NcaCondArgs& a);
+hipError_t nca_launch_cond_steps_fwd_pc(const NcaCondArgs& a, hipStream_t st);   // hipErrorInvalidValue where the question above says no
+// bytes of ms_done (counters + abort word, padded to 64) for a grid
+inline size_t nca_cond_ms_done_bytes(int B, int H, int W) { return (((size_t)B * (H / 4) * (W / 16) + 1) * 4 + 63) & ~(size_t)63; }
 // the launch nca_launch_cond_step_fwd makes for `a` runs a kernel that reads a.fire_words (shape, alignment -- of a.fire_words too: 8 bytes --, test hooks)
 bool nca_cond_fire_words_ok(const NcaCondArgs& a);
 bool nca_cond_pc_fire_words_ok(const NcaCondArgs& a);   // the same question inside the producer/consumer family (nca_cond_pc.hip)
 // fire words of steps step0 .. step0 + Tc - 1, [Tc][B][H/4][W/16] (nca_cond_fire.hip)
+// done_zero: null, or the fused-steps path's per-tile step counters and abort word (NcaCondArgs::ms_done), which the launch zeroes too
 hipError_t nca_launch_cond_fire_words(unsigned long long* words, int Tc, int B, int H, int W, float fire_rate, uint64_t seed, uint64_t step0,
-                                      hipStream_t st);
+                                      hipStream_t st, unsigned* done_zero = nullptr);
 
 // One backward step of the ConditionedNCA grow loop (nca_cond_bwd.hip).  f describes forward step t exactly as
 // it was launched (x_in = states[t], pre_in = pre[t] or null for t == 0, goal, u / seed+step, weights).

@@ -26,6 +26,8 @@ struct NcaModes {
     NcaMode<bool> no_fire_words;   // a grow's steps draw their fire masks themselves                                             hook bit 7
     NcaMode<int> pc_wg_cap;        // at most this many workgroups per producer/consumer step launch (0: no cap)                  hook bits 8-15
     NcaMode<int> fire_words_cap;   // at most this many steps per fire-word launch; set, it also waives the minimum grow length   hook bits 16-23
+    NcaMode<bool> pc_no_fused_steps;   // a grow's steps go out one launch each, also where a fused-steps launch exists               hook bit 24
+    NcaMode<int> fused_steps_cap;  // at most this many steps per fused-steps launch (0: a fire-word chunk's steps in one launch)     hook bits 25-27
     NcaMode<int> cond_precision;   // 0 = exact-f32 MFMA (default), 1 = bf16x3 emulation in the producer/consumer kernel          ncahip_cond_precision
     // ConditionedNCA backward (nca_cond_bwd.hip, nca_cond_bwd_fm.hip)
     NcaMode<bool> bwd_bf16_exact;  // bf16-history backward with exact-f32 products instead of bf16 MFMA   NCAHIP_BWD_BF16_EXACT at load / hook bit 2

@@ -66,5 +66,7 @@ extern "C" int ncahip_debug_force_generic(int on) {
     m.no_fire_words = (on & 128) != 0;      // bit 7: ncahip_cond_grow_fwd_f32's steps draw their fire masks themselves
     m.pc_wg_cap = (on >> 8) & 255;          // bits 8-15: at most this many workgroups per producer/consumer step launch (0: no cap)
     m.fire_words_cap = (on >> 16) & 255;    // bits 16-23: at most this many steps per fire-word launch (0: no cap); waives the minimum grow length
+    m.pc_no_fused_steps = (on & (1 << 24)) != 0;   // bit 24: one launch per step, also where ncahip_cond_grow_fwd_f32 would fuse a chunk's steps
+    m.fused_steps_cap = (on >> 25) & 7;     // bits 25-27: at most this many steps per fused-steps launch (0: no cap)
     return 0;
 }

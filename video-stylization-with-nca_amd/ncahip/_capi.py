@@ -50,6 +50,8 @@ SIGNATURES = {
     "ncahip_philox_uniform_f32": [_P, _I, _I, _I, _U64, _U64, _P],
     "ncahip_cond_fire_words": [_P, _I, _I, _I, _I, _F, _U64, _U64, _P],
     "ncahip_debug_fire_word_launches": [],
+    "ncahip_debug_fused_step_launches": [],
+    "ncahip_cond_fused_steps_layout": [_I, _I, _I, _I, _I, _P, _P, _P],
     "ncahip_pack_fire_mask_u32": [_P, _P, _I, _I, _I, _I, _F, _I, _P],
     "ncahip_dynca_step_bwd_w2_workspace": [_I, _I, _I, _I, _I],
     "ncahip_dynca_step_bwd_w2_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P, _P, _P, _P, _I, _P,

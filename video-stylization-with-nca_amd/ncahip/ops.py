@@ -86,11 +86,17 @@ def _w(t: torch.Tensor, name: str, like: torch.Tensor) -> torch.Tensor:
     return _dev(t.float(), name)
 
 
+NO_FUSED_STEPS = 1 << 24        # force_generic bit: the off switch of cond_grow's fused-steps launches
+FUSED_STEPS_CAP_SHIFT = 25      # force_generic bits 25-27: steps per fused-steps launch
+
+
 def force_generic(on) -> None:
     """Test hook (see ncahip.h; the bits are decoded in csrc/nca_modes.hip): True/1 = generic any-shape kernels, 2 = symmetric wave-private ConditionedNCA
     kernel, 32 = fp32 producer/consumer step without firing-cell lists, 64 = firing-cell lists without the carry across
     tiles, 128 = cond_grow's steps draw their fire masks in the kernel (no fire words), n << 8 = at most n workgroups per
-    producer/consumer step launch, n << 16 = at most n steps per fire-word launch (and no minimum grow length or grid size), False/0 = defaults."""
+    producer/consumer step launch, n << 16 = at most n steps per fire-word launch (and no minimum grow length or grid size),
+    NO_FUSED_STEPS (1 << 24) = cond_grow's steps go out one launch each (no fused-steps launches), n << 25 (n <= 7) = at most n steps
+    per fused-steps launch, False/0 = defaults."""
     lib().ncahip_debug_force_generic(int(on))
 
 
@@ -182,7 +188,8 @@ def dynca_direction(dirs: torch.Tensor):
 
 
 def reset_modes() -> None:
-    """Every process-wide mode back to what a fresh process without environment overrides has: force_generic(0), cond precision
+    """Every process-wide mode back to what a fresh process without environment overrides has: force_generic(0) (every hook bit, the
+    fused-steps off switch and its cap included), cond precision
     'exact', DyNCA precision 'f32' (its bf16 range narrow), no direction field attached, no dropped tiles, persistent_steps = True, persistent_cond = False.
     Needs no GPU.  Takes the locks of dynca_precision and dynca_direction; it must not be called inside a block of either (the block
     would put its previous mode back on exit)."""
@@ -339,6 +346,11 @@ def cond_fire_words(Tc: int, B: int, H: int, W: int, fire_rate: float, seed: int
 def fire_word_launches() -> int:
     """Test hook: fire-word launches of the last cond_grow on the per-step fp32 kernels (0: its steps drew in the kernel)."""
     return int(lib().ncahip_debug_fire_word_launches())
+
+
+def fused_step_launches() -> int:
+    """Test hook: fused-steps launches (several steps per launch) of the last cond_grow on the fp32 kernels (0: one launch per step)."""
+    return int(lib().ncahip_debug_fused_step_launches())
 
 
 # ------------------------------------------------------------------------------------ DyNCA
