@@ -4,7 +4,7 @@ has no CPU fallback (the CPU restatement lives in oracle/ and is test infrastruc
 import contextlib
 import re
 import threading
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -458,15 +458,19 @@ def _clip_fmt(dtype) -> int:
     raise TypeError(f"ncahip: clip frames / images are float32 (channels first) or uint8 (channels last), got {dtype}")
 
 
+def _frames_dims(frames: torch.Tensor):
+    """(fmt, F, B, c, H, W) of clip frames: [F,B,c,H,W] float32 or [F,B,H,W,c] uint8."""
+    fmt = _clip_fmt(frames.dtype)
+    s = tuple(frames.shape)
+    F_, B, c, H, W = s[:2] + s[4:] + s[2:4] if fmt == _capi.CLIP_U8_NHWC else s
+    return fmt, F_, B, c, H, W
+
+
 def clip_cond(frames: torch.Tensor, k3: torch.Tensor, gray="mean", apply_tanh: bool = True) -> torch.Tensor:
     """frames [F,B,3,H,W] float32 in [-1, 1] or [F,B,H,W,3] uint8 -> cond [F,B,3,H,W] = EdgeExtractor(grey(frame)) in one launch
     (ncahip_clip_cond).  gray: 'mean', 'luma' or three weights; k3: the EdgeExtractor's three 3 x 3 filters."""
-    fmt = _clip_fmt(frames.dtype)
+    fmt, F_, B, three, H, W = _frames_dims(frames)
     frames = _dev(frames, "frames", frames.dtype)
-    if fmt == _capi.CLIP_U8_NHWC:
-        F_, B, H, W, three = frames.shape
-    else:
-        F_, B, three, H, W = frames.shape
     assert three == 3, tuple(frames.shape)
     wr, wg, wb = GRAY_WEIGHTS[gray] if isinstance(gray, str) else gray
     k3 = _w(k3.reshape(-1), "k3", frames)
@@ -480,40 +484,60 @@ def clip_cond(frames: torch.Tensor, k3: torch.Tensor, gray="mean", apply_tanh: b
 OUT_FORMATS = ("rgb24", "i420", "nv12")
 
 
-def _clip_img_fmt(out_dtype, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited", c_out: int = 3, H: int = 2,
-                  W: int = 2) -> int:
-    """The image format word of the clip entry points: _clip_fmt(out_dtype) for 'rgb24' (as before), NCAHIP_CLIP_YUV420(...) for the planar
-    formats 'i420' / 'nv12', which need out_dtype=torch.uint8, c_out == 3 and even H, W (ValueError before anything runs)."""
-    if out_format not in OUT_FORMATS:
-        raise ValueError(f"out_format must be one of {OUT_FORMATS}, got {out_format!r}")
-    if out_format == "rgb24":
-        return _clip_fmt(out_dtype)
-    rgb_yuv_coeffs(yuv_matrix, yuv_range)
-    if out_dtype != torch.uint8:
-        raise ValueError(f"out_format={out_format!r} needs out_dtype=torch.uint8 (planar YUV images are bytes), got {out_dtype}")
-    if c_out != 3:
-        raise ValueError(f"out_format={out_format!r} needs an RGB image (c_out == 3), got c_out = {c_out}")
-    if H % 2 or W % 2:
-        raise ValueError(f"out_format={out_format!r} needs even H and W (4:2:0), got {H} x {W}")
-    return _capi.clip_yuv420(_capi.YUV_LAYOUTS[out_format], _capi.YUV_MATRICES[yuv_matrix], _capi.YUV_RANGES[yuv_range])
+class ImageSpec(NamedTuple):
+    """The images of a clip call, built and validated by ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W) before
+    anything runs: 'rgb24' is float32 [.., c_out, H, W] or uint8 [.., H, W, c_out]; the planar formats 'i420' / 'nv12' are uint8
+    [.., 3H/2, W] and need out_dtype=torch.uint8, c_out == 3 and even H, W (ValueError).  fmt: the image format word of the C entry points
+    (_clip_fmt(out_dtype), or NCAHIP_CLIP_YUV420(...)); shape: one sample's image -- a driver's images are [n, B, *shape]."""
+    out_dtype: torch.dtype
+    out_format: str
+    yuv_matrix: str
+    yuv_range: str
+    c_out: int
+    H: int
+    W: int
+    fmt: int
+    shape: tuple
+    planar: bool
+
+    @classmethod
+    def of(cls, out_dtype, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited", c_out: int = 3, H: int = 2, W: int = 2):
+        if out_format not in OUT_FORMATS:
+            raise ValueError(f"out_format must be one of {OUT_FORMATS}, got {out_format!r}")
+        if out_format == "rgb24":
+            fmt = _clip_fmt(out_dtype)
+            shape = (H, W, c_out) if fmt == _capi.CLIP_U8_NHWC else (c_out, H, W)
+        else:
+            rgb_yuv_coeffs(yuv_matrix, yuv_range)
+            if out_dtype != torch.uint8:
+                raise ValueError(f"out_format={out_format!r} needs out_dtype=torch.uint8 (planar YUV images are bytes), got {out_dtype}")
+            if c_out != 3:
+                raise ValueError(f"out_format={out_format!r} needs an RGB image (c_out == 3), got c_out = {c_out}")
+            if H % 2 or W % 2:
+                raise ValueError(f"out_format={out_format!r} needs even H and W (4:2:0), got {H} x {W}")
+            fmt = _capi.clip_yuv420(_capi.YUV_LAYOUTS[out_format], _capi.YUV_MATRICES[yuv_matrix], _capi.YUV_RANGES[yuv_range])
+            shape = (3 * H // 2, W)
+        return cls(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W, fmt, shape, out_format != "rgb24")
+
+    @property
+    def keywords(self) -> dict:
+        """The spec as the keywords of the clip drivers and the emit wrappers."""
+        return {"out_dtype": self.out_dtype, "out_format": self.out_format, "yuv_matrix": self.yuv_matrix, "yuv_range": self.yuv_range}
+
+    def images(self, n: int, B: int, device, into: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The images tensor [n, B, *shape] of a clip driver: a new one, or the caller's `into` after checking that it is what a new one
+        would be."""
+        want = (n, B) + self.shape
+        if into is None:
+            return torch.empty(want, device=device, dtype=self.out_dtype)
+        if into.is_cuda and into.dtype == self.out_dtype and tuple(into.shape) == want and into.is_contiguous():
+            return into
+        raise ValueError(f"images must be a contiguous {self.out_dtype} device tensor {want}, got {tuple(into.shape)} {into.dtype}")
 
 
-def _clip_images(n: int, B: int, c_out: int, H: int, W: int, out_dtype, device, fmt: Optional[int] = None) -> torch.Tensor:
-    if fmt is not None and fmt >= 0x100:
-        return torch.empty(n, B, 3 * H // 2, W, device=device, dtype=torch.uint8)
-    if _clip_fmt(out_dtype) == _capi.CLIP_U8_NHWC:
-        return torch.empty(n, B, H, W, c_out, device=device, dtype=torch.uint8)
-    return torch.empty(n, B, c_out, H, W, device=device, dtype=torch.float32)
-
-
-def _clip_images_into(images: Optional[torch.Tensor], n: int, B: int, c_out: int, H: int, W: int, out_dtype, device, fmt: int) -> torch.Tensor:
-    """The images tensor of a clip driver: a new one, or the caller's after checking that it is what a new one would be."""
-    if images is None:
-        return _clip_images(n, B, c_out, H, W, out_dtype, device, fmt)
-    want = _clip_images(0, B, c_out, H, W, out_dtype, device, fmt)
-    if not images.is_cuda or images.dtype != want.dtype or tuple(images.shape) != (n,) + tuple(want.shape[1:]) or not images.is_contiguous():
-        raise ValueError(f"images must be a contiguous {want.dtype} device tensor {(n,) + tuple(want.shape[1:])}, got {tuple(images.shape)} {images.dtype}")
-    return images
+def _clip_img_fmt(out_dtype, *spec) -> int:
+    """The format word of ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)."""
+    return ImageSpec.of(out_dtype, *spec).fmt
 
 
 def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709",
@@ -523,10 +547,30 @@ def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32, out_form
     the state -- bit for bit rgb_to_yuv420 of the uint8 image."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
-    img = _clip_images(1, B, c_out, H, W, out_dtype, x.device, fmt)[0]
-    check(lib().ncahip_clip_emit(_p(x), _p(img), fmt, B, C, c_out, H, W, _stream()), "clip_emit")
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    img = spec.images(1, B, x.device)[0]
+    check(lib().ncahip_clip_emit(_p(x), _p(img), spec.fmt, B, C, c_out, H, W, _stream()), "clip_emit")
     return img
+
+
+def _clip_persist(nbytes: int, calls: int, device, while_capturing: bool = True):
+    """(ws, nbytes or 0, epoch) of a clip driver's persistent launches: `calls` consecutive epochs of the workspace of `nbytes` bytes
+    (0: the persistent kernel is switched off or does not cover the shape), or no workspace."""
+    if nbytes and calls < (1 << 20) - 2 and (while_capturing or not torch.cuda.is_current_stream_capturing()):
+        ws, epoch = _persist_workspace(nbytes, device, count=calls)
+        return ws, nbytes, epoch
+    return None, 0, 0
+
+
+def _dynca_clip_buffers(x: torch.Tensor, C: int, calls: int, step_n: int, us, seed: int, two_scale: bool, spec: ImageSpec, images):
+    """What the two DyNCA clip drivers set up alike: (states, pc, us, seed, images) -- the ring of two state slots with x in the first (x
+    may lack the last of the C channels), the coarse scratch of the fused two-scale step, _u_args for all steps and spec.images."""
+    B, cx, H, W = x.shape
+    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
+    states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
+    states[0, :, :cx].copy_(x)
+    pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
+    return states, pc, us, seed, spec.images(calls, B, x.device, images)
 
 
 def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], w: DyncaWeights, steps_per_frame: int, step_n: int,
@@ -540,37 +584,25 @@ def dynca_clip(x: torch.Tensor, cond: torch.Tensor, us: Optional[torch.Tensor], 
     shape and dtype to write into instead of a new one (what a caller that stages downloads hands in)."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
     cond = _dev(cond, "cond")
     F_ = cond.shape[0]
     assert cond.shape == (F_, B, 3, H, W), (tuple(cond.shape), tuple(x.shape))
-    calls = F_ * steps_per_frame
-    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
     assert w.c == C and w.k1 == 4 * C + 3, (w.c, w.k1, C)
-    states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
-    states[0].copy_(x)
-    images = _clip_images_into(images, calls, B, c_out, H, W, out_dtype, x.device, fmt)
-    pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
-    ws, nbytes, epoch = None, 0, 0
-    if persistent_steps:
-        nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, 3)
-        if nbytes and calls < (1 << 20) - 2:
-            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_dynca_clip_f32(_p(states), _p(cond), _p(images), fmt, F_, steps_per_frame, step_n, _p(us), _p(w.w1),
+    calls = F_ * steps_per_frame
+    states, pc, us, seed, images = _dynca_clip_buffers(x, C, calls, step_n, us, seed, two_scale, spec, images)
+    ws, nbytes, epoch = _clip_persist(lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, 3) if persistent_steps else 0, calls, x.device)
+    check(lib().ncahip_dynca_clip_f32(_p(states), _p(cond), _p(images), spec.fmt, F_, steps_per_frame, step_n, _p(us), _p(w.w1),
                                       _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode], int(two_scale), update_rate,
-                                      seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "dynca_clip")
+                                      seed, step0, _p(pc), _p(ws), nbytes, epoch, _stream()), "dynca_clip")
     return images, states[0]
 
 
 def clip_gray(frames: torch.Tensor, gray="mean") -> torch.Tensor:
     """frames [F,B,3,H,W] float32 in [-1, 1] or [F,B,H,W,3] uint8 -> grey [F,B,H,W] float32 in one launch (ncahip_clip_gray): what the
     extra-channel models take as their last state channel.  gray: 'mean', 'luma' or three weights."""
-    fmt = _clip_fmt(frames.dtype)
+    fmt, F_, B, three, H, W = _frames_dims(frames)
     frames = _dev(frames, "frames", frames.dtype)
-    if fmt == _capi.CLIP_U8_NHWC:
-        F_, B, H, W, three = frames.shape
-    else:
-        F_, B, three, H, W = frames.shape
     assert three == 3, tuple(frames.shape)
     wr, wg, wb = GRAY_WEIGHTS[gray] if isinstance(gray, str) else gray
     out = torch.empty(F_, B, H, W, device=frames.device, dtype=torch.float32)
@@ -588,9 +620,9 @@ def clip_emit_inject(state: torch.Tensor, c_out: int = 3, gray_plane: Optional[t
     if gray_plane is not None:
         gray_plane = _dev(gray_plane, "gray_plane")
         assert gray_plane.numel() == B * H * W, (tuple(gray_plane.shape), tuple(state.shape))
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
-    img = _clip_images(1, B, c_out, H, W, out_dtype, state.device, fmt)[0] if emit else None
-    check(lib().ncahip_clip_emit_inject(_p(state), _p(img), fmt, _p(gray_plane), B, C, c_out, H, W, _stream()), "clip_emit_inject")
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    img = spec.images(1, B, state.device)[0] if emit else None
+    check(lib().ncahip_clip_emit_inject(_p(state), _p(img), spec.fmt, _p(gray_plane), B, C, c_out, H, W, _stream()), "clip_emit_inject")
     return img
 
 
@@ -606,7 +638,7 @@ def dynca_clip_xc(x: torch.Tensor, gray: torch.Tensor, cond: Optional[torch.Tens
     x = _dev(x, "x")
     B, cx, H, W = x.shape
     C = w.c
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, c_out, H, W)
     gray = _dev(gray, "gray")
     F_ = gray.shape[0]
     assert gray.shape == (F_, B, H, W) and cx in (C - 1, C), (tuple(gray.shape), tuple(x.shape), C)
@@ -614,22 +646,14 @@ def dynca_clip_xc(x: torch.Tensor, gray: torch.Tensor, cond: Optional[torch.Tens
     if cond is not None:
         cond = _dev(cond, "cond")
         assert cond.shape == (B, 2, H, W), tuple(cond.shape)
-    calls = F_ * steps_per_frame
-    us, seed = _u_args(us, calls * step_n, B, H, W, seed)
     assert w.k1 == 4 * C + c_cond, (w.c, w.k1, c_cond)
-    states = torch.empty(2, B, C, H, W, device=x.device, dtype=torch.float32)
-    states[0, :, :cx].copy_(x)
-    images = _clip_images_into(images, calls, B, c_out, H, W, out_dtype, x.device, fmt)
-    pc = torch.empty(B, 4 * C, H // 2, W // 2, device=x.device, dtype=torch.float32) if two_scale else None
-    ws, nbytes, epoch = None, 0, 0
-    if persistent_steps:
-        nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, c_cond)
-        if nbytes and calls < (1 << 20) - 2:
-            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_dynca_clip_xc_f32(_p(states), _p(gray), _p(cond), c_cond, _p(images), fmt, F_, steps_per_frame, step_n,
+    calls = F_ * steps_per_frame
+    states, pc, us, seed, images = _dynca_clip_buffers(x, C, calls, step_n, us, seed, two_scale, spec, images)
+    ws, nbytes, epoch = _clip_persist(lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, c_cond) if persistent_steps else 0, calls, x.device)
+    check(lib().ncahip_dynca_clip_xc_f32(_p(states), _p(gray), _p(cond), c_cond, _p(images), spec.fmt, F_, steps_per_frame, step_n,
                                          _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, c_out, H, W, w.fc, PAD_MODES[pad_mode],
-                                         int(two_scale), update_rate, seed, step0, _p(pc), _p(ws), nbytes if ws is not None else 0, epoch,
-                                         _stream()), "dynca_clip_xc")
+                                         int(two_scale), update_rate, seed, step0, _p(pc), _p(ws), nbytes, epoch, _stream()),
+          "dynca_clip_xc")
     return images, states[0]
 
 
@@ -765,12 +789,8 @@ def clip_encode(frames: torch.Tensor, encoder_module) -> torch.Tensor:
     encoder_module: an ncahip.encoder.ImageEncoder that encoder_clip_ok accepts (anything else raises: there is no fallback here)."""
     if not encoder_clip_ok(encoder_module):
         raise _capi.NcaHipError("ncahip: clip_encode covers ncahip.encoder.ImageEncoder with at most 4 image channels and an embedding of at most 32")
-    fmt = _clip_fmt(frames.dtype)
+    fmt, F_, B, ch, H, W = _frames_dims(frames)
     frames = _dev(frames, "frames", frames.dtype)
-    if fmt == _capi.CLIP_U8_NHWC:
-        F_, B, H, W, ch = frames.shape
-    else:
-        F_, B, ch, H, W = frames.shape
     enc = encoder_module
     assert ch == enc.channels, (tuple(frames.shape), enc.channels)
     E = enc.embed[0].out_channels
@@ -789,9 +809,9 @@ def clip_emit_unit(state: torch.Tensor, out_dtype=torch.float32, out_format: str
     out_format 'i420' / 'nv12' as clip_emit: the uint8 image as planar YUV 4:2:0 [B,3H/2,W]."""
     x = _dev(state, "state")
     B, C, H, W = x.shape
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
-    img = _clip_images(1, B, 3, H, W, out_dtype, x.device, fmt)[0]
-    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), fmt, B, C, H, W, _stream()), "clip_emit_unit")
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
+    img = spec.images(1, B, x.device)[0]
+    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), spec.fmt, B, C, H, W, _stream()), "clip_emit_unit")
     return img
 
 
@@ -806,7 +826,7 @@ def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w
     dynca_clip."""
     x = _dev(x, "x")
     B, C, H, W = x.shape
-    fmt = _clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
     goal = _dev(goal, "goal")
     F_, gch = goal.shape[0], goal.shape[2]
     assert goal.shape == (F_, B, gch, H, W) and 0 < gch <= C, (tuple(goal.shape), tuple(x.shape))
@@ -816,15 +836,12 @@ def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w
     states = torch.empty(4, B, C, H, W, device=x.device, dtype=torch.float32)
     states[0].copy_(x)
     pre = torch.empty(2, B, H, W, device=x.device, dtype=torch.uint8)
-    images = _clip_images_into(images, calls, B, 3, H, W, out_dtype, x.device, fmt)
-    ws, nbytes, epoch = None, 0, 0
-    if persistent_cond and not torch.cuda.is_current_stream_capturing():
-        nbytes = lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch)
-        if nbytes and calls < (1 << 20) - 2:
-            ws, epoch = _persist_workspace(nbytes, x.device, count=calls)
-    check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), fmt, F_, steps_per_frame, step_n, _p(us),
+    images = spec.images(calls, B, x.device, images)
+    ws, nbytes, epoch = _clip_persist(lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch) if persistent_cond else 0, calls, x.device,
+                                      while_capturing=False)
+    check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), spec.fmt, F_, steps_per_frame, step_n, _p(us),
                                      _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
-                                     lo, hi, seed, step0, _p(ws), nbytes if ws is not None else 0, epoch, _stream()), "cond_clip")
+                                     lo, hi, seed, step0, _p(ws), nbytes, epoch, _stream()), "cond_clip")
     return images, states[0]
 
 

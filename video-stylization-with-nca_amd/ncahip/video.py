@@ -66,27 +66,20 @@ def _widen(frames: torch.Tensor) -> torch.Tensor:
     return (frames.float() / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2).contiguous()
 
 
-def _clip_route(nca_model, h: torch.Tensor) -> bool:
-    """True when ncahip_dynca_clip_f32 covers the model: edge conditioning, perception_scales [0] or the fused [0, 1], an fp32
-    state on the GPU."""
-    if getattr(nca_model, "conditioning", None) != "edges" or not h.is_cuda or h.dtype != torch.float32 or h.shape[0] != 1:
-        return False
-    scales = list(getattr(nca_model, "perception_scales", [0]))
-    return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
-
-
 def _extra_channels(nca_model) -> bool:
     """True for the ExtraChannels family: the grey frame is the model's last state channel, not a cond_img."""
     from .models import dynca_extra
     return isinstance(nca_model, dynca_extra.DyNCA)
 
 
-def _clip_route_xc(nca_model, h: torch.Tensor) -> bool:
-    """True when ncahip_dynca_clip_xc_f32 covers an extra-channel model: perception_scales [0] or the fused [0, 1], an fp32 state on
-    the GPU, one sample."""
+def _clip_route(nca_model, h: torch.Tensor) -> bool:
+    """True when ncahip_dynca_clip_f32 (edge conditioning) or ncahip_dynca_clip_xc_f32 (an extra-channel model) covers the model:
+    perception_scales [0] or the fused [0, 1], an fp32 state on the GPU, one sample."""
+    if not (_extra_channels(nca_model) or getattr(nca_model, "conditioning", None) == "edges"):
+        return False
     if not h.is_cuda or h.dtype != torch.float32 or h.shape[0] != 1:
         return False
-    scales = list(nca_model.perception_scales)
+    scales = list(getattr(nca_model, "perception_scales", [0]))
     return scales == [0] or (scales == [0, 1] and nca_model._two_scale_fused(h))
 
 
@@ -258,23 +251,13 @@ def _chunks(fn, frames: torch.Tensor, per_call: int, dev):
         side.synchronize()           # no copy out of the caller's buffer is in flight once the call returns
 
 
-def _images_spec(out_dtype, out_format, yuv_matrix, yuv_range, c_out: int, hh: int, ww: int):
-    """(shape of one image, the drivers' keywords for it), validated before anything runs: planar output needs out_dtype=torch.uint8,
-    c_out == 3 and even H, W (ValueError)."""
-    from . import ops
-    ops._clip_img_fmt(out_dtype, out_format, yuv_matrix, yuv_range, c_out, hh, ww)
-    if out_format != "rgb24":
-        return (3 * hh // 2, ww), {"out_format": out_format, "yuv_matrix": yuv_matrix, "yuv_range": yuv_range}
-    return ((hh, ww, c_out) if out_dtype == torch.uint8 else (c_out, hh, ww)), {}
-
-
-def _check_out(out, n_images: int, shape, out_dtype):
+def _check_out(out, n_images: int, spec):
     """out= of the clip calls: None, or a contiguous tensor of exactly the images' shape and dtype (ValueError otherwise)."""
     if out is None:
         return
-    want = (n_images,) + tuple(shape)
-    if not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != out_dtype or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous {out_dtype} tensor {want} (the images of this call), got "
+    want = (n_images,) + spec.shape
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != spec.out_dtype or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {spec.out_dtype} tensor {want} (the images of this call), got "
                          f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out)} {getattr(out, 'dtype', '')}")
 
 
@@ -334,25 +317,140 @@ class _Downloads:
             self.side.synchronize()
 
 
-def _deliver(sink, outs, imgs: torch.Tensor):
-    """One chunk's images [n, *shape] on their way out: kept for the final cat (out=None, as before) or handed to the sink."""
-    if sink is None:
-        outs.append(imgs)
-    else:
-        sink.put(imgs)
+class _Route:
+    """What differs between the clip calls: a route takes the chunks of _run_clip in order and carries the state `h`.  fused: run(ci,
+    chunk, buf) makes the images [n * k, *spec.shape] of chunk ci ([n,3,H,W] float32 or [n,H,W,3] uint8) in one driver call, in `buf`
+    [n * k, 1, *spec.shape] when there is one.  Otherwise (the Python loops) run(ci, chunk, buf) yields them one by one as float32
+    [1,c,H,W] in [0, 1]; _run_clip gives them the call's dtype and format."""
+    fused = False
+
+    def __init__(self, model, h: torch.Tensor, k: int, step_n: int):
+        self.model, self.h, self.k, self.step_n = model, h, k, step_n
 
 
-def _deliver_loop(sink, outs, chunk_imgs):
-    """The loop routes' images of one chunk (a list of [1, *shape])."""
-    if sink is None:
-        outs.extend(chunk_imgs)
-    elif chunk_imgs:
-        imgs = torch.cat(chunk_imgs)
-        buf = sink.staging(imgs.shape[0])
-        if buf is not None:
-            buf[:, 0].copy_(imgs)
-            imgs = buf[:, 0]
-        sink.put(imgs)
+def _loop_image(img: torch.Tensor, spec) -> torch.Tensor:
+    """A loop route's image as the call's: float32 as it is, or truncated to uint8 [1,H,W,c] and from there to planar YUV."""
+    if spec.out_dtype == torch.uint8:
+        img = (img * 255.0).to(torch.uint8).permute(0, 2, 3, 1)
+    return rgb_to_yuv420(img.contiguous(), spec.out_format, spec.yuv_matrix, spec.yuv_range) if spec.planar else img
+
+
+def _run_clip(fn, route: _Route, frames: torch.Tensor, shrink, per_call: int, dev, spec, out):
+    """The chunk pipeline of both clip calls (fn: the entry point, which records the routes taken), returning (images, state).  Per chunk
+    of per_call frames: upload (_chunks), shrink, the staging buffer of out= (_Downloads), the route, the images on their way to `out` or
+    to the final cat.  raw and chunk are dropped before the next chunk is asked for (_chunks: at most two uploaded chunks alive)."""
+    k = route.k
+    fn.last_path, fn.last_download = "clip" if route.fused else "loop", None
+    sink = None if out is None else _Downloads(fn, out, spec.shape, per_call * k, dev)
+    outs = []
+    try:
+        for ci, raw in enumerate(_chunks(fn, frames, per_call, dev)):
+            chunk = shrink(raw)
+            buf = None if sink is None else sink.staging(chunk.shape[0] * k)
+            if route.fused:
+                imgs = [route.run(ci, chunk, buf)]
+            else:
+                imgs = [_loop_image(img, spec) for img in route.run(ci, chunk, buf)]
+                if sink is not None and imgs:              # one tensor per chunk, in the staging buffer when there is one
+                    imgs = [torch.cat(imgs) if buf is None else buf[:, 0].copy_(torch.cat(imgs))]
+            if sink is None:
+                outs.extend(imgs)
+            elif imgs:
+                sink.put(imgs[0])
+            del raw, chunk                                 # (_chunks: at most two uploaded chunks alive)
+    finally:
+        if sink is not None:
+            sink.finish()                # no copy into the caller's buffer is in flight once the call returns
+    fn.last_state = route.h
+    if sink is not None:
+        return out, route.h
+    return (torch.cat(outs) if outs else torch.empty((0,) + spec.shape, dtype=spec.out_dtype, device=dev)), route.h
+
+
+def _check_precision(nca_model, h: torch.Tensor, precision: str, direction) -> None:
+    """stylize_clip(precision='bf16' / 'bf16_wide'): ValueError unless the model, its steps and the state run in that arithmetic."""
+    from . import ops
+    if precision == "f32":
+        return
+    fc = nca_model.w1.out_channels
+    if precision == "bf16" and not ops.dynca_bf16_ok(nca_model.c_in, fc):
+        raise ValueError(f"precision='bf16' covers C <= 16 and fc <= 128 (ops.dynca_bf16_ok); the model has C = {nca_model.c_in}, fc = {fc}")
+    if precision == "bf16_wide" and not ops.dynca_bf16_wide_ok(nca_model.c_in, fc):
+        raise ValueError(f"precision='bf16_wide' covers C <= 32 and fc <= 256 (ops.dynca_bf16_wide_ok); the model has C = {nca_model.c_in}, fc = {fc}")
+    if not ops.dynca_bf16_ok(nca_model.c_in, fc):
+        # 'bf16_wide' beyond the narrow range: the single-scale unsteered step only, whatever the state is
+        if nca_model._multiscale():
+            raise ValueError(f"precision='bf16_wide' needs the fused step kernels; multi-scale perception at C = {nca_model.c_in}, fc = {fc} "
+                             "runs the composed multi-scale step")
+        if direction is not None:
+            raise ValueError(f"precision='bf16_wide' does not steer beyond C <= 16 and fc <= 128 (ops.dynca_bf16_ok): a direction on a model "
+                             f"with C = {nca_model.c_in}, fc = {fc} would run in fp32")
+    if not h.is_cuda or h.dtype != torch.float32:
+        raise ValueError(f"precision={precision!r} needs a float32 state on the GPU (the state stays fp32), got {h.dtype} on {h.device}")
+    if nca_model._composed(h):
+        raise ValueError(f"precision={precision!r} needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
+
+
+class _DyncaClip(_Route):
+    """stylize_clip's clip route, edge-conditioned and extra-channel models: per call the weights, the filter bank or the positional
+    encoding (turned by `angle`, as forward_nsteps turns it) and two_scale; per chunk ncahip_clip_cond / ncahip_clip_gray, the loop's own
+    mask draws call by call (DyNCA._draw: the generator ends where it would) and one driver call."""
+    fused = True
+
+    def __init__(self, model, h, k, step_n, gray, angle, spec):
+        from . import ops, steer
+        super().__init__(model, h, k, step_n)
+        self.gray, self.size, self.okw = gray, (spec.H, spec.W), spec.keywords
+        self.w = ops.DyncaWeights(model.w1.weight, model.w1.bias, model.w2.weight, model.w2.bias, h)
+        self.two, self.extra = list(model.perception_scales) == [0, 1], _extra_channels(model)
+        if self.extra:
+            self.pos = model._cond(h.new_empty(1, model.c_in, *self.size))       # CPE (or None): a function of the shape alone
+            if self.pos is not None and angle is not None:
+                self.pos = steer.rotate_pos_emb(self.pos, angle)
+        else:
+            layer = model.cond_layer
+            self.bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
+            self.do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
+
+    def run(self, ci, chunk, buf):
+        from . import ops
+        m, k, step_n, rate = self.model, self.k, self.step_n, 0.5
+        chunk = chunk.unsqueeze(1)                                                # [n,1,3,H,W] or [n,1,H,W,3]
+        calls = chunk.shape[0] * k
+        cond = ops.clip_gray(chunk, self.gray) if self.extra else ops.clip_cond(chunk, self.bank, self.gray, self.do_tanh)
+        us = None
+        if m.mask_rng != "philox":
+            us = torch.cat([ops.draw_fire_masks(1, *self.size, step_n, rate, "dynca", self.h.device) for _ in range(calls)])
+        args = (us, self.w, k, step_n, m.c_out, m.padding_mode, rate, m.mask_seed, m._mask_step)
+        if self.extra:                             # h keeps c_in - 1 channels: the driver's last channel is the grey frame
+            imgs, x = ops.dynca_clip_xc(self.h, cond, self.pos, *args, two_scale=self.two, images=buf, **self.okw)
+            self.h = x[:, :-1]
+        else:
+            imgs, self.h = ops.dynca_clip(self.h, cond, *args, two_scale=self.two, images=buf, **self.okw)
+        m._mask_step += calls * step_n
+        return imgs[:, 0]
+
+
+class _DyncaLoop(_Route):
+    """stylize_clip's Python loop over forward_nsteps; `direction` goes to forward_nsteps, which attaches it per call."""
+
+    def __init__(self, model, h, k, step_n, gray, direction, u8_in):
+        super().__init__(model, h, k, step_n)
+        self.gray, self.u8_in, self.extra = gray, u8_in, _extra_channels(model)
+        self.steer_kw = {} if direction is None else {"direction": direction}     # (a model without the keyword still runs unsteered clips)
+
+    def run(self, ci, chunk, buf):
+        m = self.model
+        chunk = _widen(chunk) if self.u8_in else chunk
+        for i in range(chunk.shape[0]):
+            cond = _gray(chunk[i:i + 1], self.gray)
+            for _ in range(self.k):
+                if self.extra:      # the grey frame as the last state channel, dropped again after the call
+                    x, rgb = m.forward_nsteps(torch.cat((self.h, cond.to(self.h.dtype)), 1), self.step_n, **self.steer_kw)
+                    self.h = x[:, :-1]
+                else:
+                    self.h, rgb = m.forward_nsteps(self.h, self.step_n, cond_img=cond, **self.steer_kw)
+                yield (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
 
 
 @torch.no_grad()
@@ -424,37 +522,15 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
-    n_frames = frames.shape[0]
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
-    shape, okw = _images_spec(out_dtype, out_format, out_yuv_matrix, out_yuv_range, getattr(nca_model, "c_out", 3), hh, ww)
-    _check_out(out, n_frames * k, shape, out_dtype)
-    extra = _extra_channels(nca_model)
-    if extra and state is not None and (state.dim() != 4 or state.shape[1] != nca_model.c_in - 1):
+    spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, getattr(nca_model, "c_out", 3), hh, ww)
+    _check_out(out, frames.shape[0] * k, spec)
+    if _extra_channels(nca_model) and state is not None and (state.dim() != 4 or state.shape[1] != nca_model.c_in - 1):
         raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
     h = state if state is not None else nca_model.seed(1, size=(ww, hh))
-    fused = (_clip_route_xc(nca_model, h) if extra else _clip_route(nca_model, h)) and torch.device(dev).type == "cuda"
-    if precision != "f32":
-        fc = nca_model.w1.out_channels
-        if precision == "bf16" and not ops.dynca_bf16_ok(nca_model.c_in, fc):
-            raise ValueError(f"precision='bf16' covers C <= 16 and fc <= 128 (ops.dynca_bf16_ok); the model has C = {nca_model.c_in}, fc = {fc}")
-        if precision == "bf16_wide" and not ops.dynca_bf16_wide_ok(nca_model.c_in, fc):
-            raise ValueError(f"precision='bf16_wide' covers C <= 32 and fc <= 256 (ops.dynca_bf16_wide_ok); the model has C = {nca_model.c_in}, fc = {fc}")
-        if not ops.dynca_bf16_ok(nca_model.c_in, fc):
-            # 'bf16_wide' beyond the narrow range: the single-scale unsteered step only, whatever the state is
-            if nca_model._multiscale():
-                raise ValueError(f"precision='bf16_wide' needs the fused step kernels; multi-scale perception at C = {nca_model.c_in}, fc = {fc} "
-                                 "runs the composed multi-scale step")
-            if direction is not None:
-                raise ValueError(f"precision='bf16_wide' does not steer beyond C <= 16 and fc <= 128 (ops.dynca_bf16_ok): a direction on a model "
-                                 f"with C = {nca_model.c_in}, fc = {fc} would run in fp32")
-        if not h.is_cuda or h.dtype != torch.float32:
-            raise ValueError(f"precision={precision!r} needs a float32 state on the GPU (the state stays fp32), got {h.dtype} on {h.device}")
-        if nca_model._composed(h):
-            raise ValueError(f"precision={precision!r} needs the fused step kernels; this model's perception scales / size run the composed multi-scale step")
-    stylize_clip.last_path = "clip" if fused else "loop"
-    stylize_clip.last_download = None
-    sink = None if out is None else _Downloads(stylize_clip, out, shape, per_call * k, dev)
+    fused = _clip_route(nca_model, h) and torch.device(dev).type == "cuda"
+    _check_precision(nca_model, h, precision, direction)
     dirs = angle = None
     if direction is not None:
         if h.dtype != torch.float32:
@@ -465,80 +541,9 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     with ops.dynca_precision(precision) if precision != "f32" else contextlib.nullcontext():
         # the clip route's steps run under the field; the loop route hands it to forward_nsteps, which attaches it per call
         with ops.dynca_direction(dirs) if (fused and dirs is not None) else contextlib.nullcontext():
-            try:
-                return _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev,
-                                         u8_in, direction, angle, shape, okw, sink)
-            finally:
-                if sink is not None:
-                    sink.finish()        # no copy into the caller's buffer is in flight once the call returns
-
-
-def _stylize_clip_run(nca_model, frames, h, fused, extra, n_frames, per_call, shrink, k, step_n, gray, out_dtype, hh, ww, dev, u8_in,
-                      direction=None, angle=None, shape=None, okw=None, sink=None):
-    """The two routes of stylize_clip (its arguments validated, the state seeded, the precision set, the clip route's direction field
-    attached).  direction: what the loop route passes on to forward_nsteps; angle: a tuple's angle, for the positional encoding.
-    shape, okw: _images_spec's image shape and driver keywords; sink: the _Downloads of out= (None: the images are concatenated)."""
-    from . import ops, steer
-    outs, okw = [], okw or {}
-    if fused:
-        w = ops.DyncaWeights(nca_model.w1.weight, nca_model.w1.bias, nca_model.w2.weight, nca_model.w2.bias, h)
-        rate, two = 0.5, list(nca_model.perception_scales) == [0, 1]
-        if extra:
-            pos = nca_model._cond(h.new_empty(1, nca_model.c_in, hh, ww))        # CPE (or None): a function of the shape alone
-            if pos is not None and angle is not None:
-                pos = steer.rotate_pos_emb(pos, angle)                           # as forward_nsteps turns it
-        else:
-            layer = nca_model.cond_layer
-            bank = torch.cat((layer.sobel_x.weight, layer.sobel_y.weight, layer.laplacian.weight), dim=0)
-            do_tanh = isinstance(layer.edge_transform, torch.nn.Tanh)
-        for raw in _chunks(stylize_clip, frames, per_call, dev):
-            chunk = shrink(raw).unsqueeze(1)                                      # [n,1,3,H,W] or [n,1,H,W,3]
-            n = chunk.shape[0]
-            cond = ops.clip_gray(chunk, gray) if extra else ops.clip_cond(chunk, bank, gray, do_tanh)
-            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-            us = None
-            if nca_model.mask_rng != "philox":     # the loop's own draws, call by call (DyNCA._draw): the generator ends where it would
-                us = torch.cat([ops.draw_fire_masks(1, hh, ww, step_n, rate, "dynca", h.device) for _ in range(n * k)])
-            buf = None if sink is None else sink.staging(n * k)
-            if extra:                              # h keeps c_in - 1 channels: the driver's last channel is the grey frame
-                imgs, x = ops.dynca_clip_xc(h, cond, pos, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
-                                            nca_model._mask_step, two_scale=two, out_dtype=out_dtype, images=buf, **okw)
-                h = x[:, :-1]
-            else:
-                imgs, h = ops.dynca_clip(h, cond, us, w, k, step_n, nca_model.c_out, nca_model.padding_mode, rate, nca_model.mask_seed,
-                                         nca_model._mask_step, two_scale=two, out_dtype=out_dtype, images=buf, **okw)
-            nca_model._mask_step += n * k * step_n
-            _deliver(sink, outs, imgs[:, 0])
-    else:
-        steer_kw = {} if direction is None else {"direction": direction}      # (a model without the keyword still runs unsteered clips)
-        for raw in _chunks(stylize_clip, frames, per_call, dev):
-            chunk = shrink(raw)
-            chunk = _widen(chunk) if u8_in else chunk
-            chunk_imgs = []
-            for i in range(chunk.shape[0]):
-                cond = _gray(chunk[i:i + 1], gray)
-                for _ in range(k):
-                    if extra:       # the grey frame as the last state channel, dropped again after the call
-                        x, rgb = nca_model.forward_nsteps(torch.cat((h, cond.to(h.dtype)), 1), step_n, **steer_kw)
-                        h = x[:, :-1]
-                    else:
-                        h, rgb = nca_model.forward_nsteps(h, step_n, cond_img=cond, **steer_kw)
-                    img = (rgb.float().clamp(-1.0, 1.0) + 1.0) / 2.0
-                    img = (img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img
-                    chunk_imgs.append(rgb_to_yuv420(img.contiguous(), okw["out_format"], okw["yuv_matrix"], okw["yuv_range"]) if okw else img)
-            _deliver_loop(sink, outs, chunk_imgs)
-            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-    if sink is not None:
-        images = sink.out
-    elif outs:
-        images = torch.cat(outs)
-    elif okw:
-        images = torch.empty((0,) + tuple(shape), dtype=out_dtype, device=dev)
-    else:
-        c = getattr(nca_model, "c_out", 3)
-        images = torch.empty((0, hh, ww, c) if out_dtype == torch.uint8 else (0, c, hh, ww), dtype=out_dtype, device=dev)
-    stylize_clip.last_state = h
-    return images, h
+            route = (_DyncaClip(nca_model, h, k, step_n, gray, angle, spec) if fused else
+                     _DyncaLoop(nca_model, h, k, step_n, gray, direction, u8_in))
+            return _run_clip(stylize_clip, route, frames, shrink, per_call, dev, spec, out)
 
 
 stylize_clip.last_path = None
@@ -546,10 +551,50 @@ stylize_clip.last_upload = None
 stylize_clip.last_download = None
 
 
-def _unit_image(state: torch.Tensor, out_dtype) -> torch.Tensor:
-    """clamp(state[:, :3], 0, 1) (trainer.py:36-39, utils/utils.py:34-35), float32 [B,3,H,W] or truncated to uint8 [B,H,W,3]."""
-    img = torch.clamp(state[:, :3].float(), 0.0, 1.0)
-    return (img * 255.0).to(torch.uint8).permute(0, 2, 3, 1) if out_dtype == torch.uint8 else img
+class _CondClip(_Route):
+    """stylize_clip_conditioned's clip route: per chunk ncahip_clip_encode, on chunk 0 the warm-up grow with goal[0], the loop's own mask
+    draws grow call by grow call (ConditionedNCA._draw: the generator ends where it would) and one driver call."""
+    fused = True
+
+    def __init__(self, nca, h, k, step_n, warm, spec):
+        super().__init__(nca, h.contiguous(), k, step_n)
+        self.warm, self.okw, self.w = warm, spec.keywords, nca._weights(self.h)
+        self.args = (nca._alive_ch(), nca.alpha_living_threshold, nca.cell_fire_rate, -10.0, 10.0)
+
+    def run(self, ci, chunk, buf):
+        from . import ops
+        nca, k, step_n, warm = self.model, self.k, self.step_n, self.warm
+        draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(self.h, steps)      # noqa: E731
+        chunk = chunk.unsqueeze(1)                                                # [n,1,3,H,W] or [n,1,H,W,3]
+        calls = chunk.shape[0] * k
+        goal = ops.clip_encode(chunk, nca.encoder)
+        if ci == 0 and warm > 0:
+            self.h, _, _ = ops.cond_grow(self.h, warm, goal[0], draw(warm), self.w, *self.args, nca.mask_seed, nca._mask_step)
+            nca._mask_step += warm
+        us = None if nca.mask_rng == "philox" else torch.cat([draw(step_n) for _ in range(calls)])
+        imgs, self.h = ops.cond_clip(self.h, goal, us, self.w, k, step_n, *self.args, nca.mask_seed, nca._mask_step, images=buf, **self.okw)
+        nca._mask_step += calls * step_n
+        return imgs[:, 0]
+
+
+class _CondLoop(_Route):
+    """stylize_clip_conditioned's Python loop over nca.grow, with the warm-up grow before the first frame's steps."""
+
+    def __init__(self, nca, h, k, step_n, warm, u8_in):
+        super().__init__(nca, h, k, step_n)
+        self.warm, self.u8_in = warm, u8_in
+
+    def run(self, ci, chunk, buf):
+        nca = self.model
+        if self.u8_in:      # frames as the module takes them: [n,3,H,W] float32 in [0, 1]
+            chunk = (chunk.float() / 255.0).permute(0, 3, 1, 2).contiguous()
+        for i in range(chunk.shape[0]):
+            goal_img = chunk[i:i + 1]
+            if ci == 0 and i == 0 and self.warm > 0:
+                self.h = nca.grow(self.h, self.warm, goal_img)
+            for _ in range(self.k):
+                self.h = nca.grow(self.h, self.step_n, goal_img)
+                yield torch.clamp(self.h[:, :3].float(), 0.0, 1.0)               # (trainer.py:36-39, utils/utils.py:34-35)
 
 
 @torch.no_grad()
@@ -592,10 +637,9 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
-    shape, okw = _images_spec(out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
+    spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
     if nca.num_target_channels != 3:
         raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
-    n_frames = frames.shape[0]
     if state is not None and (state.dim() != 4 or state.shape[1] != nca.num_channels or tuple(state.shape[2:]) != (hh, ww)):
         raise ValueError(f"state must be [B,{nca.num_channels},{hh},{ww}] (nca.num_channels channels, the frames' size), got {tuple(state.shape)}")
     if state is None and hh != ww:
@@ -603,73 +647,12 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     k, step_n, warm, per_call = int(steps_per_frame), int(step_n), int(warmup_steps), max(1, int(frames_per_call))
     if k < 1 or step_n < 1 or warm < 0:
         raise ValueError("steps_per_frame and step_n must be positive and warmup_steps non-negative")
-    _check_out(out, n_frames * k, shape, out_dtype)
+    _check_out(out, frames.shape[0] * k, spec)
     dev = next(nca.parameters()).device
     h = (nca.generate_seed(1, size=hh) if state is None else state).to(dev)
     fused = h.is_cuda and h.dtype == torch.float32 and h.shape[0] == 1 and ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3
-    stylize_clip_conditioned.last_path = "clip" if fused else "loop"
-    stylize_clip_conditioned.last_download = None
-    sink = None if out is None else _Downloads(stylize_clip_conditioned, out, shape, per_call * k, dev)
-    try:
-        return _stylize_clip_conditioned_run(nca, frames, h, fused, per_call, shrink, k, step_n, warm, out_dtype, hh, ww, dev, u8_in, shape, okw, sink)
-    finally:
-        if sink is not None:
-            sink.finish()                # no copy into the caller's buffer is in flight once the call returns
-
-
-def _stylize_clip_conditioned_run(nca, frames, h, fused, per_call, shrink, k, step_n, warm, out_dtype, hh, ww, dev, u8_in, shape, okw, sink):
-    """The two routes of stylize_clip_conditioned (its arguments validated, the state seeded).  shape, okw, sink as in _stylize_clip_run."""
-    from . import ops
-
-    def unit(chunk):      # frames of a chunk as the module takes them: [n,3,H,W] float32 in [0, 1]
-        return (chunk.float() / 255.0).permute(0, 3, 1, 2).contiguous() if u8_in else chunk
-
-    outs = []
-    if fused:
-        h = h.contiguous()
-        w = nca._weights(h)
-        draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(h, steps)      # noqa: E731
-        args = (nca._alive_ch(), nca.alpha_living_threshold, nca.cell_fire_rate, -10.0, 10.0)
-        for ci, raw in enumerate(_chunks(stylize_clip_conditioned, frames, per_call, dev)):
-            chunk = shrink(raw).unsqueeze(1)                                      # [n,1,3,H,W] or [n,1,H,W,3]
-            n = chunk.shape[0]
-            goal = ops.clip_encode(chunk, nca.encoder)
-            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-            if ci == 0 and warm > 0:
-                h, _, _ = ops.cond_grow(h, warm, goal[0], draw(warm), w, *args, nca.mask_seed, nca._mask_step)
-                nca._mask_step += warm
-            us = None
-            if nca.mask_rng != "philox":           # the loop's own draws, grow call by grow call: the generator ends where it would
-                us = torch.cat([draw(step_n) for _ in range(n * k)])
-            buf = None if sink is None else sink.staging(n * k)
-            imgs, h = ops.cond_clip(h, goal, us, w, k, step_n, *args, nca.mask_seed, nca._mask_step, out_dtype=out_dtype, images=buf, **okw)
-            nca._mask_step += n * k * step_n
-            _deliver(sink, outs, imgs[:, 0])
-    else:
-        for ci, raw in enumerate(_chunks(stylize_clip_conditioned, frames, per_call, dev)):
-            chunk = unit(shrink(raw))
-            chunk_imgs = []
-            for i in range(chunk.shape[0]):
-                goal_img = chunk[i:i + 1]
-                if ci == 0 and i == 0 and warm > 0:
-                    h = nca.grow(h, warm, goal_img)
-                for _ in range(k):
-                    h = nca.grow(h, step_n, goal_img)
-                    img = _unit_image(h, out_dtype)
-                    chunk_imgs.append(rgb_to_yuv420(img.contiguous(), okw["out_format"], okw["yuv_matrix"], okw["yuv_range"]) if okw else img)
-            _deliver_loop(sink, outs, chunk_imgs)
-            goal_img = None                                                       # (a view of the chunk)
-            del raw, chunk                                                        # (_chunks: at most two uploaded chunks alive)
-    if sink is not None:
-        images = sink.out
-    elif outs:
-        images = torch.cat(outs)
-    elif okw:
-        images = torch.empty((0,) + tuple(shape), dtype=out_dtype, device=dev)
-    else:
-        images = torch.empty((0, hh, ww, 3) if out_dtype == torch.uint8 else (0, 3, hh, ww), dtype=out_dtype, device=dev)
-    stylize_clip_conditioned.last_state = h
-    return images, h
+    route = _CondClip(nca, h, k, step_n, warm, spec) if fused else _CondLoop(nca, h, k, step_n, warm, u8_in)
+    return _run_clip(stylize_clip_conditioned, route, frames, shrink, per_call, dev, spec, out)
 
 
 stylize_clip_conditioned.last_path = None
