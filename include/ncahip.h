@@ -730,6 +730,42 @@ int ncahip_cond_clip_f32(float *states, uint8_t *pre, const float *goal, int goa
                          float clamp_hi, uint64_t seed, uint64_t step0, void *persist_ws, size_t persist_bytes, unsigned epoch0,
                          ncahip_stream_t stream);
 
+/* ---- a whole clip per call, ConditionedNCA on a bf16 state ------------------------------------------------------------------------
+ * The entry points above for a state and a goal stored as bf16 (uint16_t bit patterns; "bf16 state storage" above: the steps are
+ * ncahip_cond_step_fwd_bf16's).  Formats, codes and message words as their fp32 siblings'.  Nothing here synchronises.
+ * ncahip_clip_encode_bf16: ncahip_clip_encode with the goal [F,B,E,H,W] stored as bf16: the same kernel and arithmetic, the final store
+ *   rounds to bf16 (round-to-nearest-even) -- bit for bit ncahip_clip_encode followed by a cast.  Arguments, ranges and checks as
+ *   ncahip_clip_encode; the goal's bytes are halved in the overlap checks and the goal is 2-byte aligned (NCAHIP_EINVAL).
+ * ncahip_clip_emit_unit_bf16: ncahip_clip_emit_unit reading a bf16 state [B,C,H,W] (2-byte aligned: NCAHIP_EINVAL), every image format
+ *   of that entry point, the planar ones included: bit for bit the fp32 emit of the widened state.
+ * ncahip_cond_finalize_emit_bf16: ONE launch for ncahip_cond_finalize_bf16(x_pend, pre) -> x_out and then
+ *   ncahip_clip_emit_unit_bf16(x_out) -> img: the alive pool, the clamp and the image in one pass over the pending state (one launch and
+ *   one read of the state fewer per image); x_out and img are bit for bit those of the two launches.  Any B, H, W and C >= 3 (the image
+ *   is x_out[:, :3]), 2-byte aligned states; a lane takes 4 cells of a row (2 x 4 for a planar image) -- as 8-byte words where W % 4 == 0
+ *   and the states are 8-byte aligned.  x_out == x_pend only with alive_ch < 0.  NCAHIP_EINVAL: a null pointer (pre may be null with
+ *   alive_ch < 0), an unknown format, a non-positive size, C < 3, alive_ch >= C, a misaligned state or float32 image, img overlapping
+ *   x_pend, x_out or pre.  NCAHIP_ERANGE: a planar format with odd H or W.
+ * ncahip_cond_clip_bf16: the loop of ncahip_cond_clip_f32 on the bf16 step launches.  states: 4 slots of B*C*H*W bf16 values, the state
+ *   in slot 0 on entry and on return; pre: 2 slots of B*H*W bytes; goal [F,B,goal_ch,H,W] bf16 (from ncahip_clip_encode_bf16); u, seed
+ *   and step0 as ncahip_cond_clip_f32 (NULL = in-kernel Philox; bit-packed masks or float uniforms of all steps laid end to end).
+ *   There is no persistent bf16 grow, hence no workspace: every call n runs the ring of slots {cur, cur + 1} -- its step_n steps
+ *   enqueued exactly as ncahip_cond_grow_fwd_bf16 enqueues them -- and ends with ncahip_cond_finalize_emit_bf16's launch, which writes
+ *   the resolved state to slot cur (step_n odd) or to the other of slots 0 / 2 (step_n even) and image n.  At most one device-to-device
+ *   copy per call of the driver, when the state ended in slot 2.  Covers what ncahip_cond_grow_fwd_bf16 covers -- C <= 20, W % 4 == 0,
+ *   8-byte aligned states and goal -- and refuses the rest with that entry point's code (NCAHIP_ERANGE).  Arguments are checked on the
+ *   host before anything is enqueued (null or overlapping buffers, F, steps_per_frame, step_n <= 0, C < 3, an unknown format:
+ *   NCAHIP_EINVAL; a planar format with odd H or W: NCAHIP_ERANGE); then a set sticky error word refuses the call with NCAHIP_EDEVICE;
+ *   the driver stops enqueuing at the first failing launch and returns its code. */
+int ncahip_clip_encode_bf16(const void *frames, int frame_fmt, const float *k3, const float *k5, const float *w1, const float *b1, const float *w2,
+                            uint16_t *goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream);
+int ncahip_clip_emit_unit_bf16(const uint16_t *state, void *img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream);
+int ncahip_cond_finalize_emit_bf16(const uint16_t *x_pend, const uint8_t *pre, uint16_t *x_out, void *img, int img_fmt, int B, int C, int H, int W,
+                                   int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream);
+int ncahip_cond_clip_bf16(uint16_t *states, uint8_t *pre, const uint16_t *goal, int goal_ch, void *images, int img_fmt, int F, int steps_per_frame,
+                          int step_n, const float *u, const float *wp, const float *w1, const float *b1, const float *w2, const float *b2,
+                          const float *w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                          float clamp_hi, uint64_t seed, uint64_t step0, ncahip_stream_t stream);
+
 /* ---- a whole clip per call, decoder-sized frames: crop + resize of uint8 frames, bit for bit Pillow's 8-bit Image.resize -------------
  * A decoder delivers 1080p or 720p uint8 frames; the models run at 128^2 .. 512^2.  The reference shrinks on the host with Pillow:
  * preprocess_style_image (ConditioneDyNCA/utils/misc/preprocess_texture.py:9-33: symmetric centre cut, then Image.resize = bicubic) and

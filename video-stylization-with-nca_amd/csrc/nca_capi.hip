@@ -772,10 +772,14 @@ int ncahip_cond_fused_steps_layout(int B, int C, int H, int W, int chunk_cap, in
     return 0;
 }
 
+static hipError_t cond_launch_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H,
+                                                 int W, int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, hipStream_t st);
+
+// img (bf16 only; the clip driver): the grow's last launch also writes the unit image of x_final in format img_fmt (checked by the caller)
 static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring, int T, void* x_final, const void* goal, int goal_ch, const float* u,
                               const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, int B, int C,
                               int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
-                              uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
+                              uint64_t seed, uint64_t step0, ncahip_stream_t stream, void* img = nullptr, int img_fmt = 0) {
     char* const states = (char*)states_v;
     if (ring < 2 || T < 1 || !pre || !x_final) return fail(NCAHIP_EINVAL, "cond grow: ring >= 2, T >= 1, buffers required");
     if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch,
@@ -877,6 +881,9 @@ static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring,
         g_fused_step_launches.store(ms_launches, std::memory_order_relaxed);
     }
     const uint8_t* const pre_last = pre + (size_t)sl * pslot;
+    if (bf16 && img)
+        return hip_result(cond_launch_finalize_emit_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, img, img_fmt, B, C, H, W,
+                                                         alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize + image (bf16)");
     return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, B, C, H, W, alive_ch,
                                                            alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)")
                 : hip_result(nca_launch_cond_finalize((const float*)(states + (size_t)sl * slot), pre_last, (float*)x_final, B, C, H, W, alive_ch, alive_thr,
@@ -937,8 +944,9 @@ size_t ncahip_clip_encode_workspace(int F, int B, int E, int H, int W) {
     return (size_t)F * B * E * H * W * sizeof(float);
 }
 
-int ncahip_clip_encode(const void* frames, int frame_fmt, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
-                       float* goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream) {
+// the two goal types share every check; a bf16 goal has half the bytes and is 2-byte aligned
+static int clip_encode_impl(bool bf16, const void* frames, int frame_fmt, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                            void* goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream) {
     if (!frames || !k3 || !k5 || !w1 || !b1 || !w2 || !goal) return fail(NCAHIP_EINVAL, "clip_encode: null pointer");
     if (!clip_fmt_ok(frame_fmt)) return fail(NCAHIP_EINVAL, "clip_encode: unknown frame format %d", frame_fmt);
     if (F <= 0 || ch <= 0 || E <= 0 || !dims_ok(B, 1, H, W) || (size_t)F * B > 0x7fffffffu) return fail(NCAHIP_EINVAL, "clip_encode: bad size");
@@ -946,15 +954,26 @@ int ncahip_clip_encode(const void* frames, int frame_fmt, const float* k3, const
     if (frame_fmt == NCAHIP_CLIP_U8_NHWC && ch != 3) return fail(NCAHIP_ERANGE, "clip_encode: uint8 frames have 3 channels, got ch=%d", ch);
     const size_t px = (size_t)F * B * H * W;
     if ((size_t)F * B * ((H + 15) / 16) * ((W + 15) / 16) > 0x7fffffffu) return fail(NCAHIP_ERANGE, "clip_encode: more than 2^31 tiles of 16 x 16 in one launch");
-    const size_t gbytes = px * E * sizeof(float), fbytes = px * ch * clip_fmt_bytes(frame_fmt);
+    const size_t gbytes = px * E * (bf16 ? sizeof(uint16_t) : sizeof(float)), fbytes = px * ch * clip_fmt_bytes(frame_fmt);
     const size_t k1 = (size_t)(3 + ch);
     if (clip_overlap(frames, fbytes, goal, gbytes) || clip_overlap(k3, 27 * sizeof(float), goal, gbytes) || clip_overlap(k5, 25 * sizeof(float), goal, gbytes) ||
         clip_overlap(w1, E * k1 * 9 * sizeof(float), goal, gbytes) || clip_overlap(b1, E * sizeof(float), goal, gbytes) ||
         clip_overlap(w2, (size_t)E * E * 9 * sizeof(float), goal, gbytes))
         return fail(NCAHIP_EINVAL, "clip_encode: goal overlaps an input");
     if (frame_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)frames & 3) != 0) return fail(NCAHIP_EINVAL, "clip_encode: float32 frames must be 4-byte aligned");
-    return hip_result(nca_launch_clip_encode(frames, frame_fmt == NCAHIP_CLIP_U8_NHWC, k3, k5, w1, b1, w2, goal, F * B, ch, E, H, W, (hipStream_t)stream),
-                      "clip_encode");
+    if (bf16 && ((uintptr_t)goal & 1) != 0) return fail(NCAHIP_EINVAL, "clip_encode: a bf16 goal must be 2-byte aligned");
+    const bool u8 = frame_fmt == NCAHIP_CLIP_U8_NHWC;
+    return bf16 ? hip_result(nca_launch_clip_encode_bf16(frames, u8, k3, k5, w1, b1, w2, (uint16_t*)goal, F * B, ch, E, H, W, (hipStream_t)stream), "clip_encode_bf16")
+                : hip_result(nca_launch_clip_encode(frames, u8, k3, k5, w1, b1, w2, (float*)goal, F * B, ch, E, H, W, (hipStream_t)stream), "clip_encode");
+}
+
+int ncahip_clip_encode(const void* frames, int frame_fmt, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                       float* goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream) {
+    return clip_encode_impl(false, frames, frame_fmt, k3, k5, w1, b1, w2, goal, F, B, ch, E, H, W, stream);
+}
+int ncahip_clip_encode_bf16(const void* frames, int frame_fmt, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                            uint16_t* goal, int F, int B, int ch, int E, int H, int W, ncahip_stream_t stream) {
+    return clip_encode_impl(true, frames, frame_fmt, k3, k5, w1, b1, w2, goal, F, B, ch, E, H, W, stream);
 }
 
 static int check_clip_emit_unit(const void* state, const void* img, int img_fmt, int B, int C, int H, int W) {
@@ -972,6 +991,49 @@ int ncahip_clip_emit_unit(const float* state, void* img, int img_fmt, int B, int
     if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(img_fmt, B, 3, H, W)))
         return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
     return hip_result(clip_launch_emit(const_cast<float*>(state), img, img_fmt, true, nullptr, B, C, 3, H, W, (hipStream_t)stream), "clip_emit_unit");
+}
+
+// ---- the same on a state stored as bf16 ------------------------------------------------------------------------------------------
+int ncahip_clip_emit_unit_bf16(const uint16_t* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
+    if (int rc = check_clip_emit_unit(state, img, img_fmt, B, C, H, W)) return rc;
+    if (((uintptr_t)state & 1) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: a bf16 state must be 2-byte aligned");
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(uint16_t), img, clip_img_bytes(img_fmt, B, 3, H, W)))
+        return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
+    hipStream_t st = (hipStream_t)stream;
+    if (clip_fmt_planar(img_fmt)) {
+        int32_t k[10];
+        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
+        return hip_result(nca_launch_clip_emit_unit_yuv420_bf16(state, (unsigned char*)img, (img_fmt & 1) == NCAHIP_YUV_NV12, k, B, C, H, W, st), "clip_emit_unit_bf16");
+    }
+    return hip_result(nca_launch_clip_emit_unit_bf16(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, H, W, st), "clip_emit_unit_bf16");
+}
+
+// the fused launch's format word (nca_kernels.h) from an image format of the clip entry points, with the coefficients of a planar one
+static hipError_t cond_launch_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H,
+                                                 int W, int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, hipStream_t st) {
+    int32_t k[10] = {0};
+    int fmt = img_fmt == NCAHIP_CLIP_U8_NHWC ? 1 : 0;
+    if (clip_fmt_planar(img_fmt)) {
+        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
+        fmt = (img_fmt & 1) == NCAHIP_YUV_NV12 ? 3 : 2;
+    }
+    return nca_launch_cond_finalize_emit_bf16(x_pend, pre, x_out, img, fmt, k, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, st);
+}
+
+int ncahip_cond_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H, int W,
+                                   int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
+    const char* const who = "cond_finalize_emit";
+    if (!x_pend || !x_out || !img || (alive_ch >= 0 && !pre)) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
+    if (int rc = check_clip_emit_unit(x_pend, img, img_fmt, B, C, H, W)) return rc;
+    if (alive_ch >= C) return fail(NCAHIP_EINVAL, "%s: bad size (alive_ch=%d outside C=%d)", who, alive_ch, C);
+    if (alive_ch >= 0 && x_pend == x_out) return fail(NCAHIP_EINVAL, "%s: in-place needs alive_ch < 0", who);
+    if ((((uintptr_t)x_pend | (uintptr_t)x_out) & 1) != 0) return fail(NCAHIP_EINVAL, "%s: bf16 states must be 2-byte aligned", who);
+    const size_t sbytes = (size_t)B * C * H * W * sizeof(uint16_t), ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
+    if (clip_overlap(img, ibytes, x_pend, sbytes) || clip_overlap(img, ibytes, x_out, sbytes) || (pre && clip_overlap(img, ibytes, pre, (size_t)B * H * W)) ||
+        (pre && clip_overlap(x_out, sbytes, pre, (size_t)B * H * W)))
+        return fail(NCAHIP_EINVAL, "%s: the image must not overlap x_pend, x_out or pre, and x_out must not overlap pre", who);
+    return hip_result(cond_launch_finalize_emit_bf16(x_pend, pre, x_out, img, img_fmt, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, (hipStream_t)stream),
+                      "cond_finalize_emit_bf16");
 }
 
 // The driver keeps the state in slot 0 or slot 2 of `states` (cur).  A persistent call reads slot cur and writes slot cur ^ 2.  A per-step call
@@ -1042,6 +1104,49 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
     }
     if (cur != 0)   // the state returns in slot 0: the one copy of a call
         return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "cond clip (state copy)");
+    return 0;
+}
+
+// The same loop on a state stored as bf16: the per-step ring of the driver above (there is no persistent bf16 grow), each call's steps
+// enqueued by cond_grow_fwd_impl as ncahip_cond_grow_fwd_bf16 enqueues them, its last launch the fused finalize + image.
+int ncahip_cond_clip_bf16(uint16_t* states, uint8_t* pre, const uint16_t* goal, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
+                          int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
+                          const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                          float clamp_hi, uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
+    const char* const who = "cond clip (bf16)";
+    // host-side checks: nothing is enqueued before all of them have passed
+    if (!pre || !goal) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
+    if (int rc = check_clip_emit_unit(states, images, img_fmt, B, C, H, W)) return rc;
+    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
+    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
+    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
+    // the checks of ncahip_cond_grow_fwd_bf16, with its codes
+    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwdBf16)) return rc;
+    if (int rc = check_bf16_shape(states, states, goal, H, W)) return rc;
+    const bool ubits = u_is_bits(u, seed);
+    if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
+    // W % 4 == 0: every state slot and every frame's goal is 8-byte aligned as slot 0 and goal[0] are
+    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W, gslot = (size_t)B * goal_ch * H * W;
+    const size_t ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
+    const size_t sbytes = 4 * slot * sizeof(uint16_t), pbytes = 2 * pslot, gbytes = (size_t)F * gslot * sizeof(uint16_t), abytes = (size_t)calls * ibytes;
+    if (clip_overlap(states, sbytes, goal, gbytes) || clip_overlap(states, sbytes, images, abytes) || clip_overlap(states, sbytes, pre, pbytes) ||
+        clip_overlap(goal, gbytes, images, abytes) || clip_overlap(goal, gbytes, pre, pbytes) || clip_overlap(images, abytes, pre, pbytes))
+        return fail(NCAHIP_EINVAL, "%s: states, pre, goal and images must not overlap", who);
+    if (int rc = device_error_rc(who)) return rc;
+
+    int cur = 0;   // the slot that holds the state: 0 or 2
+    for (int n = 0; n < (int)calls; ++n) {
+        const int t0 = n * step_n;                                  // first step of this call within `u`
+        const int out = (step_n & 1) ? cur : cur ^ 2;
+        if (int rc = cond_grow_fwd_impl(true, states + (size_t)cur * slot, pre, 2, step_n, states + (size_t)out * slot, goal + (size_t)(n / steps_per_frame) * gslot,
+                                        goal_ch, u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate,
+                                        clamp_lo, clamp_hi, seed, step0 + (uint64_t)t0, stream, (char*)images + (size_t)n * ibytes, img_fmt))
+            return rc;
+        cur = out;
+    }
+    if (cur != 0)   // the state returns in slot 0: the one copy of a call
+        return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot * sizeof(uint16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream),
+                          "cond clip (bf16 state copy)");
     return 0;
 }
 

@@ -6,8 +6,10 @@
 //   the emit kernels with INJ: the image as above and, in the same launch, a grey plane written over state channel C - 1
 // and, for a video encoder behind the clip (include/ncahip.h, "planar YUV images"):
 //   clip_emit_yuv420_kernel   state -> one planar YUV 4:2:0 image (I420 / NV12), the uint8 image's bytes never leaving the registers
+// The three emit kernels also read a ConditionedNCA state stored as bf16 (XT = uint16_t: instantiations of their own; the widening is exact).
 #include "nca_kernels.h"
 #include "nca_clip_u8.h"
+#include "nca_clip_unit.h"
 #include "nca_yuv.h"
 
 namespace {
@@ -120,33 +122,33 @@ __device__ __forceinline__ float clip_image_value(float x) {
     return __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);
 }
 
-// img = clamp(x, 0, 1) as torch.clamp evaluates it on the device (EncoderConditioning/trainer.py:36-39): NaN passes through, then
-// min(max(x, 0), 1)
-__device__ __forceinline__ float clip_unit_value(float x) { return x != x ? x : fminf(fmaxf(x, 0.0f), 1.0f); }
-
 // UNIT selects the image definition: false = clip_image_value (the DyNCA families), true = clip_unit_value (ConditionedNCA)
 template <bool UNIT>
 __device__ __forceinline__ float clip_emit_value(float x) { return UNIT ? clip_unit_value(x) : clip_image_value(x); }
 
+// a state element widened to f32: fp32 as it is; bf16 bits (a ConditionedNCA state stored as bf16) exactly
+__device__ __forceinline__ float clip_ld(const float* x, size_t i) { return x[i]; }
+__device__ __forceinline__ float clip_ld(const uint16_t* x, size_t i) { return __uint_as_float((unsigned)x[i] << 16); }
+
 // One launch for both halves of the step between two calls of an extra-channel clip: EMIT writes the image of x[:, :c_out] into img,
 // INJ copies the plane gray [B,H,W] over channel C - 1 of the same state (xlast = x + (C - 1) * plane; c_out <= C - 1, so the two halves
-// touch different channels).  EMIT alone is the image output of the edge family.
-template <bool EMIT, bool INJ, bool UNIT = false>
-__global__ __launch_bounds__(256) void clip_emit_f32_kernel(const float* __restrict__ x, float* __restrict__ img, float* __restrict__ xlast,
+// touch different channels).  EMIT alone is the image output of the edge family.  XT: the state's element type (clip_ld; uint16_t only without INJ).
+template <bool EMIT, bool INJ, bool UNIT = false, typename XT = float>
+__global__ __launch_bounds__(256) void clip_emit_f32_kernel(const XT* __restrict__ x, float* __restrict__ img, float* __restrict__ xlast,
                                                             const float* __restrict__ gray, int B, int C, int c_out, size_t plane) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nc = (EMIT ? (size_t)c_out : 0) + (INJ ? 1 : 0);
     if (id >= (size_t)B * nc * plane) return;
     const size_t p = id % plane, c = (id / plane) % nc, b = id / (plane * nc);
     if (INJ && c == nc - 1) xlast[b * C * plane + p] = gray[b * plane + p];
-    else img[INJ ? (b * c_out + c) * plane + p : id] = clip_emit_value<UNIT>(x[(b * C + c) * plane + p]);
+    else img[INJ ? (b * c_out + c) * plane + p : id] = clip_emit_value<UNIT>(clip_ld(x, (b * C + c) * plane + p));
 }
 
 // uint8 NHWC: a lane owns 4 consecutive pixels of the flattened [B*H*W] axis = CO dwords, stored whole (bytes only for the last, partial
 // group or an output that is not 4-byte aligned).  (uint8_t)(img * 255): truncation, as np.uint8 in VideoWriter.add.  INJ as above, for
 // the lane's pixels.
-template <int CO, bool INJ, bool UNIT = false>
-__global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
+template <int CO, bool INJ, bool UNIT = false, typename XT = float>
+__global__ __launch_bounds__(256) void clip_emit_u8_kernel(const XT* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
                                                            const float* __restrict__ gray, int B, int C, size_t plane, int aligned) {
     const size_t grp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t npix = (size_t)B * plane, q0 = grp * 4;
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
         const size_t q = q0 + i < npix ? q0 + i : npix - 1;
         const size_t b = q / plane, p = q % plane;
 #pragma unroll
-        for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_emit_value<UNIT>(x[(b * C + c) * plane + p]), 255.0f);
+        for (int c = 0; c < CO; ++c) px[i * CO + c] = (unsigned char)__fmul_rn(clip_emit_value<UNIT>(clip_ld(x, (b * C + c) * plane + p)), 255.0f);
         if (INJ && q0 + i < npix) xlast[b * C * plane + p] = gray[q];
     }
     unsigned char* const o = img + q0 * CO;
@@ -175,8 +177,8 @@ __global__ __launch_bounds__(256) void clip_emit_u8_kernel(const float* __restri
 // 4 consecutive floats of each row of the three channels once, truncates them to the bytes clip_emit_u8_kernel stores and hands them to
 // nca_yuv420_store_block (nca_yuv.h: a dword of Y per row and the chroma under it; halves or bytes where a plane's phase forces them).  The
 // result is bit for bit clip_emit_u8_kernel followed by rgb_to_yuv420_kernel (nca_yuv_out.hip).  INJ as above, for the lane's pixels.
-template <bool NV12, bool INJ, bool UNIT>
-__global__ __launch_bounds__(kYuvOutThreads) void clip_emit_yuv420_kernel(const float* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
+template <bool NV12, bool INJ, bool UNIT, typename XT = float>
+__global__ __launch_bounds__(kYuvOutThreads) void clip_emit_yuv420_kernel(const XT* __restrict__ x, unsigned char* __restrict__ img, float* __restrict__ xlast,
                                                                const float* __restrict__ gray, int C, int H, int W, int bx, size_t lanes, NcaRgbYuvK k) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= lanes) return;
@@ -191,10 +193,10 @@ __global__ __launch_bounds__(kYuvOutThreads) void clip_emit_yuv420_kernel(const 
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const float* const xr = x + (b * C + c) * plane + (size_t)(y + j) * W;
+            const XT* const xr = x + (b * C + c) * plane + (size_t)(y + j) * W;
 #pragma unroll
             for (int i = 0; i < kYuvOutCols; ++i)      // columns past the row's end repeat its last pixel; nothing of them is stored
-                px[c][j][i] = (int)(unsigned char)__fmul_rn(clip_emit_value<UNIT>(xr[min(x0 + i, W - 1)]), 255.0f);
+                px[c][j][i] = (int)(unsigned char)__fmul_rn(clip_emit_value<UNIT>(clip_ld(xr, (size_t)min(x0 + i, W - 1))), 255.0f);
         }
     if (INJ) {
 #pragma unroll
@@ -295,20 +297,28 @@ hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const f
     return hipGetLastError();
 }
 
-// ConditionedNCA's image: clamp(state[:, :3], 0, 1) through the same two kernels (float32 NCHW, or uint8 NHWC with a lane owning four pixels)
-hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
+// ConditionedNCA's image: clamp(state[:, :3], 0, 1) through the same two kernels (float32 NCHW, or uint8 NHWC with a lane owning four pixels);
+// XT = uint16_t: from a state stored as bf16
+template <typename XT>
+static hipError_t clip_launch_emit_unit(const XT* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
     const size_t plane = (size_t)H * W;
     if (!img || C < 3) return hipErrorInvalidValue;
     if (!u8) {
         const size_t n = (size_t)B * 3 * plane;
-        hipLaunchKernelGGL((clip_emit_f32_kernel<true, false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img,
+        hipLaunchKernelGGL((clip_emit_f32_kernel<true, false, true, XT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img,
                            (float*)nullptr, (const float*)nullptr, B, C, 3, plane);
         return hipGetLastError();
     }
     const size_t groups = ((size_t)B * plane + 3) / 4;
-    hipLaunchKernelGGL((clip_emit_u8_kernel<3, false, true>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, state, (unsigned char*)img,
+    hipLaunchKernelGGL((clip_emit_u8_kernel<3, false, true, XT>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, state, (unsigned char*)img,
                        (float*)nullptr, (const float*)nullptr, B, C, plane, ((uintptr_t)img & 3) == 0 ? 1 : 0);
     return hipGetLastError();
+}
+hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
+    return clip_launch_emit_unit(state, img, u8, B, C, H, W, st);
+}
+hipError_t nca_launch_clip_emit_unit_bf16(const uint16_t* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
+    return clip_launch_emit_unit(state, img, u8, B, C, H, W, st);
 }
 
 // The planar image of state[:, :3] (unit: ConditionedNCA's clamp, else the DyNCA families') and, with gray, the inject of the same launch.
@@ -336,5 +346,21 @@ hipError_t nca_launch_clip_emit_yuv420(float* state, unsigned char* img, bool un
         if (nv12) clip_launch_emit_yuv420<true, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
         else clip_launch_emit_yuv420<false, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
     }
+    return hipGetLastError();
+}
+
+// the planar unit image from a state stored as bf16: the same kernel reading bf16 (no inject: that is the DyNCA families')
+hipError_t nca_launch_clip_emit_unit_yuv420_bf16(const uint16_t* state, unsigned char* img, bool nv12, const int* k, int B, int C, int H, int W,
+                                                 hipStream_t st) {
+    if (!img || C < 3 || ((H | W) & 1)) return hipErrorInvalidValue;
+    const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
+    const int bx = (W + kYuvOutCols - 1) / kYuvOutCols;
+    const size_t lanes = (size_t)B * (H / 2) * bx, blocks = (lanes + kYuvOutThreads - 1) / kYuvOutThreads;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks);
+    if (nv12) hipLaunchKernelGGL((clip_emit_yuv420_kernel<true, false, true, uint16_t>), grid, dim3(kYuvOutThreads), 0, st, state, img, (float*)nullptr,
+                                 (const float*)nullptr, C, H, W, bx, lanes, yk);
+    else hipLaunchKernelGGL((clip_emit_yuv420_kernel<false, false, true, uint16_t>), grid, dim3(kYuvOutThreads), 0, st, state, img, (float*)nullptr,
+                            (const float*)nullptr, C, H, W, bx, lanes, yk);
     return hipGetLastError();
 }

@@ -13,8 +13,10 @@
 // LDS layout (ds_read_b32 banks are dword % 32 over 32-lane halves, i.e. MFMA lane groups g = 0, 1 or 2, 3 together): feat and h1 are
 // channel-major planes whose stride is 16 mod 32, so the B reads of one half -- 16 consecutive cells of channel 4k + g and of channel
 // 4k + g + 1 -- fall on disjoint banks.  (The h1 stores of a half go to channels 4 apart, a 2-way conflict: 4 stores per 18 MFMAs.)
-#include "nca_common.h"
-#include "nca_kernels.h"
+//
+// The goal leaves as fp32, or -- for a state stored as bf16 (nca_cond_bf16.hip) -- rounded to bf16 on the final store: the same kernel
+// and arithmetic, one more instantiation per (NEB, U8).
+#include "nca_cond_tile.h"   // StBF16
 #include "nca_clip_u8.h"
 
 namespace {
@@ -35,11 +37,17 @@ static_assert(kImgE <= kClipStageCols, "the image tile row must fit the staged u
 // float(u8) / 255.0f with a true division: ToTensor's range [0, 1], used as it is
 __device__ __forceinline__ float enc_widen_u8(unsigned v) { return __fdiv_rn((float)v, 255.0f); }
 
+// one goal element on its way out: fp32 as it is, or rounded to bf16 (RNE, the rounding of the bf16-storage step) -- the only place
+// where the two goal types differ
+__device__ __forceinline__ void enc_store(float* p, float v) { *p = v; }
+__device__ __forceinline__ void enc_store(uint16_t* p, float v) { *p = (uint16_t)(StBF16::pk2(v, 0.0f) & 0xffffu); }
+
 // NEB: blocks of 16 output channels (E padded to 16 * NEB).  256 threads = 4 waves; wave w works on channel block w % NEB.
-template <int NEB, bool U8>
+// GT: the goal's element type, float or uint16_t (bf16 bits, for a state stored as bf16).
+template <int NEB, bool U8, typename GT>
 __global__ __launch_bounds__(256) void clip_encode_kernel(const void* __restrict__ frames, const float* __restrict__ k3, const float* __restrict__ k5,
                                                           const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-                                                          float* __restrict__ goal, int N, int ch, int E, int H, int W, int tiles_x, int tiles_y) {
+                                                          GT* __restrict__ goal, int N, int ch, int E, int H, int W, int tiles_x, int tiles_y) {
     constexpr int EP = 16 * NEB, KS2 = EP / 4;
     constexpr int kImgFloats = 4 * kImgPlane, kRawFloats = U8 ? kImgE * kRawDwords : 0;
     constexpr int kFront = kImgFloats + kRawFloats, kH1Floats = EP * kH1Stride;
@@ -179,7 +187,7 @@ __global__ __launch_bounds__(256) void clip_encode_kernel(const void* __restrict
     __syncthreads();
 
     // ---- 4. goal on the tile: one group = one row of 16 output cells
-    float* const ob = goal + n * (size_t)E * plane;
+    GT* const ob = goal + n * (size_t)E * plane;
     for (int row = wv / NEB; row < kT; row += 4 / NEB) {
         const float* const hb = s_h1 + lg * kH1Stride + row * kH1E + li;      // tap (0, 0) of this cell, channel g
         f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -194,23 +202,22 @@ __global__ __launch_bounds__(256) void clip_encode_kernel(const void* __restrict
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int e = eb * 16 + 4 * lg + rr;
-                if (e < E) ob[(size_t)e * plane + (size_t)y * W + x] = acc[rr];
+                if (e < E) enc_store(ob + (size_t)e * plane + (size_t)y * W + x, acc[rr]);
             }
         }
     }
 }
 
-template <int NEB>
+template <int NEB, typename GT>
 void clip_encode_launch(bool u8, dim3 grid, hipStream_t st, const void* frames, const float* k3, const float* k5, const float* w1, const float* b1,
-                        const float* w2, float* goal, int N, int ch, int E, int H, int W, int tiles_x, int tiles_y) {
-    if (u8) hipLaunchKernelGGL((clip_encode_kernel<NEB, true>), grid, dim3(256), 0, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
-    else hipLaunchKernelGGL((clip_encode_kernel<NEB, false>), grid, dim3(256), 0, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
+                        const float* w2, GT* goal, int N, int ch, int E, int H, int W, int tiles_x, int tiles_y) {
+    if (u8) hipLaunchKernelGGL((clip_encode_kernel<NEB, true, GT>), grid, dim3(256), 0, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
+    else hipLaunchKernelGGL((clip_encode_kernel<NEB, false, GT>), grid, dim3(256), 0, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
 }
 
-}  // namespace
-
-hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
-                                  float* goal, int N, int ch, int E, int H, int W, hipStream_t st) {
+template <typename GT>
+hipError_t clip_encode_dispatch(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2, GT* goal,
+                                int N, int ch, int E, int H, int W, hipStream_t st) {
     if (ch < 1 || ch > 4 || (u8 && ch != 3) || E < 1 || E > 32) return hipErrorInvalidValue;
     const int tiles_x = (W + kT - 1) / kT, tiles_y = (H + kT - 1) / kT;
     const size_t blocks = (size_t)N * tiles_x * tiles_y;
@@ -219,4 +226,16 @@ hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, 
     if (E <= 16) clip_encode_launch<1>(u8, grid, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
     else clip_encode_launch<2>(u8, grid, st, frames, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, tiles_x, tiles_y);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                                  float* goal, int N, int ch, int E, int H, int W, hipStream_t st) {
+    return clip_encode_dispatch(frames, u8, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, st);
+}
+
+hipError_t nca_launch_clip_encode_bf16(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                                       uint16_t* goal, int N, int ch, int E, int H, int W, hipStream_t st) {
+    return clip_encode_dispatch(frames, u8, k3, k5, w1, b1, w2, goal, N, ch, E, H, W, st);
 }

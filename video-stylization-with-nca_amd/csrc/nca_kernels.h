@@ -269,6 +269,14 @@ hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int
 // E <= 32; w1 [E,3+ch,3,3], b1 [E], w2 [E,E,3,3]; hipErrorInvalidValue outside that range
 hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
                                   float* goal, int N, int ch, int E, int H, int W, hipStream_t st);
+// the same kernel and arithmetic with the goal rounded to bf16 (RNE) on the final store: nca_launch_clip_encode, then a cast
+hipError_t nca_launch_clip_encode_bf16(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
+                                       uint16_t* goal, int N, int ch, int E, int H, int W, hipStream_t st);
+// ConditionedNCA's image from a state stored as bf16: the emit kernels of nca_launch_clip_emit_unit / nca_launch_clip_emit_yuv420 (unit)
+// reading bf16 -- bit for bit their image of the widened state
+hipError_t nca_launch_clip_emit_unit_bf16(const uint16_t* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st);
+hipError_t nca_launch_clip_emit_unit_yuv420_bf16(const uint16_t* state, unsigned char* img, bool nv12, const int* k, int B, int C, int H, int W,
+                                                 hipStream_t st);
 
 // nca_resize.hip: crop + Pillow-exact 8-bit resize of N uint8 frames [N,H,W,3] -> [N,out_h,out_w,3]: horizontal pass into tmp
 // [N,ch,out_w,3], vertical pass into dst.  kx [out_w,ksize_x] / bx [out_w,2] and ky [out_h,ksize_y] / by [out_h,2]: device tables as
@@ -324,6 +332,10 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_step_fwd_bf16(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_finalize_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, int B, int C, int H, int W,
                                          int alive_ch, float thr, float lo, float hi, hipStream_t st);
+// the finalize above and the unit image of its result in ONE launch (C >= 3).  fmt: 0 = float32 [B,3,H,W], 1 = uint8 [B,H,W,3], 2 = I420,
+// 3 = NV12 ([B,3H/2,W]: H and W even, k = nca_rgb_yuv_build_coeffs' ten words in HOST memory; k is not read for fmt 0 and 1)
+hipError_t nca_launch_cond_finalize_emit_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, void* img, int fmt, const int* k, int B, int C, int H,
+                                              int W, int alive_ch, float thr, float lo, float hi, hipStream_t st);
 
 // diagnostic build hook (-DNCA_STAMPS): buffer that receives s_memtime stamps, [wave][tile][8]
 void nca_debug_set_stamp_buffer(unsigned long long* p);

@@ -121,6 +121,11 @@ SIGNATURES = {
     "ncahip_clip_emit_unit": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ncahip_cond_clip_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _U64, _U64,
                              _P, ctypes.c_size_t, ctypes.c_uint, _P],
+    # the ConditionedNCA clip on a bf16 state
+    "ncahip_clip_encode_bf16": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ncahip_clip_emit_unit_bf16": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "ncahip_cond_finalize_emit_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P],
+    "ncahip_cond_clip_bf16": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _U64, _U64, _P],
     "ncahip_resize_ksize": [_I, _I, _I],
     "ncahip_resize_tables": [_I, _I, _I, _P, _P, _I],
     "ncahip_clip_resize_workspace": [_I, _I, _I],

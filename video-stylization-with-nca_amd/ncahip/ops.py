@@ -783,10 +783,14 @@ def encoder_clip_ok(encoder) -> bool:
             and tuple(e2.weight.shape) == (E, E, 3, 3) and e0.padding == (1, 1) and e2.padding == (1, 1))
 
 
-def clip_encode(frames: torch.Tensor, encoder_module) -> torch.Tensor:
+def clip_encode(frames: torch.Tensor, encoder_module, dtype=torch.float32) -> torch.Tensor:
     """frames [F,B,ch,H,W] float32 in [0, 1] or [F,B,H,W,3] uint8 -> goal [F,B,E,H,W] = encoder_module(frame) for every frame in one launch
     (ncahip_clip_encode: fixed filters, 3 x 3 conv + bias + ReLU, 3 x 3 conv, on the exact-f32 MFMA).  Inference only: no gradient.
-    encoder_module: an ncahip.encoder.ImageEncoder that encoder_clip_ok accepts (anything else raises: there is no fallback here)."""
+    encoder_module: an ncahip.encoder.ImageEncoder that encoder_clip_ok accepts (anything else raises: there is no fallback here).
+    dtype=torch.bfloat16: the goal of a bf16 state (ncahip_clip_encode_bf16: the same kernel, the store rounds) -- bit for bit
+    clip_encode(frames, encoder_module).to(torch.bfloat16), without the fp32 goal."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ncahip: clip_encode writes a float32 or bfloat16 goal, got {dtype}")
     if not encoder_clip_ok(encoder_module):
         raise _capi.NcaHipError("ncahip: clip_encode covers ncahip.encoder.ImageEncoder with at most 4 image channels and an embedding of at most 32")
     fmt, F_, B, ch, H, W = _frames_dims(frames)
@@ -797,22 +801,42 @@ def clip_encode(frames: torch.Tensor, encoder_module) -> torch.Tensor:
     k3 = _w(torch.cat((enc.sobel_x.weight, enc.sobel_y.weight, enc.laplacian.weight), dim=0).reshape(-1), "k3", frames)
     k5 = _w(enc.gaussian_blur.weight.reshape(-1), "k5", frames)
     w1, b1, w2 = _w(enc.embed[0].weight, "embed.0.weight", frames), _w(enc.embed[0].bias, "embed.0.bias", frames), _w(enc.embed[2].weight, "embed.2.weight", frames)
-    goal = torch.empty(F_, B, E, H, W, device=frames.device, dtype=torch.float32)
+    goal = torch.empty(F_, B, E, H, W, device=frames.device, dtype=dtype)
     assert goal.numel() * 4 == lib().ncahip_clip_encode_workspace(F_, B, E, H, W)
-    check(lib().ncahip_clip_encode(_p(frames), fmt, _p(k3), _p(k5), _p(w1), _p(b1), _p(w2), _p(goal), F_, B, ch, E, H, W, _stream()), "clip_encode")
+    fn = lib().ncahip_clip_encode if dtype == torch.float32 else lib().ncahip_clip_encode_bf16
+    check(fn(_p(frames), fmt, _p(k3), _p(k5), _p(w1), _p(b1), _p(w2), _p(goal), F_, B, ch, E, H, W, _stream()), "clip_encode")
     return goal
 
 
 def clip_emit_unit(state: torch.Tensor, out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709",
                    yuv_range: str = "limited") -> torch.Tensor:
     """State [B,C,H,W] -> clamp(state[:, :3], 0, 1) as float32 [B,3,H,W], or truncated to uint8 [B,H,W,3] (ncahip_clip_emit_unit).
-    out_format 'i420' / 'nv12' as clip_emit: the uint8 image as planar YUV 4:2:0 [B,3H/2,W]."""
-    x = _dev(state, "state")
+    out_format 'i420' / 'nv12' as clip_emit: the uint8 image as planar YUV 4:2:0 [B,3H/2,W].  A bfloat16 state gives the image of the
+    widened state, bit for bit (ncahip_clip_emit_unit_bf16)."""
+    dt, sfx = _state_dtype(state)
+    x = _dev(state, "state", dt)
     B, C, H, W = x.shape
     spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
     img = spec.images(1, B, x.device)[0]
-    check(lib().ncahip_clip_emit_unit(_p(x), _p(img), spec.fmt, B, C, H, W, _stream()), "clip_emit_unit")
+    fn = lib().ncahip_clip_emit_unit if sfx == "f32" else lib().ncahip_clip_emit_unit_bf16
+    check(fn(_p(x), _p(img), spec.fmt, B, C, H, W, _stream()), "clip_emit_unit")
     return img
+
+
+def cond_finalize_emit(x_pend: torch.Tensor, pre: Optional[torch.Tensor], alive_ch: int = 3, thr: float = 0.1, lo: float = -10.0, hi: float = 10.0,
+                       out_dtype=torch.float32, out_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited"):
+    """cond_finalize and clip_emit_unit of its result in ONE launch, for a bfloat16 pending state (ncahip_cond_finalize_emit_bf16): returns
+    (x_out, image), bit for bit those of the two calls."""
+    x_pend = _dev(x_pend, "x_pend", torch.bfloat16)
+    B, C, H, W = x_pend.shape
+    if pre is not None:
+        pre = _dev(pre, "pre", torch.uint8)
+    spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
+    out = torch.empty_like(x_pend)
+    img = spec.images(1, B, x_pend.device)[0]
+    check(lib().ncahip_cond_finalize_emit_bf16(_p(x_pend), _p(pre), _p(out), _p(img), spec.fmt, B, C, H, W, alive_ch, thr, lo, hi, _stream()),
+          "cond_finalize_emit")
+    return out, img
 
 
 def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w: CondWeights, steps_per_frame: int, step_n: int,
@@ -823,20 +847,28 @@ def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w
     {grow(state, step_n) with goal[f], one image clamp(state[:, :3], 0, 1)}.  us: None (Philox: seed, step0), or the masks / uniforms of all
     F * steps_per_frame * step_n steps.  With persistent_cond the calls go to the one-launch grow where it applies.
     Returns (images [F * steps_per_frame, B, 3, H, W] float32 or [.., B, H, W, 3] uint8, final state [B,C,H,W]).  out_format and images as
-    dynca_clip."""
-    x = _dev(x, "x")
+    dynca_clip.
+    A bfloat16 `x` runs ncahip_cond_clip_bf16 (the bf16-storage steps, the finalize and the image of a call in one launch): it needs a
+    bfloat16 goal (clip_encode(dtype=torch.bfloat16)) and ignores persistent_cond -- there is no persistent bf16 grow."""
+    dt, sfx = _state_dtype(x)
+    x = _dev(x, "x", dt)
     B, C, H, W = x.shape
     spec = ImageSpec.of(out_dtype, out_format, yuv_matrix, yuv_range, 3, H, W)
-    goal = _dev(goal, "goal")
+    goal = _dev(goal, "goal", dt)
     F_, gch = goal.shape[0], goal.shape[2]
     assert goal.shape == (F_, B, gch, H, W) and 0 < gch <= C, (tuple(goal.shape), tuple(x.shape))
     calls = F_ * steps_per_frame
     us, seed = _u_args(us, calls * step_n, B, H, W, seed)
     assert w.c == C
-    states = torch.empty(4, B, C, H, W, device=x.device, dtype=torch.float32)
+    states = torch.empty(4, B, C, H, W, device=x.device, dtype=dt)
     states[0].copy_(x)
     pre = torch.empty(2, B, H, W, device=x.device, dtype=torch.uint8)
     images = spec.images(calls, B, x.device, images)
+    if sfx == "bf16":
+        check(lib().ncahip_cond_clip_bf16(_p(states), _p(pre), _p(goal), gch, _p(images), spec.fmt, F_, steps_per_frame, step_n, _p(us),
+                                          _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
+                                          lo, hi, seed, step0, _stream()), "cond_clip (bf16)")
+        return images, states[0]
     ws, nbytes, epoch = _clip_persist(lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch) if persistent_cond else 0, calls, x.device,
                                       while_capturing=False)
     check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), spec.fmt, F_, steps_per_frame, step_n, _p(us),

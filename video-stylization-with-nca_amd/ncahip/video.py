@@ -553,7 +553,8 @@ stylize_clip.last_download = None
 
 class _CondClip(_Route):
     """stylize_clip_conditioned's clip route: per chunk ncahip_clip_encode, on chunk 0 the warm-up grow with goal[0], the loop's own mask
-    draws grow call by grow call (ConditionedNCA._draw: the generator ends where it would) and one driver call."""
+    draws grow call by grow call (ConditionedNCA._draw: the generator ends where it would) and one driver call.  The state's dtype picks
+    the arithmetic: a bfloat16 `h` (precision='bf16') gets a bfloat16 goal and the bf16-storage steps (ncahip_cond_clip_bf16)."""
     fused = True
 
     def __init__(self, nca, h, k, step_n, warm, spec):
@@ -567,7 +568,7 @@ class _CondClip(_Route):
         draw = lambda steps: None if nca.mask_rng == "philox" else nca._draw(self.h, steps)      # noqa: E731
         chunk = chunk.unsqueeze(1)                                                # [n,1,3,H,W] or [n,1,H,W,3]
         calls = chunk.shape[0] * k
-        goal = ops.clip_encode(chunk, nca.encoder)
+        goal = ops.clip_encode(chunk, nca.encoder, dtype=self.h.dtype)
         if ci == 0 and warm > 0:
             self.h, _, _ = ops.cond_grow(self.h, warm, goal[0], draw(warm), self.w, *self.args, nca.mask_seed, nca._mask_step)
             nca._mask_step += warm
@@ -600,8 +601,8 @@ class _CondLoop(_Route):
 @torch.no_grad()
 def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                              warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8, size=None, crop="conditioned",
-                             resample: str = "lanczos", pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
-                             out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited",
+                             resample: str = "lanczos", precision: str = "f32", pixel_format: str = "rgb24", yuv_matrix: str = "bt709",
+                             yuv_range: str = "limited", out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited",
                              out: Optional[torch.Tensor] = None):
     """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
     loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
@@ -620,6 +621,16 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     ConditionedNCA._draw draws them per grow call, in order, and _mask_step advances as in the loop.  Anything else (a custom encoder, a bf16
     state) runs the loop above in Python.  stylize_clip_conditioned.last_path records the route: 'clip' or 'loop'.
 
+    precision: 'f32' (the default: everything above, a bf16 state included, as it always was) or 'bf16' -- the call runs on a bfloat16
+    state with the bf16-storage steps (include/ncahip.h, "bf16 state storage": state and goal travel as bf16, the UpdateNet runs on bf16
+    MFMA).  state=None seeds as before and casts the seed (exact: zeros and ones); a float32 state is rounded once at entry; a bfloat16
+    state is taken as it is.  The returned state is bfloat16, and passing it back is lossless.  With one sample and an ImageEncoder the
+    fused kernel covers, the chunk runs on the clip route: ncahip_clip_encode_bf16 (the fused encoder, its store rounded), the warm-up
+    grow, then ncahip_cond_clip_bf16, whose last launch per image resolves the state and writes the image in one pass; otherwise the loop
+    above runs on the bfloat16 state.  Mask draws, _mask_step, frames_per_call independence, size=, pixel_format=, out_format= and out=
+    work as with 'f32'.  Needs a model on the GPU with num_channels <= 20 and W % 4 == 0 (what the bf16-storage kernels cover): anything
+    else raises ValueError before any work rather than computing in the other arithmetic.
+
     size=(H, W): decoder-sized frames, as in stylize_clip: uint8 [F,h,w,3] frames only (float frames: ValueError), each chunk uploaded at
     its native size and shrunk on the device by resize_frames(chunk, size, crop, resample) -- the reference's load_image (crop='conditioned',
     Lanczos), bit for bit -- on both routes; seeding, the state check and the images use (H, W).  size=None: crop and resample are not
@@ -634,10 +645,19 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     caller's tensor (a pinned one on a side stream while the next chunk computes), as in stylize_clip;
     stylize_clip_conditioned.last_download records 'overlapped', 'sync' or None."""
     from . import ops
+    if precision not in ("f32", "bf16"):
+        raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
     spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
+    if precision == "bf16":
+        if nca.num_channels > 20:
+            raise ValueError(f"precision='bf16' covers num_channels <= 20 (the bf16-storage step kernels); the model has {nca.num_channels}")
+        if ww % 4:
+            raise ValueError(f"precision='bf16' needs W % 4 == 0 (the bf16-storage step kernels), got W = {ww}")
+        if next(nca.parameters()).device.type != "cuda":
+            raise ValueError(f"precision='bf16' needs a model on the GPU, got {next(nca.parameters()).device}")
     if nca.num_target_channels != 3:
         raise ValueError(f"stylize_clip_conditioned needs an RGB model (num_target_channels == 3), got {nca.num_target_channels}")
     if state is not None and (state.dim() != 4 or state.shape[1] != nca.num_channels or tuple(state.shape[2:]) != (hh, ww)):
@@ -650,7 +670,10 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     _check_out(out, frames.shape[0] * k, spec)
     dev = next(nca.parameters()).device
     h = (nca.generate_seed(1, size=hh) if state is None else state).to(dev)
-    fused = h.is_cuda and h.dtype == torch.float32 and h.shape[0] == 1 and ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3
+    if precision == "bf16":
+        h = h.to(torch.bfloat16)
+    fused = (h.is_cuda and h.dtype == (torch.float32 if precision == "f32" else torch.bfloat16) and h.shape[0] == 1 and
+             ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3)
     route = _CondClip(nca, h, k, step_n, warm, spec) if fused else _CondLoop(nca, h, k, step_n, warm, u8_in)
     return _run_clip(stylize_clip_conditioned, route, frames, shrink, per_call, dev, spec, out)
 
