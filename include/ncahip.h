@@ -372,6 +372,50 @@ int ncahip_dynca_nsteps_bwd_ms_bfmma_f32(const float *states, int T, const float
                                          float *g_x0, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
                                          void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
 
+/* ---- "bf16-MFMA training", the WIDE range: 1 <= C <= 32, 1 <= fc <= 256, single-scale, fp32 state history -------------------------
+ * The contract is the one of "bf16-MFMA training" above, word for word; only the range changes.  The caller records the T + 1
+ * history slots with ncahip_dynca_precision(1) plus ncahip_dynca_bf16_range(1) (ring = T + 1) and hands them to the entry points
+ * below, which read NO process-wide setting: the range is in their names.
+ *   - Inside the narrow range (C <= 16 and fc <= 128) they run the narrow kernels: bit-equal to ncahip_dynca_step_bwd_bfmma_f32,
+ *     ncahip_gram_rows_bf16 and ncahip_dynca_nsteps_bwd_bfmma_f32.  Outside the wide range: NCAHIP_ERANGE, workspace queries 0.
+ *     The narrow entry points keep refusing every shape outside their range.
+ *   - Outside the narrow range the forward's layer-1 pre-activation comes from NcaDyncaBf16<CP,FC,HAS_COND>::layer1
+ *     (csrc/nca_dynca_bf16.h) at the class the forward picks: <32,128> if fc <= 128; else <16,256> if C <= 16; else <32,256>.  The
+ *     backward forms a1 with that class's pack_y / layer1 -- the same K1S, K1Q and chunk order -- so the gate is the forward's bit
+ *     for bit.  It takes the hidden layer in 128-wide slices, one launch per slice (a <16,256> forward as two <16,128> slices, a
+ *     <32,256> forward as two <32,128> slices): y_out is written once, dh_out is the full [B,fc,H,W].
+ *   - dh = W2b^T gb over the 32 channel slots of C > 16 is TWO v_mfma_f32_16x16x16_bf16 products into one accumulator, channels
+ *     0..15 first, then 16..31.  dL/dy = W1b^T dhb sums the hidden units slice by slice: the second slice's accumulators start at
+ *     the first slice's fp32 result; inside a slice the order is the narrow range's.  dW2 | db2 take one K = 32 product per
+ *     16-channel tile and hidden tile.  All of this is fixed and deterministic: two runs give the same bits, and the vector and
+ *     any-shape kernels agree bit for bit.
+ * ncahip_dynca_step_bwd_bfmma_wide_f32: the argument list of ncahip_dynca_step_bwd_bfmma_f32; dh_out [B,fc,H,W] and y_out
+ * [B,4C,H,W] bf16, gw2_out [C*fc + C], so that  dW1 | db1 = ncahip_gram_rows_bf16_wide(dh_out, y_out, cond).
+ * ncahip_gram_rows_bf16_wide: ncahip_gram_rows_bf16 with ma <= 256 and nb = nb1 + nb2 <= 132 -- same arguments, same output layout
+ * [ma x nb | ma row sums], same accumulate flag; operands go from memory straight into v_mfma_f32_16x16x32_bf16, the output is
+ * tiled over blocks of 128 rows x up to 80 columns, the row sums are taken once, the summation order is fixed.
+ * ncahip_dynca_nsteps_bwd_bfmma_wide_f32: argument list, outputs and refusals of ncahip_dynca_nsteps_bwd_bfmma_f32 (null pointer,
+ * T < 1, workspace too small or not 16-byte aligned, aliasing, an attached direction field: all before any launch).             */
+size_t ncahip_dynca_step_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc);
+int ncahip_dynca_step_bwd_bfmma_wide_f32(const float *x_t, const float *cond, const float *u,
+                                         const float *w1, const float *b1, const float *w2, const float *b2,
+                                         int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                         float update_rate, uint64_t seed, uint64_t step,
+                                         const float *g_next, float *g_x, uint16_t *y_out, uint16_t *dh_out,
+                                         float *dy_scratch, float *gw2_out, int accumulate, void *workspace,
+                                         size_t workspace_bytes, ncahip_stream_t stream);
+size_t ncahip_gram_rows_bf16_wide_workspace(int ma, int nb, int B, int HW);
+int ncahip_gram_rows_bf16_wide(const uint16_t *a, int ma, const uint16_t *b1, int nb1, const float *b2, int nb2, int B, int HW,
+                               float *out, int accumulate, void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+size_t ncahip_dynca_nsteps_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc, int c_cond);
+int ncahip_dynca_nsteps_bwd_bfmma_wide_f32(const float *states, int T, const float *cond, const float *u,
+                                           const float *w1, const float *b1, const float *w2, const float *b2,
+                                           int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                           float update_rate, uint64_t seed, uint64_t step0,
+                                           const float *g_final, const float *g_states,
+                                           float *g_x0, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                                           void *workspace, size_t workspace_bytes, ncahip_stream_t stream);
+
 /* Weight-gradient products of the DyNCA backward with the cell axis as K (replaces the library GEMMs over transposed
  * copies that autograd through dynca.py:127-128 amounts to):
  *     out[i*nb + j] = sum over all B*HW cells of a[., i, .] * b[., j, .]     i < ma, j < nb = nb1 + nb2

@@ -1322,11 +1322,13 @@ struct DyncaBwdPlan {
     size_t n, off_g[2], off_y, off_dy, off_dh, off_ws2, off_wsg, off_acc1, off_acc2, off_pc, off_dpc, off_dxc, off_x32, total;
     int grid2, gridg, K1;
 };
-// bfmma: the bf16-MFMA training mode -- y and dh are bf16 (half the floats), the gram partials are nca_gram_bf16_grid slabs
+// bfmma: the bf16-MFMA training mode -- y and dh are bf16 (half the floats), the gram partials are nca_gram_bf16_grid slabs; its buffers
+// hold the whole hidden layer (narrow range: fc <= 128 anyway; wide range: the step launcher slices, dh, the slabs and the accumulators
+// have the full layout and the layer-1 weight gradient is ONE product per step)
 DyncaBwdPlan dynca_bwd_plan(int B, int C, int H, int W, int fc, int c_cond, bool two_scale = false, bool bf16 = false, bool bfmma = false) {
     DyncaBwdPlan p{};
-    p.nsl = (fc + 127) / 128;
-    p.fs = fc < 128 ? fc : 128;
+    p.nsl = bfmma ? 1 : (fc + 127) / 128;
+    p.fs = (bfmma || fc < 128) ? fc : 128;
     p.K1 = 4 * C + c_cond;
     p.n = (size_t)B * C * H * W;
     p.grid2 = two_scale ? nca_dynca_bwd_ms_grid(B, H, W) : nca_dynca_bwd_grid_c(B, C, H, W);
@@ -1366,7 +1368,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
                                 const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                 float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                 float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
-                                size_t workspace_bytes, ncahip_stream_t stream, bool bfmma = false) {
+                                size_t workspace_bytes, ncahip_stream_t stream, bool bfmma = false, bool bfmma_wide = false) {
     const char* const states = (const char*)states_v;
     const bool bf16 = sb == 2;
     if (int rc = dynca_dir_refuse("dynca nsteps bwd")) return rc;
@@ -1377,8 +1379,10 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16): B*C*H*W %% 4 == 0 and 8-byte aligned states required");
     if ((size_t)(128 > 4 * C ? 128 : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    if (bfmma && !nca_dynca_bf16_shape_ok(C, fc))   // bf16-MFMA training mode: the history is a mode-1 one, the backward its own kernels
+    if (bfmma && !bfmma_wide && !nca_dynca_bf16_shape_ok(C, fc))   // bf16-MFMA training mode: the history is a mode-1 one, the backward its own kernels
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16 MFMA): C=%d fc=%d outside the mode's range (C <= 16, fc <= 128)", C, fc);
+    if (bfmma_wide && (!bfmma || two_scale || !nca_dynca_bf16_wide_shape_ok(C, fc) || nca_dynca_bf16_shape_ok(C, fc)))   // (the wide entry point sends narrow shapes to the narrow path)
+        return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16 MFMA, wide): C=%d fc=%d outside the mode's wide range (C <= 32, fc <= 256, single-scale)", C, fc);
     if (two_scale) {
         if (int rc = check_ms(C, H, W, fc, pad_mode, workspace)) return rc;
     }
@@ -1419,7 +1423,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
             if (int rc = hip_result(nca_launch_dynca_coarse_perceive(x_t, pcb, B, C, H, W, pad_mode, st), "dynca nsteps bwd coarse perceive")) return rc;
         }
         for (int sl = 0; sl < p.nsl; ++sl) {
-            const int h0 = sl * 128, fs = fc - h0 < 128 ? fc - h0 : 128;
+            const int h0 = sl * 128, fs = bfmma ? fc : (fc - h0 < 128 ? fc - h0 : 128);
             NcaDyncaArgs a{x_t, nullptr, cond, u_at(u, ubits, t, uslot), w1 + (size_t)h0 * p.K1, b1 + h0, w2 + h0, b2, B, C, H, W,
                            fs, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t, gcur, nullptr, dh, dy, g_out};
             a.w2_ld = fc;
@@ -1427,11 +1431,13 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
             a.gw2_ws = ws2;
             a.pc = pcb;
             a.ybuf = sl == 0 ? y : nullptr;
-            if (bfmma) {   // one slice (fc <= 128); y and dh are bf16 buffers in the same workspace regions
-                if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16(a, st), "dynca nsteps bwd step (bf16 MFMA)")) return rc;
+            if (bfmma) {   // the whole layer (wide range: sliced inside the step launcher); y and dh are bf16 buffers in the same workspace regions
+                if (int rc = hip_result(bfmma_wide ? nca_launch_dynca_step_bwd_mlp_bf16_wide(a, st) : nca_launch_dynca_step_bwd_mlp_bf16(a, st),
+                                        "dynca nsteps bwd step (bf16 MFMA)")) return rc;
                 if (int rc = hip_result(nca_launch_reduce_rows(ws2, acc2, p.grid2, C * fs + C, st, true), "dynca nsteps bwd reduce")) return rc;
-                if (int rc = hip_result(nca_launch_gram_rows_bf16(reinterpret_cast<const uint16_t*>(dh), fs, reinterpret_cast<const uint16_t*>(y), 4 * C,
-                                                                  cond, c_cond, B, H * W, acc1, wsg, st, true), "dynca nsteps bwd gram (bf16 MFMA)")) return rc;
+                const auto gram = bfmma_wide ? nca_launch_gram_rows_bf16_wide : nca_launch_gram_rows_bf16;
+                if (int rc = hip_result(gram(reinterpret_cast<const uint16_t*>(dh), fs, reinterpret_cast<const uint16_t*>(y), 4 * C,
+                                             cond, c_cond, B, H * W, acc1, wsg, st, true), "dynca nsteps bwd gram (bf16 MFMA)")) return rc;
                 continue;
             }
             if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp(a, st, sl > 0), "dynca nsteps bwd step")) return rc;
@@ -1458,7 +1464,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     }
     // accumulators -> gradients in the reference layouts: w1 [fc, K1] rows of a slice are contiguous, w2 [C, fc] columns are not
     for (int sl = 0; sl < p.nsl && e == hipSuccess; ++sl) {
-        const int h0 = sl * 128, fs = fc - h0 < 128 ? fc - h0 : 128;
+        const int h0 = sl * 128, fs = bfmma ? fc : (fc - h0 < 128 ? fc - h0 : 128);
         const float* const s1 = acc1 + (size_t)sl * a1n;
         const float* const s2 = acc2 + (size_t)sl * a2n;
         e = hipMemcpyAsync(g_w1 + (size_t)h0 * p.K1, s1, (size_t)fs * p.K1 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -1593,6 +1599,73 @@ int ncahip_dynca_nsteps_bwd_ms_bfmma_f32(const float* states, int T, const float
                                          size_t workspace_bytes, ncahip_stream_t stream) {
     return dynca_nsteps_bwd_impl(true, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
                                  g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true);
+}
+
+// ---- the wide range of the bf16-MFMA training mode (C <= 32, fc <= 256, single-scale): a narrow shape runs the narrow path -----------
+size_t ncahip_gram_rows_bf16_wide_workspace(int ma, int nb, int B, int HW) {
+    if (ma <= 0 || ma > 256 || nb <= 0 || nb > 132 || B <= 0 || HW <= 0) return 0;
+    return (size_t)nca_gram_bf16_grid(B, HW) * ((size_t)ma * nb + ma) * sizeof(float);
+}
+
+int ncahip_gram_rows_bf16_wide(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
+                               float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!a || !b1 || !out || !workspace || (nb2 > 0) != (b2 != nullptr)) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: null pointer");
+    if (ma <= 0 || nb1 <= 0 || nb2 < 0 || B <= 0 || HW <= 0) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: bad size");
+    const int nb = nb1 + nb2;
+    if (ma > 256 || nb > 132) return fail(NCAHIP_ERANGE, "gram_rows_bf16_wide: ma=%d nb=%d outside (<=256 x <=132)", ma, nb);
+    if ((((uintptr_t)a | (uintptr_t)b1) & 1) != 0 || (((uintptr_t)b2 | (uintptr_t)out | (uintptr_t)workspace) & 3) != 0)
+        return fail(NCAHIP_ERANGE, "gram_rows_bf16_wide: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)");
+    if (workspace_bytes < ncahip_gram_rows_bf16_wide_workspace(ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: workspace too small");
+    return hip_result(nca_launch_gram_rows_bf16_wide(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream, accumulate != 0),
+                      "gram_rows_bf16_wide");
+}
+
+size_t ncahip_dynca_step_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || !nca_dynca_bf16_wide_shape_ok(C, fc)) return 0;
+    return (size_t)nca_dynca_bwd_grid_c(B, C, H, W) * ((size_t)C * fc + C) * sizeof(float);
+}
+
+int ncahip_dynca_step_bwd_bfmma_wide_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
+                                         const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                         float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
+                                         uint16_t* y_out, uint16_t* dh_out, float* dy_scratch, float* gw2_out, int accumulate,
+                                         void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (nca_dynca_bf16_shape_ok(C, fc))   // the narrow range: the narrow entry point, its kernels and its refusals
+        return ncahip_dynca_step_bwd_bfmma_f32(x_t, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, g_x,
+                                               y_out, dh_out, dy_scratch, gw2_out, accumulate, workspace, workspace_bytes, stream);
+    if (int rc = dynca_dir_refuse("dynca step bwd_bfmma_wide")) return rc;
+    if (!g_next || !g_x || !y_out || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: null pointer");
+    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, 256)) return rc;   // NCAHIP_ERANGE beyond C = 32 / fc = 256
+    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: g_next and g_x must not alias");
+    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
+        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma_wide: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
+    if (workspace_bytes < ncahip_dynca_step_bwd_bfmma_wide_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: workspace too small");
+    if (((uintptr_t)workspace & 3) != 0 || (((uintptr_t)y_out | (uintptr_t)dh_out) & 1) != 0)
+        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma_wide: misaligned workspace (4 bytes) or bf16 output (2 bytes)");
+    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
+                   g_next, nullptr, reinterpret_cast<float*>(dh_out), dy_scratch, g_x};
+    a.gw2_ws = (float*)workspace;
+    a.ybuf = reinterpret_cast<float*>(y_out);
+    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
+    a.u_bits = u_is_bits(u, seed);
+    if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16_wide(a, (hipStream_t)stream), "dynca_step_bwd_bfmma_wide")) return rc;
+    if (int rc = hip_result(nca_launch_dynca_step_bwd_stencil(a, (hipStream_t)stream), "dynca_step_bwd_bfmma_wide stencil")) return rc;
+    return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
+                                             (hipStream_t)stream, accumulate != 0), "dynca_step_bwd_bfmma_wide reduce");
+}
+
+size_t ncahip_dynca_nsteps_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc, int c_cond) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_wide_shape_ok(C, fc) || 4 * C + c_cond > 132) return 0;
+    return dynca_bwd_plan(B, C, H, W, fc, c_cond, false, false, true).total;
+}
+int ncahip_dynca_nsteps_bwd_bfmma_wide_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
+                                           const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                                           float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
+                                           float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
+                                           size_t workspace_bytes, ncahip_stream_t stream) {
+    const bool wide = !nca_dynca_bf16_shape_ok(C, fc);   // a narrow shape: exactly ncahip_dynca_nsteps_bwd_bfmma_f32
+    return dynca_nsteps_bwd_impl(false, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true, wide);
 }
 
 // ---- relaxed-EMD part of the OT appearance loss (nca_ot.hip) ---------------------------------------------------------

@@ -4,8 +4,9 @@
 // MFMA sequence per accumulator.  The weight images exist once.  The layer-1 operand packing and MFMA sequence exist TWICE: inside mlp
 // (every forward kernel of the narrow range) and as pack_y / layer1 (the bf16-MFMA backward, and mlp_wide), see the note at layer1; test_gpu_dynca_train_bf16.py compares
 // the two on the device at both shape classes, with and without conditioning.  The narrow range is C <= 16 (one 16-row output tile)
-// and fc <= 128; the wide range (ncahip_dynca_bf16_range 1, forward per-step kernels only: mlp_wide, nca_dynca_bf16_wide.hip) is C <= 32
-// (two output tiles) and fc <= 256.  fc is a multiple of 32 after padding.
+// and fc <= 128; the wide range (ncahip_dynca_bf16_range 1: the forward per-step kernels, mlp_wide, nca_dynca_bf16_wide.hip; and the sliced
+// backward of the training mode, nca_dynca_bwd_bf16_wide.hip, see w2tw_src) is C <= 32 (two output tiles) and fc <= 256.  fc is a multiple
+// of 32 after padding.
 //
 // k order.  v_mfma_f32_16x16x32_bf16 takes eight k values per lane: lane (g, i) supplies k = 8g + j, j = 0..7.
 //   layer 1: lane (g, cell) holds y slots s = 0..K1S-1 (s = 4c'+f < CP: channel 4c'+g, filter f; s = CP: conditioning channel g) --
@@ -197,6 +198,16 @@ struct NcaDyncaBf16 {
         const int jj = idx & 1, l = (idx >> 1) & 63, m = idx >> 7;
         const int ch = 4 * (l >> 4) + 2 * jj + hf, k = 16 * m + (l & 15);
         return (ch < C && k < fc) ? (long)ch * fc + k : -1;
+    }
+    // The wide range of that backward (nca_dynca_bwd_bf16_wide.hip) takes the hidden layer in 128-wide slices at the FORWARD's channel
+    // class: w1_src / w1t_src / pack_y / layer1 above on the slice's rows of w1 and b1 (K1S, K1Q and the chunk order depend on CP and
+    // the conditioning alone, so a slice's a1 has the bits the forward's <CP, 256> class gives those hidden units).  W2^T of a slice
+    // with M2T channel tiles: image [tile m][channel tile t][lane] of 8 bytes, lane (g, i), j  <->  W2[ch = 16t + 4g + j][hidden 16m + i],
+    // rows `ld` apart (the full layer's fc); words idx = ((m * M2T + t) * 64 + lane) * 2 + jj.  dh sums the tiles in the order t = 0, 1.
+    static __device__ __forceinline__ long w2tw_src(int idx, int hf, int C, int fc, int ld) {
+        const int jj = idx & 1, l = (idx >> 1) & 63, e = idx >> 7, t = e % M2T, m = e / M2T;
+        const int ch = 16 * t + 4 * (l >> 4) + 2 * jj + hf, k = 16 * m + (l & 15);
+        return (ch < C && k < fc) ? (long)ch * ld + k : -1;
     }
     static __device__ __forceinline__ long w1t_src(int idx, int hf, int C, int CC, int fc) {
         const int jj = idx & 3, l = (idx >> 2) & 63, e = idx >> 8, mj = e % MJ, p = e / MJ;

@@ -2,7 +2,8 @@
 // one launcher and the one dispatch ladder.  nca_dynca_fwd.hip instantiates the forward variants, nca_dynca_bwd.hip the backward
 // ones, nca_dynca_steer.hip (a unit of its own) the steered forward variants DyncaSteered<V>, nca_dynca_bwd_bf16.hip (a unit of its
 // own) the two bf16-MFMA backward variants, nca_dynca_bf16_wide.hip (a unit of its own) DyncaFwdBf at the three wide shape classes
-// <32, 128>, <16, 256> and <32, 256> (its own small ladder).  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
+// <32, 128>, <16, 256> and <32, 256> (its own small ladder), nca_dynca_bwd_bf16_wide.hip (a unit of its own) the sliced bf16-MFMA backward
+// variants of those classes.  The generic ConditionedNCA step (nca_cond_generic.hip) has the same structure.
 //
 // One persistent launch per NCA step.  A workgroup (4 waves) owns TH x TW cell tiles:
 //   1. the state tile (+1 halo, pad mode resolved at load time; ConditionedNCA: the pending
@@ -90,7 +91,11 @@ struct DyncaCfg {
 //   STEER the perception's Sobel pair rotated by the cell's direction (NcaDyncaArgs::dirs, ncahip_dynca_direction): DyncaSteered<V> of a
 //        forward variant V with fp32 storage.  A switch and not a launch-uniform branch on the pointer: with the branch the unsteered
 //        kernels took up to 60 more registers, and the bf16-MFMA and one-launch kernels spilled ("Steered perception")
-struct DyncaVariant { static constexpr bool BWD = false, B16 = false, ACC = false, W2F = false, MS = false, BF = false, STEER = false; };
+//   SL   bf16-MFMA backward of the wide range (nca_dynca_bwd_bf16_wide.hip): the launch takes one 128-wide SLICE of the hidden layer at
+//        the forward's channel class (one or two 16-channel tiles).  w2, dh_out and the dW2 slabs keep the row stride of the FULL layer
+//        (NcaDyncaArgs::w2_ld), the caller offsets the pointers; with ACC the launch adds to the dL/dy of the earlier slices and leaves
+//        y_out and db2 to the first
+struct DyncaVariant { static constexpr bool BWD = false, B16 = false, ACC = false, W2F = false, MS = false, BF = false, STEER = false, SL = false; };
 template <class V>
 struct DyncaSteered : V { static constexpr bool STEER = true; };   // V steered: nca_dynca_steer.hip instantiates these
 struct DyncaFwd : DyncaVariant {};                                                                  // forward, exact fp32
@@ -107,6 +112,9 @@ struct DyncaBwdW2Acc : DyncaVariant { static constexpr bool BWD = true, W2F = tr
 // nca_dynca_bwd_bf16.hip (a unit of its own) instantiates these two.
 struct DyncaBwdBf : DyncaVariant { static constexpr bool BWD = true, W2F = true, BF = true; };                  // backward, fused dW2, bf16 MFMA
 struct DyncaBwdBfMs : DyncaVariant { static constexpr bool BWD = true, W2F = true, MS = true, BF = true; };    // the same, two-scale
+// the wide range of that mode (nca_dynca_bwd_bf16_wide.hip): one launch per 128-wide slice, the first and the later ones
+struct DyncaBwdBfSl : DyncaVariant { static constexpr bool BWD = true, W2F = true, BF = true, SL = true; };
+struct DyncaBwdBfSlAcc : DyncaVariant { static constexpr bool BWD = true, W2F = true, BF = true, SL = true, ACC = true; };
 
 // BWD = true: the backward data path of the same step (autograd through dynca.py:117-138).  Recomputes the
 // hidden layer, then dh = (W2^T (G*mask)) * 1[h>0] and dL/dy = W1^T dh on MFMA (accumulator tile == next B
@@ -114,12 +122,13 @@ struct DyncaBwdBfMs : DyncaVariant { static constexpr bool BWD = true, W2F = tru
 // (dW2 = (G*mask) h^T, dW1 = dh y^T, K = all cells) are plain library GEMMs on those buffers.
 template <int CP, int FC, bool HAS_COND, int TH, int TW, int NT, bool VEC, typename V>
 __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128)) ? 1 : 2) void dynca_step_fwd_kernel(const NcaDyncaArgs a) {   // CP > 16: 140 KB of LDS -> one workgroup per CU anyway: 512 registers (bf16 MFMA at FC = 256: 85 KB, the same)
-    constexpr bool BWD = V::BWD, B16 = V::B16, ACC = V::ACC, W2F = V::W2F, MS = V::MS, BF = V::BF, STEER = V::STEER;
+    constexpr bool BWD = V::BWD, B16 = V::B16, ACC = V::ACC, W2F = V::W2F, MS = V::MS, BF = V::BF, STEER = V::STEER, SL = V::SL;
     // the wide range of the bf16-MFMA forward (ncahip_dynca_bf16_range 1; nca_dynca_bf16_wide.hip): two output tiles and / or FC = 256
     constexpr bool BFW = BF && (CP > 16 || FC > 128);
     static_assert(!STEER || (!BWD && !B16), "steered: the forward variants with fp32 storage");
     static_assert(!MS || (TH % 2 == 0 && TW % 2 == 0), "the two-scale step: a tile covers whole coarse cells");
-    static_assert(!BFW || (!BWD && !MS && !STEER && !ACC && !B16), "bf16 MFMA, wide range: the plain forward only");
+    static_assert(!BFW || (BWD ? SL : (!MS && !STEER && !ACC && !B16)), "bf16 MFMA, wide range: the plain forward, and the sliced backward");
+    static_assert(!SL || (BWD && BF && W2F && !MS && FC == 128), "slices: the single-scale bf16-MFMA backward, 128 hidden units per launch");
     using K = DyncaCfg<CP, FC, HAS_COND, TH, TW, NT, BF>;
     using Pos = TilePos<TH, TW>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -160,11 +169,15 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128))
         // backward never forms layer 2), W1^T behind the variant's carve; all rounded to bf16 (RNE) here, once.  b2 is not needed.
         using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
         auto bmap_w1 = [&](int idx, int hf) -> long { return BFK::w1_src(idx, hf, C, CC, fc); };
-        auto bmap_w2t = [&](int idx, int hf) -> long { return BFK::w2t_src(idx, hf, C, fc); };
+        auto bmap_w2t = [&](int idx, int hf) -> long {
+            if constexpr (SL) return BFK::w2tw_src(idx, hf, C, fc, a.w2_ld ? a.w2_ld : fc);   // both channel tiles, rows of the full layer
+            else return BFK::w2t_src(idx, hf, C, fc);
+        };
         auto bmap_w1t = [&](int idx, int hf) -> long { return BFK::w1t_src(idx, hf, C, CC, fc); };
-        static_assert(BFK::W2T_WORDS == BFK::W2_WORDS, "W2^T takes the place of the forward's W2 image");
+        constexpr int kW2tWords = (SL ? K::M2T : 1) * BFK::W2T_WORDS;
+        static_assert(kW2tWords == K::W2_FLOATS, "W2^T takes the place of the forward's W2 image");
         FillP<BFK::W1_WORDS> f1;
-        FillP<BFK::W2T_WORDS> f2;
+        FillP<kW2tWords> f2;
         FillP<BFK::W1T_WORDS> f5;
         FillV<FC> f3;
         fill_issue_pk(f1, a.w1, tid, bmap_w1);
@@ -389,6 +402,7 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128))
                 }
             }
             if constexpr (BWD && BF) {
+                if constexpr (!SL) {   // the narrow range; the lines up to the else are as they were (not re-indented): these kernels' streams are held fixed
                 // ---- backward data path on bf16 MFMA ("bf16-MFMA training", include/ncahip.h) -------------------------------
                 // Lane (g, ci) of group n holds, in the accumulator layout throughout: a1 / dh of hidden 16m + 4g + r, gb of channel
                 // 4g + r, dL/dy of (filter g, channel 4mj + r), all of cell ci.  Every operand is rounded once (RNE) and every
@@ -527,6 +541,169 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128))
                         for (int r = 0; r < 4; ++r)
                             if (4 * mj + r < C)
                                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dY[mj][n][r]), rdy, (int)voy, (int)((unsigned)(4 * mj + r) * plane4), 0);
+                }
+                } else {
+                    // ---- the same on one 128-wide slice of a wide layer and K::M2T channel tiles (nca_dynca_bwd_bf16_wide.hip) -------
+                    using BFK = NcaDyncaBf16<CP, FC, HAS_COND>;
+                    // Two channel tiles (CP = 32): gb, db2 and the transposed gb exist per tile t (channels 16t + 4g + r); dh sums the two
+                    // tiles' 16x16x16 products in the order t = 0, 1; dW2 | db2 take one K = 32 product per tile and hidden tile.
+                    static_assert(NT == 2, "dW2 takes the pass's 2 x 16 cells as ONE K = 32 product");
+                    const int fcf = a.w2_ld ? a.w2_ld : fc;   // rows of dh_out per batch item: the full layer's
+                    typedef short nca_s16x4 __attribute__((ext_vector_type(4)));
+                    typedef unsigned nca_u32x2 __attribute__((ext_vector_type(2)));
+                    const nca_u32x4* const W1B = reinterpret_cast<const nca_u32x4*>(W1L) + lane;
+                    const nca_u32x2* const W2T = reinterpret_cast<const nca_u32x2*>(W2L) + lane;
+                    const nca_u32x4* const W1T = reinterpret_cast<const nca_u32x4*>(smem + K::LDS_FLOATS_BWD_W2 + (MS ? 4 * CP * K::PCS : 0)) + lane;
+                    auto lo16 = [](unsigned w) { return __uint_as_float(w << 16); };
+                    auto hi16 = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
+                    bool live[NT];
+                    size_t cello[NT];
+                    nca_u32x2 gbp[K::M2T][NT];      // gb = bf16(g * mask), channels 16t + 4g .. 16t + 4g + 3
+                    unsigned doTp[K::M2T][4];       // the same, transposed: channel 16t + ci of cells (n, 4s + g), k = 4n + s
+#pragma unroll
+                    for (int t = 0; t < K::M2T; ++t) {   // one channel tile at a time through the wave's transposition tiles
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            if (t == 0) {
+                                const int gy = ty0 + r0[n], gx = tx0 + q0[n];
+                                live[n] = gy < H && gx < W;
+                                cello[n] = live[n] ? (size_t)gy * W + gx : 0;
+                            }
+                            const float mk = MK[r0[n] * TW + q0[n]];
+                            const float* const gp = a.g_next + (size_t)b * C * plane + cello[n];
+                            float gm[4];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int ch = 16 * t + 4 * g + r;
+                                const float gv = gp[(size_t)min(ch, C - 1) * plane];
+                                gm[r] = (live[n] && ch < C) ? gv * mk : 0.0f;
+                            }
+                            gbp[t][n] = nca_u32x2{nca_pk_bf16(gm[0], gm[1]), nca_pk_bf16(gm[2], gm[3])};
+                            const f32x4 gr = f32x4{lo16(gbp[t][n][0]), hi16(gbp[t][n][0]), lo16(gbp[t][n][1]), hi16(gbp[t][n][1])};
+                            *reinterpret_cast<f32x4*>(TBW + n * 16 * K::TBS + ci * K::TBS + 4 * g) = gr;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) b2acc[t][r] += gr[r];   // db2 sums the rounded operand
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            float t4[4];
+#pragma unroll
+                            for (int s_ = 0; s_ < 4; ++s_) t4[s_] = TBW[n * 16 * K::TBS + (4 * s_ + g) * K::TBS + ci];
+                            doTp[t][2 * n] = nca_pk_bf16(t4[0], t4[1]);         // exact: the values are bf16 already
+                            doTp[t][2 * n + 1] = nca_pk_bf16(t4[2], t4[3]);
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    }
+                    nca_u32x4 PB[NT][BFK::K1Q];
+                    BFK::template pack_y<NT>(P, PB);
+                    // yb out: slot s = 4c' + f of lane (g, cell) is row f*C + 4c' + g of perceive_torch's output (conditioning slot: not written)
+                    if constexpr (!ACC) {   // later slices: the first one wrote it
+                        uint16_t* const yo = reinterpret_cast<uint16_t*>(a.ybuf) + (size_t)b * 4 * C * plane;
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            if (!live[n]) continue;
+#pragma unroll
+                            for (int s = 0; s < CP; ++s)
+                                if ((s & ~3) + g < C) {
+                                    const unsigned w = PB[n][s >> 3][(s & 7) >> 1];
+                                    yo[(size_t)((s & 3) * C + (s & ~3) + g) * plane + cello[n]] = (uint16_t)((s & 1) ? (w >> 16) : (w & 0xffffu));
+                                }
+                        }
+                    }
+                    uint16_t* const dho = reinterpret_cast<uint16_t*>(a.dhbuf) + (size_t)b * fcf * plane;
+                    f32x4 dY[K::MJ][NT];
+#pragma unroll
+                    for (int mj = 0; mj < K::MJ; ++mj)
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) dY[mj][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if constexpr (ACC) {   // a later slice: the accumulators start at the dL/dy the earlier slices wrote (cells outside the image: cell 0, never stored)
+                        const unsigned pl4 = (unsigned)plane * 4u;
+                        const __amdgpu_buffer_rsrc_t rprev = __builtin_amdgcn_make_buffer_rsrc(a.dybuf + (size_t)b * 4 * C * plane, 0, -1, 0x00020000);
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            const unsigned vprev = (unsigned)cello[n] * 4u + (unsigned)(g * C) * pl4;
+#pragma unroll
+                            for (int mj = 0; mj < K::MJ; ++mj)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r)
+                                    dY[mj][n][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rprev, (int)vprev, (int)((unsigned)min(4 * mj + r, C - 1) * pl4), 0));
+                        }
+                    }
+#pragma unroll
+                    for (int p = 0; p < BFK::M1P; ++p) {
+                        nca_u32x4 dhb[NT];
+#pragma unroll
+                        for (int hf = 0; hf < 2; ++hf) {
+                            const int m = 2 * p + hf;
+                            f32x4 acc1[NT], dacc[NT];
+                            BFK::template layer1<NT>(W1B, B1L, m, g, PB, acc1);
+#pragma unroll
+                            for (int t = 0; t < K::M2T; ++t) {
+                                const nca_u32x2 wt2 = W2T[(m * K::M2T + t) * 64];
+#pragma unroll
+                                for (int n = 0; n < NT; ++n)
+                                    dacc[n] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(nca_s16x4, wt2), __builtin_bit_cast(nca_s16x4, gbp[t][n]),
+                                                                                        t == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : dacc[n], 0, 0, 0);
+                            }
+#pragma unroll
+                            for (int n = 0; n < NT; ++n) {
+                                float hv[4], dv[4];
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) {
+                                    hv[r] = __int_as_float(max(__float_as_int(acc1[n][r]), 0));   // relu, as the forward takes it
+                                    dv[r] = acc1[n][r] > 0.0f ? dacc[n][r] : 0.0f;                // relu' = 0 at exactly 0
+                                }
+                                const unsigned h01 = nca_pk_bf16(hv[0], hv[1]), h23 = nca_pk_bf16(hv[2], hv[3]);
+                                const unsigned d01 = nca_pk_bf16(dv[0], dv[1]), d23 = nca_pk_bf16(dv[2], dv[3]);
+                                dhb[n][2 * hf] = d01;
+                                dhb[n][2 * hf + 1] = d23;
+                                if (live[n]) {
+                                    uint16_t* const o = dho + (size_t)(16 * m + 4 * g) * plane + cello[n];
+                                    if (16 * m + 4 * g + 0 < fc) o[0] = (uint16_t)(d01 & 0xffffu);
+                                    if (16 * m + 4 * g + 1 < fc) o[plane] = (uint16_t)(d01 >> 16);
+                                    if (16 * m + 4 * g + 2 < fc) o[2 * plane] = (uint16_t)(d23 & 0xffffu);
+                                    if (16 * m + 4 * g + 3 < fc) o[3 * plane] = (uint16_t)(d23 >> 16);
+                                }
+                                // hb of the group, for dW2 (cells outside the image and hidden units beyond fc meet gb = 0 / are never read)
+                                *reinterpret_cast<f32x4*>(TBW + n * 16 * K::TBS + ci * K::TBS + 4 * g) = f32x4{lo16(h01), hi16(h01), lo16(h23), hi16(h23)};
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            nca_u32x4 hTp;
+#pragma unroll
+                            for (int n = 0; n < NT; ++n) {
+                                float t4[4];
+#pragma unroll
+                                for (int s_ = 0; s_ < 4; ++s_) t4[s_] = TBW[n * 16 * K::TBS + (4 * s_ + g) * K::TBS + ci];
+                                hTp[2 * n] = nca_pk_bf16(t4[0], t4[1]);
+                                hTp[2 * n + 1] = nca_pk_bf16(t4[2], t4[3]);
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tiles are rewritten by the next hidden tile
+#pragma unroll
+                            for (int t = 0; t < K::M2T; ++t)
+                                w2acc[m][t] = nca_mfma_bf16(nca_u32x4{doTp[t][0], doTp[t][1], doTp[t][2], doTp[t][3]}, hTp, w2acc[m][t]);
+                        }
+#pragma unroll
+                        for (int mj = 0; mj < K::MJ; ++mj) {
+                            const nca_u32x4 wt1 = W1T[(p * K::MJ + mj) * 64];
+#pragma unroll
+                            for (int n = 0; n < NT; ++n) dY[mj][n] = nca_mfma_bf16(wt1, dhb[n], dY[mj][n]);
+                        }
+                    }
+                    // dL/dy out, fp32: tile mj, register r of lane (g, cell) = channel 4mj + r, filter g -> plane g*C + 4mj + r
+                    const unsigned plane4 = (unsigned)plane * 4u;
+                    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(a.dybuf + (size_t)b * 4 * C * plane, 0, -1, 0x00020000);
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+                        if (!live[n]) continue;
+                        const unsigned voy = (unsigned)cello[n] * 4u + (unsigned)(g * C) * plane4;
+#pragma unroll
+                        for (int mj = 0; mj < K::MJ; ++mj)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (4 * mj + r < C)
+                                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dY[mj][n][r]), rdy, (int)voy, (int)((unsigned)(4 * mj + r) * plane4), 0);
+                    }
                 }
             } else if constexpr (BWD) {
                 // ---- backward data path -----------------------------------------------------------------
@@ -856,14 +1033,16 @@ __global__ __launch_bounds__(kThreads, (CP > 16 || V::MS || (V::BF && FC > 128))
                 if (ci == 0) sw[CH * FC + 16 * m2 + 4 * g + r] = v;
             }
         __syncthreads();
-        float* const slab = a.gw2_ws + (size_t)blockIdx.x * ((size_t)C * fc + C);
+        // SL: the slab has the full layer's layout [C x fcw | C]; the caller's gw2_ws points at this slice's first column, db2 is the first slice's
+        const int fcw = SL ? (a.w2_ld ? a.w2_ld : fc) : fc;
+        float* const slab = a.gw2_ws + (size_t)blockIdx.x * ((size_t)C * fcw + C);
         for (int i = tid; i < C * fc; i += kThreads) {
             const int ch = i / fc, hid = i - ch * fc, o = ch * FC + hid;
-            slab[i] = (smem[o] + smem[SW + o]) + (smem[2 * SW + o] + smem[3 * SW + o]);
+            slab[SL ? ch * fcw + hid : i] = (smem[o] + smem[SW + o]) + (smem[2 * SW + o] + smem[3 * SW + o]);
         }
-        if (tid < C) {
+        if (tid < C && !(SL && ACC)) {
             const int o = CH * FC + tid;
-            slab[(size_t)C * fc + tid] = (smem[o] + smem[SW + o]) + (smem[2 * SW + o] + smem[3 * SW + o]);
+            slab[(size_t)C * fcw + tid] = (smem[o] + smem[SW + o]) + (smem[2 * SW + o] + smem[3 * SW + o]);
         }
     }
 }

@@ -228,6 +228,12 @@ hipError_t nca_launch_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* 
                                      float* out, float* ws, hipStream_t st, bool accumulate = false);
 // nca_dynca_bwd_bf16.hip: MLP part of one backward step in the bf16-MFMA training mode (ybuf / dhbuf point at bf16 buffers)
 hipError_t nca_launch_dynca_step_bwd_mlp_bf16(const NcaDyncaArgs& a, hipStream_t st);
+// nca_dynca_bwd_bf16_wide.hip: the same in the wide range (C <= 32, fc <= 256, outside the narrow one; single-scale): one launch per 128-wide
+// slice at the forward's channel class; dhbuf [B,fc,H,W] and the gw2_ws slabs [C*fc + C] have the whole layer's layout
+hipError_t nca_launch_dynca_step_bwd_mlp_bf16_wide(const NcaDyncaArgs& a, hipStream_t st);
+// nca_gram_bf16.hip: nca_launch_gram_rows_bf16 up to ma <= 256, nb1 + nb2 <= 132 (inside the old range: that launcher itself)
+hipError_t nca_launch_gram_rows_bf16_wide(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
+                                          float* out, float* ws, hipStream_t st, bool accumulate = false);
 hipError_t nca_launch_reduce_wp(const float* part, float* dst, int B, int C, int H, int W, hipStream_t st);
 // nca_ot.hip: relaxed-EMD part of the OT appearance loss (gather / normalise, N x N cosine distances reduced in registers, adjoints)
 int nca_ot_bands(int N);   // column-minimum partials per column (one per 32-row band)

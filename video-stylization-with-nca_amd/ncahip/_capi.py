@@ -88,6 +88,15 @@ SIGNATURES = {
     "ncahip_dynca_nsteps_bwd_ms_bfmma_workspace": [_I, _I, _I, _I, _I, _I],
     "ncahip_dynca_nsteps_bwd_ms_bfmma_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P, _P, _P, _P, _P, _P,
                                              _P, ctypes.c_size_t, _P],
+    # the wide range of that mode (C <= 32, fc <= 256, single-scale)
+    "ncahip_gram_rows_bf16_wide_workspace": [_I, _I, _I, _I],
+    "ncahip_gram_rows_bf16_wide": [_P, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, ctypes.c_size_t, _P],
+    "ncahip_dynca_step_bwd_bfmma_wide_workspace": [_I, _I, _I, _I, _I],
+    "ncahip_dynca_step_bwd_bfmma_wide_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P, _P, _P, _P, _P, _I, _P,
+                                             ctypes.c_size_t, _P],
+    "ncahip_dynca_nsteps_bwd_bfmma_wide_workspace": [_I, _I, _I, _I, _I, _I],
+    "ncahip_dynca_nsteps_bwd_bfmma_wide_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _U64, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, ctypes.c_size_t, _P],
     "ncahip_cond_grow_bwd_workspace": [_I, _I, _I, _I, _I],
     "ncahip_cond_grow_bwd_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F,
                                  _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -145,6 +154,8 @@ _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ct
              "ncahip_clip_cond_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_bf16_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_bfmma_workspace": ctypes.c_size_t,
              "ncahip_dynca_nsteps_bwd_bfmma_workspace": ctypes.c_size_t, "ncahip_dynca_nsteps_bwd_ms_bfmma_workspace": ctypes.c_size_t,
+             "ncahip_gram_rows_bf16_wide_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_bfmma_wide_workspace": ctypes.c_size_t,
+             "ncahip_dynca_nsteps_bwd_bfmma_wide_workspace": ctypes.c_size_t,
              "ncahip_clip_encode_workspace": ctypes.c_size_t, "ncahip_clip_resize_workspace": ctypes.c_size_t}
 
 _lib = None

@@ -139,18 +139,24 @@ class _DyncaNSteps(torch.autograd.Function):
 
 
 def dynca_train_precision(model, x) -> str:
-    """The precision a differentiated forward_nsteps of `model` on state `x` runs in: the model's train_precision where the bf16-MFMA
-    training mode covers the shape (ops.dynca_bf16_ok), "f32" otherwise -- outside the range the setting is ignored, forward and
-    backward are then the exact ones.  Where the mode WOULD be selected, a bfloat16 pool raises: bf16 state storage is outside the mode
-    (outside the range the setting is ignored for a bfloat16 pool as for any other, and dynca_nsteps_autograd asks only when it
-    differentiates)."""
+    """The precision a differentiated forward_nsteps of `model` on state `x` runs in: "bf16" where the model's train_precision is
+    "bf16" or "bf16_wide" and the shape is inside the narrow range of the bf16-MFMA training mode (ops.dynca_bf16_ok); "bf16_wide" where
+    it is "bf16_wide", the shape is outside the narrow and inside the wide range (ops.dynca_bf16_wide_ok) and the model is single-scale;
+    "f32" otherwise -- there the setting is ignored, forward and backward are the exact ones.  Where the mode WOULD be selected, a
+    bfloat16 pool raises: bf16 state storage is outside the mode (elsewhere the setting is ignored for a bfloat16 pool as for any
+    other, and dynca_nsteps_autograd asks only when it differentiates)."""
     want = getattr(model, "train_precision", "f32")
-    if want != "bf16" or not ops.dynca_bf16_ok(x.shape[1], model.w1.weight.shape[0]):
+    C, fc = x.shape[1], model.w1.weight.shape[0]
+    if want in ("bf16", "bf16_wide") and ops.dynca_bf16_ok(C, fc):
+        eff = "bf16"
+    elif want == "bf16_wide" and ops.dynca_bf16_wide_ok(C, fc) and list(getattr(model, "perception_scales", [0])) == [0]:
+        eff = "bf16_wide"
+    else:
         return "f32"
     if x.dtype == torch.bfloat16:
-        raise ValueError("ncahip: train_precision='bf16' (bf16-MFMA training) takes a float32 state; a bfloat16 pool is bf16 STORAGE, "
+        raise ValueError(f"ncahip: train_precision={want!r} (bf16-MFMA training) takes a float32 state; a bfloat16 pool is bf16 STORAGE, "
                          "which that mode does not cover")
-    return "bf16"
+    return eff
 
 
 def dynca_nsteps_autograd(model, x, cond, T, update_rate, want_states=False, two_scale=False):

@@ -31,7 +31,7 @@ class DyNCATrainer:
                  inject_seed_step: int = 8, device: Optional[torch.device] = None, reseed_offset: int = 424,
                  train_precision: Optional[str] = None):
         self.model, self.loss_fn = model, loss_fn
-        if train_precision is not None:       # "f32" / "bf16" (bf16-MFMA training, models.dynca.DyNCA.train_precision); None: the model's own
+        if train_precision is not None:       # "f32" / "bf16" / "bf16_wide" (bf16-MFMA training, models.dynca.DyNCA.train_precision); None: the model's own
             model.train_precision = train_precision
         self.device = device if device is not None else next(model.parameters()).device
         self.size, self.batch_size = size, batch_size

@@ -110,8 +110,10 @@ class DyNCA(nn.Module):
 
     # Precision of a DIFFERENTIATED forward_nsteps / forward (autograd.dynca_nsteps_autograd): "f32" (default) = the exact kernels,
     # "bf16" = the bf16-MFMA training mode of include/ncahip.h (mode-1 forward history, backward on bf16 MFMA) where C <= 16 and
-    # fc <= 128, ignored elsewhere.  Per model, no process-wide state; the ambient ops.dynca_precision does not reach autograd.
-    TRAIN_PRECISIONS = ("f32", "bf16")
+    # fc <= 128, ignored elsewhere; "bf16_wide" = that, and the mode's wide range (single-scale models up to C = 32 / fc = 256: the
+    # forward records under ops.dynca_precision("bf16_wide")), ignored beyond it (autograd.dynca_train_precision).  Per model, no
+    # process-wide state; the ambient ops.dynca_precision does not reach autograd.
+    TRAIN_PRECISIONS = ("f32", "bf16", "bf16_wide")
 
     @property
     def train_precision(self):
@@ -120,7 +122,7 @@ class DyNCA(nn.Module):
     @train_precision.setter
     def train_precision(self, value):
         if value not in DyNCA.TRAIN_PRECISIONS:
-            raise ValueError(f"train_precision must be 'f32' or 'bf16', got {value!r}")
+            raise ValueError(f"train_precision must be 'f32', 'bf16' or 'bf16_wide', got {value!r}")
         self._train_precision = value
 
     # ------------------------------------------------------------------ helpers

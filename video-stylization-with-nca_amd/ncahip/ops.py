@@ -105,7 +105,7 @@ def set_cond_precision(mode) -> None:
     check(lib().ncahip_cond_precision({"exact": 0, "bf16x3": 1}.get(mode, mode)), "cond_precision")
 
 
-_DYNCA_PRECISIONS = ("f32", "bf16")         # ncahip_dynca_precision modes 0 / 1 (what the backward's `precision` takes)
+_DYNCA_PRECISIONS = ("f32", "bf16", "bf16_wide")   # what the backward's `precision` takes: exact, bf16-MFMA training, its wide range
 # the forward's names: (ncahip_dynca_precision mode, ncahip_dynca_bf16_range) pairs
 _DYNCA_FWD_PRECISIONS = {"f32": (0, 0), "bf16": (1, 0), "bf16_wide": (1, 1)}
 _dynca_precision_lock = threading.RLock()
@@ -941,11 +941,18 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
     one caller-owned workspace.  g_final must already include any cotangent of x_T itself; g_states (optional, [T+1,...])
     adds dL/dx_t cotangents of the intermediate states t < T (forward_nsteps' return_middle_feature).
     precision="bf16": the bf16-MFMA training mode (ncahip_dynca_nsteps_bwd_bfmma_f32 / _ms_bfmma_f32, contract in include/ncahip.h):
-    `states` must be a float32 history recorded under dynca_precision("bf16"), C <= 16 and fc <= 128.  The ambient dynca_precision
-    plays no part here.
+    `states` must be a float32 history recorded under dynca_precision("bf16"), C <= 16 and fc <= 128.  precision="bf16_wide": the wide
+    range of that mode (ncahip_dynca_nsteps_bwd_bfmma_wide_f32): single-scale, C <= 32 and fc <= 256, a float32 history recorded under
+    dynca_precision("bf16_wide"); inside the narrow range that entry point runs the narrow kernels, bit for bit precision="bf16" (with
+    two_scale=True the narrow two-scale driver is called; two_scale=True at a wide-only shape raises ValueError).  The ambient
+    dynca_precision plays no part here.
     Returns dict x0, w1 [fc,4C+cc], b1, w2 [C,fc], b2."""
     if precision not in _DYNCA_PRECISIONS:
-        raise ValueError(f"dynca backward precision must be 'f32' or 'bf16', got {precision!r}")
+        raise ValueError(f"dynca backward precision must be 'f32', 'bf16' or 'bf16_wide', got {precision!r}")
+    if precision == "bf16_wide" and two_scale:      # the wide entry point is single-scale; a narrow two-scale model has the narrow mode's driver
+        if not dynca_bf16_ok(states.shape[2], w.fc):
+            raise ValueError("ncahip: the wide range of the bf16-MFMA DyNCA backward is single-scale (two_scale=True needs C <= 16 and fc <= 128)")
+        precision = "bf16"
     dt, dsfx = _state_dtype(states)      # bfloat16 history: ncahip_dynca_nsteps_bwd_bf16 (storage format only, fp32 gradients)
     states, g = _dev(states, "states", dt), _dev(g_final.float(), "g_final")
     _, B, C, H, W = states.shape
@@ -974,6 +981,12 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
         if not dynca_bf16_ok(C, fc):
             raise _capi.NcaHipError(f"ncahip: the bf16-MFMA DyNCA backward covers C <= 16 and fc <= 128, got C={C} fc={fc}")
         fn, wsfn = f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_f32", f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_workspace"
+    if precision == "bf16_wide":
+        if dsfx == "bf16":
+            raise _capi.NcaHipError("ncahip: the bf16-MFMA DyNCA backward takes a float32 history (bf16 state storage is out of its scope)")
+        if not dynca_bf16_wide_ok(C, fc):
+            raise _capi.NcaHipError(f"ncahip: the wide bf16-MFMA DyNCA backward covers C <= 32 and fc <= 256, got C={C} fc={fc}")
+        fn, wsfn = "ncahip_dynca_nsteps_bwd_bfmma_wide_f32", "ncahip_dynca_nsteps_bwd_bfmma_wide_workspace"
     nbytes = getattr(lib(), wsfn)(B, C, H, W, fc, c_cond)
     ws = _workspace(nbytes, dev)
     check(getattr(lib(), fn)(_p(states), T, _p(cond), _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, H, W, fc,
