@@ -99,8 +99,8 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     static_assert(!FW || FC, "fire words: the kernels with firing-cell lists");
     static_assert(!MS || (CARRY && FW && kNtStore), "several steps per launch: the narrow-carve fire-word kernels, write-through stores");
     constexpr int AUX = MS ? 16 : kAuxCoherent;   // cache policy of the state-type accesses (issue_loads)
-    // MS: `a` is the view of the step a wave is working on -- the producer refills its part from the wave's words in LDS before every
-    // tile (view_in below), the consumer's part, x_out, changes at a step boundary (next_step); otherwise the launch's arguments themselves
+    // MS: `a` is the view of the step a wave is working on -- its pointers are formed where a tile needs them (view_in / view_out below)
+    // from two scalars of the wave and the launch's arguments; otherwise the launch's arguments themselves
     [[maybe_unused]] NcaCondArgs a_step;
     if constexpr (MS) a_step = a_launch;
     const NcaCondArgs& a = MS ? a_step : a_launch;
@@ -212,61 +212,86 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     };
     int tile_no = 0;
     // ---- MS: the step a wave is at, the gate and the publication ---------------------------------------------------------------
-    // What a wave needs only at a step boundary (the walk's first position, the ring's bases, the step counts) and the producer's
-    // view of its step wait in LDS, on the dead W1 / W2 images above the four carries (valid once the consumers hold the weights in
-    // registers: the second barrier).  The consumer's tile loop reads none of it: an LDS round trip there is exposed time, so what
-    // it needs per tile (x_out, the counter value, its unpublished tiles) stays in registers.
+    // What a wave needs only at a step boundary (the walk's first position) waits in LDS, on the dead W1 / W2 images above the four
+    // carries (valid once the consumers hold the weights in registers: the second barrier).  The step itself is two 32-bit scalars
+    // per wave: `step`, the step of the launch, and `ring_in`, the ring index of its input slot, (ms_t0 + step) mod ms_ring, advanced
+    // by compare-and-reset at a step boundary.  The pointers of the step -- cond_grow_fwd_impl's step_args -- are formed from these two
+    // and the launch's own arguments at the point of use, on the scalar ALU, and the two are opaque there: a pointer carried across
+    // the tile loop is a 64-bit value the compiler parks in VGPR lanes and reads back in the middle of a tile, a kernel argument is
+    // re-loaded.  The consumer's tile loop reads no LDS word for it: a round trip there is exposed time.
     constexpr int kCarrySize = [] { if constexpr (CARRY) return FireCarry<CP>::SIZE; else return 0; }();
     [[maybe_unused]] int step = 0, gbase = 0;   // MS: step of the launch, and its first round's number (rounds count on across steps)
+    [[maybe_unused]] int ring_in = 0;           // MS: ring slot the step reads
+    if constexpr (MS) ring_in = a_launch.ms_t0 % a_launch.ms_ring;   // the launch's only division besides the walk's
     typedef __attribute__((address_space(1))) unsigned gu32;   // a counter is a global agent-scope access, never a flat or plain one
-    constexpr int kMsList = 64, kMsWave = 24, kMsPair = 2 * kMsWave;   // unpublished tiles a consumer can hold (its lanes); words per wave, per pair
+    constexpr int kMsList = 64, kMsWave = 8, kMsPair = 2 * kMsWave;   // unpublished tiles a consumer can hold (its lanes); words per wave, per pair
     static_assert(!MS || 4 * (kCarrySize + kMsPair) <= K::OFF_W3, "carries and the MS state fit on the W1 / W2 images");
     [[maybe_unused]] int* const WS_ = reinterpret_cast<int*>(smem) + 4 * kCarrySize + pair * kMsPair + (producer ? kMsWave : 0);   // this wave's words
-    enum { MS_R = 0, MS_T, MS_SX, MS_SY, MS_B, MS_NSTEPS, MS_T0, MS_RING, MS_RIN, MS_STATES, MS_PRE = MS_STATES + 2, MS_XIN = MS_PRE + 2,
-           MS_PIN = MS_XIN + 2, MS_XOUT = MS_PIN + 2, MS_POUT = MS_XOUT + 2, MS_FW = MS_POUT + 2, MS_END = MS_FW + 2 };
+    enum { MS_R = 0, MS_T, MS_SX, MS_SY, MS_B, MS_END };
     static_assert(MS_END <= kMsWave, "a wave's words");
     [[maybe_unused]] auto ms_get = [&](int i) -> int { return __builtin_amdgcn_readfirstlane(WS_[i]); };
-    [[maybe_unused]] auto ms_get64 = [&](int i) -> size_t { return (size_t)(unsigned)ms_get(i) | ((size_t)(unsigned)ms_get(i + 1) << 32); };
     [[maybe_unused]] gu32* const done = reinterpret_cast<gu32*>((uintptr_t)a_launch.ms_done);
     [[maybe_unused]] const int tgh = H >> 2, tgw = W >> 4;     // the counters' grid (whole 4 x 16 tiles: FW)
-    [[maybe_unused]] auto ms_put64 = [&](int i, size_t v) { WS_[i] = (int)(unsigned)v, WS_[i + 1] = (int)(unsigned)(v >> 32); };   // one lane
-    // the step's view: what the producer reads and writes / where the consumer stores
+    // the producer's view: what the tile's loads read (x_in, pre_in -- none at the grow's step 0 --, the step's fire words) and
+    // where its pre mask bytes go
     [[maybe_unused]] auto view_in = [&]() {
-        a_step.x_in = reinterpret_cast<const float*>(ms_get64(MS_XIN));
-        a_step.pre_in = reinterpret_cast<const uint8_t*>(ms_get64(MS_PIN));
-        a_step.pre_out = reinterpret_cast<uint8_t*>(ms_get64(MS_POUT));
-        a_step.fire_words = reinterpret_cast<const unsigned long long*>(ms_get64(MS_FW));
+        int s = step, ri = ring_in;
+        asm volatile("" : "+s"(s), "+s"(ri));
+        const size_t pslot = (size_t)a_launch.B * a_launch.H * a_launch.W, slot = pslot * (size_t)a_launch.C * 4u;
+        const int ro = ri + 1 == a_launch.ms_ring ? 0 : ri + 1;
+        a_step.x_in = reinterpret_cast<const float*>(a_launch.ms_states + (size_t)ri * slot);
+        a_step.pre_in = a_launch.ms_t0 + s == 0 ? nullptr : a_launch.ms_pre + (size_t)ri * pslot;
+        a_step.pre_out = a_launch.ms_pre + (size_t)ro * pslot;
+        a_step.fire_words = a_launch.fire_words + (size_t)s * (pslot >> 6);
+        // the channel counts the loads' predicates compare with: opaque too, or every comparison is hoisted out of the tile loop as a
+        // 64-bit lane mask of its own, parked in VGPR lanes with the rest
+        int gc = a_launch.goal_ch, ac = a_launch.alive_ch;
+        asm volatile("" : "+s"(gc), "+s"(ac));
+        a_step.goal_ch = gc;
+        a_step.alive_ch = ac;
     };
-    // the next step of the launch: ring slots as cond_grow_fwd_impl's step_args chooses them (never the grow's step 0: a pre mask comes in)
+    // the consumer's view: where the step's state goes
+    [[maybe_unused]] auto view_out = [&]() {
+        int ri = ring_in;
+        asm volatile("" : "+s"(ri));
+        const size_t slot = (size_t)a_launch.B * a_launch.H * a_launch.W * (size_t)a_launch.C * 4u;
+        const int ro = ri + 1 == a_launch.ms_ring ? 0 : ri + 1;
+        a_step.x_out = reinterpret_cast<float*>(a_launch.ms_states + (size_t)ro * slot);
+    };
+    // the next step of the launch
     [[maybe_unused]] auto next_step = [&]() {
-        const size_t slot = (size_t)a_launch.B * C * H * W * 4u, pslot = (size_t)a_launch.B * H * W;
-        const int ring = ms_get(MS_RING);
-        int ring_in = ms_get(MS_RIN) + 1;
-        if (ring_in == ring) ring_in = 0;
-        const size_t ring_out = ring_in + 1 == ring ? 0 : ring_in + 1;
-        const size_t x_in = ms_get64(MS_XOUT), pre_in = ms_get64(MS_POUT), fw = ms_get64(MS_FW) + (pslot >> 6) * sizeof(unsigned long long);
-        const size_t x_out = ms_get64(MS_STATES) + ring_out * slot, pre_out = ms_get64(MS_PRE) + ring_out * pslot;
-        if (lane == 0) {
-            WS_[MS_RIN] = ring_in;
-            ms_put64(MS_XIN, x_in), ms_put64(MS_PIN, pre_in), ms_put64(MS_XOUT, x_out), ms_put64(MS_POUT, pre_out), ms_put64(MS_FW, fw);
-        }
-        wave_sync();
-        a_step.x_out = reinterpret_cast<float*>(x_out);   // the consumer's only use of the view: kept in registers (the producer refills its view per tile)
+        ++step;
+        gbase += n_rounds;
+        if (++ring_in == a_launch.ms_ring) ring_in = 0;
     };
     // Producer gate of tile t for a step with `need` earlier steps in the grow: lanes 0..8 read the counters of the 3 x 3 tile
     // neighbourhood (same batch item; the tile itself included), lane 9 (and a lane whose neighbour lies outside the image) the abort
     // word.  The wait that makes this step's reads correct also makes its writes safe: the tile's output overwrites the ring slot its
     // neighbours READ one step earlier (ring == 2; a longer ring only moves that slot further away), and they have published that
     // step -- every load of it long retired -- before the tile is even staged.
+    // The first look is taken BEFORE the producer waits for its tile buffer (gate_look, ahead of await(1, ...)): one round trip beyond
+    // the L2 off the path between "buffer free" and "loads issued".  Within a grow the counters only grow and the abort word is sticky
+    // (only the grow's first fire-word launch zeroes them, before any step launch), so a look that finds the gate open is as good
+    // later; a look that finds it closed falls into the poll loop.  The tile's loads stay behind the check either way.
     constexpr int kGateSpins = 1 << 17;   // x (one L2 round trip + s_sleep 16): some 0.2 s, against waits of at most a few steps
-    [[maybe_unused]] auto gate = [&](const WTile& t, int step_no) {
-        const unsigned need = (unsigned)(ms_get(MS_T0) + step_no);
+    struct GateLook { gu32* p; bool nb; unsigned v; };
+    [[maybe_unused]] auto gate_look = [&](const WTile& t) -> GateLook {
         const int dy = (lane >= 3) + (lane >= 6) - 1, dx = lane - 3 * (dy + 1) - 1;
         const int ny = (t.ty0 >> 2) + dy, nx = (t.tx0 >> 4) + dx;
         const bool nb = lane < 9 && ny >= 0 && ny < tgh && nx >= 0 && nx < tgw;
         const unsigned ntile = (unsigned)(a_launch.B * tgh * tgw);
-        gu32* const p = done + (nb ? (unsigned)((t.b * tgh + ny) * tgw + nx) : ntile);
-        for (int spins = 0;;) {
+        GateLook g{done + (nb ? (unsigned)((t.b * tgh + ny) * tgw + nx) : ntile), nb, 0u};
+        if (lane < 10) g.v = __hip_atomic_load(g.p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return g;
+    };
+    [[maybe_unused]] auto gate = [&](const GateLook& g, int step_no) {
+        const unsigned need = (unsigned)(a_launch.ms_t0 + step_no);
+        const unsigned ntile = (unsigned)(a_launch.B * tgh * tgw);
+        gu32* const p = g.p;
+        const bool nb = g.nb;
+        const bool early = __builtin_amdgcn_ballot_w64(lane < 10 && !nb && g.v != 0u) != 0ull ||   // some gate gave up: drain, no polling
+                           __builtin_amdgcn_ballot_w64(nb && g.v < need) == 0ull;
+        if (!early) for (int spins = 0;;) {
             unsigned v = need;
             if (lane < 10) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__builtin_amdgcn_ballot_w64(lane < 10 && !nb && v != 0u) != 0ull) break;   // some gate gave up: drain, no polling
@@ -288,6 +313,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     // 60 -> 64 us bf16: border tiles force waits inside the issue sequence, and the producer is off the critical path.)
     auto produce = [&](const WTile& t, int which) {
         if (!t.valid) return;
+        if constexpr (MS) view_in();
         TileRegs<CP, ST> R;
         const TileLds L = lds_of(which);
         if (t.inner) {
@@ -431,6 +457,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                     for (int k = 0; k < 4; ++k) L.XR[(4 * g + k) * XRS + xcell] = CX[(4 * g + k) * KC::XCS + col];
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if constexpr (MS) view_out();
                 store_carry<CP, EXACT, kNtStore>(a, CX, lane, old, *CPIX, *CBAT);
                 if (old && has) park_x();
                 carry_n = flush ? 0 : carry_n + rem - 16;
@@ -476,6 +503,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
 #ifdef NCA_STAMPS
         if (a.seed == 0xD1ACull || a.seed == 0xD1ADull || a.seed == 0xD1AEull) return;   // diagnostic knob: no store (0xD1AE: nothing else changed)
 #endif
+        if constexpr (MS) view_out();
         if (t.inner) store_tile<CP, false, EXACT, kNtStore && !BF, ST>(a, t, L.XR, lane);   // bf16 rows are 32-byte segments: let the L2 merge them
         else store_tile<CP, true, EXACT, kNtStore && !BF, ST>(a, t, L.XR, lane);
         NCA_STAMP(8);
@@ -488,11 +516,6 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
     [[maybe_unused]] auto ms_save = [&]() {
         if (lane == 0) {
             WS_[MS_R] = pos.r, WS_[MS_T] = pos.t, WS_[MS_SX] = pos.sx, WS_[MS_SY] = pos.sy, WS_[MS_B] = pos.b;
-            WS_[MS_NSTEPS] = a_launch.ms_steps, WS_[MS_T0] = a_launch.ms_t0, WS_[MS_RING] = a_launch.ms_ring;
-            WS_[MS_RIN] = a_launch.ms_t0 % a_launch.ms_ring;
-            ms_put64(MS_STATES, (uintptr_t)a_launch.ms_states), ms_put64(MS_PRE, (uintptr_t)a_launch.ms_pre);
-            ms_put64(MS_XIN, (uintptr_t)a_launch.x_in), ms_put64(MS_PIN, (uintptr_t)a_launch.pre_in), ms_put64(MS_XOUT, (uintptr_t)a_launch.x_out);
-            ms_put64(MS_POUT, (uintptr_t)a_launch.pre_out), ms_put64(MS_FW, (uintptr_t)a_launch.fire_words);
         }
         wave_sync();
     };
@@ -540,25 +563,32 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                 if constexpr (!MS) {
                     break;
                 } else {   // the first tile of the next step follows the last of this one
-                    if (step + 1 >= ms_get(MS_NSTEPS)) break;
-                    ++step;
-                    gbase += n_rounds;
+                    if (step + 1 >= a_launch.ms_steps) break;
+                    tile_no = 0;   // stamps only: every step stamps its tiles, the last step's stay
                     next_step();
                     pn = ms_pos0();
                 }
             }
             const WTile nxt = tile_of(pn);
             __builtin_amdgcn_s_setprio(0);
-            await(1, gbase + pn.k - 2);       // the consumer is done with the round that used this buffer
+            NCA_STAMP(0);
+            [[maybe_unused]] GateLook look{nullptr, false, 0u};
             if constexpr (MS) {
-                if (step > 0 && nxt.valid) gate(nxt, step);   // the launch's first step reads what earlier launches wrote
+                if (step > 0 && nxt.valid) look = gate_look(nxt);   // the launch's first step reads what earlier launches wrote
             }
+            await(1, gbase + pn.k - 2);       // the consumer is done with the round that used this buffer
+            NCA_STAMP(1);
+            if constexpr (MS) {
+                if (step > 0 && nxt.valid) gate(look, step);
+            }
+            NCA_STAMP(2);
             __builtin_amdgcn_s_setprio(3);
+            NCA_STAMP(3);
 #ifdef NCA_STAMPS
             if (a.seed != 0xD1A6ull && (a.seed < 0xD1AAull || a.seed > 0xD1ADull))  // diagnostic knob (stamps build only): idle producers
 #endif
-            if constexpr (MS) view_in();
             produce(nxt, which ^ 1);
+            NCA_STAMP(14);
             post(0, gbase + pn.k);
             cur = nxt;
             pos = pn;
@@ -586,7 +616,9 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
             while (pos.k < n_rounds) {
                 const Pos pn = advance(pos);
                 const WTile nxt = tile_of(pn);
+                NCA_STAMP(0);
                 await(0, gbase + pos.k);  // this round's tile has been staged
+                NCA_STAMP(1);
                 if (tile_no == 2) NCA_KSTAMP(4);            // light stamps around one steady-state tile
 #ifdef NCA_STAMPS
                 if (a.seed != 0xD1A7ull)  // diagnostic knob: idle consumers
@@ -607,6 +639,7 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                         }
                     }
                 }
+                NCA_STAMP(14);
                 if (tile_no == 2) NCA_KSTAMP(6);
                 if (tile_no == 3) NCA_KSTAMP(7);
                 cur = nxt;
@@ -624,9 +657,9 @@ __global__ __launch_bounds__(kThreadsW, 2) void cond_step_fwd_pc_kernel(const Nc
                 // own producer's among them, may be waiting for exactly these), then walk the same tiles again
                 ready = npend;
                 publish();
-                if (++step >= ms_get(MS_NSTEPS)) break;
-                gbase += n_rounds;
+                if (step + 1 >= a_launch.ms_steps) break;
                 ++pub_val;
+                tile_no = 0;   // stamps only
                 next_step();
                 pos = ms_pos0();
                 cur = tile_of(pos);
@@ -708,6 +741,8 @@ bool nca_cond_pc_fused_steps_ok(const NcaCondArgs& a) {
     // nothing overlaps the gate.  And at most kFusedMaxRounds: the fused launch saves about half of a step's fixed cost and pays
     // 8 - 10 % more per round (profiles/r9a_fixed_cost_fit.txt, B x 16 x 256^2 on 256 CUs: F 17.4 -> 9.2 us, v 7.18 -> 7.76 us per
     // round), which is -7 % per step at 4 rounds, -5 % at 8, even at 16 and +4.5 % at 32; the line through those crosses at 15.
+    // With the step view formed per tile and the gate's first look ahead of the hand-off wait (profiles/r10a_fixed_cost_fit.txt) F is
+    // 8.2 -> 7.3 us and v unchanged, 7.96 -> 7.94 us against 7.35 us: the per-round cost did not move, the cap stays.
     // A set fire-word chunk cap (test hook) waives the upper bound, as it waives the minimum grow length.
     constexpr long kFusedMaxRounds = 12;
     const long nst = (long)a.B * ((a.W + 15) / 16) * ((a.H + 15) / 16);
