@@ -613,7 +613,9 @@ int ncahip_cond_grow_bwd_bf16(const uint16_t *states, const uint8_t *pre, int T,
  * `workspace`, tag = epoch * 4096 + step, so neighbours need no counters and the call is ONE launch (no copy, no memset).
  * Workspace contract: ncahip_dynca_nsteps_persist_workspace bytes, 256-byte aligned, ZEROED ONCE by the caller when allocated;
  * every call on it passes a strictly larger `epoch` than the one before (1, 2, ... < 2^20; zero it again and restart at 1 when
- * that runs out) -- stale pairs of earlier launches then never match.  Covered: C <= 16, fc <= 128, H % 16 == 0, W % 16 == 0,
+ * that runs out) -- stale pairs of earlier launches then never match.  Because the epoch is a kernel argument the call can NOT be
+ * captured into a graph and replayed (a replay would repeat the epoch and meet the previous replay's equally tagged pairs): on a
+ * stream that is capturing, both entry points return NCAHIP_ERANGE after the argument checks, nothing enqueued.  Covered: C <= 16, fc <= 128, H % 16 == 0, W % 16 == 0,
  * T < 4096, and every tile's workgroup resident at once (occupancy x CUs >= B * H/16 * W/16: 1 x 256 x 256 is exactly one per CU
  * of an MI355X); NCAHIP_ERANGE otherwise -- the caller then runs ncahip_dynca_nsteps_fwd_f32.  The workspace query returns 0 for
  * shapes that are never covered.  A neighbour that never becomes resident (another process holding CUs) makes a bounded poll
@@ -642,7 +644,8 @@ int ncahip_dynca_nsteps_fwd_persist_ms_f32(const float *x_in, float *x_out, int 
  * slot 0 is the input and only x_final is defined (pre may be NULL).
  * Workspace contract: ncahip_cond_grow_persist_workspace bytes (pure host arithmetic; 0 for shapes that are never covered),
  * 256-byte aligned, ZEROED ONCE by the caller; every call passes a strictly larger epoch (1 .. 2^20 - 1).  Because the epoch is a
- * kernel argument the call can NOT be captured into a graph and replayed.
+ * kernel argument the call can NOT be captured into a graph and replayed: on a stream that is capturing it returns NCAHIP_ERANGE after
+ * the argument checks and the sticky-word refusal, nothing enqueued.
  * Covered: C <= 20, hidden == 64, goal_ch >= 0, alive_ch >= 0 or < 0, H % 16 == 0, W % 16 == 0, T < 4096, bit-packed fire masks
  * (NCAHIP_SEED_U_IS_BITS) or in-kernel Philox (u == NULL), 16-byte aligned states / x_final / goal, precision mode 0 and no
  * ncahip_debug_force_generic bit, and B * H/16 * W/16 tiles <= the device's CUs (one workgroup per CU, every tile resident);
@@ -689,7 +692,9 @@ int ncahip_debug_persist_drop_tiles(int n);
  *   ncahip_dynca_nsteps_fwd_persist_f32 / _ms_f32 with epoch epoch0 + n (persist_ws as that entry point documents; NCAHIP_EINVAL when
  *   epoch0 < 1 or epoch0 + F * steps_per_frame >= 2^20); from its first NCAHIP_ERANGE on, and always with persist_ws == NULL, the calls
  *   run on ncahip_dynca_nsteps_fwd_f32 / _ms_f32 with ring 2 over `states`.  What those entry points cover, this one covers, with their
- *   bits; what they refuse, it refuses with their code.
+ *   bits; what they refuse, it refuses with their code.  Because the epochs are kernel arguments the persistent launches can NOT be
+ *   captured into a graph and replayed: on a capturing stream the first call's persistent entry point returns NCAHIP_ERANGE, so a captured
+ *   clip holds the per-step launches only (pass persist_ws == NULL there and no epoch is spent).
  *   Arguments are checked on the host before anything is enqueued (null or overlapping buffers, F, steps_per_frame, step_n <= 0, c_out,
  *   an unknown format, the epoch range: NCAHIP_EINVAL; shapes the step entry points refuse: their code); a set sticky error word refuses
  *   the call with NCAHIP_EDEVICE, as the grow drivers do; the driver stops enqueuing at the first failing launch and returns its code. */
@@ -719,7 +724,9 @@ int ncahip_dynca_clip_f32(float *states, const float *cond, void *images, int im
  *   with cond, then image n is written.  A clip is one inject launch, then per call the step launch(es) and one emit + inject launch.
  *   gray: [F,B,H,W], from ncahip_clip_gray.  cond: ONE map [B,c_cond,H,W] for all frames, c_cond = 2; or NULL with c_cond = 0.
  *   states, u, two_scale, pc_scratch, persist_ws / epoch0, the routes (persistent entry points, per-step ring from the first NCAHIP_ERANGE
- *   on), the host-side checks, the sticky error word and the return codes: as ncahip_dynca_clip_f32, with which it shares its body.  In
+ *   on), the host-side checks, the sticky error word and the return codes: as ncahip_dynca_clip_f32, with which it shares its body.  As
+ *   there, the persistent launches can NOT be captured into a graph and replayed: on a capturing stream their entry point returns
+ *   NCAHIP_ERANGE and the captured clip holds the per-step launches only.  In
  *   addition NCAHIP_EINVAL for gray == NULL, c_cond other than 0 or 2, a cond pointer that does not match c_cond, c_out > C-1, and gray
  *   overlapping states, cond or images.  On return slot 0 of states holds all C channels, the last one the extra channel as the last
  *   call's steps left it: dropping it (h = state[:, :-1]) is the caller's job. */
@@ -760,7 +767,8 @@ int ncahip_dynca_clip_xc_f32(float *states, const float *gray, const float *cond
  *   With persist_ws != NULL each call n first goes to ncahip_cond_grow_fwd_persist_f32 (ring 2) with epoch epoch0 + n (persist_ws as that
  *   entry point documents; NCAHIP_EINVAL when epoch0 < 1 or epoch0 + F * steps_per_frame >= 2^20); from its first NCAHIP_ERANGE on (float
  *   uniforms included), and always with persist_ws == NULL, the calls run on ncahip_cond_grow_fwd_f32 with ring 2.  What those entry points
- *   cover, this one covers, with their bits; what they refuse, it refuses with their code.
+ *   cover, this one covers, with their bits; what they refuse, it refuses with their code.  A capturing stream is such a refusal
+ *   (NCAHIP_ERANGE: the persistent grow can NOT be captured into a graph and replayed), so a captured clip holds the per-step launches only.
  *   Arguments are checked on the host before anything is enqueued (null or overlapping buffers, F, steps_per_frame, step_n <= 0, C < 3, an
  *   unknown format, the epoch range: NCAHIP_EINVAL; shapes the grow drivers refuse: their code); then a set sticky error word refuses the call
  *   with NCAHIP_EDEVICE; the driver stops enqueuing at the first failing launch and returns its code. */

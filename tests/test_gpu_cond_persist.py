@@ -328,27 +328,7 @@ def test_fallbacks(ops):
     ops.check_errors()
 
 
-def test_graph_capture_takes_the_per_step_kernels(ops):
-    gen = torch.Generator().manual_seed(9)
-    x = (torch.rand(2, 16, 64, 64, generator=gen) * 0.4).to(DEV)
-    w = _w(ops, _prm(16, seed=4), x)
-    ops.persistent_cond = False
-    ref = ops.cond_grow(x, 6, None, None, w, 3, seed=2)[0].clone()
-    ops.persistent_cond = True
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        ops.cond_grow(x, 6, None, None, w, 3, seed=2)                  # warm-up outside capture (workspaces, attributes)
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with _Spy(ops) as spy:
-        with torch.cuda.graph(g):
-            out = ops.cond_grow(x, 6, None, None, w, 3, seed=2)[0]
-    assert spy.seen == []
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(ref, out)
+# (the graph-capture test of this module lives in test_gpu_graph_replay.py: test_graph_capture_takes_the_per_step_kernels)
 
 
 def test_epochs_interleaved_with_dynca_persistent(ops):

@@ -43,6 +43,17 @@ int check_bits(bool bits, int B, int H, int W, float rate, bool dynca) {
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// n floats of zeros for an accumulator that a driver's kernels add to: hipMemsetAsync -- except on a capturing stream, where a kernel
+// writes them.  A replayed graph does not keep a memset node ahead of the kernel nodes behind it (measured on the backward rows of
+// tests/test_gpu_graph_replay.py: the accumulators were zeroed under the first step's flush, every replay gave other gradients); a
+// kernel node it does keep in its place.  Outside a capture nothing changes.
+hipError_t nca_zero_async(float* p, size_t n, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipError_t e = hipStreamIsCapturing(st, &cs); e != hipSuccess) return e;
+    if (cs == hipStreamCaptureStatusNone) return hipMemsetAsync(p, 0, n * sizeof(float), st);
+    return nca_launch_zero_words(reinterpret_cast<uint32_t*>(p), n, st);
+}
+
 bool dims_ok(int B, int C, int H, int W) {
     return B > 0 && C > 0 && H > 0 && W > 0 && (size_t)B * C * H * W < ((size_t)1 << 40);
 }
@@ -344,6 +355,17 @@ size_t ncahip_dynca_nsteps_persist_workspace(int B, int C, int H, int W, int fc,
     return 256 + align256((size_t)2 * nca_dynca_persist_xch_pairs(B, C, H, W, true) * sizeof(unsigned long long));
 }
 
+// The persistent launches take their epoch as a kernel argument: captured into a graph, every replay would run with the captured epoch
+// and meet the previous replay's equally tagged pairs.  On a capturing stream the entry points refuse with the code their callers
+// already answer with the per-step kernels; the query enqueues nothing.
+static int persist_refuse_capture(const char* who, ncahip_stream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (int rc = hip_result(hipStreamIsCapturing((hipStream_t)stream, &cs), "persist (capture status)")) return rc;
+    if (cs == hipStreamCaptureStatusNone) return 0;
+    return fail(NCAHIP_ERANGE, "%s: the stream is capturing a graph and a persistent launch cannot be captured (its epoch is a kernel argument, "
+                "a replay would repeat it); use the per-step entry point", who);
+}
+
 static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, int T, const float* cond, const float* u, const float* w1,
                                         const float* b1, const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond,
                                         int pad_mode, float update_rate, uint64_t seed, uint64_t step0, void* workspace,
@@ -365,6 +387,7 @@ static int dynca_persist_impl(bool two_scale, const float* x_in, float* x_out, i
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
     if (int rc = device_error_rc("dynca nsteps persist")) return rc;
+    if (int rc = persist_refuse_capture("dynca nsteps persist", stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
     NcaDyncaPersistArgs a{x_in, x_out, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0,
                           (int*)workspace, epoch, (unsigned long long*)((char*)workspace + 256),
@@ -430,6 +453,7 @@ int ncahip_cond_grow_fwd_persist_f32(float* states, uint8_t* pre, int ring, int 
     if (!nca_cond_fwd_default())
         return fail(NCAHIP_ERANGE, "cond grow persist: only the default exact-f32 producer/consumer family has a persistent twin; use ncahip_cond_grow_fwd_f32");
     if (int rc = device_error_rc("cond grow")) return rc;
+    if (int rc = persist_refuse_capture("cond grow persist", stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
     NcaCondPersistArgs a{states, states, pre, ring == T + 1 ? 1 : 0, x_final, goal, ubits ? u : nullptr, wp, w1, b1, w2, b2, w3,
                          B, C, H, W, goal_ch, alive_ch, T, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0, (int*)workspace, epoch,
@@ -1405,8 +1429,8 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     float* const dpc = two_scale ? (float*)(ws + p.off_dpc) : nullptr;
     float* const dxc = two_scale ? (float*)(ws + p.off_dxc) : nullptr;
     const size_t a1n = (size_t)p.fs * p.K1 + p.fs, a2n = (size_t)C * p.fs + C;
-    hipError_t e = hipMemsetAsync(acc1, 0, (size_t)p.nsl * a1n * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(acc2, 0, (size_t)p.nsl * a2n * sizeof(float), st);
+    hipError_t e = nca_zero_async(acc1, (size_t)p.nsl * a1n, st);
+    if (e == hipSuccess) e = nca_zero_async(acc2, (size_t)p.nsl * a2n, st);
     if (e != hipSuccess) return hip_result(e, "dynca nsteps bwd memset");
     const size_t slot = p.n, uslot = (size_t)B * H * W;
     const float* gcur = g_final;
@@ -1904,9 +1928,9 @@ static int cond_grow_bwd_impl(const void* states_v, int sb, const uint8_t* pre, 
     void* pscr = p; p += align256(nca_cond_bwd_fm_pscr_bytes(B, C, H, W));   // front kernel -> matrix kernel scratch (operand order)
     void* doscr = p; p += align256(nca_cond_bwd_fm_doscr_bytes(B, C, H, W));
     float* opimg = (float*)p;   // the matrix kernel's operand image, built once per call (the weights do not change between the steps)
-    hipError_t e = hipMemsetAsync(slabs, 0, (size_t)nslab * sf * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(wpp, 0, (size_t)nblk * 27 * sizeof(float), st);
-    if (e == hipSuccess && goal_ch > 0) e = hipMemsetAsync(g_goal, 0, (size_t)B * goal_ch * H * W * sizeof(float), st);
+    hipError_t e = nca_zero_async(slabs, (size_t)nslab * sf, st);
+    if (e == hipSuccess) e = nca_zero_async(wpp, (size_t)nblk * 27, st);
+    if (e == hipSuccess && goal_ch > 0) e = nca_zero_async(g_goal, (size_t)B * goal_ch * H * W, st);
     if (e != hipSuccess) return hip_result(e, "cond grow bwd memset");
     const float* gcur = g_final;
     auto step_args = [&](int t, const float* g_in) {

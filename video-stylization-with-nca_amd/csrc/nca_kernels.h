@@ -365,3 +365,4 @@ hipError_t nca_launch_philox_uniform(float* u, int B, int H, int W, uint64_t see
 // fire masks of T steps, bit-packed: mode 0 = clamp(u,0,1) < rate (nca.py:171-174), 1 = floorf(u + rate) >= 1 (dynca.py:131)
 hipError_t nca_launch_pack_fire_mask(const float* u, uint32_t* bits, int T, size_t cells, float rate, int mode, hipStream_t st);
 hipError_t nca_launch_selftest(int* result, hipStream_t st);
+hipError_t nca_launch_zero_words(uint32_t* p, size_t n, hipStream_t st);   // n 32-bit words of zeros from a kernel (nca_zero_async in nca_capi.hip)

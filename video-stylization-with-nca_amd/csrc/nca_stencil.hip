@@ -434,9 +434,21 @@ __global__ void selftest_kernel(int* result) {
     if (lane == 0) result[0] = bad == 0ull ? 1 : 0;
 }
 
+// n 32-bit words of zeros, grid-stride: what a driver enqueues in place of hipMemsetAsync on a capturing stream (nca_zero_async)
+__global__ void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+hipError_t nca_launch_zero_words(uint32_t* p, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255) / 256, cap = (size_t)nca_cu_count() * 8;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, st, p, n);
+    return hipGetLastError();
+}
 
 hipError_t nca_launch_dynca_perceive(const float* x, float* y, int B, int C, int H, int W, int pad, hipStream_t st) {
     const bool vec = (W % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) % 16 == 0);

@@ -414,8 +414,9 @@ def dynca_nsteps(x: torch.Tensor, T: int, cond: Optional[torch.Tensor], us: Opti
         cond = _dev(cond, "cond")
     us, seed = _u_args(us, T, B, H, W, seed)
     assert w.c == C and w.k1 == 4 * C + c_cond, (w.c, w.k1, C, c_cond)
-    if not keep_history and sfx == "f32" and persistent_steps:
-        # small grids (B = 1 video inference): all T steps in ONE launch, one workgroup per tile (ncahip_dynca_nsteps_fwd_persist_f32);
+    if not keep_history and sfx == "f32" and persistent_steps and not torch.cuda.is_current_stream_capturing():
+        # small grids (B = 1 video inference): all T steps in ONE launch, one workgroup per tile (ncahip_dynca_nsteps_fwd_persist_f32;
+        # its epoch is a kernel argument, so never inside a captured graph: no workspace is asked for and no epoch consumed there);
         # NCAHIP_ERANGE = shape not covered or not every tile resident on this device -> the per-step kernels below
         nbytes = lib().ncahip_dynca_nsteps_persist_workspace(B, C, H, W, w.fc, c_cond)
         if nbytes:
@@ -553,10 +554,11 @@ def clip_emit(x: torch.Tensor, c_out: int = 3, out_dtype=torch.float32, out_form
     return img
 
 
-def _clip_persist(nbytes: int, calls: int, device, while_capturing: bool = True):
+def _clip_persist(nbytes: int, calls: int, device):
     """(ws, nbytes or 0, epoch) of a clip driver's persistent launches: `calls` consecutive epochs of the workspace of `nbytes` bytes
-    (0: the persistent kernel is switched off or does not cover the shape), or no workspace."""
-    if nbytes and calls < (1 << 20) - 2 and (while_capturing or not torch.cuda.is_current_stream_capturing()):
+    (0: the persistent kernel is switched off or does not cover the shape), or no workspace.  Never while the current stream is capturing
+    a graph: the epochs are kernel arguments, a replay would repeat them (include/ncahip.h), so the drivers then run the per-step kernels."""
+    if nbytes and calls < (1 << 20) - 2 and not torch.cuda.is_current_stream_capturing():
         ws, epoch = _persist_workspace(nbytes, device, count=calls)
         return ws, nbytes, epoch
     return None, 0, 0
@@ -869,8 +871,7 @@ def cond_clip(x: torch.Tensor, goal: torch.Tensor, us: Optional[torch.Tensor], w
                                           _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
                                           lo, hi, seed, step0, _stream()), "cond_clip (bf16)")
         return images, states[0]
-    ws, nbytes, epoch = _clip_persist(lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch) if persistent_cond else 0, calls, x.device,
-                                      while_capturing=False)
+    ws, nbytes, epoch = _clip_persist(lib().ncahip_cond_grow_persist_workspace(B, C, H, W, w.hidden, gch) if persistent_cond else 0, calls, x.device)
     check(lib().ncahip_cond_clip_f32(_p(states), _p(pre), _p(goal), gch, _p(images), spec.fmt, F_, steps_per_frame, step_n, _p(us),
                                      _p(w.wp), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), _p(w.w3), B, C, H, W, w.hidden, alive_ch, thr, fire_rate,
                                      lo, hi, seed, step0, _p(ws), nbytes, epoch, _stream()), "cond_clip")
