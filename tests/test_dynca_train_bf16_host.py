@@ -454,10 +454,10 @@ def test_exports_are_in_header_library_and_binding():
     assert "mode-1 history" in header.lower() or "MODE-1 history" in header
 
 
-def _nsteps_args(fn_ms, T=1, B=1, C=12, H=16, W=16, fc=96, cc=0, pad=1, ptr=0x1000, ws=0x10000, nbytes=1 << 30, **null):
+def _nsteps_args(fn_ms, T=1, B=1, C=12, H=16, W=16, fc=96, cc=0, pad=1, ptr=0x1000, ws=0x10000, nbytes=1 << 30, rate=0.5, seed=0, **null):
     """argument tuple of the nsteps drivers with dummy (never dereferenced) pointers; null: names to pass as NULL"""
     P = lambda n: None if null.get(n) else ptr                      # noqa: E731
-    return (P("states"), T, None if cc == 0 else ptr, ptr, ptr, ptr, ptr, ptr, B, C, H, W, fc, cc, pad, 0.5, 0, 0, P("g_final"), None,
+    return (P("states"), T, None if cc == 0 else ptr, ptr, ptr, ptr, ptr, ptr, B, C, H, W, fc, cc, pad, rate, seed, 0, P("g_final"), None,
             None if null.get("g_x0") else 0x5000, ptr, ptr, ptr, ptr, None if null.get("workspace") else ws, nbytes, None)
 
 
@@ -535,6 +535,181 @@ def test_workspace_queries_are_host_arithmetic():
     assert s[0] > 0 and s == sorted(s), s
     # the mode's scratch is smaller than the exact backward's: y and dh are bf16
     assert L.ncahip_dynca_nsteps_bwd_bfmma_workspace(8, 16, 256, 256, 128, 3) < L.ncahip_dynca_nsteps_bwd_workspace(8, 16, 256, 256, 128, 3)
+
+
+# ------------------------------------------------------------------ precedence: two faults in one call
+# The single-fault refusals above do not see the ORDER of the checks.  Every case below plants two faults in one call of a backward entry
+# point (dummy pointers, refused on the host: nothing is dereferenced or launched) and expects the code and the whole message of the
+# check that comes first.  The literals were recorded from the library before the entry points were given one body per stage; they
+# hold the merged bodies to the order every entry point had.  test_dynca_train_bf16_wide_host.py (the wide range) and
+# test_dynca_step_bwd_host.py (the two exact stage entries) use the same caller.
+BITS = 0x5354494255                      # NCAHIP_SEED_U_IS_BITS with update_rate = 1.0: the bit-packed masks' refusal
+SHORT = dict(nbytes=16)                  # a workspace far below every query's figure
+
+
+def _step_args(entry, C=12, fc=96, H=16, W=16, rate=0.5, seed=0, g_next=0x1000, g_x=0x3000, ws=0x10000, nbytes=1 << 30):
+    """argument tuple of a single-step stage entry (dummy pointers); the entries differ in their own outputs behind g_x"""
+    p = 0x1000
+    own = {"ncahip_dynca_step_bwd_f32": (p, p, p, None), "ncahip_dynca_step_bwd_w2_f32": (p, p, p, 0, ws, nbytes, None)}
+    return (p, None, p, p, p, p, p, 1, C, H, W, fc, 0, 1, rate, seed, 0, g_next, g_x) + own.get(entry, (p, p, p, p, 0, ws, nbytes, None))
+
+
+def _gram_args(a=0x1000, ma=96, nb1=48, nb2=3, HW=256, ws=0x10000, nbytes=1 << 30):
+    return (a, ma, 0x1000, nb1, 0x1000, nb2, 1, HW, 0x1000, 0, ws, nbytes, None)
+
+
+def refusal(entry, direction=False, **kw):
+    """(code, message) of one refused call of a backward entry point; direction: with a direction field attached"""
+    from ncahip import _capi
+    L = _capi.lib()
+    args = _gram_args(**kw) if "gram" in entry else _step_args(entry, **kw) if "_step_" in entry else _nsteps_args(None, **kw)
+    if direction:
+        assert L.ncahip_dynca_direction(0x2000, 1, 16, 16) == 0
+    try:
+        return getattr(L, entry)(*args), L.ncahip_last_error().decode()
+    finally:
+        assert L.ncahip_dynca_direction(None, 0, 0, 0) == 0
+
+
+def check_two_faults(entry, faults, call, want):
+    got = refusal(entry, **call)
+    print(f"{entry} [{faults}]: {got}")
+    assert got == want, (entry, faults, got, want)
+
+
+TWO_FAULTS = [
+    ('ncahip_dynca_nsteps_bwd_f32', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'T0+range', dict(T=0, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'range+alias', dict(ptr=0x5000, C=33),
+     (-2, 'dynca step: C=33 fc=96 c_cond=0 exceeds (32,1024,4)')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_f32', '4GiB+range', dict(H=4096, W=4096, C=33),
+     (-2, 'dynca step: C=33 fc=96 c_cond=0 exceeds (32,1024,4)')),
+    ('ncahip_dynca_nsteps_bwd_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'T0+range', dict(T=0, C=20),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'range+alias', dict(ptr=0x5000, C=20),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', '4GiB+range', dict(H=4096, W=4096, C=20),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'oddW+short', dict(W=15, nbytes=16),
+     (-2, 'dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)')),
+    ('ncahip_dynca_nsteps_bwd_ms_f32', 'C20+oddW', dict(C=20, W=15),
+     (-2, 'dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'T0+range', dict(T=0, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'range+alias', dict(ptr=0x5000, C=33),
+     (-2, 'dynca step: C=33 fc=96 c_cond=0 exceeds (32,1024,4)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', '4GiB+range', dict(H=4096, W=4096, C=33),
+     (-2, 'dynca step: C=33 fc=96 c_cond=0 exceeds (32,1024,4)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_bf16', 'unaligned_history+short', dict(ptr=0x1004, nbytes=16),
+     (-2, 'dynca nsteps bwd (bf16): B*C*H*W % 4 == 0 and 8-byte aligned states required')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'T0+range', dict(T=0, C=20),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'range+alias', dict(ptr=0x5000, C=20),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', '4GiB+range', dict(H=4096, W=4096, C=20),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'T0+range', dict(T=0, C=20),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'range+alias', dict(ptr=0x5000, C=20),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', '4GiB+range', dict(H=4096, W=4096, C=20),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'oddW+short', dict(W=15, nbytes=16),
+     (-2, 'dynca two-scale step: H and W must be even (the x2 resampling is then the exact 2x2 mean / (0.25, 0.75) blend)')),
+    ('ncahip_dynca_nsteps_bwd_ms_bfmma_f32', 'range+oddW', dict(C=20, W=15),
+     (-2, "dynca nsteps bwd (bf16 MFMA): C=20 fc=96 outside the mode's range (C <= 16, fc <= 128)")),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'direction+null', dict(direction=True, g_next=None),
+     (-1, 'dynca step bwd_bfmma: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'null+C33', dict(g_next=None, C=33),
+     (-1, 'dynca step bwd_bfmma: null pointer')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'range+alias', dict(g_next=0x3000, C=20),
+     (-2, 'dynca step bwd_bfmma: C=20 fc=96 outside the bf16-MFMA range (C <= 16, fc <= 128)')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'alias+4GiB', dict(g_next=0x3000, H=4096, W=4096),
+     (-1, 'dynca step bwd_bfmma: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'alias+short', dict(g_next=0x3000, nbytes=16),
+     (-1, 'dynca step bwd_bfmma: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'short+misaligned', dict(nbytes=16, ws=0x10002),
+     (-1, 'dynca step bwd_bfmma: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'misaligned', dict(ws=0x10002),
+     (-2, 'dynca step bwd_bfmma: misaligned workspace (4 bytes) or bf16 output (2 bytes)')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-1, 'dynca step bwd_bfmma: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca step bwd_bfmma: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_gram_rows_bf16', 'null+range', dict(a=None, ma=129),
+     (-1, 'gram_rows_bf16: null pointer')),
+    ('ncahip_gram_rows_bf16', 'size+range', dict(HW=0, ma=129),
+     (-1, 'gram_rows_bf16: bad size')),
+    ('ncahip_gram_rows_bf16', 'range+misaligned', dict(ws=0x10002, nb1=80),
+     (-2, 'gram_rows_bf16: ma=96 nb=83 outside (<=128 x <=79)')),
+    ('ncahip_gram_rows_bf16', 'misaligned+short', dict(ws=0x10002, nbytes=16),
+     (-2, 'gram_rows_bf16: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)')),
+]
+
+
+@pytest.mark.parametrize("entry,faults,call,want", TWO_FAULTS, ids=[f"{e[7:]}-{f}" for e, f, _, _ in TWO_FAULTS])
+def test_the_first_of_two_faults_is_reported(entry, faults, call, want):
+    check_two_faults(entry, faults, call, want)
 
 
 # ------------------------------------------------------------------ Python plumbing without a device

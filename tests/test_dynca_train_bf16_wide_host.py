@@ -18,8 +18,8 @@ import torch
 
 from oracle import nca_oracle as O
 from test_dynca_bf16_host import _rb, bf16_inputs
-from test_dynca_train_bf16_host import (RATE, _mats, _nsteps_args, check_dh, check_dy, check_t1, contract_backward, contract_history,
-                                        cpu_stage_outputs, rel_l2, run_stage_checks, stage_step)
+from test_dynca_train_bf16_host import (BITS, RATE, _mats, _nsteps_args, check_dh, check_dy, check_t1, check_two_faults, contract_backward,
+                                        contract_history, cpu_stage_outputs, rel_l2, run_stage_checks, stage_step)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -237,6 +237,86 @@ def test_workspace_queries_are_host_arithmetic():
     assert s[0] > 0 and s == sorted(s), s
     assert qg(96, 51, 2, 256) == L.ncahip_gram_rows_bf16_workspace(96, 51, 2, 256)
     assert q(4, 32, 512, 512, 256, 3) < L.ncahip_dynca_nsteps_bwd_workspace(4, 32, 512, 512, 256, 3)
+
+
+# ------------------------------------------------------------------ precedence: two faults in one call
+# The wide entry points under the cases and the caller of test_dynca_train_bf16_host.py ("precedence: two faults in one call"), at a
+# wide shape and at a narrow one: there they answer with the narrow entry points' checks and messages.  Literals recorded the same way.
+TWO_FAULTS = [
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'direction+null', dict(direction=True, states=True),
+     (-1, 'dynca nsteps bwd: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'null+C33', dict(states=True, C=33),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'T0+range', dict(T=0, C=20, fc=257),
+     (-1, 'dynca nsteps bwd: null pointer or T < 1')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'range+alias', dict(ptr=0x5000, C=20, fc=257),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'alias+short', dict(ptr=0x5000, nbytes=16),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'short+misaligned', dict(nbytes=16, ws=0x10004),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', '4GiB+range', dict(H=4096, W=4096, C=20, fc=257),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'alias+short@C20fc160', dict(ptr=0x5000, nbytes=16, C=20, fc=160),
+     (-1, 'dynca step: x_in and x_out must not alias (halo reads)')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'short+misaligned@C20fc160', dict(nbytes=16, ws=0x10004, C=20, fc=160),
+     (-1, 'dynca nsteps bwd: workspace too small')),
+    ('ncahip_dynca_nsteps_bwd_bfmma_wide_f32', 'bits+short@C20fc160', dict(nbytes=16, rate=1.0, seed=BITS, C=20, fc=160),
+     (-2, 'bit-packed fire masks (DyNCA): 0 <= update_rate < 1 required (floor(u + rate) must be 0 or 1)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'direction+null', dict(direction=True, g_next=None, C=20, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'null+C33', dict(g_next=None, C=33, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: null pointer')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'range+alias', dict(g_next=0x3000, C=20, fc=257),
+     (-2, 'dynca step: C=20 fc=257 c_cond=0 exceeds (32,256,4)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'alias+4GiB', dict(g_next=0x3000, H=4096, W=4096, C=20, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'alias+short', dict(g_next=0x3000, nbytes=16, C=20, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'short+misaligned', dict(nbytes=16, ws=0x10002, C=20, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'misaligned', dict(ws=0x10002, C=20, fc=160),
+     (-2, 'dynca step bwd_bfmma_wide: misaligned workspace (4 bytes) or bf16 output (2 bytes)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'bits+short', dict(nbytes=16, rate=1.0, seed=BITS, C=20, fc=160),
+     (-1, 'dynca step bwd_bfmma_wide: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', '4GiB+short', dict(nbytes=16, H=4096, W=4096, C=20, fc=160),
+     (-2, 'dynca step bwd_bfmma_wide: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'direction+null@narrow', dict(direction=True, g_next=None),
+     (-1, 'dynca step bwd_bfmma: a direction field is attached (ncahip_dynca_direction) and this entry point does not steer; detach it first')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'null+C33@narrow', dict(g_next=None, C=33),
+     (-1, 'dynca step bwd_bfmma_wide: null pointer')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'range+alias@narrow', dict(g_next=0x3000, fc=257),
+     (-2, 'dynca step: C=12 fc=257 c_cond=0 exceeds (32,256,4)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'alias+4GiB@narrow', dict(g_next=0x3000, H=4096, W=4096),
+     (-1, 'dynca step bwd_bfmma: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'alias+short@narrow', dict(g_next=0x3000, nbytes=16),
+     (-1, 'dynca step bwd_bfmma: g_next and g_x must not alias')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'short+misaligned@narrow', dict(nbytes=16, ws=0x10002),
+     (-1, 'dynca step bwd_bfmma: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'misaligned@narrow', dict(ws=0x10002),
+     (-2, 'dynca step bwd_bfmma: misaligned workspace (4 bytes) or bf16 output (2 bytes)')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', 'bits+short@narrow', dict(nbytes=16, rate=1.0, seed=BITS),
+     (-1, 'dynca step bwd_bfmma: workspace too small')),
+    ('ncahip_dynca_step_bwd_bfmma_wide_f32', '4GiB+short@narrow', dict(nbytes=16, H=4096, W=4096),
+     (-2, 'dynca step bwd_bfmma: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)')),
+    ('ncahip_gram_rows_bf16_wide', 'null+range', dict(a=None, ma=257, nb1=80),
+     (-1, 'gram_rows_bf16_wide: null pointer')),
+    ('ncahip_gram_rows_bf16_wide', 'size+range', dict(HW=0, ma=257, nb1=80),
+     (-1, 'gram_rows_bf16_wide: bad size')),
+    ('ncahip_gram_rows_bf16_wide', 'range+misaligned', dict(ws=0x10002, ma=160, nb1=131),
+     (-2, 'gram_rows_bf16_wide: ma=160 nb=134 outside (<=256 x <=132)')),
+    ('ncahip_gram_rows_bf16_wide', 'misaligned+short', dict(ws=0x10002, nbytes=16, ma=160, nb1=80),
+     (-2, 'gram_rows_bf16_wide: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)')),
+]
+
+
+@pytest.mark.parametrize("entry,faults,call,want", TWO_FAULTS, ids=[f"{e[7:]}-{f}" for e, f, _, _ in TWO_FAULTS])
+def test_the_first_of_two_faults_is_reported(entry, faults, call, want):
+    check_two_faults(entry, faults, call, want)
 
 
 # ------------------------------------------------------------------ Python plumbing without a device

@@ -21,9 +21,9 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-int hip_result(hipError_t e, const char* what) {
+int hip_result(hipError_t e, const char* what, const char* part = "") {
     if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+    snprintf(g_err, sizeof(g_err), "%s%s: %s", what, part, hipGetErrorString(e));
     return (int)e;
 }
 
@@ -1294,26 +1294,66 @@ int ncahip_clip_resize_yuv420_u8(const uint8_t* src, int layout, const int32_t* 
                                                     dst, out_h, out_w, (unsigned char*)workspace, (hipStream_t)stream), "clip_resize_yuv420");
 }
 
+// ---- the DyNCA backward: an entry point names its variant with a constant record and makes one forwarding call; every check is
+// written once ----------------------------------------------------------------------------------------------------------------
+namespace {
+// mma: the fp32 kernels, or the bf16-MFMA training mode in its narrow range (C <= 16, fc <= 128) or its wide one (C <= 32, fc <= 256,
+// single-scale).  The range is what an entry point refuses by; which kernels run inside it the shape alone tells (dynca_bwd_mlp_bf16
+// below, nca_launch_gram_rows_bf16_wide): the wide entry points send narrow shapes to the narrow path.
+enum DyncaBwdMma { kBwdExact, kBwdBfNarrow, kBwdBfWide };
+struct DyncaBwdVariant { bool two_scale; int state_bytes; DyncaBwdMma mma; };   // a driver; state_bytes: 4 = fp32 history, 2 = bf16 (storage format only)
+constexpr DyncaBwdVariant kBwdF32{false, 4, kBwdExact}, kBwdMs{true, 4, kBwdExact}, kBwdBf16{false, 2, kBwdExact},
+                          kBwdBfmma{false, 4, kBwdBfNarrow}, kBwdMsBfmma{true, 4, kBwdBfNarrow}, kBwdBfmmaWide{false, 4, kBwdBfWide};
+// a single-step stage entry: its name in a refusal and in a launch error, its mode, the widest layer check_dynca lets through, the mode's range
+struct DyncaStepBwd { const char *who, *label; DyncaBwdMma mma; int max_fc; const char* range; };
+constexpr DyncaStepBwd kStepBwdF32{"dynca step bwd", "dynca_step_bwd", kBwdExact, kMaxFc, ""},
+                       kStepBwdW2{"dynca step bwd_w2", "dynca_step_bwd_w2", kBwdExact, kMaxFc, ""},
+                       kStepBwdBfmma{"dynca step bwd_bfmma", "dynca_step_bwd_bfmma", kBwdBfNarrow, kMaxFc, "(C <= 16, fc <= 128)"},
+                       kStepBwdBfmmaWide{"dynca step bwd_bfmma_wide", "dynca_step_bwd_bfmma_wide", kBwdBfWide, 256, "(C <= 32, fc <= 256)"};
+
+// "Is this shape in range": a workspace query and its entry point ask the same function (always true for the fp32 kernels: check_dynca is their range).  The MLP stage: (C, fc)
+bool dynca_bwd_mlp_range_ok(DyncaBwdMma mma, int C, int fc) {
+    return mma == kBwdExact || (mma == kBwdBfNarrow ? nca_dynca_bf16_shape_ok(C, fc) : nca_dynca_bf16_wide_shape_ok(C, fc));
+}
+// a driver: also the 4C + c_cond columns of its layer-1 weight-gradient product (what a query adds; past check_dynca, c_cond <= 4 fits both)
+bool dynca_bwd_range_ok(DyncaBwdMma mma, int C, int fc, int c_cond) {
+    return dynca_bwd_mlp_range_ok(mma, C, fc) && (mma == kBwdExact || 4 * C + c_cond <= (mma == kBwdBfNarrow ? kNcaGramBf : kNcaGramBfWide).nb);
+}
+// the MLP launch of the bf16-MFMA backward: the two launchers share the wide range out between them by shape (each refuses the other's)
+hipError_t dynca_bwd_mlp_bf16(const NcaDyncaArgs& a, hipStream_t st) {
+    return nca_dynca_bf16_shape_ok(a.C, a.fc) ? nca_launch_dynca_step_bwd_mlp_bf16(a, st) : nca_launch_dynca_step_bwd_mlp_bf16_wide(a, st);
+}
+// the backward kernels store [rows, H, W] planes of one batch item (rows = the hidden units of a launch, or 4C) through 32-bit offsets
+int check_store_offsets(const char* who, const char* rows_name, int rows, int C, int H, int W) {
+    if ((size_t)(rows > 4 * C ? rows : 4 * C) * H * W * sizeof(float) < ((size_t)1 << 32)) return 0;
+    return fail(NCAHIP_ERANGE, "%s: %s*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)", who, rows_name);
+}
+// What every single-step stage entry checks first, in this order.  a: the step as the entry will launch it; null_ptr: one of the entry's
+// own pointers is null.  The wide entry's check_dynca is its range refusal (NCAHIP_ERANGE beyond C = 32 / fc = 256): the one below it is unreachable there, as for the exact entries
+int dynca_step_bwd_checks(const DyncaStepBwd& v, bool null_ptr, const NcaDyncaArgs& a) {
+    if (int rc = dynca_dir_refuse(v.who)) return rc;
+    if (null_ptr) return fail(NCAHIP_EINVAL, "%s: null pointer", v.who);
+    if (int rc = check_dynca(a.x_in, a.g_out, a.cond, a.w1, a.b1, a.w2, a.b2, a.B, a.C, a.H, a.W, a.fc, a.c_cond, a.pad_mode, v.max_fc)) return rc;
+    if (!dynca_bwd_mlp_range_ok(v.mma, a.C, a.fc)) return fail(NCAHIP_ERANGE, "%s: C=%d fc=%d outside the bf16-MFMA range %s", v.who, a.C, a.fc, v.range);
+    if (a.g_next == a.g_out) return fail(NCAHIP_EINVAL, "%s: g_next and g_x must not alias", v.who);
+    return check_store_offsets(v.who, "fc", a.fc, a.C, a.H, a.W);
+}
+}  // namespace
+
 int ncahip_dynca_step_bwd_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
                               const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                               float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x, float* h_out,
                               float* dh_out, float* dy_scratch, ncahip_stream_t stream) {
-    if (int rc = dynca_dir_refuse("dynca step bwd")) return rc;
-    if (!g_next || !g_x || !h_out || !dh_out || !dy_scratch) return fail(NCAHIP_EINVAL, "dynca step bwd: null pointer");
-    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd: g_next and g_x must not alias");
-    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
-        return fail(NCAHIP_ERANGE, "dynca step bwd: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
-                   g_next, h_out, dh_out, dy_scratch, g_x};
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
+    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, h_out, dh_out, dy_scratch, g_x};
     a.u_bits = u_is_bits(u, seed);
-    return hip_result(nca_launch_dynca_step_bwd(a, (hipStream_t)stream), "dynca_step_bwd");
+    if (int rc = dynca_step_bwd_checks(kStepBwdF32, !g_next || !g_x || !h_out || !dh_out || !dy_scratch, a)) return rc;
+    if (int rc = check_bits(a.u_bits, B, H, W, update_rate, true)) return rc;
+    return hip_result(nca_launch_dynca_step_bwd(a, (hipStream_t)stream), kStepBwdF32.label);
 }
 
 // ---- backward of one DyNCA step with the layer-2 weight gradient fused in (no h buffer) ---------------------------------
 size_t ncahip_dynca_step_bwd_w2_workspace(int B, int C, int H, int W, int fc) {
-    if (!dims_ok(B, C, H, W) || fc <= 0) return 0;
+    if (!dims_ok(B, C, H, W) || fc <= 0 || !dynca_bwd_mlp_range_ok(kStepBwdW2.mma, C, fc)) return 0;
     return (size_t)nca_dynca_bwd_grid(B, H, W) * ((size_t)C * fc + C) * sizeof(float);
 }
 
@@ -1322,40 +1362,39 @@ int ncahip_dynca_step_bwd_w2_f32(const float* x_t, const float* cond, const floa
                                  float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
                                  float* dh_out, float* dy_scratch, float* gw2_out, int accumulate, void* workspace,
                                  size_t workspace_bytes, ncahip_stream_t stream) {
-    if (int rc = dynca_dir_refuse("dynca step bwd_w2")) return rc;
-    if (!g_next || !g_x || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_w2: null pointer");
-    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_w2: g_next and g_x must not alias");
-    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
-        return fail(NCAHIP_ERANGE, "dynca step bwd_w2: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    if (workspace_bytes < ncahip_dynca_step_bwd_w2_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "dynca step bwd_w2: workspace too small");
-    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
-                   g_next, nullptr, dh_out, dy_scratch, g_x};
+    const DyncaStepBwd& v = kStepBwdW2;
+    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, nullptr, dh_out, dy_scratch, g_x};
     a.gw2_ws = (float*)workspace;
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
     a.u_bits = u_is_bits(u, seed);
-    if (int rc = hip_result(nca_launch_dynca_step_bwd(a, (hipStream_t)stream), "dynca_step_bwd_w2")) return rc;
+    if (int rc = dynca_step_bwd_checks(v, !g_next || !g_x || !dh_out || !dy_scratch || !gw2_out || !workspace, a)) return rc;
+    if (workspace_bytes < ncahip_dynca_step_bwd_w2_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "%s: workspace too small", v.who);
+    if (int rc = check_bits(a.u_bits, B, H, W, update_rate, true)) return rc;
+    if (int rc = hip_result(nca_launch_dynca_step_bwd(a, (hipStream_t)stream), v.label)) return rc;
     return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
-                                             (hipStream_t)stream, accumulate != 0), "dynca_step_bwd_w2 reduce");
+                                             (hipStream_t)stream, accumulate != 0), v.label, " reduce");
 }
 
 // ---- backward of ncahip_dynca_nsteps_fwd_f32: the whole T-step loop on the stream, caller-owned workspace ----------------
 namespace {
 struct DyncaBwdPlan {
-    int nsl, fs;                 // hidden-layer slices of at most 128 units (fs = width of the full slices)
+    int nsl, fs, fc;             // hidden-layer slices of at most 128 units (fs = width of the full slices, fc = the whole layer)
     size_t n, off_g[2], off_y, off_dy, off_dh, off_ws2, off_wsg, off_acc1, off_acc2, off_pc, off_dpc, off_dxc, off_x32, total;
     int grid2, gridg, K1;
+    struct Slice { int h0, fs; };   // slice sl: its first hidden unit and its width (a single slice is the whole layer)
+    Slice slice(int sl) const { return {sl * 128, nsl == 1 ? fc : (fc - sl * 128 < 128 ? fc - sl * 128 : 128)}; }
 };
-// bfmma: the bf16-MFMA training mode -- y and dh are bf16 (half the floats), the gram partials are nca_gram_bf16_grid slabs; its buffers
+// The bf16-MFMA training mode: y and dh are bf16 (half the floats), the gram partials are nca_gram_bf16_grid slabs; its buffers
 // hold the whole hidden layer (narrow range: fc <= 128 anyway; wide range: the step launcher slices, dh, the slabs and the accumulators
 // have the full layout and the layer-1 weight gradient is ONE product per step)
-DyncaBwdPlan dynca_bwd_plan(int B, int C, int H, int W, int fc, int c_cond, bool two_scale = false, bool bf16 = false, bool bfmma = false) {
+DyncaBwdPlan dynca_bwd_plan(const DyncaBwdVariant& v, int B, int C, int H, int W, int fc, int c_cond) {
+    const bool bfmma = v.mma != kBwdExact;
     DyncaBwdPlan p{};
+    p.fc = fc;
     p.nsl = bfmma ? 1 : (fc + 127) / 128;
     p.fs = (bfmma || fc < 128) ? fc : 128;
     p.K1 = 4 * C + c_cond;
     p.n = (size_t)B * C * H * W;
-    p.grid2 = two_scale ? nca_dynca_bwd_ms_grid(B, H, W) : nca_dynca_bwd_grid_c(B, C, H, W);
+    p.grid2 = v.two_scale ? nca_dynca_bwd_ms_grid(B, H, W) : nca_dynca_bwd_grid_c(B, C, H, W);
     p.gridg = bfmma ? nca_gram_bf16_grid(B, H * W) : nca_gram_grid(B, H * W);
     size_t o = 0;
     auto take = [&](size_t floats) { size_t at = o; o += (floats * sizeof(float) + 255) & ~(size_t)255; return at; };
@@ -1368,51 +1407,45 @@ DyncaBwdPlan dynca_bwd_plan(int B, int C, int H, int W, int fc, int c_cond, bool
     p.off_wsg = take((size_t)p.gridg * ((size_t)p.fs * p.K1 + p.fs));
     p.off_acc1 = take((size_t)p.nsl * ((size_t)p.fs * p.K1 + p.fs));
     p.off_acc2 = take((size_t)p.nsl * ((size_t)C * p.fs + C));
-    if (two_scale) {   // coarse-level perception, its gradient, and dL/dx of the coarse level
+    if (v.two_scale) {   // coarse-level perception, its gradient, and dL/dx of the coarse level
         p.off_pc = take(p.n);      // 4C * (H/2) * (W/2) = C*H*W floats
         p.off_dpc = take(p.n);
         p.off_dxc = take(p.n / 4);
     }
-    if (bf16) p.off_x32 = take(p.n);   // x_t widened to fp32
+    if (v.state_bytes == 2) p.off_x32 = take(p.n);   // x_t widened to fp32
     p.total = o;
     return p;
 }
-}  // namespace
 
-size_t ncahip_dynca_nsteps_bwd_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond).total;
-}
-size_t ncahip_dynca_nsteps_bwd_ms_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond, true).total;
+size_t dynca_nsteps_bwd_query(const DyncaBwdVariant& v, int B, int C, int H, int W, int fc, int c_cond) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !dynca_bwd_range_ok(v.mma, C, fc, c_cond)) return 0;
+    return dynca_bwd_plan(v, B, C, H, W, fc, c_cond).total;
 }
 
-static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, int T, const float* cond, const float* u, const float* w1, const float* b1,
-                                const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
-                                float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
-                                float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
-                                size_t workspace_bytes, ncahip_stream_t stream, bool bfmma = false, bool bfmma_wide = false) {
+int dynca_nsteps_bwd_impl(const DyncaBwdVariant& v, const void* states_v, int T, const float* cond, const float* u, const float* w1, const float* b1,
+                          const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                          float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
+                          float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
+                          size_t workspace_bytes, ncahip_stream_t stream) {
     const char* const states = (const char*)states_v;
-    const bool bf16 = sb == 2;
+    const bool two_scale = v.two_scale, bf16 = v.state_bytes == 2, bfmma = v.mma != kBwdExact;
     if (int rc = dynca_dir_refuse("dynca nsteps bwd")) return rc;
     if (T < 1 || !states || !g_final || !g_x0 || !g_w1 || !g_b1 || !g_w2 || !g_b2 || !workspace)
         return fail(NCAHIP_EINVAL, "dynca nsteps bwd: null pointer or T < 1");
     if (int rc = check_dynca(states, g_x0, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, kMaxFcFwd)) return rc;
     if (bf16 && ((((size_t)B * C * H * W) & 3) != 0 || ((uintptr_t)states & 7) != 0))
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16): B*C*H*W %% 4 == 0 and 8-byte aligned states required");
-    if ((size_t)(128 > 4 * C ? 128 : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
-        return fail(NCAHIP_ERANGE, "dynca nsteps bwd: 4C*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    if (bfmma && !bfmma_wide && !nca_dynca_bf16_shape_ok(C, fc))   // bf16-MFMA training mode: the history is a mode-1 one, the backward its own kernels
+    if (int rc = check_store_offsets("dynca nsteps bwd", "4C", 128, C, H, W)) return rc;
+    if (v.mma == kBwdBfNarrow && !dynca_bwd_range_ok(v.mma, C, fc, c_cond))   // bf16-MFMA training mode: the history is a mode-1 one, the backward its own kernels
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16 MFMA): C=%d fc=%d outside the mode's range (C <= 16, fc <= 128)", C, fc);
-    if (bfmma_wide && (!bfmma || two_scale || !nca_dynca_bf16_wide_shape_ok(C, fc) || nca_dynca_bf16_shape_ok(C, fc)))   // (the wide entry point sends narrow shapes to the narrow path)
+    if (v.mma == kBwdBfWide && !dynca_bwd_range_ok(v.mma, C, fc, c_cond))     // (a narrow shape is in the wide range too: it runs the narrow path)
         return fail(NCAHIP_ERANGE, "dynca nsteps bwd (bf16 MFMA, wide): C=%d fc=%d outside the mode's wide range (C <= 32, fc <= 256, single-scale)", C, fc);
     if (two_scale) {
         if (int rc = check_ms(C, H, W, fc, pad_mode, workspace)) return rc;
     }
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, update_rate, true)) return rc;
-    const DyncaBwdPlan p = dynca_bwd_plan(B, C, H, W, fc, c_cond, two_scale, bf16, bfmma);
+    const DyncaBwdPlan p = dynca_bwd_plan(v, B, C, H, W, fc, c_cond);
     if (workspace_bytes < p.total) return fail(NCAHIP_EINVAL, "dynca nsteps bwd: workspace too small");
     if (((uintptr_t)workspace & 15) != 0) return fail(NCAHIP_ERANGE, "dynca nsteps bwd: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -1435,7 +1468,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     const size_t slot = p.n, uslot = (size_t)B * H * W;
     const float* gcur = g_final;
     for (int t = T - 1; t >= 0; --t) {
-        const float* x_t = reinterpret_cast<const float*>(states + (size_t)t * slot * sb);
+        const float* x_t = reinterpret_cast<const float*>(states + (size_t)t * slot * v.state_bytes);
         if (bf16) {   // bf16 history (storage format only: the DyNCA step computes in fp32 on the widened state)
             float* const x32 = (float*)(ws + p.off_x32);
             if (int rc = hip_result(nca_launch_widen_bf16(reinterpret_cast<const uint16_t*>(x_t), x32, slot, st), "dynca nsteps bwd widen")) return rc;
@@ -1447,7 +1480,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
             if (int rc = hip_result(nca_launch_dynca_coarse_perceive(x_t, pcb, B, C, H, W, pad_mode, st), "dynca nsteps bwd coarse perceive")) return rc;
         }
         for (int sl = 0; sl < p.nsl; ++sl) {
-            const int h0 = sl * 128, fs = bfmma ? fc : (fc - h0 < 128 ? fc - h0 : 128);
+            const auto [h0, fs] = p.slice(sl);
             NcaDyncaArgs a{x_t, nullptr, cond, u_at(u, ubits, t, uslot), w1 + (size_t)h0 * p.K1, b1 + h0, w2 + h0, b2, B, C, H, W,
                            fs, c_cond, pad_mode, update_rate, seed, step0 + (uint64_t)t, gcur, nullptr, dh, dy, g_out};
             a.w2_ld = fc;
@@ -1456,12 +1489,10 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
             a.pc = pcb;
             a.ybuf = sl == 0 ? y : nullptr;
             if (bfmma) {   // the whole layer (wide range: sliced inside the step launcher); y and dh are bf16 buffers in the same workspace regions
-                if (int rc = hip_result(bfmma_wide ? nca_launch_dynca_step_bwd_mlp_bf16_wide(a, st) : nca_launch_dynca_step_bwd_mlp_bf16(a, st),
-                                        "dynca nsteps bwd step (bf16 MFMA)")) return rc;
+                if (int rc = hip_result(dynca_bwd_mlp_bf16(a, st), "dynca nsteps bwd step (bf16 MFMA)")) return rc;
                 if (int rc = hip_result(nca_launch_reduce_rows(ws2, acc2, p.grid2, C * fs + C, st, true), "dynca nsteps bwd reduce")) return rc;
-                const auto gram = bfmma_wide ? nca_launch_gram_rows_bf16_wide : nca_launch_gram_rows_bf16;
-                if (int rc = hip_result(gram(reinterpret_cast<const uint16_t*>(dh), fs, reinterpret_cast<const uint16_t*>(y), 4 * C,
-                                             cond, c_cond, B, H * W, acc1, wsg, st, true), "dynca nsteps bwd gram (bf16 MFMA)")) return rc;
+                if (int rc = hip_result(nca_launch_gram_rows_bf16_wide(reinterpret_cast<const uint16_t*>(dh), fs, reinterpret_cast<const uint16_t*>(y), 4 * C,
+                                                                       cond, c_cond, B, H * W, acc1, wsg, st, true), "dynca nsteps bwd gram (bf16 MFMA)")) return rc;
                 continue;
             }
             if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp(a, st, sl > 0), "dynca nsteps bwd step")) return rc;
@@ -1488,7 +1519,7 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     }
     // accumulators -> gradients in the reference layouts: w1 [fc, K1] rows of a slice are contiguous, w2 [C, fc] columns are not
     for (int sl = 0; sl < p.nsl && e == hipSuccess; ++sl) {
-        const int h0 = sl * 128, fs = bfmma ? fc : (fc - h0 < 128 ? fc - h0 : 128);
+        const auto [h0, fs] = p.slice(sl);
         const float* const s1 = acc1 + (size_t)sl * a1n;
         const float* const s2 = acc2 + (size_t)sl * a2n;
         e = hipMemcpyAsync(g_w1 + (size_t)h0 * p.K1, s1, (size_t)fs * p.K1 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -1500,13 +1531,18 @@ static int dynca_nsteps_bwd_impl(bool two_scale, const void* states_v, int sb, i
     }
     return hip_result(e, "dynca nsteps bwd copy");
 }
+}  // namespace
+
+size_t ncahip_dynca_nsteps_bwd_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdF32, B, C, H, W, fc, c_cond); }
+size_t ncahip_dynca_nsteps_bwd_ms_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdMs, B, C, H, W, fc, c_cond); }
+size_t ncahip_dynca_nsteps_bwd_bf16_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdBf16, B, C, H, W, fc, c_cond); }
 
 int ncahip_dynca_nsteps_bwd_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
                                 const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                 float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                 float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                 size_t workspace_bytes, ncahip_stream_t stream) {
-    return dynca_nsteps_bwd_impl(false, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+    return dynca_nsteps_bwd_impl(kBwdF32, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
                                  g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
 }
 int ncahip_dynca_nsteps_bwd_ms_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
@@ -1514,20 +1550,15 @@ int ncahip_dynca_nsteps_bwd_ms_f32(const float* states, int T, const float* cond
                                    float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                    float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                    size_t workspace_bytes, ncahip_stream_t stream) {
-    return dynca_nsteps_bwd_impl(true, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+    return dynca_nsteps_bwd_impl(kBwdMs, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
                                  g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
-}
-
-size_t ncahip_dynca_nsteps_bwd_bf16_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond, false, true).total;
 }
 int ncahip_dynca_nsteps_bwd_bf16(const uint16_t* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
                                  const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                  float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                  float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                  size_t workspace_bytes, ncahip_stream_t stream) {
-    return dynca_nsteps_bwd_impl(false, states, 2, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+    return dynca_nsteps_bwd_impl(kBwdBf16, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
                                  g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
 }
 
@@ -1549,147 +1580,115 @@ int ncahip_gram_rows_f32(const float* a, int ma, const float* b1, int nb1, const
                                            accumulate != 0), "gram_rows");
 }
 
-// ---- the bf16-MFMA training mode of DyNCA: stage entry points (the drivers are ncahip_dynca_nsteps_bwd_bfmma_f32 / _ms_) ----------
-size_t ncahip_gram_rows_bf16_workspace(int ma, int nb, int B, int HW) {
-    if (ma <= 0 || ma > 128 || nb <= 0 || nb > 79 || B <= 0 || HW <= 0) return 0;
+// ---- the bf16-MFMA training mode of DyNCA: stage entry points (the drivers are ncahip_dynca_nsteps_bwd_bfmma_f32 / _ms_ / _wide_) ----
+namespace {
+size_t gram_rows_bf16_query(const NcaGramBfRange& r, int ma, int nb, int B, int HW) {
+    if (ma <= 0 || nb <= 0 || B <= 0 || HW <= 0 || !nca_gram_bf16_fits(r, ma, nb)) return 0;
     return (size_t)nca_gram_bf16_grid(B, HW) * ((size_t)ma * nb + ma) * sizeof(float);
 }
 
-int ncahip_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
-                          float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
-    if (!a || !b1 || !out || !workspace || (nb2 > 0) != (b2 != nullptr)) return fail(NCAHIP_EINVAL, "gram_rows_bf16: null pointer");
-    if (ma <= 0 || nb1 <= 0 || nb2 < 0 || B <= 0 || HW <= 0) return fail(NCAHIP_EINVAL, "gram_rows_bf16: bad size");
+int gram_rows_bf16_impl(const char* who, const NcaGramBfRange& r, const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B,
+                        int HW, float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!a || !b1 || !out || !workspace || (nb2 > 0) != (b2 != nullptr)) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
+    if (ma <= 0 || nb1 <= 0 || nb2 < 0 || B <= 0 || HW <= 0) return fail(NCAHIP_EINVAL, "%s: bad size", who);
     const int nb = nb1 + nb2;
-    if (ma > 128 || nb > 79) return fail(NCAHIP_ERANGE, "gram_rows_bf16: ma=%d nb=%d outside (<=128 x <=79)", ma, nb);
+    if (!nca_gram_bf16_fits(r, ma, nb)) return fail(NCAHIP_ERANGE, "%s: ma=%d nb=%d outside (<=%d x <=%d)", who, ma, nb, r.ma, r.nb);
     if ((((uintptr_t)a | (uintptr_t)b1) & 1) != 0 || (((uintptr_t)b2 | (uintptr_t)out | (uintptr_t)workspace) & 3) != 0)
-        return fail(NCAHIP_ERANGE, "gram_rows_bf16: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)");
-    if (workspace_bytes < ncahip_gram_rows_bf16_workspace(ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "gram_rows_bf16: workspace too small");
-    return hip_result(nca_launch_gram_rows_bf16(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream, accumulate != 0),
-                      "gram_rows_bf16");
+        return fail(NCAHIP_ERANGE, "%s: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)", who);
+    if (workspace_bytes < gram_rows_bf16_query(r, ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "%s: workspace too small", who);
+    // one launcher for both ranges: inside the narrow one it IS nca_launch_gram_rows_bf16
+    return hip_result(nca_launch_gram_rows_bf16_wide(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream, accumulate != 0), who);
 }
 
-size_t ncahip_dynca_step_bwd_bfmma_workspace(int B, int C, int H, int W, int fc) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || !nca_dynca_bf16_shape_ok(C, fc)) return 0;
+size_t dynca_step_bwd_bfmma_query(const DyncaStepBwd& v, int B, int C, int H, int W, int fc) {
+    if (!dims_ok(B, C, H, W) || fc <= 0 || !dynca_bwd_mlp_range_ok(v.mma, C, fc)) return 0;
     return (size_t)nca_dynca_bwd_grid_c(B, C, H, W) * ((size_t)C * fc + C) * sizeof(float);
 }
 
+int dynca_step_bwd_bfmma_impl(const DyncaStepBwd& v, const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
+                              const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
+                              float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
+                              uint16_t* y_out, uint16_t* dh_out, float* dy_scratch, float* gw2_out, int accumulate,
+                              void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
+                   g_next, nullptr, reinterpret_cast<float*>(dh_out), dy_scratch, g_x};
+    a.gw2_ws = (float*)workspace;
+    a.ybuf = reinterpret_cast<float*>(y_out);
+    a.u_bits = u_is_bits(u, seed);
+    if (int rc = dynca_step_bwd_checks(v, !g_next || !g_x || !y_out || !dh_out || !dy_scratch || !gw2_out || !workspace, a)) return rc;
+    if (workspace_bytes < dynca_step_bwd_bfmma_query(v, B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "%s: workspace too small", v.who);
+    if (((uintptr_t)workspace & 3) != 0 || (((uintptr_t)y_out | (uintptr_t)dh_out) & 1) != 0)
+        return fail(NCAHIP_ERANGE, "%s: misaligned workspace (4 bytes) or bf16 output (2 bytes)", v.who);
+    if (int rc = check_bits(a.u_bits, B, H, W, update_rate, true)) return rc;
+    if (int rc = hip_result(dynca_bwd_mlp_bf16(a, (hipStream_t)stream), v.label)) return rc;
+    if (int rc = hip_result(nca_launch_dynca_step_bwd_stencil(a, (hipStream_t)stream), v.label, " stencil")) return rc;
+    return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
+                                             (hipStream_t)stream, accumulate != 0), v.label, " reduce");
+}
+}  // namespace
+
+size_t ncahip_gram_rows_bf16_workspace(int ma, int nb, int B, int HW) { return gram_rows_bf16_query(kNcaGramBf, ma, nb, B, HW); }
+int ncahip_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
+                          float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    return gram_rows_bf16_impl("gram_rows_bf16", kNcaGramBf, a, ma, b1, nb1, b2, nb2, B, HW, out, accumulate, workspace, workspace_bytes, stream);
+}
+
+size_t ncahip_dynca_step_bwd_bfmma_workspace(int B, int C, int H, int W, int fc) { return dynca_step_bwd_bfmma_query(kStepBwdBfmma, B, C, H, W, fc); }
 int ncahip_dynca_step_bwd_bfmma_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
                                     const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                     float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
                                     uint16_t* y_out, uint16_t* dh_out, float* dy_scratch, float* gw2_out, int accumulate,
                                     void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
-    if (int rc = dynca_dir_refuse("dynca step bwd_bfmma")) return rc;
-    if (!g_next || !g_x || !y_out || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: null pointer");
-    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode)) return rc;
-    if (!nca_dynca_bf16_shape_ok(C, fc)) return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: C=%d fc=%d outside the bf16-MFMA range (C <= 16, fc <= 128)", C, fc);
-    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: g_next and g_x must not alias");
-    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
-        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    if (workspace_bytes < ncahip_dynca_step_bwd_bfmma_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma: workspace too small");
-    if (((uintptr_t)workspace & 3) != 0 || (((uintptr_t)y_out | (uintptr_t)dh_out) & 1) != 0)
-        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma: misaligned workspace (4 bytes) or bf16 output (2 bytes)");
-    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
-                   g_next, nullptr, reinterpret_cast<float*>(dh_out), dy_scratch, g_x};
-    a.gw2_ws = (float*)workspace;
-    a.ybuf = reinterpret_cast<float*>(y_out);
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
-    a.u_bits = u_is_bits(u, seed);
-    if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16(a, (hipStream_t)stream), "dynca_step_bwd_bfmma")) return rc;
-    if (int rc = hip_result(nca_launch_dynca_step_bwd_stencil(a, (hipStream_t)stream), "dynca_step_bwd_bfmma stencil")) return rc;
-    return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
-                                             (hipStream_t)stream, accumulate != 0), "dynca_step_bwd_bfmma reduce");
+    return dynca_step_bwd_bfmma_impl(kStepBwdBfmma, x_t, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, g_x,
+                                     y_out, dh_out, dy_scratch, gw2_out, accumulate, workspace, workspace_bytes, stream);
 }
 
-size_t ncahip_dynca_nsteps_bwd_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_shape_ok(C, fc) || 4 * C + c_cond > 79) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond, false, false, true).total;
-}
-size_t ncahip_dynca_nsteps_bwd_ms_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_shape_ok(C, fc) || 4 * C + c_cond > 79) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond, true, false, true).total;
-}
+size_t ncahip_dynca_nsteps_bwd_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdBfmma, B, C, H, W, fc, c_cond); }
+size_t ncahip_dynca_nsteps_bwd_ms_bfmma_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdMsBfmma, B, C, H, W, fc, c_cond); }
 int ncahip_dynca_nsteps_bwd_bfmma_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
                                       const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                       float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                       float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                       size_t workspace_bytes, ncahip_stream_t stream) {
-    return dynca_nsteps_bwd_impl(false, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
-                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true);
+    return dynca_nsteps_bwd_impl(kBwdBfmma, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
 }
 int ncahip_dynca_nsteps_bwd_ms_bfmma_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
                                          const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                          float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                          float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                          size_t workspace_bytes, ncahip_stream_t stream) {
-    return dynca_nsteps_bwd_impl(true, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
-                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true);
+    return dynca_nsteps_bwd_impl(kBwdMsBfmma, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
 }
 
 // ---- the wide range of the bf16-MFMA training mode (C <= 32, fc <= 256, single-scale): a narrow shape runs the narrow path -----------
-size_t ncahip_gram_rows_bf16_wide_workspace(int ma, int nb, int B, int HW) {
-    if (ma <= 0 || ma > 256 || nb <= 0 || nb > 132 || B <= 0 || HW <= 0) return 0;
-    return (size_t)nca_gram_bf16_grid(B, HW) * ((size_t)ma * nb + ma) * sizeof(float);
-}
-
+size_t ncahip_gram_rows_bf16_wide_workspace(int ma, int nb, int B, int HW) { return gram_rows_bf16_query(kNcaGramBfWide, ma, nb, B, HW); }
 int ncahip_gram_rows_bf16_wide(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                float* out, int accumulate, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
-    if (!a || !b1 || !out || !workspace || (nb2 > 0) != (b2 != nullptr)) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: null pointer");
-    if (ma <= 0 || nb1 <= 0 || nb2 < 0 || B <= 0 || HW <= 0) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: bad size");
-    const int nb = nb1 + nb2;
-    if (ma > 256 || nb > 132) return fail(NCAHIP_ERANGE, "gram_rows_bf16_wide: ma=%d nb=%d outside (<=256 x <=132)", ma, nb);
-    if ((((uintptr_t)a | (uintptr_t)b1) & 1) != 0 || (((uintptr_t)b2 | (uintptr_t)out | (uintptr_t)workspace) & 3) != 0)
-        return fail(NCAHIP_ERANGE, "gram_rows_bf16_wide: misaligned pointer (bf16: 2 bytes; fp32 and workspace: 4 bytes)");
-    if (workspace_bytes < ncahip_gram_rows_bf16_wide_workspace(ma, nb, B, HW)) return fail(NCAHIP_EINVAL, "gram_rows_bf16_wide: workspace too small");
-    return hip_result(nca_launch_gram_rows_bf16_wide(a, ma, b1, nb1, b2, nb2, B, HW, out, (float*)workspace, (hipStream_t)stream, accumulate != 0),
-                      "gram_rows_bf16_wide");
+    return gram_rows_bf16_impl("gram_rows_bf16_wide", kNcaGramBfWide, a, ma, b1, nb1, b2, nb2, B, HW, out, accumulate, workspace, workspace_bytes, stream);
 }
 
-size_t ncahip_dynca_step_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || !nca_dynca_bf16_wide_shape_ok(C, fc)) return 0;
-    return (size_t)nca_dynca_bwd_grid_c(B, C, H, W) * ((size_t)C * fc + C) * sizeof(float);
-}
-
+size_t ncahip_dynca_step_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc) { return dynca_step_bwd_bfmma_query(kStepBwdBfmmaWide, B, C, H, W, fc); }
 int ncahip_dynca_step_bwd_bfmma_wide_f32(const float* x_t, const float* cond, const float* u, const float* w1, const float* b1,
                                          const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                          float update_rate, uint64_t seed, uint64_t step, const float* g_next, float* g_x,
                                          uint16_t* y_out, uint16_t* dh_out, float* dy_scratch, float* gw2_out, int accumulate,
                                          void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
-    if (nca_dynca_bf16_shape_ok(C, fc))   // the narrow range: the narrow entry point, its kernels and its refusals
-        return ncahip_dynca_step_bwd_bfmma_f32(x_t, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, g_x,
-                                               y_out, dh_out, dy_scratch, gw2_out, accumulate, workspace, workspace_bytes, stream);
-    if (int rc = dynca_dir_refuse("dynca step bwd_bfmma_wide")) return rc;
-    if (!g_next || !g_x || !y_out || !dh_out || !dy_scratch || !gw2_out || !workspace) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: null pointer");
-    if (int rc = check_dynca(x_t, g_x, cond, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, 256)) return rc;   // NCAHIP_ERANGE beyond C = 32 / fc = 256
-    if (g_next == g_x) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: g_next and g_x must not alias");
-    if ((size_t)(fc > 4 * C ? fc : 4 * C) * H * W * sizeof(float) >= ((size_t)1 << 32))
-        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma_wide: fc*H*W*4 must stay below 4 GiB (32-bit store offsets inside a batch item)");
-    if (workspace_bytes < ncahip_dynca_step_bwd_bfmma_wide_workspace(B, C, H, W, fc)) return fail(NCAHIP_EINVAL, "dynca step bwd_bfmma_wide: workspace too small");
-    if (((uintptr_t)workspace & 3) != 0 || (((uintptr_t)y_out | (uintptr_t)dh_out) & 1) != 0)
-        return fail(NCAHIP_ERANGE, "dynca step bwd_bfmma_wide: misaligned workspace (4 bytes) or bf16 output (2 bytes)");
-    NcaDyncaArgs a{x_t, nullptr, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step,
-                   g_next, nullptr, reinterpret_cast<float*>(dh_out), dy_scratch, g_x};
-    a.gw2_ws = (float*)workspace;
-    a.ybuf = reinterpret_cast<float*>(y_out);
-    if (int rc = check_bits(u_is_bits(u, seed), B, H, W, update_rate, true)) return rc;
-    a.u_bits = u_is_bits(u, seed);
-    if (int rc = hip_result(nca_launch_dynca_step_bwd_mlp_bf16_wide(a, (hipStream_t)stream), "dynca_step_bwd_bfmma_wide")) return rc;
-    if (int rc = hip_result(nca_launch_dynca_step_bwd_stencil(a, (hipStream_t)stream), "dynca_step_bwd_bfmma_wide stencil")) return rc;
-    return hip_result(nca_launch_reduce_rows((const float*)workspace, gw2_out, nca_dynca_bwd_grid_c(B, C, H, W), C * fc + C,
-                                             (hipStream_t)stream, accumulate != 0), "dynca_step_bwd_bfmma_wide reduce");
+    const DyncaStepBwd& v = nca_dynca_bf16_shape_ok(C, fc) ? kStepBwdBfmma : kStepBwdBfmmaWide;   // the narrow range: the narrow entry point, its kernels and its refusals
+    return dynca_step_bwd_bfmma_impl(v, x_t, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step, g_next, g_x,
+                                     y_out, dh_out, dy_scratch, gw2_out, accumulate, workspace, workspace_bytes, stream);
 }
 
-size_t ncahip_dynca_nsteps_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc, int c_cond) {
-    if (!dims_ok(B, C, H, W) || fc <= 0 || c_cond < 0 || !nca_dynca_bf16_wide_shape_ok(C, fc) || 4 * C + c_cond > 132) return 0;
-    return dynca_bwd_plan(B, C, H, W, fc, c_cond, false, false, true).total;
-}
+// a narrow shape is inside the wide range and runs the narrow kernels: then exactly ncahip_dynca_nsteps_bwd_bfmma_f32
+size_t ncahip_dynca_nsteps_bwd_bfmma_wide_workspace(int B, int C, int H, int W, int fc, int c_cond) { return dynca_nsteps_bwd_query(kBwdBfmmaWide, B, C, H, W, fc, c_cond); }
 int ncahip_dynca_nsteps_bwd_bfmma_wide_f32(const float* states, int T, const float* cond, const float* u, const float* w1, const float* b1,
                                            const float* w2, const float* b2, int B, int C, int H, int W, int fc, int c_cond, int pad_mode,
                                            float update_rate, uint64_t seed, uint64_t step0, const float* g_final, const float* g_states,
                                            float* g_x0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, void* workspace,
                                            size_t workspace_bytes, ncahip_stream_t stream) {
-    const bool wide = !nca_dynca_bf16_shape_ok(C, fc);   // a narrow shape: exactly ncahip_dynca_nsteps_bwd_bfmma_f32
-    return dynca_nsteps_bwd_impl(false, states, 4, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
-                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream, true, wide);
+    return dynca_nsteps_bwd_impl(kBwdBfmmaWide, states, T, cond, u, w1, b1, w2, b2, B, C, H, W, fc, c_cond, pad_mode, update_rate, seed, step0, g_final,
+                                 g_states, g_x0, g_w1, g_b1, g_w2, g_b2, workspace, workspace_bytes, stream);
 }
 
 // ---- relaxed-EMD part of the OT appearance loss (nca_ot.hip) ---------------------------------------------------------

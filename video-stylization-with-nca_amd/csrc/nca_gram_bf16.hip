@@ -215,7 +215,7 @@ int nca_gram_bf16_grid(int B, int HW) {
 hipError_t nca_launch_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                      float* out, float* ws, hipStream_t st, bool accumulate) {
     const int nb = nb1 + nb2, grid = nca_gram_bf16_grid(B, HW);
-    if (ma < 1 || ma > 128 || nb1 < 1 || nb2 < 0 || nb > 79 || (nb2 > 0 && !b2)) return hipErrorInvalidValue;
+    if (ma < 1 || nb1 < 1 || nb2 < 0 || !nca_gram_bf16_fits(kNcaGramBf, ma, nb) || (nb2 > 0 && !b2)) return hipErrorInvalidValue;
     const GramBfArgs ga{a, b1, b2, ws, ma, nb1, nb2, B, HW};
     const bool vec = HW % 8 == 0 && (((uintptr_t)a | (uintptr_t)b1 | (uintptr_t)b2) & 15u) == 0;
     hipError_t e;
@@ -235,8 +235,8 @@ hipError_t nca_launch_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* 
 hipError_t nca_launch_gram_rows_bf16_wide(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                           float* out, float* ws, hipStream_t st, bool accumulate) {
     const int nb = nb1 + nb2, grid = nca_gram_bf16_grid(B, HW);
-    if (ma < 1 || ma > 256 || nb1 < 1 || nb2 < 0 || nb > 132 || (nb2 > 0 && !b2)) return hipErrorInvalidValue;
-    if (ma <= 128 && nb <= 79) return nca_launch_gram_rows_bf16(a, ma, b1, nb1, b2, nb2, B, HW, out, ws, st, accumulate);
+    if (ma < 1 || nb1 < 1 || nb2 < 0 || !nca_gram_bf16_fits(kNcaGramBfWide, ma, nb) || (nb2 > 0 && !b2)) return hipErrorInvalidValue;
+    if (nca_gram_bf16_fits(kNcaGramBf, ma, nb)) return nca_launch_gram_rows_bf16(a, ma, b1, nb1, b2, nb2, B, HW, out, ws, st, accumulate);
     const GramBfArgs ga{a, b1, b2, ws, ma, nb1, nb2, B, HW};
     const bool vec = HW % 8 == 0 && (((uintptr_t)a | (uintptr_t)b1 | (uintptr_t)b2) & 15u) == 0;
     const int tiles = (nb + 16) / 16, cblocks = (tiles + 4) / 5, nbt = (tiles + cblocks - 1) / cblocks;   // column tiles covering nb + 1 columns, at most five per block

@@ -224,6 +224,10 @@ hipError_t nca_launch_gram_rows(const float* a, int ma, const float* b1, int nb1
                                 float* out, float* ws, hipStream_t st, bool accumulate = false);
 // nca_gram_bf16.hip: the same product over bf16 operands (a, b1: bf16; b2: fp32, rounded as loaded); ma <= 128, nb1 + nb2 <= 79
 int nca_gram_bf16_grid(int B, int HW);
+// the two ranges of that product (rows ma x columns nb = nb1 + nb2): this launcher's, and nca_launch_gram_rows_bf16_wide's below
+struct NcaGramBfRange { int ma, nb; };
+constexpr NcaGramBfRange kNcaGramBf{128, 79}, kNcaGramBfWide{256, 132};
+inline bool nca_gram_bf16_fits(const NcaGramBfRange& r, int ma, int nb) { return ma <= r.ma && nb <= r.nb; }
 hipError_t nca_launch_gram_rows_bf16(const uint16_t* a, int ma, const uint16_t* b1, int nb1, const float* b2, int nb2, int B, int HW,
                                      float* out, float* ws, hipStream_t st, bool accumulate = false);
 // nca_dynca_bwd_bf16.hip: MLP part of one backward step in the bf16-MFMA training mode (ybuf / dhbuf point at bf16 buffers)

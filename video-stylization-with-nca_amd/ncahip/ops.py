@@ -105,7 +105,6 @@ def set_cond_precision(mode) -> None:
     check(lib().ncahip_cond_precision({"exact": 0, "bf16x3": 1}.get(mode, mode)), "cond_precision")
 
 
-_DYNCA_PRECISIONS = ("f32", "bf16", "bf16_wide")   # what the backward's `precision` takes: exact, bf16-MFMA training, its wide range
 # the forward's names: (ncahip_dynca_precision mode, ncahip_dynca_bf16_range) pairs
 _DYNCA_FWD_PRECISIONS = {"f32": (0, 0), "bf16": (1, 0), "bf16_wide": (1, 1)}
 _dynca_precision_lock = threading.RLock()
@@ -929,8 +928,17 @@ def gram_rows(a: torch.Tensor, b1: torch.Tensor, b2: Optional[torch.Tensor] = No
     return out[:ma * nb].view(ma, nb), out[ma * nb:]
 
 
-def _gram_fits(ma: int, nb: int) -> bool:
-    return (ma <= 32 and nb <= 128) or (ma <= 128 and nb <= 144)
+_DYNCA_BWD = {   # dynca_nsteps_backward's drivers: (precision, two_scale, history storage) -> (entry point, its workspace query)
+    ("f32", False, "f32"): ("ncahip_dynca_nsteps_bwd_f32", "ncahip_dynca_nsteps_bwd_workspace"),
+    ("f32", True, "f32"): ("ncahip_dynca_nsteps_bwd_ms_f32", "ncahip_dynca_nsteps_bwd_ms_workspace"),
+    ("f32", False, "bf16"): ("ncahip_dynca_nsteps_bwd_bf16", "ncahip_dynca_nsteps_bwd_bf16_workspace"),
+    ("bf16", False, "f32"): ("ncahip_dynca_nsteps_bwd_bfmma_f32", "ncahip_dynca_nsteps_bwd_bfmma_workspace"),
+    ("bf16", True, "f32"): ("ncahip_dynca_nsteps_bwd_ms_bfmma_f32", "ncahip_dynca_nsteps_bwd_ms_bfmma_workspace"),
+    ("bf16_wide", False, "f32"): ("ncahip_dynca_nsteps_bwd_bfmma_wide_f32", "ncahip_dynca_nsteps_bwd_bfmma_wide_workspace"),
+}
+# what the backward's `precision` takes beside "f32" (exact): bf16-MFMA training and its wide range -- the range of each, and its words in a refusal
+_DYNCA_BFMMA = {"bf16": (dynca_bf16_ok, "the bf16-MFMA DyNCA backward covers C <= 16 and fc <= 128"),
+                "bf16_wide": (dynca_bf16_wide_ok, "the wide bf16-MFMA DyNCA backward covers C <= 32 and fc <= 256")}
 
 
 def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us: Optional[torch.Tensor], w: DyncaWeights,
@@ -948,7 +956,7 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
     two_scale=True the narrow two-scale driver is called; two_scale=True at a wide-only shape raises ValueError).  The ambient
     dynca_precision plays no part here.
     Returns dict x0, w1 [fc,4C+cc], b1, w2 [C,fc], b2."""
-    if precision not in _DYNCA_PRECISIONS:
+    if precision != "f32" and precision not in _DYNCA_BFMMA:
         raise ValueError(f"dynca backward precision must be 'f32', 'bf16' or 'bf16_wide', got {precision!r}")
     if precision == "bf16_wide" and two_scale:      # the wide entry point is single-scale; a narrow two-scale model has the narrow mode's driver
         if not dynca_bf16_ok(states.shape[2], w.fc):
@@ -972,28 +980,19 @@ def dynca_nsteps_backward(states: torch.Tensor, cond: Optional[torch.Tensor], us
     out = {"x0": torch.empty(B, C, H, W, device=dev, dtype=f32), "w1": torch.empty(fc, k1, device=dev, dtype=f32),
            "b1": torch.empty(fc, device=dev, dtype=f32), "w2": torch.empty(C, fc, device=dev, dtype=f32),
            "b2": torch.empty(C, device=dev, dtype=f32)}
-    sfx = "_ms" if two_scale else ""       # two_scale: backward through ncahip_dynca_nsteps_fwd_ms_f32's steps
-    assert not (two_scale and dsfx == "bf16"), "the two-scale step is an fp32 kernel"
-    fn = "ncahip_dynca_nsteps_bwd_bf16" if dsfx == "bf16" else f"ncahip_dynca_nsteps_bwd{sfx}_f32"
-    wsfn = "ncahip_dynca_nsteps_bwd_bf16_workspace" if dsfx == "bf16" else f"ncahip_dynca_nsteps_bwd{sfx}_workspace"
-    if precision == "bf16":
+    assert not (two_scale and dsfx == "bf16"), "the two-scale step is an fp32 kernel"      # two_scale: backward through ncahip_dynca_nsteps_fwd_ms_f32's steps
+    if precision in _DYNCA_BFMMA:
+        covers, words = _DYNCA_BFMMA[precision]
         if dsfx == "bf16":
             raise _capi.NcaHipError("ncahip: the bf16-MFMA DyNCA backward takes a float32 history (bf16 state storage is out of its scope)")
-        if not dynca_bf16_ok(C, fc):
-            raise _capi.NcaHipError(f"ncahip: the bf16-MFMA DyNCA backward covers C <= 16 and fc <= 128, got C={C} fc={fc}")
-        fn, wsfn = f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_f32", f"ncahip_dynca_nsteps_bwd{sfx}_bfmma_workspace"
-    if precision == "bf16_wide":
-        if dsfx == "bf16":
-            raise _capi.NcaHipError("ncahip: the bf16-MFMA DyNCA backward takes a float32 history (bf16 state storage is out of its scope)")
-        if not dynca_bf16_wide_ok(C, fc):
-            raise _capi.NcaHipError(f"ncahip: the wide bf16-MFMA DyNCA backward covers C <= 32 and fc <= 256, got C={C} fc={fc}")
-        fn, wsfn = "ncahip_dynca_nsteps_bwd_bfmma_wide_f32", "ncahip_dynca_nsteps_bwd_bfmma_wide_workspace"
+        if not covers(C, fc):
+            raise _capi.NcaHipError(f"ncahip: {words}, got C={C} fc={fc}")
+    fn, wsfn = _DYNCA_BWD[precision, bool(two_scale), dsfx]
     nbytes = getattr(lib(), wsfn)(B, C, H, W, fc, c_cond)
     ws = _workspace(nbytes, dev)
-    check(getattr(lib(), fn)(_p(states), T, _p(cond), _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, H, W, fc,
-                                            c_cond, PAD_MODES[pad_mode], update_rate, seed, step0, _p(g), _p(g_states), _p(out["x0"]),
-                                            _p(out["w1"]), _p(out["b1"]), _p(out["w2"]), _p(out["b2"]), _p(ws), nbytes, _stream()),
-          "dynca_nsteps_bwd" + sfx)
+    check(getattr(lib(), fn)(_p(states), T, _p(cond), _p(us), _p(w.w1), _p(w.b1), _p(w.w2), _p(w.b2), B, C, H, W, fc, c_cond, PAD_MODES[pad_mode],
+                             update_rate, seed, step0, _p(g), _p(g_states), _p(out["x0"]), _p(out["w1"]), _p(out["b1"]), _p(out["w2"]), _p(out["b2"]), _p(ws),
+                             nbytes, _stream()), "dynca_nsteps_bwd" + ("_ms" if two_scale else ""))
     return out
 
 
