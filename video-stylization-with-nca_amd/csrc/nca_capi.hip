@@ -488,31 +488,17 @@ static bool clip_overlap(const void* a, size_t an, const void* b, size_t bn) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + bn && pb < pa + an;
 }
-// images (never frames) may also leave as planar YUV 4:2:0: NCAHIP_CLIP_YUV420(layout, matrix, range) = 0x100 .. 0x107
-static bool clip_fmt_planar(int fmt) { return (fmt & ~7) == 0x100; }
-static bool clip_img_fmt_ok(int fmt) { return clip_fmt_ok(fmt) || clip_fmt_planar(fmt); }
+// images (never frames) may also leave as planar YUV 4:2:0: the record nca_img_out makes of an image format (nca_kernels.h)
 // bytes of one image of B samples: [B,c,H,W] float32, [B,H,W,c] uint8 or [B,3H/2,W] uint8 (c == 3, H and W even: checked before)
-static size_t clip_img_bytes(int fmt, int B, int c, int H, int W) {
-    return clip_fmt_planar(fmt) ? (size_t)B * H * W / 2 * 3 : (size_t)B * c * H * W * clip_fmt_bytes(fmt);
+static size_t clip_img_bytes(const NcaImgOut& io, int B, int c, int H, int W) {
+    return io.planar() ? (size_t)B * H * W / 2 * 3 : (size_t)B * c * H * W * (io.kind == kImgU8 ? 1 : sizeof(float));
 }
 // what a planar image format adds to an emit's checks: three channels (NCAHIP_EINVAL) and even sides (NCAHIP_ERANGE)
-static int check_clip_planar(const char* who, int img_fmt, int c_out, int H, int W) {
-    if (!clip_fmt_planar(img_fmt)) return 0;
+static int check_clip_planar(const char* who, const NcaImgOut& io, int c_out, int H, int W) {
+    if (!io.planar()) return 0;
     if (c_out != 3) return fail(NCAHIP_EINVAL, "%s: a planar YUV image is made of 3 channels, got c_out=%d", who, c_out);
     if ((H | W) & 1) return fail(NCAHIP_ERANGE, "%s: 4:2:0 images have even sides, got %d x %d", who, H, W);
     return 0;
-}
-// One image out of a state in format img_fmt: the float32 / uint8 launchers as before; a planar format builds its coefficients (the one
-// builder, host arithmetic) and writes the planes from the state.  unit: ConditionedNCA's image; gray: the inject of the same launch.
-static hipError_t clip_launch_emit(float* state, void* img, int img_fmt, bool unit, const float* gray, int B, int C, int c_out, int H, int W,
-                                   hipStream_t st) {
-    if (img && clip_fmt_planar(img_fmt)) {
-        int32_t k[10];
-        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
-        return nca_launch_clip_emit_yuv420(state, (unsigned char*)img, unit, (img_fmt & 1) == NCAHIP_YUV_NV12, k, gray, B, C, H, W, st);
-    }
-    const bool u8 = img_fmt == NCAHIP_CLIP_U8_NHWC;
-    return unit ? nca_launch_clip_emit_unit(state, img, u8, B, C, H, W, st) : nca_launch_clip_emit_inject(state, img, u8, gray, B, C, c_out, H, W, st);
 }
 
 size_t ncahip_clip_cond_workspace(int F, int B, int H, int W) {
@@ -533,22 +519,24 @@ int ncahip_clip_cond(const void* frames, int frame_fmt, const float* k3, float g
                                            (hipStream_t)stream), "clip_cond");
 }
 
-static int check_clip_emit(const void* state, const void* img, int img_fmt, int B, int C, int c_out, int H, int W, bool need_img = true) {
+// the checks of an image out of state[:, :c_out]; *io: the record of img_fmt, for the launcher
+static int check_clip_emit(const void* state, const void* img, int img_fmt, NcaImgOut* io, int B, int C, int c_out, int H, int W, bool need_img = true) {
     if (!state || (need_img && !img)) return fail(NCAHIP_EINVAL, "clip emit: null pointer");
-    if (!clip_img_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
+    if (!nca_img_out(img_fmt, io)) return fail(NCAHIP_EINVAL, "clip emit: unknown image format %d", img_fmt);
     if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit: bad size");
     if (c_out < 1 || c_out > 4 || c_out > C) return fail(NCAHIP_EINVAL, "clip emit: c_out=%d must be in 1..4 and at most C=%d", c_out, C);
-    if (int rc = check_clip_planar("clip emit", img_fmt, c_out, H, W)) return rc;
-    if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit: float32 images must be 4-byte aligned");
+    if (int rc = check_clip_planar("clip emit", *io, c_out, H, W)) return rc;
+    if (io->kind == kImgF32 && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit: float32 images must be 4-byte aligned");
     return 0;
 }
 
 int ncahip_clip_emit(const float* state, void* img, int img_fmt, int B, int C, int c_out, int H, int W, ncahip_stream_t stream) {
-    if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W)) return rc;
-    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(img_fmt, B, c_out, H, W)))
+    NcaImgOut io;
+    if (int rc = check_clip_emit(state, img, img_fmt, &io, B, C, c_out, H, W)) return rc;
+    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(io, B, c_out, H, W)))
         return fail(NCAHIP_EINVAL, "clip emit: the image overlaps the state");
     // without a grey plane the launcher only reads the state
-    return hip_result(clip_launch_emit(const_cast<float*>(state), img, img_fmt, false, nullptr, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit");
+    return hip_result(nca_launch_clip_emit({const_cast<float*>(state), false, img, io, false, nullptr, B, C, c_out, H, W}, (hipStream_t)stream), "clip_emit");
 }
 
 int ncahip_clip_gray(const void* frames, int frame_fmt, float gray_r, float gray_g, float gray_b, float* gray, int F, int B, int H, int W,
@@ -571,14 +559,29 @@ static int check_extra_channel(const char* who, int C, int c_out) {
 
 int ncahip_clip_emit_inject(float* state, void* img, int img_fmt, const float* gray, int B, int C, int c_out, int H, int W, ncahip_stream_t stream) {
     if (!img && !gray) return fail(NCAHIP_EINVAL, "clip emit_inject: neither an image nor a grey plane (null pointer for both halves)");
-    if (int rc = check_clip_emit(state, img, img_fmt, B, C, c_out, H, W, false)) return rc;
+    NcaImgOut io;
+    if (int rc = check_clip_emit(state, img, img_fmt, &io, B, C, c_out, H, W, false)) return rc;
     if (int rc = check_extra_channel("clip emit_inject", C, c_out)) return rc;
     const size_t sbytes = (size_t)B * C * H * W * sizeof(float), gbytes = (size_t)B * H * W * sizeof(float);
-    const size_t ibytes = clip_img_bytes(img_fmt, B, c_out, H, W);
+    const size_t ibytes = clip_img_bytes(io, B, c_out, H, W);
     if ((img && clip_overlap(state, sbytes, img, ibytes)) || (gray && clip_overlap(state, sbytes, gray, gbytes)) ||
         (img && gray && clip_overlap(img, ibytes, gray, gbytes)))
         return fail(NCAHIP_EINVAL, "clip emit_inject: state, image and grey plane must not overlap");
-    return hip_result(clip_launch_emit(state, img, img_fmt, false, gray, B, C, c_out, H, W, (hipStream_t)stream), "clip_emit_inject");
+    return hip_result(nca_launch_clip_emit({state, false, img, io, false, gray, B, C, c_out, H, W}, (hipStream_t)stream), "clip_emit_inject");
+}
+
+// What every clip driver checks of its counts: F * steps_per_frame calls (*calls) of step_n steps each ...
+static int check_clip_counts(const char* who, int F, int steps_per_frame, int step_n, uint64_t* calls) {
+    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
+    *calls = (uint64_t)F * (uint64_t)steps_per_frame;
+    if (*calls > 0x7fffffffu || *calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
+    return 0;
+}
+// ... and, behind its overlap test, of the epochs that a persistent workspace hands to those calls
+static int check_clip_epochs(const char* who, const void* persist_ws, unsigned epoch0, uint64_t calls) {
+    if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
+        return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
+    return 0;
 }
 
 // The body of the two clip drivers.  gray == NULL: ncahip_dynca_clip_f32 (cond [F] maps, one per frame).  gray != NULL:
@@ -589,15 +592,15 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
                            uint64_t seed, uint64_t step0, float* pc_scratch, void* persist_ws, size_t persist_bytes, unsigned epoch0,
                            ncahip_stream_t stream) {
     // host-side checks: nothing is enqueued before all of them have passed
-    if (int rc = check_clip_emit(states, images, img_fmt, B, C, c_out, H, W)) return rc;
+    NcaImgOut io;   // the image record of this call: built once, handed to every emit
+    if (int rc = check_clip_emit(states, images, img_fmt, &io, B, C, c_out, H, W)) return rc;
     if (gray) {
         if (int rc = check_extra_channel(who, C, c_out)) return rc;
     }
-    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
-    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
-    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
+    uint64_t calls = 0;
+    if (int rc = check_clip_counts(who, F, steps_per_frame, step_n, &calls)) return rc;
     const size_t slot = (size_t)B * C * H * W, uslot = (size_t)B * H * W, cslot = (size_t)B * c_cond * H * W;
-    const size_t ibytes = clip_img_bytes(img_fmt, B, c_out, H, W);
+    const size_t ibytes = clip_img_bytes(io, B, c_out, H, W);
     const size_t sbytes = 2 * slot * sizeof(float), cbytes = (cond_per_frame ? (size_t)F : 1) * cslot * sizeof(float);
     const size_t gbytes = (size_t)F * uslot * sizeof(float);
     if ((cond && clip_overlap(states, sbytes, cond, cbytes)) || clip_overlap(states, sbytes, images, (size_t)calls * ibytes) ||
@@ -605,8 +608,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         (gray && (clip_overlap(states, sbytes, gray, gbytes) || clip_overlap(gray, gbytes, images, (size_t)calls * ibytes) ||
                   (cond && clip_overlap(gray, gbytes, cond, cbytes)))))
         return fail(NCAHIP_EINVAL, "%s: states, %scond and images must not overlap", who, gray ? "gray, " : "");
-    if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
-        return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
+    if (int rc = check_clip_epochs(who, persist_ws, epoch0, calls)) return rc;
     // the direction field of this call: read once, handed to every step the clip enqueues
     const NcaDyncaDir dir = nca_dynca_dir_snapshot();
     const DyncaFwdKind kind = two_scale ? kDyncaFwdMs : kDyncaFwdF32;
@@ -628,7 +630,7 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
     bool persist = persist_ws != nullptr;
     int cur = 0;   // the slot that holds the state
     if (gray) {    // the first frame's grey; every later one goes in with the image of the call before it
-        if (int rc = hip_result(nca_launch_clip_emit_inject(states, nullptr, false, gray, B, C, c_out, H, W, st), "dynca clip (inject)")) return rc;
+        if (int rc = hip_result(nca_launch_clip_emit({states, false, nullptr, io, false, gray, B, C, c_out, H, W}, st), "dynca clip (inject)")) return rc;
     }
     for (int n = 0; n < (int)calls; ++n) {
         const float* const cf = cond_per_frame ? cond + (size_t)(n / steps_per_frame) * cslot : cond;
@@ -660,9 +662,8 @@ static int dynca_clip_impl(const char* who, float* states, const float* gray, co
         // image n and, in the same launch, the grey of the call that follows (the repeats j > 0 of a frame included: the channel has
         // evolved); after the last call the channel stays as the steps left it
         const float* const gnext = gray && n + 1 < (int)calls ? gray + (size_t)((n + 1) / steps_per_frame) * uslot : nullptr;
-        if (int rc = hip_result(clip_launch_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, img_fmt, false, gnext, B, C, c_out, H, W, st),
-                                "dynca clip (emit)"))
-            return rc;
+        const NcaClipEmitArgs e{states + (size_t)cur * slot, false, (char*)images + (size_t)n * ibytes, io, false, gnext, B, C, c_out, H, W};
+        if (int rc = hip_result(nca_launch_clip_emit(e, st), "dynca clip (emit)")) return rc;
     }
     if (cur == 1)   // the state returns in slot 0
         return hip_result(hipMemcpyAsync(states, states + slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "dynca clip (state copy)");
@@ -796,14 +797,11 @@ int ncahip_cond_fused_steps_layout(int B, int C, int H, int W, int chunk_cap, in
     return 0;
 }
 
-static hipError_t cond_launch_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H,
-                                                 int W, int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, hipStream_t st);
-
-// img (bf16 only; the clip driver): the grow's last launch also writes the unit image of x_final in format img_fmt (checked by the caller)
+// img (bf16 only; the clip driver): the grow's last launch also writes the unit image *io of x_final (checked by the caller)
 static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring, int T, void* x_final, const void* goal, int goal_ch, const float* u,
                               const float* wp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, int B, int C,
                               int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo, float clamp_hi,
-                              uint64_t seed, uint64_t step0, ncahip_stream_t stream, void* img = nullptr, int img_fmt = 0) {
+                              uint64_t seed, uint64_t step0, ncahip_stream_t stream, void* img = nullptr, const NcaImgOut* io = nullptr) {
     char* const states = (char*)states_v;
     if (ring < 2 || T < 1 || !pre || !x_final) return fail(NCAHIP_EINVAL, "cond grow: ring >= 2, T >= 1, buffers required");
     if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch,
@@ -906,8 +904,8 @@ static int cond_grow_fwd_impl(bool bf16, void* states_v, uint8_t* pre, int ring,
     }
     const uint8_t* const pre_last = pre + (size_t)sl * pslot;
     if (bf16 && img)
-        return hip_result(cond_launch_finalize_emit_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, img, img_fmt, B, C, H, W,
-                                                         alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize + image (bf16)");
+        return hip_result(nca_launch_cond_finalize_emit_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, img, *io, B, C, H, W,
+                                                             alive_ch, alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize + image (bf16)");
     return bf16 ? hip_result(nca_launch_cond_finalize_bf16((const uint16_t*)(states + (size_t)sl * slot), pre_last, (uint16_t*)x_final, B, C, H, W, alive_ch,
                                                            alive_thr, clamp_lo, clamp_hi, st), "cond_grow finalize (bf16)")
                 : hip_result(nca_launch_cond_finalize((const float*)(states + (size_t)sl * slot), pre_last, (float*)x_final, B, C, H, W, alive_ch, alive_thr,
@@ -1000,93 +998,88 @@ int ncahip_clip_encode_bf16(const void* frames, int frame_fmt, const float* k3, 
     return clip_encode_impl(true, frames, frame_fmt, k3, k5, w1, b1, w2, goal, F, B, ch, E, H, W, stream);
 }
 
-static int check_clip_emit_unit(const void* state, const void* img, int img_fmt, int B, int C, int H, int W) {
+static int check_clip_emit_unit(const void* state, const void* img, int img_fmt, NcaImgOut* io, int B, int C, int H, int W) {
     if (!state || !img) return fail(NCAHIP_EINVAL, "clip emit_unit: null pointer");
-    if (!clip_img_fmt_ok(img_fmt)) return fail(NCAHIP_EINVAL, "clip emit_unit: unknown image format %d", img_fmt);
+    if (!nca_img_out(img_fmt, io)) return fail(NCAHIP_EINVAL, "clip emit_unit: unknown image format %d", img_fmt);
     if (!dims_ok(B, C, H, W)) return fail(NCAHIP_EINVAL, "clip emit_unit: bad size");
     if (C < 3) return fail(NCAHIP_EINVAL, "clip emit_unit: the image is state[:, :3], C=%d has fewer than 3 channels", C);
-    if (int rc = check_clip_planar("clip emit_unit", img_fmt, 3, H, W)) return rc;
-    if (img_fmt == NCAHIP_CLIP_F32_NCHW && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: float32 images must be 4-byte aligned");
+    if (int rc = check_clip_planar("clip emit_unit", *io, 3, H, W)) return rc;
+    if (io->kind == kImgF32 && ((uintptr_t)img & 3) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: float32 images must be 4-byte aligned");
     return 0;
 }
 
+// the two state types share every check; a state stored as bf16 has half the bytes and is 2-byte aligned
+static int clip_emit_unit_impl(bool bf16, const void* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
+    NcaImgOut io;
+    if (int rc = check_clip_emit_unit(state, img, img_fmt, &io, B, C, H, W)) return rc;
+    if (bf16 && ((uintptr_t)state & 1) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: a bf16 state must be 2-byte aligned");
+    if (clip_overlap(state, (size_t)B * C * H * W * (bf16 ? sizeof(uint16_t) : sizeof(float)), img, clip_img_bytes(io, B, 3, H, W)))
+        return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
+    return hip_result(nca_launch_clip_emit({const_cast<void*>(state), bf16, img, io, true, nullptr, B, C, 3, H, W}, (hipStream_t)stream),
+                      bf16 ? "clip_emit_unit_bf16" : "clip_emit_unit");
+}
+
 int ncahip_clip_emit_unit(const float* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
-    if (int rc = check_clip_emit_unit(state, img, img_fmt, B, C, H, W)) return rc;
-    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(float), img, clip_img_bytes(img_fmt, B, 3, H, W)))
-        return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
-    return hip_result(clip_launch_emit(const_cast<float*>(state), img, img_fmt, true, nullptr, B, C, 3, H, W, (hipStream_t)stream), "clip_emit_unit");
+    return clip_emit_unit_impl(false, state, img, img_fmt, B, C, H, W, stream);
 }
-
-// ---- the same on a state stored as bf16 ------------------------------------------------------------------------------------------
 int ncahip_clip_emit_unit_bf16(const uint16_t* state, void* img, int img_fmt, int B, int C, int H, int W, ncahip_stream_t stream) {
-    if (int rc = check_clip_emit_unit(state, img, img_fmt, B, C, H, W)) return rc;
-    if (((uintptr_t)state & 1) != 0) return fail(NCAHIP_EINVAL, "clip emit_unit: a bf16 state must be 2-byte aligned");
-    if (clip_overlap(state, (size_t)B * C * H * W * sizeof(uint16_t), img, clip_img_bytes(img_fmt, B, 3, H, W)))
-        return fail(NCAHIP_EINVAL, "clip emit_unit: the image overlaps the state");
-    hipStream_t st = (hipStream_t)stream;
-    if (clip_fmt_planar(img_fmt)) {
-        int32_t k[10];
-        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
-        return hip_result(nca_launch_clip_emit_unit_yuv420_bf16(state, (unsigned char*)img, (img_fmt & 1) == NCAHIP_YUV_NV12, k, B, C, H, W, st), "clip_emit_unit_bf16");
-    }
-    return hip_result(nca_launch_clip_emit_unit_bf16(state, img, img_fmt == NCAHIP_CLIP_U8_NHWC, B, C, H, W, st), "clip_emit_unit_bf16");
-}
-
-// the fused launch's format word (nca_kernels.h) from an image format of the clip entry points, with the coefficients of a planar one
-static hipError_t cond_launch_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H,
-                                                 int W, int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, hipStream_t st) {
-    int32_t k[10] = {0};
-    int fmt = img_fmt == NCAHIP_CLIP_U8_NHWC ? 1 : 0;
-    if (clip_fmt_planar(img_fmt)) {
-        nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, k);
-        fmt = (img_fmt & 1) == NCAHIP_YUV_NV12 ? 3 : 2;
-    }
-    return nca_launch_cond_finalize_emit_bf16(x_pend, pre, x_out, img, fmt, k, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, st);
+    return clip_emit_unit_impl(true, state, img, img_fmt, B, C, H, W, stream);
 }
 
 int ncahip_cond_finalize_emit_bf16(const uint16_t* x_pend, const uint8_t* pre, uint16_t* x_out, void* img, int img_fmt, int B, int C, int H, int W,
                                    int alive_ch, float alive_thr, float clamp_lo, float clamp_hi, ncahip_stream_t stream) {
     const char* const who = "cond_finalize_emit";
+    NcaImgOut io;
     if (!x_pend || !x_out || !img || (alive_ch >= 0 && !pre)) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
-    if (int rc = check_clip_emit_unit(x_pend, img, img_fmt, B, C, H, W)) return rc;
+    if (int rc = check_clip_emit_unit(x_pend, img, img_fmt, &io, B, C, H, W)) return rc;
     if (alive_ch >= C) return fail(NCAHIP_EINVAL, "%s: bad size (alive_ch=%d outside C=%d)", who, alive_ch, C);
     if (alive_ch >= 0 && x_pend == x_out) return fail(NCAHIP_EINVAL, "%s: in-place needs alive_ch < 0", who);
     if ((((uintptr_t)x_pend | (uintptr_t)x_out) & 1) != 0) return fail(NCAHIP_EINVAL, "%s: bf16 states must be 2-byte aligned", who);
-    const size_t sbytes = (size_t)B * C * H * W * sizeof(uint16_t), ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
+    const size_t sbytes = (size_t)B * C * H * W * sizeof(uint16_t), ibytes = clip_img_bytes(io, B, 3, H, W);
     if (clip_overlap(img, ibytes, x_pend, sbytes) || clip_overlap(img, ibytes, x_out, sbytes) || (pre && clip_overlap(img, ibytes, pre, (size_t)B * H * W)) ||
         (pre && clip_overlap(x_out, sbytes, pre, (size_t)B * H * W)))
         return fail(NCAHIP_EINVAL, "%s: the image must not overlap x_pend, x_out or pre, and x_out must not overlap pre", who);
-    return hip_result(cond_launch_finalize_emit_bf16(x_pend, pre, x_out, img, img_fmt, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, (hipStream_t)stream),
+    return hip_result(nca_launch_cond_finalize_emit_bf16(x_pend, pre, x_out, img, io, B, C, H, W, alive_ch, alive_thr, clamp_lo, clamp_hi, (hipStream_t)stream),
                       "cond_finalize_emit_bf16");
 }
 
+// The body of the two drivers; bf16: states and goal hold bf16, and there is no persistent grow (persist_ws == NULL).
 // The driver keeps the state in slot 0 or slot 2 of `states` (cur).  A persistent call reads slot cur and writes slot cur ^ 2.  A per-step call
 // runs the ring {cur, cur + 1}: after step_n steps the pending state lies in slot cur + (step_n & 1); the finalize writes the resolved state
 // to slot cur when step_n is odd (the input is dead by then) and to slot cur ^ 2 when it is even (x_final must not be the pending slot).
-int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
-                         int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
-                         const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
-                         float clamp_hi, uint64_t seed, uint64_t step0, void* persist_ws, size_t persist_bytes, unsigned epoch0,
-                         ncahip_stream_t stream) {
-    const char* const who = "cond clip";
+// Each call's steps are enqueued by cond_grow_fwd_impl as ncahip_cond_grow_fwd_f32 / _bf16 enqueue them; fp32: an emit launch follows,
+// bf16: the grow's last launch is the fused finalize + image.
+static int cond_clip_impl(bool bf16, void* states_v, uint8_t* pre, const void* goal_v, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
+                          int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
+                          const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                          float clamp_hi, uint64_t seed, uint64_t step0, void* persist_ws, size_t persist_bytes, unsigned epoch0,
+                          ncahip_stream_t stream) {
+    const char* const who = bf16 ? "cond clip (bf16)" : "cond clip";
+    char* const states = (char*)states_v;
+    const char* const goal = (const char*)goal_v;
     // host-side checks: nothing is enqueued before all of them have passed
     if (!pre || !goal) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
-    if (int rc = check_clip_emit_unit(states, images, img_fmt, B, C, H, W)) return rc;
-    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
-    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
-    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
-    // the checks of the grow drivers (ncahip_cond_grow_fwd_f32 takes no T = 0, so they are shared as functions): their codes
-    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwd)) return rc;
+    NcaImgOut io;   // the image record of this call: built once, handed to every emit
+    if (int rc = check_clip_emit_unit(states, images, img_fmt, &io, B, C, H, W)) return rc;
+    uint64_t calls = 0;
+    if (int rc = check_clip_counts(who, F, steps_per_frame, step_n, &calls)) return rc;
+    // the checks of the grow drivers (they take no T = 0, so they are shared as functions): their codes
+    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch,
+                            bf16 ? kMaxCCondFwdBf16 : kMaxCCondFwd))
+        return rc;
+    if (bf16) {   // W % 4 == 0: every state slot and every frame's goal is 8-byte aligned as slot 0 and goal[0] are
+        if (int rc = check_bf16_shape(states, states, goal, H, W)) return rc;
+    }
     const bool ubits = u_is_bits(u, seed);
     if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
-    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W, gslot = (size_t)B * goal_ch * H * W;
-    const size_t ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
-    const size_t sbytes = 4 * slot * sizeof(float), pbytes = 2 * pslot, gbytes = (size_t)F * gslot * sizeof(float), abytes = (size_t)calls * ibytes;
+    const size_t esize = bf16 ? sizeof(uint16_t) : sizeof(float), pslot = (size_t)B * H * W;
+    const size_t slot = pslot * C * esize, gslot = pslot * goal_ch * esize;   // bytes
+    const size_t ibytes = clip_img_bytes(io, B, 3, H, W);
+    const size_t sbytes = 4 * slot, pbytes = 2 * pslot, gbytes = (size_t)F * gslot, abytes = (size_t)calls * ibytes;
     if (clip_overlap(states, sbytes, goal, gbytes) || clip_overlap(states, sbytes, images, abytes) || clip_overlap(states, sbytes, pre, pbytes) ||
         clip_overlap(goal, gbytes, images, abytes) || clip_overlap(goal, gbytes, pre, pbytes) || clip_overlap(images, abytes, pre, pbytes))
         return fail(NCAHIP_EINVAL, "%s: states, pre, goal and images must not overlap", who);
-    if (persist_ws && (epoch0 < 1 || (uint64_t)epoch0 + calls >= (1u << 20)))
-        return fail(NCAHIP_EINVAL, "%s: epochs epoch0 .. epoch0 + F * steps_per_frame must lie in [1, 2^20) (zero the workspace and restart at 1 when they run out)", who);
+    if (int rc = check_clip_epochs(who, persist_ws, epoch0, calls)) return rc;
     if (persist_ws) {
         const size_t need = ncahip_cond_grow_persist_workspace(B, C, H, W, hidden, goal_ch);
         if (need != 0 && persist_bytes < need) return fail(NCAHIP_EINVAL, "%s: persistent workspace too small", who);
@@ -1097,15 +1090,16 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
     bool persist = persist_ws != nullptr;
     int cur = 0;   // the slot that holds the state: 0 or 2
     for (int n = 0; n < (int)calls; ++n) {
-        const float* const gf = goal + (size_t)(n / steps_per_frame) * gslot;
+        const char* const gf = goal + (size_t)(n / steps_per_frame) * gslot;
         const int t0 = n * step_n;                                  // first step of this call within `u`
         const uint64_t s0 = step0 + (uint64_t)t0;
-        float* const in = states + (size_t)cur * slot;
+        char* const in = states + (size_t)cur * slot;
+        void* const img = (char*)images + (size_t)n * ibytes;
         bool done = false;
         if (persist) {
-            const int rc = ncahip_cond_grow_fwd_persist_f32(in, nullptr, 2, step_n, states + (size_t)(cur ^ 2) * slot, gf, goal_ch, u_at(u, ubits, t0, pslot),
-                                                            wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi,
-                                                            seed, s0, persist_ws, persist_bytes, epoch0 + (unsigned)n, stream);
+            const int rc = ncahip_cond_grow_fwd_persist_f32((float*)in, nullptr, 2, step_n, (float*)(states + (size_t)(cur ^ 2) * slot), (const float*)gf, goal_ch,
+                                                            u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate,
+                                                            clamp_lo, clamp_hi, seed, s0, persist_ws, persist_bytes, epoch0 + (unsigned)n, stream);
             if (rc == 0) {
                 cur ^= 2;
                 done = true;
@@ -1117,61 +1111,36 @@ int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goa
         }
         if (!done) {
             const int out = (step_n & 1) ? cur : cur ^ 2;
-            if (int rc = ncahip_cond_grow_fwd_f32(in, pre, 2, step_n, states + (size_t)out * slot, gf, goal_ch, u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2,
-                                                  w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, s0, stream))
+            if (int rc = cond_grow_fwd_impl(bf16, in, pre, 2, step_n, states + (size_t)out * slot, gf, goal_ch, u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2, w3,
+                                            B, C, H, W, hidden, alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, s0, stream, bf16 ? img : nullptr, &io))
                 return rc;
             cur = out;
         }
-        if (int rc = hip_result(clip_launch_emit(states + (size_t)cur * slot, (char*)images + (size_t)n * ibytes, img_fmt, true, nullptr, B, C, 3, H, W, st),
-                                "cond clip (emit)"))
-            return rc;
+        if (!bf16) {
+            if (int rc = hip_result(nca_launch_clip_emit({states + (size_t)cur * slot, false, img, io, true, nullptr, B, C, 3, H, W}, st), "cond clip (emit)"))
+                return rc;
+        }
     }
     if (cur != 0)   // the state returns in slot 0: the one copy of a call
-        return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, st), "cond clip (state copy)");
+        return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot, hipMemcpyDeviceToDevice, st),
+                          bf16 ? "cond clip (bf16 state copy)" : "cond clip (state copy)");
     return 0;
 }
 
-// The same loop on a state stored as bf16: the per-step ring of the driver above (there is no persistent bf16 grow), each call's steps
-// enqueued by cond_grow_fwd_impl as ncahip_cond_grow_fwd_bf16 enqueues them, its last launch the fused finalize + image.
+int ncahip_cond_clip_f32(float* states, uint8_t* pre, const float* goal, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
+                         int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
+                         float clamp_hi, uint64_t seed, uint64_t step0, void* persist_ws, size_t persist_bytes, unsigned epoch0,
+                         ncahip_stream_t stream) {
+    return cond_clip_impl(false, states, pre, goal, goal_ch, images, img_fmt, F, steps_per_frame, step_n, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden,
+                          alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0, persist_ws, persist_bytes, epoch0, stream);
+}
 int ncahip_cond_clip_bf16(uint16_t* states, uint8_t* pre, const uint16_t* goal, int goal_ch, void* images, int img_fmt, int F, int steps_per_frame,
                           int step_n, const float* u, const float* wp, const float* w1, const float* b1, const float* w2, const float* b2,
                           const float* w3, int B, int C, int H, int W, int hidden, int alive_ch, float alive_thr, float fire_rate, float clamp_lo,
                           float clamp_hi, uint64_t seed, uint64_t step0, ncahip_stream_t stream) {
-    const char* const who = "cond clip (bf16)";
-    // host-side checks: nothing is enqueued before all of them have passed
-    if (!pre || !goal) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
-    if (int rc = check_clip_emit_unit(states, images, img_fmt, B, C, H, W)) return rc;
-    if (F <= 0 || steps_per_frame <= 0 || step_n <= 0) return fail(NCAHIP_EINVAL, "%s: F, steps_per_frame and step_n must be positive", who);
-    const uint64_t calls = (uint64_t)F * (uint64_t)steps_per_frame;
-    if (calls > 0x7fffffffu || calls * (uint64_t)step_n > 0x7fffffffu) return fail(NCAHIP_EINVAL, "%s: F * steps_per_frame * step_n must stay below 2^31", who);
-    // the checks of ncahip_cond_grow_fwd_bf16, with its codes
-    if (int rc = check_cond(states, states + 1, pre, goal, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, goal_ch, alive_ch, kMaxCCondFwdBf16)) return rc;
-    if (int rc = check_bf16_shape(states, states, goal, H, W)) return rc;
-    const bool ubits = u_is_bits(u, seed);
-    if (int rc = check_bits(ubits, B, H, W, fire_rate, false)) return rc;
-    // W % 4 == 0: every state slot and every frame's goal is 8-byte aligned as slot 0 and goal[0] are
-    const size_t slot = (size_t)B * C * H * W, pslot = (size_t)B * H * W, gslot = (size_t)B * goal_ch * H * W;
-    const size_t ibytes = clip_img_bytes(img_fmt, B, 3, H, W);
-    const size_t sbytes = 4 * slot * sizeof(uint16_t), pbytes = 2 * pslot, gbytes = (size_t)F * gslot * sizeof(uint16_t), abytes = (size_t)calls * ibytes;
-    if (clip_overlap(states, sbytes, goal, gbytes) || clip_overlap(states, sbytes, images, abytes) || clip_overlap(states, sbytes, pre, pbytes) ||
-        clip_overlap(goal, gbytes, images, abytes) || clip_overlap(goal, gbytes, pre, pbytes) || clip_overlap(images, abytes, pre, pbytes))
-        return fail(NCAHIP_EINVAL, "%s: states, pre, goal and images must not overlap", who);
-    if (int rc = device_error_rc(who)) return rc;
-
-    int cur = 0;   // the slot that holds the state: 0 or 2
-    for (int n = 0; n < (int)calls; ++n) {
-        const int t0 = n * step_n;                                  // first step of this call within `u`
-        const int out = (step_n & 1) ? cur : cur ^ 2;
-        if (int rc = cond_grow_fwd_impl(true, states + (size_t)cur * slot, pre, 2, step_n, states + (size_t)out * slot, goal + (size_t)(n / steps_per_frame) * gslot,
-                                        goal_ch, u_at(u, ubits, t0, pslot), wp, w1, b1, w2, b2, w3, B, C, H, W, hidden, alive_ch, alive_thr, fire_rate,
-                                        clamp_lo, clamp_hi, seed, step0 + (uint64_t)t0, stream, (char*)images + (size_t)n * ibytes, img_fmt))
-            return rc;
-        cur = out;
-    }
-    if (cur != 0)   // the state returns in slot 0: the one copy of a call
-        return hip_result(hipMemcpyAsync(states, states + (size_t)cur * slot, slot * sizeof(uint16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream),
-                          "cond clip (bf16 state copy)");
-    return 0;
+    return cond_clip_impl(true, states, pre, goal, goal_ch, images, img_fmt, F, steps_per_frame, step_n, u, wp, w1, b1, w2, b2, w3, B, C, H, W, hidden,
+                          alive_ch, alive_thr, fire_rate, clamp_lo, clamp_hi, seed, step0, nullptr, 0, 0, stream);
 }
 
 // ---- decoder-sized uint8 frames: crop + Pillow-exact resize before the clip front ends (nca_resize.hip) ----------------------------

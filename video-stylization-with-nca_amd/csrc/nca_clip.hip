@@ -263,104 +263,57 @@ hipError_t nca_launch_clip_gray(const void* frames, bool u8, float wr, float wg,
     return hipGetLastError();
 }
 
-template <int CO>
-static void clip_launch_emit_u8(bool inj, dim3 grid, hipStream_t st, const float* x, unsigned char* o, float* xlast, const float* gray, int B, int C,
-                                size_t plane, int aligned) {
-    if (inj) hipLaunchKernelGGL((clip_emit_u8_kernel<CO, true>), grid, dim3(256), 0, st, x, o, xlast, gray, B, C, plane, aligned);
-    else hipLaunchKernelGGL((clip_emit_u8_kernel<CO, false>), grid, dim3(256), 0, st, x, o, xlast, gray, B, C, plane, aligned);
-}
+// the emit kernels of a float32 state: uint8, the DyNCA families' image, by [c_out - 1][inject]; planar by [NV12][inject][unit]
+static const decltype(&clip_emit_u8_kernel<1, false>) kClipEmitU8[4][2] = {
+    {clip_emit_u8_kernel<1, false>, clip_emit_u8_kernel<1, true>}, {clip_emit_u8_kernel<2, false>, clip_emit_u8_kernel<2, true>},
+    {clip_emit_u8_kernel<3, false>, clip_emit_u8_kernel<3, true>}, {clip_emit_u8_kernel<4, false>, clip_emit_u8_kernel<4, true>}};
+static const decltype(&clip_emit_yuv420_kernel<false, false, false>) kClipEmitYuv420[2][2][2] = {
+    {{clip_emit_yuv420_kernel<false, false, false>, clip_emit_yuv420_kernel<false, false, true>},
+     {clip_emit_yuv420_kernel<false, true, false>, clip_emit_yuv420_kernel<false, true, true>}},
+    {{clip_emit_yuv420_kernel<true, false, false>, clip_emit_yuv420_kernel<true, false, true>},
+     {clip_emit_yuv420_kernel<true, true, false>, clip_emit_yuv420_kernel<true, true, true>}}};
 
-hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const float* gray, int B, int C, int c_out, int H, int W, hipStream_t st) {
+// One image out of a state and, with gray, the inject of the same launch (nca_kernels.h).  A lane owns an element (float32 image, or no
+// image), four pixels (uint8; `aligned`: the image is 4-byte aligned) or a 2 x kYuvOutCols block (planar).
+hipError_t nca_launch_clip_emit(const NcaClipEmitArgs& a, hipStream_t st) {
+    const int B = a.B, C = a.C, H = a.H, W = a.W;
+    const bool inj = a.gray != nullptr, planar = a.img && a.out.planar();
+    if ((!a.img && !inj) || a.c_out < 1 || a.c_out > 4 || (inj && (a.unit || a.c_out > C - 1))) return hipErrorInvalidValue;
+    if ((a.unit || planar) && (C < 3 || a.c_out != 3)) return hipErrorInvalidValue;
+    if ((planar && ((H | W) & 1)) || (a.bf16 && !a.unit)) return hipErrorInvalidValue;
     const size_t plane = (size_t)H * W;
-    if (!img && !gray) return hipErrorInvalidValue;
-    if (gray && c_out > C - 1) return hipErrorInvalidValue;
-    float* const xlast = state + (size_t)(C - 1) * plane;
-    if (!img || !u8) {
-        const size_t n = (size_t)B * ((img ? c_out : 0) + (gray ? 1 : 0)) * plane;
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (!img) hipLaunchKernelGGL((clip_emit_f32_kernel<false, true>), grid, dim3(256), 0, st, state, (float*)nullptr, xlast, gray, B, C, c_out, plane);
-        else if (gray) hipLaunchKernelGGL((clip_emit_f32_kernel<true, true>), grid, dim3(256), 0, st, state, (float*)img, xlast, gray, B, C, c_out, plane);
-        else hipLaunchKernelGGL((clip_emit_f32_kernel<true, false>), grid, dim3(256), 0, st, state, (float*)img, xlast, gray, B, C, c_out, plane);
-        return hipGetLastError();
-    }
-    const size_t groups = ((size_t)B * plane + 3) / 4;
-    const dim3 grid((unsigned)((groups + 255) / 256));
-    const int aligned = ((uintptr_t)img & 3) == 0;
-    unsigned char* const o = (unsigned char*)img;
-    switch (c_out) {
-        case 1: clip_launch_emit_u8<1>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
-        case 2: clip_launch_emit_u8<2>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
-        case 3: clip_launch_emit_u8<3>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
-        case 4: clip_launch_emit_u8<4>(gray != nullptr, grid, st, state, o, xlast, gray, B, C, plane, aligned); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-// ConditionedNCA's image: clamp(state[:, :3], 0, 1) through the same two kernels (float32 NCHW, or uint8 NHWC with a lane owning four pixels);
-// XT = uint16_t: from a state stored as bf16
-template <typename XT>
-static hipError_t clip_launch_emit_unit(const XT* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
-    const size_t plane = (size_t)H * W;
-    if (!img || C < 3) return hipErrorInvalidValue;
-    if (!u8) {
-        const size_t n = (size_t)B * 3 * plane;
-        hipLaunchKernelGGL((clip_emit_f32_kernel<true, false, true, XT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state, (float*)img,
-                           (float*)nullptr, (const float*)nullptr, B, C, 3, plane);
-        return hipGetLastError();
-    }
-    const size_t groups = ((size_t)B * plane + 3) / 4;
-    hipLaunchKernelGGL((clip_emit_u8_kernel<3, false, true, XT>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, state, (unsigned char*)img,
-                       (float*)nullptr, (const float*)nullptr, B, C, plane, ((uintptr_t)img & 3) == 0 ? 1 : 0);
-    return hipGetLastError();
-}
-hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
-    return clip_launch_emit_unit(state, img, u8, B, C, H, W, st);
-}
-hipError_t nca_launch_clip_emit_unit_bf16(const uint16_t* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st) {
-    return clip_launch_emit_unit(state, img, u8, B, C, H, W, st);
-}
-
-// The planar image of state[:, :3] (unit: ConditionedNCA's clamp, else the DyNCA families') and, with gray, the inject of the same launch.
-// k: ncahip_rgb_yuv_coeffs' ten words in host memory.  H and W even (the caller checked).
-template <bool NV12, bool UNIT>
-static void clip_launch_emit_yuv420(bool inj, dim3 grid, hipStream_t st, const float* x, unsigned char* o, float* xlast, const float* gray, int C, int H,
-                                    int W, int bx, size_t lanes, const NcaRgbYuvK& k) {
-    if (inj) hipLaunchKernelGGL((clip_emit_yuv420_kernel<NV12, true, UNIT>), grid, dim3(kYuvOutThreads), 0, st, x, o, xlast, gray, C, H, W, bx, lanes, k);
-    else hipLaunchKernelGGL((clip_emit_yuv420_kernel<NV12, false, UNIT>), grid, dim3(kYuvOutThreads), 0, st, x, o, xlast, gray, C, H, W, bx, lanes, k);
-}
-
-hipError_t nca_launch_clip_emit_yuv420(float* state, unsigned char* img, bool unit, bool nv12, const int* k, const float* gray, int B, int C, int H, int W,
-                                       hipStream_t st) {
-    if (!img || C < 3 || ((H | W) & 1) || (gray && (unit || C < 4))) return hipErrorInvalidValue;
-    const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
-    const int bx = (W + kYuvOutCols - 1) / kYuvOutCols;
-    const size_t lanes = (size_t)B * (H / 2) * bx, blocks = (lanes + kYuvOutThreads - 1) / kYuvOutThreads;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
-    float* const xlast = state + (size_t)(C - 1) * H * W;
-    if (unit) {
-        if (nv12) clip_launch_emit_yuv420<true, true>(false, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
-        else clip_launch_emit_yuv420<false, true>(false, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+    float* const x = (float*)a.state;
+    const uint16_t* const xh = (const uint16_t*)a.state;   // a.bf16
+    float* const xlast = inj ? x + (size_t)(C - 1) * plane : nullptr;
+    if (planar) {
+        const int32_t* const k = a.out.k;
+        const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
+        const int bx = (W + kYuvOutCols - 1) / kYuvOutCols;
+        const size_t lanes = (size_t)B * (H / 2) * bx, blocks = (lanes + kYuvOutThreads - 1) / kYuvOutThreads;
+        if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+        const bool nv12 = a.out.kind == kImgNV12;
+        auto go = [&](auto kernel, auto* xs) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kYuvOutThreads), 0, st, xs, (unsigned char*)a.img, xlast, a.gray, C, H, W, bx, lanes, yk);
+        };
+        if (a.bf16) go(nv12 ? clip_emit_yuv420_kernel<true, false, true, uint16_t> : clip_emit_yuv420_kernel<false, false, true, uint16_t>, xh);
+        else go(kClipEmitYuv420[nv12][inj][a.unit], x);
+    } else if (!a.img || a.out.kind == kImgF32) {
+        const size_t n = (size_t)B * ((a.img ? a.c_out : 0) + (inj ? 1 : 0)) * plane;
+        auto go = [&](auto kernel, auto* xs) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xs, (float*)a.img, xlast, a.gray, B, C, a.c_out, plane);
+        };
+        if (a.bf16) go(clip_emit_f32_kernel<true, false, true, uint16_t>, xh);
+        else if (a.unit) go(clip_emit_f32_kernel<true, false, true, float>, x);
+        else go(!a.img ? clip_emit_f32_kernel<false, true> : inj ? clip_emit_f32_kernel<true, true> : clip_emit_f32_kernel<true, false>, x);
     } else {
-        if (nv12) clip_launch_emit_yuv420<true, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
-        else clip_launch_emit_yuv420<false, false>(gray != nullptr, grid, st, state, img, xlast, gray, C, H, W, bx, lanes, yk);
+        const size_t groups = ((size_t)B * plane + 3) / 4;
+        const int aligned = ((uintptr_t)a.img & 3) == 0;
+        auto go = [&](auto kernel, auto* xs) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, xs, (unsigned char*)a.img, xlast, a.gray, B, C, plane, aligned);
+        };
+        if (a.bf16) go(clip_emit_u8_kernel<3, false, true, uint16_t>, xh);
+        else if (a.unit) go(clip_emit_u8_kernel<3, false, true, float>, x);
+        else go(kClipEmitU8[a.c_out - 1][inj], x);
     }
-    return hipGetLastError();
-}
-
-// the planar unit image from a state stored as bf16: the same kernel reading bf16 (no inject: that is the DyNCA families')
-hipError_t nca_launch_clip_emit_unit_yuv420_bf16(const uint16_t* state, unsigned char* img, bool nv12, const int* k, int B, int C, int H, int W,
-                                                 hipStream_t st) {
-    if (!img || C < 3 || ((H | W) & 1)) return hipErrorInvalidValue;
-    const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
-    const int bx = (W + kYuvOutCols - 1) / kYuvOutCols;
-    const size_t lanes = (size_t)B * (H / 2) * bx, blocks = (lanes + kYuvOutThreads - 1) / kYuvOutThreads;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
-    if (nv12) hipLaunchKernelGGL((clip_emit_yuv420_kernel<true, false, true, uint16_t>), grid, dim3(kYuvOutThreads), 0, st, state, img, (float*)nullptr,
-                                 (const float*)nullptr, C, H, W, bx, lanes, yk);
-    else hipLaunchKernelGGL((clip_emit_yuv420_kernel<false, false, true, uint16_t>), grid, dim3(kYuvOutThreads), 0, st, state, img, (float*)nullptr,
-                            (const float*)nullptr, C, H, W, bx, lanes, yk);
     return hipGetLastError();
 }

@@ -54,7 +54,6 @@ __global__ __launch_bounds__(256) void cond_finalize_bf16_kernel(const uint16_t*
 // launch that is all latency -- with one lane walking all C channels of its cells, 1 x 20 x 256^2 took 8.4 us against the 6.5 us of
 // the two launches.  VEC (wave-uniform): W % 4 == 0 and 8-byte aligned state tensors -- a row's four cells travel as one 8-byte word;
 // otherwise cell by cell, columns past the row's end skipped.
-enum { kImgF32 = 0, kImgU8 = 1, kImgI420 = 2, kImgNV12 = 3 };
 constexpr int kFinEmitThreads = 64;   // one wave per workgroup: small grids still reach every CU
 constexpr int kFinEmitCh = 4;         // channels per lane (>= 3: the image's channels sit in one group)
 
@@ -187,17 +186,17 @@ __global__ __launch_bounds__(kFinEmitThreads) void cond_finalize_emit_bf16_kerne
 
 }  // namespace
 
-// fmt: 0 = float32 [B,3,H,W], 1 = uint8 [B,H,W,3], 2 = I420, 3 = NV12 ([B,3H/2,W]; H and W even; k: nca_rgb_yuv_build_coeffs' ten words, host)
-hipError_t nca_launch_cond_finalize_emit_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, void* img, int fmt, const int* k, int B, int C, int H,
+hipError_t nca_launch_cond_finalize_emit_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, void* img, const NcaImgOut& io, int B, int C, int H,
                                               int W, int alive_ch, float thr, float lo, float hi, hipStream_t st) {
-    if (!img || C < 3 || fmt < kImgF32 || fmt > kImgNV12 || (fmt >= kImgI420 && (!k || ((H | W) & 1)))) return hipErrorInvalidValue;
-    const int rows = fmt >= kImgI420 ? 2 : 1;
+    const int fmt = io.kind;
+    if (!img || C < 3 || fmt < kImgF32 || fmt > kImgNV12 || (io.planar() && ((H | W) & 1))) return hipErrorInvalidValue;
+    const int rows = io.planar() ? 2 : 1;
     const size_t lanes = (size_t)B * (H / rows) * ((W + 3) / 4), blocks = (lanes + kFinEmitThreads - 1) / kFinEmitThreads;
     if (blocks == 0 || blocks > 0x7fffffffu || C > 65535 * kFinEmitCh) return hipErrorInvalidValue;
     const int vec = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 7) == 0;
     const int img_vec = W % 4 == 0 && ((uintptr_t)img & (fmt == kImgF32 ? 15 : 3)) == 0;
-    NcaRgbYuvK yk{};
-    if (fmt >= kImgI420) yk = NcaRgbYuvK{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
+    const int32_t* const k = io.k;   // zero unless planar
+    const NcaRgbYuvK yk{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
     const dim3 grid((unsigned)blocks, (unsigned)((C + kFinEmitCh - 1) / kFinEmitCh)), blk(kFinEmitThreads);
     switch (fmt) {
         case kImgF32: hipLaunchKernelGGL(cond_finalize_emit_bf16_kernel<kImgF32>, grid, blk, 0, st, x, pre, out, img, B, C, H, W, alive_ch, thr, lo, hi, vec, img_vec, yk); break;

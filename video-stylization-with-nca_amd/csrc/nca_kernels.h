@@ -270,11 +270,31 @@ hipError_t nca_launch_slw_bwd(const float* s, const float* t, const int* jmap, c
 hipError_t nca_launch_clip_cond(const void* frames, bool u8, const float* k3, float wr, float wg, float wb, int do_tanh, float* cond, int N, int H,
                                 int W, hipStream_t st);
 hipError_t nca_launch_clip_gray(const void* frames, bool u8, float wr, float wg, float wb, float* gray, int N, int H, int W, hipStream_t st);
-// one launch: the image of state[:, :c_out] (img != nullptr) and the plane gray [B,H,W] over state[:, C-1] (gray != nullptr, c_out <= C-1);
-// the state is only read without a grey plane
-hipError_t nca_launch_clip_emit_inject(float* state, void* img, bool u8, const float* gray, int B, int C, int c_out, int H, int W, hipStream_t st);
-// ConditionedNCA's image clamp(state[:, :3], 0, 1): float32 [B,3,H,W] or (u8) uint8 [B,H,W,3]; C >= 3
-hipError_t nca_launch_clip_emit_unit(const float* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st);
+// The image a clip call writes: float32 [B,c,H,W], uint8 [B,H,W,c], or planar YUV 4:2:0 uint8 [B,3H/2,W] (H and W even) with the ten
+// words of nca_rgb_yuv_build_coeffs (zero for the other kinds).  nca_img_out (nca_yuv_out.hip, host) builds it from an img_fmt of
+// include/ncahip.h -- NCAHIP_CLIP_F32_NCHW, NCAHIP_CLIP_U8_NHWC, NCAHIP_CLIP_YUV420(layout, matrix, range) -- and is the one place that
+// knows that word's layout; false: no such format
+enum NcaImgKind { kImgF32 = 0, kImgU8 = 1, kImgI420 = 2, kImgNV12 = 3 };
+struct NcaImgOut {
+    NcaImgKind kind;
+    int32_t k[10];
+    bool planar() const { return kind >= kImgI420; }
+};
+bool nca_img_out(int img_fmt, NcaImgOut* out);
+// One launch: the image of state[:, :c_out] (img != nullptr) and the plane gray [B,H,W] over state[:, C-1] (gray != nullptr, c_out <=
+// C-1); the state is only read without a grey plane.  unit: ConditionedNCA's image clamp(state[:, :3], 0, 1) (C >= 3, c_out == 3, no
+// grey), also from a state stored as bf16 (bf16: unit only) -- bit for bit the image of the widened state.  A planar image has c_out ==
+// 3 and is bit for bit the uint8 image followed by nca_launch_clip_rgb_to_yuv420.  hipErrorInvalidValue outside that.
+struct NcaClipEmitArgs {
+    void* state;        // [B,C,H,W] float32, or bf16
+    bool bf16;
+    void* img;          // nullptr: the grey plane only
+    NcaImgOut out;
+    bool unit;
+    const float* gray;
+    int B, C, c_out, H, W;
+};
+hipError_t nca_launch_clip_emit(const NcaClipEmitArgs& a, hipStream_t st);
 // nca_encoder.hip: ImageEncoder.forward of N = F*B frames in one launch: float32 [N,ch,H,W] (ch <= 4) or (u8) uint8 [N,H,W,3] -> goal [N,E,H,W],
 // E <= 32; w1 [E,3+ch,3,3], b1 [E], w2 [E,E,3,3]; hipErrorInvalidValue outside that range
 hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
@@ -282,11 +302,6 @@ hipError_t nca_launch_clip_encode(const void* frames, bool u8, const float* k3, 
 // the same kernel and arithmetic with the goal rounded to bf16 (RNE) on the final store: nca_launch_clip_encode, then a cast
 hipError_t nca_launch_clip_encode_bf16(const void* frames, bool u8, const float* k3, const float* k5, const float* w1, const float* b1, const float* w2,
                                        uint16_t* goal, int N, int ch, int E, int H, int W, hipStream_t st);
-// ConditionedNCA's image from a state stored as bf16: the emit kernels of nca_launch_clip_emit_unit / nca_launch_clip_emit_yuv420 (unit)
-// reading bf16 -- bit for bit their image of the widened state
-hipError_t nca_launch_clip_emit_unit_bf16(const uint16_t* state, void* img, bool u8, int B, int C, int H, int W, hipStream_t st);
-hipError_t nca_launch_clip_emit_unit_yuv420_bf16(const uint16_t* state, unsigned char* img, bool nv12, const int* k, int B, int C, int H, int W,
-                                                 hipStream_t st);
 
 // nca_resize.hip: crop + Pillow-exact 8-bit resize of N uint8 frames [N,H,W,3] -> [N,out_h,out_w,3]: horizontal pass into tmp
 // [N,ch,out_w,3], vertical pass into dst.  kx [out_w,ksize_x] / bx [out_w,2] and ky [out_h,ksize_y] / by [out_h,2]: device tables as
@@ -308,10 +323,6 @@ void nca_yuv_build_coeffs(int matrix, int range, int32_t k[6]);
 // nca_rgb_yuv_build_coeffs in HOST memory
 hipError_t nca_launch_clip_rgb_to_yuv420(const unsigned char* src, bool nv12, int N, int H, int W, const int* k, unsigned char* dst, hipStream_t st);
 void nca_rgb_yuv_build_coeffs(int matrix, int range, int32_t k[10]);
-// nca_clip.hip: the planar image [B,3H/2,W] of state[:, :3] straight from the fp32 state -- bit for bit the uint8 emit (unit: nca_launch_clip_emit_unit,
-// else nca_launch_clip_emit_inject with c_out = 3) followed by nca_launch_clip_rgb_to_yuv420; gray != NULL (not with unit): the inject of the same launch
-hipError_t nca_launch_clip_emit_yuv420(float* state, unsigned char* img, bool unit, bool nv12, const int* k, const float* gray, int B, int C, int H, int W,
-                                       hipStream_t st);
 // host only (no GPU call): table row width (-1: does not fit an int), and the tables of one axis; filter 0 = bicubic, 1 = Lanczos.  The
 // builder returns 0, or the 1-based row that breaks an integer bound of the passes
 int nca_resize_ksize(int in, int out, int filter);
@@ -342,9 +353,8 @@ hipError_t nca_launch_cond_step_fwd_pc(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_step_fwd_bf16(const NcaCondArgs& a, hipStream_t st);
 hipError_t nca_launch_cond_finalize_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, int B, int C, int H, int W,
                                          int alive_ch, float thr, float lo, float hi, hipStream_t st);
-// the finalize above and the unit image of its result in ONE launch (C >= 3).  fmt: 0 = float32 [B,3,H,W], 1 = uint8 [B,H,W,3], 2 = I420,
-// 3 = NV12 ([B,3H/2,W]: H and W even, k = nca_rgb_yuv_build_coeffs' ten words in HOST memory; k is not read for fmt 0 and 1)
-hipError_t nca_launch_cond_finalize_emit_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, void* img, int fmt, const int* k, int B, int C, int H,
+// the finalize above and the unit image of its result in ONE launch (C >= 3; a planar image: H and W even)
+hipError_t nca_launch_cond_finalize_emit_bf16(const uint16_t* x, const uint8_t* pre, uint16_t* out, void* img, const NcaImgOut& io, int B, int C, int H,
                                               int W, int alive_ch, float thr, float lo, float hi, hipStream_t st);
 
 // diagnostic build hook (-DNCA_STAMPS): buffer that receives s_memtime stamps, [wave][tile][8]

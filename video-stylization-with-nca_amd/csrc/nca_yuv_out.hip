@@ -9,6 +9,7 @@
 //
 // rgb_to_yuv420_kernel: a lane owns 2 rows x 4 columns of one image.  Its 12 source bytes per row come in as the (at most 4)
 // memory-aligned dwords that hold them -- inside the tensor only, at any alignment of src -- and are shifted into place in registers.
+#include "../../include/ncahip.h"
 #include "nca_common.h"
 #include "nca_kernels.h"
 #include "nca_yuv.h"
@@ -95,4 +96,15 @@ void nca_rgb_yuv_build_coeffs(int matrix, int range, int32_t k[10]) {
     k[8] = rgb_yuv_quantise(-(cv * kb));
     k[7] = -k[6] - k[8];
     k[9] = range == 0 ? 16 : 0;
+}
+
+// The image record of an img_fmt of the clip entry points (nca_kernels.h).  NCAHIP_CLIP_YUV420(layout, matrix, range) is 0x100 | layout |
+// matrix << 1 | range << 2 with one bit each: nothing else takes that word apart.
+bool nca_img_out(int img_fmt, NcaImgOut* out) {
+    *out = NcaImgOut{img_fmt == NCAHIP_CLIP_U8_NHWC ? kImgU8 : kImgF32, {0}};
+    if (img_fmt == NCAHIP_CLIP_F32_NCHW || img_fmt == NCAHIP_CLIP_U8_NHWC) return true;
+    if (img_fmt < NCAHIP_CLIP_YUV420(0, 0, 0) || img_fmt > NCAHIP_CLIP_YUV420(1, 1, 1)) return false;
+    out->kind = (img_fmt & 1) == NCAHIP_YUV_NV12 ? kImgNV12 : kImgI420;
+    nca_rgb_yuv_build_coeffs((img_fmt >> 1) & 1, (img_fmt >> 2) & 1, out->k);
+    return true;
 }
