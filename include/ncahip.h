@@ -958,6 +958,31 @@ int ncahip_rgb_yuv_coeffs(int matrix, int range, int32_t k[10]);
 int ncahip_clip_rgb_to_yuv420_u8(const uint8_t *src, int layout, int N, int H, int W, const int32_t *k, uint8_t *dst,
                                  ncahip_stream_t stream);
 
+/* ---- images at delivery size: the 8-bit resize with planar YUV 4:2:0 out --------------------------------------------------------------
+ * The clip entry points emit images at the model grid (256^2); an encoder takes them at the size they are delivered in (1080p), as planar
+ * YUV.  Enlarging an RGB24 image is ncahip_clip_resize_u8 (Pillow's 8-bit resize enlarges as it shrinks: fs = 1, ksize = 2 s + 1).
+ * ncahip_clip_resize_u8_yuv420: src [N,H,W,3] uint8 and the crop, the tables kx / bx / ky / by with their row widths and the workspace
+ *   (ncahip_clip_resize_workspace(N, crop_h, out_w)) exactly as ncahip_clip_resize_u8 takes them; layout NCAHIP_YUV_I420 / NCAHIP_YUV_NV12;
+ *   k: ncahip_rgb_yuv_coeffs' ten words in HOST memory (they travel as kernel arguments); dst [N, 3 out_h / 2, out_w] uint8.
+ *   The result is, bit for bit, ncahip_clip_resize_u8 into an RGB24 image followed by ncahip_clip_rgb_to_yuv420_u8 of that image: the RGB
+ *   bytes are clamped after the vertical pass's >> 22, before any YUV arithmetic; luma per pixel; chroma from the 2 x 2 block's channel
+ *   sums with one rounding.  No full-size RGB image exists: 1.5 bytes are written per delivered pixel instead of 3 written, 3 read and 1.5
+ *   written.  Two launches for all N images: the horizontal pass of ncahip_clip_resize_u8, unchanged, and a vertical pass in which a lane
+ *   owns 2 output rows x 4 columns -- it walks the union of the two rows' tap ranges over the intermediate image once (each row's
+ *   (ymin, n) cut to the crop; a row's coefficient is 0 outside its own range), keeps 24 accumulators, forms the bytes in registers and
+ *   stores as the planar emit does: one dword of Y per row and the chroma under it, whole dwords, 16-bit halves or single bytes by the
+ *   segment's alignment in memory, half as much for the last lane of a row with out_w % 4 == 2.  Intermediate rows are 3 out_w bytes, a
+ *   multiple of 4 only when out_w % 4 == 0: a lane's 12 bytes are read as the memory-aligned dwords that hold them, inside the workspace
+ *   only.  Any alignment of src and dst.  Nothing synchronises.
+ *   NCAHIP_EINVAL: null src / dst / k, an unknown layout, a non-positive size, a short workspace, overlapping src / dst / workspace.
+ *   NCAHIP_ERANGE: odd out_h or out_w, H, W, out_h or out_w above 16384, ksize_x or ksize_y above 2048, a crop outside the frame, a null
+ *   or not 4-byte aligned table or workspace.  All checked before the first launch.  Same size and no crop: the tables are the identity
+ *   and dst = ncahip_clip_rgb_to_yuv420_u8(src). */
+int ncahip_clip_resize_u8_yuv420(const uint8_t *src, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t *kx,
+                                 const int32_t *bx, int ksize_x, const int32_t *ky, const int32_t *by, int ksize_y, int layout,
+                                 const int32_t *k, uint8_t *dst, int out_h, int out_w, void *workspace, size_t workspace_bytes,
+                                 ncahip_stream_t stream);
+
 /* ---- fire masks as bits --------------------------------------------------------------------------------------------
  * Every entry point above that takes `u` (the per-step uniform draws of nca.py:172 / dynca.py:131) also accepts the fire
  * masks ALREADY EVALUATED and bit-packed: pass a non-NULL `u` that points at uint32_t words together with

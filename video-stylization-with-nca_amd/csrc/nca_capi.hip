@@ -1171,10 +1171,11 @@ size_t ncahip_clip_resize_workspace(int N, int crop_h, int out_w) {
     return (size_t)N * crop_h * out_w * 3;
 }
 
-// the checks of the two resize entry points; frame_bytes: H * W * 3 (RGB24) or H * W * 3 / 2 (planar 4:2:0)
+// the checks of the resize entry points; frame_bytes: H * W * 3 (RGB24) or H * W * 3 / 2 (planar 4:2:0); planar_dst: dst is
+// [N, 3 out_h / 2, out_w], half the bytes
 static int clip_resize_check(const char* who, const uint8_t* src, size_t frame_bytes, int N, int H, int W, int x0, int y0, int crop_w, int crop_h,
                              const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst,
-                             int out_h, int out_w, void* workspace, size_t workspace_bytes) {
+                             int out_h, int out_w, void* workspace, size_t workspace_bytes, bool planar_dst = false) {
     if (!src || !dst) return fail(NCAHIP_EINVAL, "%s: null pointer", who);
     if (N <= 0 || H <= 0 || W <= 0 || crop_w <= 0 || crop_h <= 0 || out_h <= 0 || out_w <= 0 || ksize_x <= 0 || ksize_y <= 0)
         return fail(NCAHIP_EINVAL, "%s: bad size", who);
@@ -1189,7 +1190,7 @@ static int clip_resize_check(const char* who, const uint8_t* src, size_t frame_b
     if (!workspace || ((uintptr_t)workspace & 3) != 0) return fail(NCAHIP_ERANGE, "%s: null or misaligned workspace (4-byte aligned)", who);
     const size_t need = ncahip_clip_resize_workspace(N, crop_h, out_w);
     if (workspace_bytes < need) return fail(NCAHIP_EINVAL, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-    const size_t sbytes = (size_t)N * frame_bytes, dbytes = (size_t)N * out_h * out_w * 3;
+    const size_t sbytes = (size_t)N * frame_bytes, dbytes = (size_t)N * out_h * out_w * 3 / (planar_dst ? 2 : 1);
     if (clip_overlap(src, sbytes, dst, dbytes) || clip_overlap(src, sbytes, workspace, need) || clip_overlap(dst, dbytes, workspace, need))
         return fail(NCAHIP_EINVAL, "%s: frames, output and workspace must not overlap", who);
     return 0;
@@ -1261,6 +1262,19 @@ int ncahip_clip_resize_yuv420_u8(const uint8_t* src, int layout, const int32_t* 
     if ((H | W) & 1) return fail(NCAHIP_ERANGE, "clip_resize_yuv420: 4:2:0 frames have even sides, got %d x %d", H, W);
     return hip_result(nca_launch_clip_resize_yuv420(src, layout == NCAHIP_YUV_NV12, k, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y,
                                                     dst, out_h, out_w, (unsigned char*)workspace, (hipStream_t)stream), "clip_resize_yuv420");
+}
+
+int ncahip_clip_resize_u8_yuv420(const uint8_t* src, int N, int H, int W, int x0, int y0, int crop_w, int crop_h, const int32_t* kx, const int32_t* bx,
+                                 int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, int layout, const int32_t* k, uint8_t* dst, int out_h,
+                                 int out_w, void* workspace, size_t workspace_bytes, ncahip_stream_t stream) {
+    if (!k) return fail(NCAHIP_EINVAL, "clip_resize_u8_yuv420: null pointer");
+    if (!yuv_layout_ok(layout)) return fail(NCAHIP_EINVAL, "clip_resize_u8_yuv420: unknown layout %d", layout);
+    if (int rc = clip_resize_check("clip_resize_u8_yuv420", src, (size_t)H * W * 3, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y,
+                                   dst, out_h, out_w, workspace, workspace_bytes, true))
+        return rc;
+    if ((out_h | out_w) & 1) return fail(NCAHIP_ERANGE, "clip_resize_u8_yuv420: 4:2:0 images have even sides, got %d x %d", out_h, out_w);
+    return hip_result(nca_launch_clip_resize_u8_yuv420(src, N, H, W, x0, y0, crop_w, crop_h, kx, bx, ksize_x, ky, by, ksize_y, layout == NCAHIP_YUV_NV12,
+                                                       k, dst, out_h, out_w, (unsigned char*)workspace, (hipStream_t)stream), "clip_resize_u8_yuv420");
 }
 
 // ---- the DyNCA backward: an entry point names its variant with a constant record and makes one forwarding call; every check is

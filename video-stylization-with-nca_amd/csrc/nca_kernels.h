@@ -314,6 +314,12 @@ hipError_t nca_launch_clip_resize(const unsigned char* src, int N, int H, int W,
 hipError_t nca_launch_clip_resize_yuv420(const unsigned char* src, bool nv12, const int* k, int N, int H, int W, int x0, int y0, int cw, int ch,
                                          const int* kx, const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst,
                                          int out_h, int out_w, unsigned char* tmp, hipStream_t st);
+// nca_launch_clip_resize with planar YUV 4:2:0 IMAGES: dst [N,3 out_h/2,out_w] (I420, or NV12), out_h and out_w even.  The same
+// horizontal pass, then a vertical pass that writes the planes with the ten coefficient words k (HOST memory, nca_rgb_yuv_build_coeffs);
+// the result is nca_launch_clip_resize, then nca_launch_clip_rgb_to_yuv420
+hipError_t nca_launch_clip_resize_u8_yuv420(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx,
+                                            const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, bool nv12, const int* k,
+                                            unsigned char* dst, int out_h, int out_w, unsigned char* tmp, hipStream_t st);
 // nca_yuv.hip: the crop (x0, y0, cw, ch) of N planar YUV 4:2:0 frames [N,3H/2,W] -> RGB [N,ch,cw,3] uint8, one launch; any alignment
 hipError_t nca_launch_clip_yuv420_to_rgb(const unsigned char* src, bool nv12, int N, int H, int W, int x0, int y0, int cw, int ch, const int* k,
                                          unsigned char* dst, hipStream_t st);

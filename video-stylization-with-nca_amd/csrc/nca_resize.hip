@@ -20,6 +20,9 @@
 // instantiations stage the luma segment and the chroma samples under it the same way, behind the rows, and one lane per staged pixel
 // writes the converted RGB bytes (nca_yuv.h: include/ncahip.h's integer arithmetic, nearest chroma) into the rows the tap loop reads;
 // everything after that, the vertical pass included, is the RGB24 code, and no full-size RGB image exists.
+// Planar YUV 4:2:0 images (ncahip_clip_resize_u8_yuv420): the horizontal pass is the RGB24 one, and resize_v_yuv420_kernel takes the
+// vertical pass's place: a lane forms 2 rows x 4 columns of RGB bytes in registers and stores the planes with the planar emit's block
+// writer (nca_yuv.h), so no full-size RGB image exists on the way out either.
 // |k| < 2^23 and pixels < 2^8: the multiply-adds are 24-bit (v_mad_i32_i24).  The tables come from device memory and are not trusted with
 // addresses: every row's (first tap, count) is cut to the staged segment / the crop before the tap loop, so a bad table gives wrong
 // pixels, never a read outside the frame.  Offsets per image are 64-bit.
@@ -192,14 +195,93 @@ __global__ __launch_bounds__(kRszThreads) void resize_v_kernel(const unsigned ch
     }
 }
 
+// The vertical pass that writes planar YUV 4:2:0 (ncahip_clip_resize_u8_yuv420): grid (ceil(ceil(out_w / 4) / 64), out_h / 2, frames),
+// block 64.  tmp [N, ch, out_w, 3] (`total` bytes) -> dst [N, 3 out_h / 2, out_w]; out_h and out_w even.  A lane owns 2 output rows x 4
+// columns, the planar emit's block: 12 bytes of an intermediate row serve both rows, so the lane walks the union of the two rows' tap
+// ranges once and gives each row its own coefficient -- 0 outside that row's (ymin, n), which adds nothing; both are cut to the crop as
+// resize_v_kernel cuts them and are wave-uniform.  24 accumulators -> the clamped RGB bytes in registers -> nca_yuv420_store_block.
+// Intermediate rows are out_w * 3 bytes: a multiple of 4 only when out_w % 4 == 0.  A lane's 12 bytes are three aligned dwords when they
+// start on one; otherwise (and for the 6 bytes of a row's last lane when out_w % 4 == 2) they come in as the memory-aligned dwords that
+// hold them, inside the workspace only, and are shifted into place.
+template <bool NV12>
+__global__ __launch_bounds__(kYuvOutThreads) void resize_v_yuv420_kernel(const unsigned char* __restrict__ tmp, size_t total, int ch,
+                                                                         const int* __restrict__ ky, const int* __restrict__ by, int ksize,
+                                                                         unsigned char* __restrict__ dst, int out_h, int out_w, NcaRgbYuvK k) {
+    constexpr int kBytes = kYuvOutCols * 3, kDw = kBytes / 4;
+    const int x0 = (int)(blockIdx.x * kYuvOutThreads + threadIdx.x) * kYuvOutCols;
+    if (x0 >= out_w) return;
+    const int y = (int)blockIdx.y * 2;
+    const size_t n = blockIdx.z;
+    const int nv = min(kYuvOutCols, out_w - x0);
+    int ymin[2], taps[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {                                          // wave-uniform, cut to the crop
+        ymin[j] = min(max(by[2 * (y + j)], 0), ch - 1);
+        taps[j] = min(max(by[2 * (y + j) + 1], 0), min(ksize, ch - ymin[j]));
+    }
+    const int* const kr0 = ky + (size_t)y * ksize;
+    const int* const kr1 = kr0 + ksize;
+    const int r0 = min(ymin[0], ymin[1]), r1 = max(ymin[0] + taps[0], ymin[1] + taps[1]);      // 0 <= r0, r1 <= ch
+    const uintptr_t mis = (uintptr_t)tmp & 3;
+    const size_t rowlen = (size_t)out_w * 3;
+    size_t first = (n * ch + (size_t)r0) * rowlen + (size_t)x0 * 3;        // first byte of the lane's segment in row r0
+    int acc[2][kBytes];
+#pragma unroll
+    for (int i = 0; i < kBytes; ++i) acc[0][i] = acc[1][i] = 1 << 21;
+    for (int r = r0; r < r1; ++r, first += rowlen) {
+        const int j0 = r - ymin[0], j1 = r - ymin[1];
+        const int k0 = j0 >= 0 && j0 < taps[0] ? kr0[j0] : 0;
+        const int k1 = j1 >= 0 && j1 < taps[1] ? kr1[j1] : 0;
+        const unsigned ph = 8u * (unsigned)((first + mis) & 3);            // the segment's first byte within its aligned dword
+        unsigned a[kDw];
+        if (ph == 0u && nv == kYuvOutCols) {
+            const unsigned* const p = reinterpret_cast<const unsigned*>(tmp + first);
+#pragma unroll
+            for (int d = 0; d < kDw; ++d) a[d] = p[d];
+        } else {
+            unsigned dw[kDw + 1];
+#pragma unroll
+            for (int d = 0; d <= kDw; ++d) {
+                dw[d] = 0u;
+                nca_stage_dword(tmp, total, mis, first, (size_t)nv * 3, d, dw[d]);
+            }
+#pragma unroll
+            for (int d = 0; d < kDw; ++d) a[d] = ph ? (dw[d] >> ph) | (dw[d + 1] << (32u - ph)) : dw[d];
+        }
+#pragma unroll
+        for (int i = 0; i < kBytes; ++i) {
+            const int v = (int)((a[i >> 2] >> (8 * (i & 3))) & 255u);
+            acc[0][i] = __mul24(v, k0) + acc[0][i];
+            acc[1][i] = __mul24(v, k1) + acc[1][i];
+        }
+    }
+    int r[2][kYuvOutCols], g[2][kYuvOutCols], b[2][kYuvOutCols];          // clamped after the >> 22, before any YUV arithmetic
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < kYuvOutCols; ++i) {
+            r[j][i] = rsz_clamp_u8(acc[j][3 * i]);
+            g[j][i] = rsz_clamp_u8(acc[j][3 * i + 1]);
+            b[j][i] = rsz_clamp_u8(acc[j][3 * i + 2]);
+        }
+    nca_yuv420_store_block<NV12>(dst, k, n, out_h, out_w, y, x0, nv, r, g, b);
+}
+
 }  // namespace
 
 namespace {
 
+// What the vertical pass writes: RGB24 [N,out_h,out_w,3] (resize_v_kernel), or planar YUV 4:2:0 [N,3 out_h/2,out_w] with the ten
+// coefficient words k (resize_v_yuv420_kernel; out_h and out_w even)
+struct RszPlanar {
+    bool on, nv12;
+    NcaRgbYuvK k;
+};
+
 // src_fmt: kSrcRgb24 (src [N,H,W,3]) or kSrcI420 / kSrcNv12 (src [N,3H/2,W], converted by the horizontal pass's loader with yk)
 hipError_t rsz_launch(int src_fmt, const NcaYuvK& yk, const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx,
                       const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, unsigned char* dst, int out_h, int out_w,
-                      unsigned char* tmp, hipStream_t st) {
+                      unsigned char* tmp, hipStream_t st, const RszPlanar& planar = RszPlanar{}) {
     const bool yuv = src_fmt != kSrcRgb24;
     // horizontal pass: the widest block of columns whose coefficient rows and one staged source row fit the LDS budget, then as many rows
     int cols = out_w < kRszMaxCols ? out_w : kRszMaxCols, fp = 0, row_dw = 0, ydw = 0, cdw = 0;
@@ -231,10 +313,23 @@ hipError_t rsz_launch(int src_fmt, const NcaYuvK& yk, const unsigned char* src, 
         // own base and the bytes from there to the tensor's end
         const unsigned char* s = src + (size_t)n0 * frame;
         unsigned char* t = tmp + (size_t)n0 * ch * rowlen;
-        unsigned char* d = dst + (size_t)n0 * out_h * rowlen;
+        unsigned char* d = dst + (size_t)n0 * out_h * (planar.on ? (size_t)out_w / 2 * 3 : (size_t)rowlen);
         hipLaunchKernelGGL(hk, dim3((unsigned)(col_blocks * bands), (unsigned)nn), dim3(kRszThreads), lds, st, s, total - (size_t)n0 * frame, H, W, x0,
                            y0, cw, ch, kx, bx, ksize_x, t, out_w, cols, rows, fp, row_dw, col_blocks, yk, ydw, cdw);
         if (hipError_t e = hipGetLastError()) return e;
+        if (planar.on) {
+            const int lanes = (out_w + kYuvOutCols - 1) / kYuvOutCols;
+            const dim3 pgrid((unsigned)((lanes + kYuvOutThreads - 1) / kYuvOutThreads), (unsigned)(out_h / 2), (unsigned)nn);
+            const size_t tbytes = (size_t)nn * ch * rowlen;
+            if (planar.nv12)
+                hipLaunchKernelGGL(resize_v_yuv420_kernel<true>, pgrid, dim3(kYuvOutThreads), 0, st, t, tbytes, ch, ky, by, ksize_y, d, out_h, out_w,
+                                   planar.k);
+            else
+                hipLaunchKernelGGL(resize_v_yuv420_kernel<false>, pgrid, dim3(kYuvOutThreads), 0, st, t, tbytes, ch, ky, by, ksize_y, d, out_h, out_w,
+                                   planar.k);
+            if (hipError_t e = hipGetLastError()) return e;
+            continue;
+        }
         const dim3 grid((unsigned)((rowlen + per_block - 1) / per_block), (unsigned)out_h, (unsigned)nn);
         if (vec)
             hipLaunchKernelGGL(resize_v_kernel<4>, grid, dim3(kRszThreads), 0, st, t, ch, ky, by, ksize_y, d, out_h, rowlen);
@@ -258,6 +353,13 @@ hipError_t nca_launch_clip_resize_yuv420(const unsigned char* src, bool nv12, co
                                          int out_h, int out_w, unsigned char* tmp, hipStream_t st) {
     return rsz_launch(nv12 ? kSrcNv12 : kSrcI420, NcaYuvK{k[0], k[1], k[2], k[3], k[4], k[5]}, src, N, H, W, x0, y0, cw, ch, kx, bx, ksize_x, ky, by,
                       ksize_y, dst, out_h, out_w, tmp, st);
+}
+
+hipError_t nca_launch_clip_resize_u8_yuv420(const unsigned char* src, int N, int H, int W, int x0, int y0, int cw, int ch, const int* kx,
+                                            const int* bx, int ksize_x, const int* ky, const int* by, int ksize_y, bool nv12, const int* k,
+                                            unsigned char* dst, int out_h, int out_w, unsigned char* tmp, hipStream_t st) {
+    const RszPlanar planar{true, nv12, NcaRgbYuvK{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]}};
+    return rsz_launch(kSrcRgb24, NcaYuvK{}, src, N, H, W, x0, y0, cw, ch, kx, bx, ksize_x, ky, by, ksize_y, dst, out_h, out_w, tmp, st, planar);
 }
 
 // ---- the table builder: plain host C++, no GPU call.  ImagingResample's precompute_coeffs + normalize_coeffs_8bpc in C double, with

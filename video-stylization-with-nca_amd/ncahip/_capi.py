@@ -144,6 +144,7 @@ SIGNATURES = {
     "ncahip_clip_resize_yuv420_u8": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, ctypes.c_size_t, _P],
     "ncahip_rgb_yuv_coeffs": [_I, _I, _P],
     "ncahip_clip_rgb_to_yuv420_u8": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "ncahip_clip_resize_u8_yuv420": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_size_t, _P],
 }
 _RESTYPES = {"ncahip_last_error": c_char_p, "ncahip_cond_grow_bwd_workspace": ctypes.c_size_t,
              "ncahip_gram_rows_workspace": ctypes.c_size_t, "ncahip_dynca_step_bwd_w2_workspace": ctypes.c_size_t,

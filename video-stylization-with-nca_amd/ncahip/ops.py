@@ -1170,17 +1170,27 @@ def _clip_resize_launch(frames: torch.Tensor, box, tx, ty, out: torch.Tensor, ws
                                       ty[0].shape[1], _p(out), out_h, out_w, _p(ws), ws.numel() * ws.element_size(), _stream()), "clip_resize")
 
 
-def clip_resize(frames: torch.Tensor, size, crop=None, resample: str = "bicubic") -> torch.Tensor:
+def _resize_out(out: Optional[torch.Tensor], want: tuple, device) -> torch.Tensor:
+    """The result tensor of a resize wrapper: a new one, or the caller's `out` after checking that it is what a new one would be."""
+    if out is None:
+        return torch.empty(want, device=device, dtype=torch.uint8)
+    if out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == want and out.is_contiguous():
+        return out
+    raise ValueError(f"out must be a contiguous uint8 device tensor {want}, got {tuple(out.shape)} {out.dtype}")
+
+
+def clip_resize(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames [N,H,W,3] uint8 on the device -> [N,out_h,out_w,3] uint8: crop = None or a box (x0, y0, w, h) in pixels, then Pillow's
     8-bit Image.resize to size = (out_h, out_w) with resample 'bicubic' or 'lanczos', bit for bit (ncahip_clip_resize_u8: two launches
-    for all N frames).  The tables come from resize_tables; their device copies are cached per (in, out, resample, device)."""
+    for all N frames).  The tables come from resize_tables; their device copies are cached per (in, out, resample, device).  out: a
+    device tensor of the result's shape to write into."""
     _resize_filter(resample)
     frames = _dev(frames, "frames", torch.uint8)
     N, H, W, out_h, out_w, box = _resize_args(frames.shape, size, crop)
     with torch.cuda.device(frames.device):
         tx = _resize_tables_dev(box[2], out_w, resample, frames.device)
         ty = _resize_tables_dev(box[3], out_h, resample, frames.device)
-        out = torch.empty(N, out_h, out_w, 3, device=frames.device, dtype=torch.uint8)
+        out = _resize_out(out, (N, out_h, out_w, 3), frames.device)
         ws = _workspace(lib().ncahip_clip_resize_workspace(N, box[3], out_w), frames.device)
         _clip_resize_launch(frames, box, tx, ty, out, ws)
     return out
@@ -1377,6 +1387,49 @@ def rgb_yuv_planes_host(rgb: np.ndarray, sums: np.ndarray, k: np.ndarray):
     U = 128 + ((k[3] * sums[..., 0] + k[4] * sums[..., 1] + k[5] * sums[..., 2] + np.int32(1 << 17)) >> 18)          # int32: < 2^27
     V = 128 + ((k[6] * sums[..., 0] + k[7] * sums[..., 1] + k[8] * sums[..., 2] + np.int32(1 << 17)) >> 18)
     return tuple(np.clip(p, 0, 255).astype(np.uint8) for p in (Y, U, V))
+
+
+def _even_size(size, what: str) -> None:
+    """Planar 4:2:0 results have even sides: ValueError for an odd (out_h, out_w)."""
+    try:
+        odd = any(int(v) % 2 for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (out_h, out_w), got {size!r}") from None
+    if odd:
+        raise ValueError(f"{what}: planar YUV 4:2:0 needs an even (out_h, out_w), got {tuple(size)}")
+
+
+def clip_resize_to_yuv420(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", out_format: str = "i420", yuv_matrix: str = "bt709",
+                          yuv_range: str = "limited", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames [N,H,W,3] uint8 on the device -> planar YUV 4:2:0 [N, 3 out_h / 2, out_w] uint8 ('i420' or 'nv12') at size = (out_h, out_w),
+    both even: ncahip_clip_resize_u8_yuv420, clip_resize's horizontal pass and a vertical pass that writes the planes -- bit for bit
+    rgb_to_yuv420(clip_resize(frames, size, crop, resample), out_format, yuv_matrix, yuv_range) without the full-size RGB image.  out: a
+    device tensor of the result's shape to write into."""
+    _resize_filter(resample)
+    layout, k = _yuv_layout(out_format), rgb_yuv_coeffs(yuv_matrix, yuv_range)
+    frames = _dev(frames, "frames", torch.uint8)
+    N, H, W, out_h, out_w, box = _resize_args(frames.shape, size, crop)
+    _even_size((out_h, out_w), "clip_resize_to_yuv420")
+    with torch.cuda.device(frames.device):
+        tx = _resize_tables_dev(box[2], out_w, resample, frames.device)
+        ty = _resize_tables_dev(box[3], out_h, resample, frames.device)
+        out = _resize_out(out, (N, 3 * out_h // 2, out_w), frames.device)
+        ws = _workspace(lib().ncahip_clip_resize_workspace(N, box[3], out_w), frames.device)
+        check(lib().ncahip_clip_resize_u8_yuv420(_p(frames), N, H, W, *box, _p(tx[0]), _p(tx[1]), tx[0].shape[1], _p(ty[0]), _p(ty[1]),
+                                                 ty[0].shape[1], layout, k.ctypes.data, _p(out), out_h, out_w, _p(ws),
+                                                 ws.numel() * ws.element_size(), _stream()), "clip_resize_u8_yuv420")
+    return out
+
+
+def clip_resize_to_yuv420_host(frames, size, crop=None, resample: str = "bicubic", out_format: str = "i420", yuv_matrix: str = "bt709",
+                               yuv_range: str = "limited"):
+    """clip_resize_to_yuv420 on the host: rgb_to_yuv420_host(clip_resize_host(...)) -- the composition is the definition -- and the route
+    for CPU tensors.  frames: a uint8 tensor or numpy array [N,H,W,3]; returns the same kind, on the host."""
+    _resize_filter(resample)
+    _yuv_layout(out_format)
+    rgb_yuv_coeffs(yuv_matrix, yuv_range)
+    _even_size(_resize_args(tuple(frames.shape), size, crop)[3:5], "clip_resize_to_yuv420")       # before the resize runs
+    return rgb_to_yuv420_host(clip_resize_host(frames, size, crop, resample), out_format, yuv_matrix, yuv_range)
 
 
 # ---------------------------------------------------------------- position sampler of the OT appearance loss (csrc/nca_ot_sample.hip)

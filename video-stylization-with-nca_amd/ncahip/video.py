@@ -20,6 +20,7 @@ the state (include/ncahip.h, "planar YUV images"), and out=<pinned host tensor> 
 side stream, chunk k while chunk k + 1 computes (_Downloads).
 """
 import contextlib
+import operator
 from typing import Iterable, Iterator, Optional
 
 import torch
@@ -143,7 +144,8 @@ def rgb_to_yuv420(frames: torch.Tensor, pixel_format: str, yuv_matrix: str = "bt
 
 
 def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubic", pixel_format: str = "rgb24", yuv_matrix: str = "bt709",
-                  yuv_range: str = "limited") -> torch.Tensor:
+                  yuv_range: str = "limited", out_format: str = "rgb24", out_yuv_matrix: str = "bt709",
+                  out_yuv_range: str = "limited") -> torch.Tensor:
     """frames [N,H,W,3] uint8 -> [N,out_h,out_w,3] uint8 on the frames' device: the reference's crop, then Pillow's 8-bit Image.resize,
     bit for bit.  size = (out_h, out_w) -- rows first; the reference hands Pillow (x, y).  crop: 'dynca' or 'conditioned'
     (reference_crop), None (the whole frame) or a box (x0, y0, w, h).  resample: 'bicubic' (Image.resize's default, what
@@ -151,8 +153,27 @@ def resize_frames(frames: torch.Tensor, size, crop=None, resample: str = "bicubi
     frames its numpy mirror ops.clip_resize_host on the same tables.
     pixel_format 'i420' / 'nv12': frames are planar YUV 4:2:0 [N, 3h/2, w] uint8 (yuv420_to_rgb); the result is resize_frames of their
     RGB, bit for bit.  CUDA frames run ncahip_clip_resize_yuv420_u8 (the conversion inside the horizontal pass's loader, no full-size
-    RGB image), CPU frames the two mirrors."""
+    RGB image), CPU frames the two mirrors.
+    out_format 'i420' / 'nv12' (even out_h and out_w): the result as planar YUV 4:2:0 [N, 3 out_h / 2, out_w] uint8 -- rgb_to_yuv420(the
+    'rgb24' result, out_format, out_yuv_matrix, out_yuv_range), bit for bit.  CUDA RGB24 frames run ncahip_clip_resize_u8_yuv420 (the
+    vertical pass writes the planes, no full-size RGB image), CPU frames ops.clip_resize_to_yuv420_host; planar frames convert the
+    resized image."""
     from . import ops
+    if out_format not in ops.OUT_FORMATS:
+        raise ValueError(f"out_format must be one of {ops.OUT_FORMATS}, got {out_format!r}")
+    if out_format != "rgb24":
+        ops.rgb_yuv_coeffs(out_yuv_matrix, out_yuv_range)
+        ops._even_size(size, "resize_frames")
+        if pixel_format != "rgb24":
+            return rgb_to_yuv420(resize_frames(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range), out_format, out_yuv_matrix,
+                                 out_yuv_range)
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f"frames must be a uint8 tensor [N,H,W,3] (the reference resizes 8-bit images), got "
+                             f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)} {getattr(frames, 'dtype', '')}")
+        if isinstance(crop, str):
+            crop = reference_crop(crop, frames.shape[1], frames.shape[2])
+        return (ops.clip_resize_to_yuv420 if frames.is_cuda else ops.clip_resize_to_yuv420_host)(frames, size, crop, resample, out_format,
+                                                                                                out_yuv_matrix, out_yuv_range)
     planar = _planar(frames, pixel_format, yuv_matrix, yuv_range)
     if planar is not None:
         if isinstance(crop, str):
@@ -335,19 +356,72 @@ def _loop_image(img: torch.Tensor, spec) -> torch.Tensor:
     return rgb_to_yuv420(img.contiguous(), spec.out_format, spec.yuv_matrix, spec.yuv_range) if spec.planar else img
 
 
-def _run_clip(fn, route: _Route, frames: torch.Tensor, shrink, per_call: int, dev, spec, out):
+class _Delivery:
+    """out_size= of the clip calls: the step between the route and the sink.  The routes run at the model grid and make uint8 RGB24
+    images there exactly as without out_size; enlarge() turns a chunk's grid images [n,H,W,3] into the images of
+    the call (spec: their ImageSpec, at the delivery size) -- 'rgb24' by ncahip_clip_resize_u8, 'i420' / 'nv12' by
+    ncahip_clip_resize_u8_yuv420 (no full-size RGB image), CPU images by the numpy mirrors -- the whole grid image, no crop."""
+
+    def __init__(self, spec, resample: str):
+        self.spec, self.resample = spec, resample
+
+    def enlarge(self, imgs: torch.Tensor, into: Optional[torch.Tensor]) -> torch.Tensor:
+        """imgs [n,H,W,3] uint8 -> [n, *spec.shape], written to `into` (a device tensor of that shape) when there is one."""
+        from . import ops
+        s, size = self.spec, (self.spec.H, self.spec.W)
+        if not imgs.is_cuda:
+            big = resize_frames(imgs, size, None, self.resample, out_format=s.out_format, out_yuv_matrix=s.yuv_matrix, out_yuv_range=s.yuv_range)
+            return big if into is None else into.copy_(big)
+        if s.planar:
+            return ops.clip_resize_to_yuv420(imgs, size, None, self.resample, s.out_format, s.yuv_matrix, s.yuv_range, out=into)
+        return ops.clip_resize(imgs, size, None, self.resample, out=into)
+
+
+def _image_specs(out_size, out_resample, out_dtype, out_format, out_yuv_matrix, out_yuv_range, c_out: int, hh: int, ww: int):
+    """(spec, deliver) of a clip call, validated before anything runs: the ImageSpec the routes emit with, and None or the _Delivery of
+    out_size=(h, w).  With out_size the routes emit uint8 RGB24 at the grid, and every rule of the images -- the dtype, c_out == 3, the
+    even sides of a planar format -- applies to the delivery size."""
+    from . import ops
+    if out_size is None:
+        return ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, c_out, hh, ww), None
+    if out_dtype != torch.uint8:
+        raise ValueError(f"out_size needs out_dtype=torch.uint8 (Pillow's resize is an 8-bit algorithm, as on the way in), got {out_dtype}")
+    try:
+        oh, ow = (operator.index(v) for v in out_size)               # integers only: 36.5 is not truncated to 36
+    except (TypeError, ValueError):
+        raise ValueError(f"out_size must be (h, w), two integers, got {out_size!r}") from None
+    if oh < 1 or ow < 1:
+        raise ValueError(f"out_size must be positive, got {out_size!r}")
+    if out_resample not in ("bicubic", "lanczos"):
+        raise ValueError(f"out_resample must be 'bicubic' or 'lanczos', got {out_resample!r}")
+    if c_out != 3:
+        raise ValueError(f"out_size needs an RGB image (c_out == 3), got c_out = {c_out}")
+    spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, c_out, oh, ow)      # (planar: even out_size)
+    ops._resize_args((1, hh, ww, 3), (oh, ow), None)
+    return ops.ImageSpec.of(torch.uint8, "rgb24", c_out=c_out, H=hh, W=ww), _Delivery(spec, out_resample)
+
+
+def _run_clip(fn, route: _Route, frames: torch.Tensor, shrink, per_call: int, dev, spec, out, deliver: Optional[_Delivery] = None):
     """The chunk pipeline of both clip calls (fn: the entry point, which records the routes taken), returning (images, state).  Per chunk
-    of per_call frames: upload (_chunks), shrink, the staging buffer of out= (_Downloads), the route, the images on their way to `out` or
-    to the final cat.  raw and chunk are dropped before the next chunk is asked for (_chunks: at most two uploaded chunks alive)."""
+    of per_call frames: upload (_chunks), shrink, the staging buffer of out= (_Downloads), the route, with out_size= the enlargement of
+    the chunk's images (deliver: the staging buffer then has the delivery shape and receives the enlarged images), the images on their way
+    to `out` or to the final cat.  raw and chunk are dropped before the next chunk is asked for (_chunks: at most two uploaded chunks
+    alive).  spec: what the route emits; the images of the call are deliver.spec's when there is a deliver."""
     k = route.k
     fn.last_path, fn.last_download = "clip" if route.fused else "loop", None
-    sink = None if out is None else _Downloads(fn, out, spec.shape, per_call * k, dev)
+    out_spec = spec if deliver is None else deliver.spec
+    sink = None if out is None else _Downloads(fn, out, out_spec.shape, per_call * k, dev)
     outs = []
     try:
         for ci, raw in enumerate(_chunks(fn, frames, per_call, dev)):
             chunk = shrink(raw)
             buf = None if sink is None else sink.staging(chunk.shape[0] * k)
-            if route.fused:
+            if deliver is not None:                        # the route as without out_size, then the step to the delivery size
+                imgs = [route.run(ci, chunk, None)] if route.fused else [_loop_image(img, spec) for img in route.run(ci, chunk, None)]
+                if imgs:
+                    grid = imgs[0] if len(imgs) == 1 else torch.cat(imgs)     # (a fused route's one tensor is not copied)
+                    imgs = [deliver.enlarge(grid.contiguous(), None if buf is None else buf[:, 0])]
+            elif route.fused:
                 imgs = [route.run(ci, chunk, buf)]
             else:
                 imgs = [_loop_image(img, spec) for img in route.run(ci, chunk, buf)]
@@ -364,7 +438,7 @@ def _run_clip(fn, route: _Route, frames: torch.Tensor, shrink, per_call: int, de
     fn.last_state = route.h
     if sink is not None:
         return out, route.h
-    return (torch.cat(outs) if outs else torch.empty((0,) + spec.shape, dtype=spec.out_dtype, device=dev)), route.h
+    return (torch.cat(outs) if outs else torch.empty((0,) + out_spec.shape, dtype=out_spec.out_dtype, device=dev)), route.h
 
 
 def _check_precision(nca_model, h: torch.Tensor, precision: str, direction) -> None:
@@ -457,7 +531,8 @@ class _DyncaLoop(_Route):
 def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_frame: int = 1, state: Optional[torch.Tensor] = None,
                  gray: str = "mean", out_dtype=torch.float32, frames_per_call: int = 32, size=None, crop="dynca", resample: str = "bicubic",
                  precision: str = "f32", direction=None, pixel_format: str = "rgb24", yuv_matrix: str = "bt709", yuv_range: str = "limited",
-                 out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited", out: Optional[torch.Tensor] = None):
+                 out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited", out: Optional[torch.Tensor] = None,
+                 out_size=None, out_resample: str = "bicubic"):
     """A whole clip per call: video_utils.py:50-83 over `frames`, returning (images, state).
 
     frames: [F,3,H,W] float32 in [-1, 1] or [F,H,W,3] uint8 (what a decoder delivers), on the host or the device.  images:
@@ -513,7 +588,16 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     out: None, or a tensor of exactly the images' shape and dtype (anything else: ValueError before any work) that receives the images
     and is returned as `images`.  A pinned host tensor with a model on the GPU is filled on a side stream, chunk k while chunk k + 1
     computes; the host waits for the last copy before the call returns (also when it raises), so every byte is valid then.  A pageable or
-    device tensor is filled by a plain copy per chunk.  stylize_clip.last_download records 'overlapped', 'sync' or None (out=None)."""
+    device tensor is filled by a plain copy per chunk.  stylize_clip.last_download records 'overlapped', 'sync' or None (out=None).
+
+    out_size=(h, w): images at delivery size.  The call runs at the model grid exactly as without it -- the same routes, state and mask
+    stream -- and every chunk's uint8 RGB24 images are enlarged on the device between the route and `out`: Pillow's 8-bit Image.resize of
+    the whole grid image (out_resample 'bicubic' or 'lanczos'), for 'rgb24' by ncahip_clip_resize_u8, for 'i420' / 'nv12' by
+    ncahip_clip_resize_u8_yuv420, whose vertical pass writes the planes (no full-size RGB image).  images: [F*steps_per_frame, h, w, 3] or
+    [F*steps_per_frame, 3h/2, w] uint8; `out` and its staging buffers have that shape.  Bit for bit resize_frames(images of the same call
+    without out_size, out_size, None, out_resample), and rgb_to_yuv420 of that for a planar format; independent of frames_per_call.  Needs
+    out_dtype=torch.uint8 and c_out == 3; a planar format needs an even out_size (the grid may then be odd).  ValueError before any work
+    for anything else.  out_size=None: out_resample is not looked at."""
     from . import ops, steer
     if precision not in ("f32", "bf16", "bf16_wide"):
         raise ValueError(f"precision must be 'f32', 'bf16' or 'bf16_wide', got {precision!r}")
@@ -524,8 +608,8 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
     k, step_n, per_call = int(steps_per_frame), int(step_n), max(1, int(frames_per_call))
     dev = nca_model.device
-    spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, getattr(nca_model, "c_out", 3), hh, ww)
-    _check_out(out, frames.shape[0] * k, spec)
+    spec, deliver = _image_specs(out_size, out_resample, out_dtype, out_format, out_yuv_matrix, out_yuv_range, getattr(nca_model, "c_out", 3), hh, ww)
+    _check_out(out, frames.shape[0] * k, spec if deliver is None else deliver.spec)
     if _extra_channels(nca_model) and state is not None and (state.dim() != 4 or state.shape[1] != nca_model.c_in - 1):
         raise ValueError(f"state must have c_in - 1 = {nca_model.c_in - 1} channels (the grey frame is appended per call), got {tuple(state.shape)}")
     h = state if state is not None else nca_model.seed(1, size=(ww, hh))
@@ -543,7 +627,7 @@ def stylize_clip(nca_model, frames: torch.Tensor, step_n: int = 8, steps_per_fra
         with ops.dynca_direction(dirs) if (fused and dirs is not None) else contextlib.nullcontext():
             route = (_DyncaClip(nca_model, h, k, step_n, gray, angle, spec) if fused else
                      _DyncaLoop(nca_model, h, k, step_n, gray, direction, u8_in))
-            return _run_clip(stylize_clip, route, frames, shrink, per_call, dev, spec, out)
+            return _run_clip(stylize_clip, route, frames, shrink, per_call, dev, spec, out, deliver)
 
 
 stylize_clip.last_path = None
@@ -603,7 +687,7 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
                              warmup_steps: int = 0, out_dtype=torch.float32, frames_per_call: int = 8, size=None, crop="conditioned",
                              resample: str = "lanczos", precision: str = "f32", pixel_format: str = "rgb24", yuv_matrix: str = "bt709",
                              yuv_range: str = "limited", out_format: str = "rgb24", out_yuv_matrix: str = "bt709", out_yuv_range: str = "limited",
-                             out: Optional[torch.Tensor] = None):
+                             out: Optional[torch.Tensor] = None, out_size=None, out_resample: str = "bicubic"):
     """A whole clip per call for a ConditionedNCA (ncahip.nca.ConditionedNCA), returning (images, state): what the reference's interactive
     loop does when the goal is switched while it runs (EncoderConditioning/visualisation.ipynb) -- the state is carried, every frame is the
     goal of its own steps:
@@ -643,14 +727,19 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
 
     out_format, out_yuv_matrix, out_yuv_range, out: planar YUV 4:2:0 images [F*steps_per_frame, 3H/2, W] uint8 and delivery into a
     caller's tensor (a pinned one on a side stream while the next chunk computes), as in stylize_clip;
-    stylize_clip_conditioned.last_download records 'overlapped', 'sync' or None."""
+    stylize_clip_conditioned.last_download records 'overlapped', 'sync' or None.
+
+    out_size, out_resample: images at delivery size [F*steps_per_frame, h, w, 3] or [F*steps_per_frame, 3h/2, w] uint8, as in stylize_clip:
+    the call runs at the grid as without it (both routes, 'f32' and 'bf16'), and every chunk's uint8 images are enlarged on the device on
+    their way to `out` -- bit for bit resize_frames(images of the same call without out_size, out_size, None, out_resample), and
+    rgb_to_yuv420 of that for a planar format.  Needs out_dtype=torch.uint8; a planar format needs an even out_size."""
     from . import ops
     if precision not in ("f32", "bf16"):
         raise ValueError(f"precision must be 'f32' or 'bf16', got {precision!r}")
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     u8_in, hh, ww, shrink = _source(frames, size, crop, resample, pixel_format, yuv_matrix, yuv_range)
-    spec = ops.ImageSpec.of(out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
+    spec, deliver = _image_specs(out_size, out_resample, out_dtype, out_format, out_yuv_matrix, out_yuv_range, 3, hh, ww)
     if precision == "bf16":
         if nca.num_channels > 20:
             raise ValueError(f"precision='bf16' covers num_channels <= 20 (the bf16-storage step kernels); the model has {nca.num_channels}")
@@ -667,7 +756,7 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     k, step_n, warm, per_call = int(steps_per_frame), int(step_n), int(warmup_steps), max(1, int(frames_per_call))
     if k < 1 or step_n < 1 or warm < 0:
         raise ValueError("steps_per_frame and step_n must be positive and warmup_steps non-negative")
-    _check_out(out, frames.shape[0] * k, spec)
+    _check_out(out, frames.shape[0] * k, spec if deliver is None else deliver.spec)
     dev = next(nca.parameters()).device
     h = (nca.generate_seed(1, size=hh) if state is None else state).to(dev)
     if precision == "bf16":
@@ -675,7 +764,7 @@ def stylize_clip_conditioned(nca, frames: torch.Tensor, step_n: int = 8, steps_p
     fused = (h.is_cuda and h.dtype == (torch.float32 if precision == "f32" else torch.bfloat16) and h.shape[0] == 1 and
              ops.encoder_clip_ok(nca.encoder) and nca.encoder.channels == 3)
     route = _CondClip(nca, h, k, step_n, warm, spec) if fused else _CondLoop(nca, h, k, step_n, warm, u8_in)
-    return _run_clip(stylize_clip_conditioned, route, frames, shrink, per_call, dev, spec, out)
+    return _run_clip(stylize_clip_conditioned, route, frames, shrink, per_call, dev, spec, out, deliver)
 
 
 stylize_clip_conditioned.last_path = None
